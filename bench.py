@@ -1,8 +1,21 @@
 #!/usr/bin/env python3
 """bench.py — MLUPS and fraction of the HBM roofline of the D2Q9-BGK timestep on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: it sets up, warms up as the headline has always been warmed up
+(the same steps once in a context of its own, then the calibration launches `pre_warmup`, then W steps), times K steps,
+writes its outputs if --dump-outputs is given and prints the line; `result_ok` then only says that the timed context's
+av_vels record is finite and positive.  --full adds everything else this file measures and checks: `value_cold`, the
+comparison of the timed record with the fp32 oracle (`result_check`), the CPU baseline, the side legs (1024x1024 input,
+weak scaling, reference-rule figures, HBM-bound siblings) and the per-rank launch-set profiles.  With N ranks both kinds
+of run first check every halo transport (`transport_check`): only a transport that passed is timed.
+
+--dump-outputs DIR writes what the timed context holds after its last step, as a caller of lbm_download receives it:
+DIR/av_vels.npy (float32, one entry per step run) and DIR/cells.npy (float32: the whole 9 x ny x nx state up to
+DUMP_CELLS values, beyond that DUMP_CELLS values at seeded positions, the same for every run on the same grid).  The
+inputs (grid, obstacles, rest state) depend on the arguments alone, so two builds can be compared output for output.
 
 `python bench.py --gpus N` with N > 1 and no launcher around it starts its own ranks: before anything touches the GPU
 it runs `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process (one rank per GPU over
@@ -428,9 +441,10 @@ def profile_all_ranks(env, sim, nsteps, extra):
     return [json.loads(b.decode().strip()) for b in gather_blobs(env.dist, blob, env.world, env.device)]
 
 
-def rank_leg(env, params, obstacles, transports, warmup, steps, fuse=-1, profile=True, want_av=False, before=None):
+def rank_leg(env, params, obstacles, transports, warmup, steps, fuse=-1, profile=True, want_av=False, before=None, dump=False):
     """One workload over the ranks, once per halo transport — a fresh context each, so that a transport that fails
-    leaves nothing behind for the next.  Returns {transport: {...}}; a failed transport has an "error" instead of times."""
+    leaves nothing behind for the next.  Returns {transport: {...}}; a failed transport has an "error" instead of times.
+    dump: keep what --dump-outputs writes ("outputs", read back before any profiled step)."""
     runs = {}
     for tr in transports:
         entry, rs = {}, None
@@ -445,8 +459,10 @@ def rank_leg(env, params, obstacles, transports, warmup, steps, fuse=-1, profile
             entry["wall_s"], entry["loop_ms"] = timed_run(env, sim, warmup, steps)
             entry["row_range"] = sim.row_range()
             entry["options"] = {k: sim.get_option(k) for k in OPTION_KEYS}
-            if want_av:
+            if want_av or dump:
                 entry["av"] = rs.av_vels()     # collective (RCCL all-reduce): every rank got here
+            if dump:
+                entry["outputs"] = {"cells": output_sample(env, sim, *entry["row_range"]), "av_vels": entry["av"]}
             if profile:
                 per = max(entry["options"]["multistep"], entry["options"]["launch_steps"], 1)
                 entry["per_rank"] = profile_all_ranks(env, sim, 8 * per, dict(rows=entry["row_range"][1] - entry["row_range"][0]))
@@ -467,6 +483,42 @@ def rank_leg(env, params, obstacles, transports, warmup, steps, fuse=-1, profile
 def max_rel(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-30)))
+
+
+DUMP_CELLS = 1 << 23    # float32 values of the state --dump-outputs writes at most: 32 MiB, av_vels adds a few KB
+
+
+def dump_positions(shape):
+    """flat positions into the float32[9][ny][nx] state of the values --dump-outputs writes: None (all of them) up to
+    DUMP_CELLS values, else DUMP_CELLS draws from a fixed seed, sorted, repeats dropped"""
+    total = int(np.prod(shape))
+    if total <= DUMP_CELLS:
+        return None
+    return np.unique(np.random.default_rng(2026).integers(0, total, DUMP_CELLS, dtype=np.int64))
+
+
+def output_sample(env, sim, y0, y1):
+    """the state values --dump-outputs writes, read back from a context after its last timed step: float32[9][ny][nx] or
+    the values at dump_positions().  With ranks (a collective) every rank keeps the values of its own rows [y0, y1) and
+    zeroes the others; the ranks' vectors are added up, which is exact with one non-zero term per position."""
+    cells = sim.download(av_vels=False)[0]
+    shape = cells.shape
+    pos = dump_positions(shape)
+    vals = cells.reshape(-1).copy() if pos is None else cells.reshape(-1)[pos]
+    del cells
+    if env.dist is not None:
+        rows = (np.arange(vals.size) if pos is None else pos) // shape[2] % shape[1]
+        vals[(rows < y0) | (rows >= y1)] = 0.0
+        vals = sum_over_ranks(env.dist, vals, env.device).astype(np.float32)
+    return vals.reshape(shape) if pos is None else vals
+
+
+def write_outputs(path, outputs):
+    """--dump-outputs: one float32 .npy per output; returns what the record says about them"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {name + ".npy": list(np.shape(a)) for name, a in outputs.items()}
 
 
 def fault_legs(transport=None):
@@ -761,6 +813,9 @@ def roofline_of(nx, rows_local, steps, loop_ms, multistep, fused, deep, twin):
 
 
 OPTION_KEYS = ("fuse", "pair", "launch_steps", "multistep", "halo_depth", "resident")
+# a plain run's first context runs at most this many warm-up and timed steps each: up to there it launches what the timed leg
+# launches, and on the headline grid a first launch costs well under 0.1 % of more timed steps than that
+WARM_STEPS = 512
 
 
 def kernel_label(o):
@@ -857,10 +912,17 @@ def main():
     ap.add_argument("--budget-s", type=float, default=600.0,
                     help="N > 1: a side leg (1024x1024 strong scaling, weak scaling) is started only while the run is younger than this "
                          "many seconds; the headline record is printed before them either way")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cold", action="store_true", help="skip `value_cold` (the same steps before any calibration launch)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the 1024x1024, weak-scaling and reference-rule side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also value_cold, the oracle comparison of the timed record, the CPU baseline, the side legs and the "
+                         "per-rank profiles (module docstring); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed context's state and av_vels after its last step to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-cold", action="store_true", help="skip the first context (the same steps before any calibration launch; "
+                                                           "with --full timed as `value_cold`)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the 1024x1024, weak-scaling and reference-rule side measurements")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     launched = "WORLD_SIZE" in os.environ
     one_process = False
@@ -913,7 +975,7 @@ def main():
     params = lbm_amd.make_params(nx, ny, total_steps, 10, 0.1, args.accel, 1.85, obstacles)
     ndev = args.gpus if one_process else 1
 
-    def plain_leg(p, ob, warmup, steps, fuse=-1, want_av=False, before=None):
+    def plain_leg(p, ob, warmup, steps, fuse=-1, want_av=False, before=None, dump=False):
         """one context in this process (one slab, or --launcher one-process: one slab per device)"""
         with (lbm_amd.LBM(p, ob, devices=[i % visible for i in range(ndev)]) if ndev > 1 else lbm_amd.LBM(p, ob)) as sim:
             if fuse >= 0:
@@ -925,9 +987,11 @@ def main():
             e["wall_s"], e["loop_ms"] = timed_run(env, sim, warmup, steps)
             e["row_range"] = sim.row_range()
             e["options"] = {k: sim.get_option(k) for k in OPTION_KEYS}
-            if want_av:
+            if want_av or dump:
                 e["av"] = sim.download(cells=False)[1]
-            if ndev > 1:
+            if dump:
+                e["outputs"] = {"cells": output_sample(env, sim, *e["row_range"]), "av_vels": e["av"]}
+            if ndev > 1 and args.full:
                 per = max(e["options"]["multistep"], e["options"]["launch_steps"], 1)
                 st = sim.run_profiled(8 * per)
                 e["per_rank"] = [{k: (round(v, 2) if isinstance(v, float) else v) for k, v in st.items()}]
@@ -935,26 +999,32 @@ def main():
 
     # ---- `value_cold`: the same W + K steps BEFORE anything else has run on the chip (no copy calibration, no issue-rate
     # calibration): the first ~40 ms of the VALU-bound default kernel run 8-10 % below its steady state on a chip that has
-    # not been loaded yet (profiles/r02_cold_start.txt), and a 20-step record is mostly those milliseconds
-    cold = None
+    # not been loaded yet (profiles/r02_cold_start.txt), and a 20-step record is mostly those milliseconds.
+    # A plain run keeps this first context as a warm-up and reports no rate for it: its launches are the first of every kernel
+    # instance the timed leg launches (each timestep depth is an instance of its own: 20 steps run as 7 + 7 + 6), and `value`
+    # has always been measured after it.  There it runs at most WARM_STEPS warm-up and timed steps each.
+    cold, first = None, None
     if not args.no_cold:
+        w, k = (args.warmup, args.steps) if args.full else (min(args.warmup, WARM_STEPS), min(args.steps, WARM_STEPS))
+        first = {"warmup": w, "steps": k}
         if rank_mode:
-            c = list(rank_leg(env, params, obstacles, ["peer" if rehearsal else "rccl"], args.warmup, args.steps, args.fuse,
-                              profile=False).values())[0]
+            c = list(rank_leg(env, params, obstacles, ["peer" if rehearsal else "rccl"], w, k, args.fuse, profile=False).values())[0]
         else:
-            c = plain_leg(params, obstacles, args.warmup, args.steps, args.fuse)
-        if "wall_s" in c:
+            c = plain_leg(params, obstacles, w, k, args.fuse)
+        if "wall_s" in c and args.full:
             cold = round(nx * ny * args.steps / c["wall_s"] / 1e6, 1)
 
     # ---- the two roofline denominators (a float4 copy of 1 GiB each way; packed-FMA issue rate, ~1.9 ms per launch) are
     # measured anyway — and measured BETWEEN the creation of a timed leg's context and its W warm-up steps they also bring
     # the chip to its working clock (context creation leaves it idle for a second; the first ~40 ms after that run 8-25 %
     # below the steady state).  That is a warm-up beyond --warmup, so the line says so: `pre_warmup`, and `value_cold`.
+    # A plain run keeps these launches: `value` has always been measured after them.
     calib = {"copy_gbps": None, "valu_tera": None}
-    pre = {"copy_launches": 0, "copy_ms": 0.0, "valu_calib_launches": 0, "valu_calib_ms": 0.0, "legs": 0,
+    pre = {"copy_launches": 0, "copy_ms": 0.0, "valu_calib_launches": 0, "valu_calib_ms": 0.0, "legs": 0, "first_context": first,
            "what": "calibration launches (1 GiB float4 copy: once; packed-FMA issue rate: before every timed leg) that run "
                    "between the creation of a leg's context and its W warm-up steps; `value_cold` is the same W + K steps "
-                   "with none of them, in a context of its own, measured first"}
+                   "with none of them, in a context of its own, measured first (`first_context`: the steps that context ran; "
+                   "a plain run reports no rate for it)"}
 
     def pre_warm():
         try:
@@ -991,11 +1061,13 @@ def main():
         log("transports that passed: %s" % transports, rank)
 
     # ---- the timed region(s): one per halo transport, the faster one is reported as `value` -----------------------
+    dump = bool(args.dump_outputs)
     if rank_mode:
-        runs = rank_leg(env, params, obstacles, transports, args.warmup, args.steps, args.fuse, want_av=True, before=pre_warm)
+        runs = rank_leg(env, params, obstacles, transports, args.warmup, args.steps, args.fuse, profile=args.full, want_av=True,
+                        before=pre_warm, dump=dump)
     else:
         runs = {"single" if ndev == 1 else "one-process": plain_leg(params, obstacles, args.warmup, args.steps, args.fuse, want_av=True,
-                                                                    before=pre_warm)}
+                                                                    before=pre_warm, dump=dump)}
     copy_gbps, valu_tera = calib["copy_gbps"], calib["valu_tera"]
     good = {k: v for k, v in runs.items() if "wall_s" in v}
 
@@ -1053,9 +1125,20 @@ def main():
                                     "stores over HIP IPC — a test of the N > 1 code path, NOT a benchmark" % (world, visible))
         if b.get("per_rank"):
             out["per_rank_launch_set_us"] = b["per_rank"]
+        if dump:
+            out["outputs"] = dict(write_outputs(args.dump_outputs, b["outputs"]), dir=args.dump_outputs,
+                                  cells_sampled=b["outputs"]["cells"].ndim == 1)
 
     def judge_result():
-        """`result_ok`: av_vels of the timed context against the oracle's record of the same steps"""
+        """`result_ok`: av_vels of the timed context against the oracle's record of the same steps (--full); a plain run only
+        looks at the record itself"""
+        if not args.full:
+            av = good[best]["av"]
+            good_ok = bool(len(av) > 0 and np.all(np.isfinite(av)) and av[-1] > 0)
+            out["result_ok"] = good_ok
+            out["result_check"] = {"compared_steps": 0, "what": "av_vels[0..%d) of the timed context finite and positive; "
+                                                                "the comparison with the fp32 oracle runs with --full" % len(av)}
+            return good_ok
         if not av_oracle:
             # no baseline leg in this run: a few steps of the OpenMP build of the same oracle, for the check alone
             os.environ["OMP_NUM_THREADS"] = str(max(1, min(16, len(os.sched_getaffinity(0)) // max(1, world))))
@@ -1079,7 +1162,7 @@ def main():
             out.setdefault("skipped_legs", []).append("%s: the run was older than --budget-s %.0f s" % (name, args.budget_s))
         return not late
 
-    extra = not args.no_extra and (nx, ny) != (1024, 1024)
+    extra = args.full and not args.no_extra and (nx, ny) != (1024, 1024)
     if extra and rank_mode and transports:
         if side_leg_allowed("also"):
             # ---- the 1024x1024 input of the reference row-partitioned over the same ranks (BASELINE config 4: strong scaling)
@@ -1188,7 +1271,7 @@ def main():
             out["reference_rule"] = ref
     if rank == 0 and out is not None and good:
         # ---- CPU baseline (rank 0, N = 1 only) and the oracle record `result_ok` is judged on -------------------------
-        if world == 1 and ndev == 1 and not args.no_cpu_baseline and not rank_mode:
+        if world == 1 and ndev == 1 and args.full and not args.no_cpu_baseline and not rank_mode:
             out["cpu_baseline"] = cpu_baseline(nx, ny, obstacles, args.accel, av_out=av_oracle)
         if "result_ok" not in out:
             ok = judge_result()

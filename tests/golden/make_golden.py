@@ -16,9 +16,11 @@ Usage (from the repo root, ≈3-4 min on 8 cores):  python tests/golden/make_gol
 import gzip
 import io
 import json
+import lzma
 import os
 import sys
 import time
+import zipfile
 
 import numpy as np
 
@@ -31,8 +33,26 @@ SIZES = ["128x128", "128x256", "256x256", "1024x1024"]
 
 
 def load_gz_cols(path, cols):
-    with gzip.open(path, "rt") as f:
+    with (lzma.open(path, "rt") if path.endswith(".xz") else gzip.open(path, "rt")) as f:
         return np.loadtxt(io.StringIO(f.read()), usecols=cols)
+
+
+def shipped_golden(size, name):
+    """tests/golden/check/<size>.<name>.dat.gz, or .xz where gzip would leave it above 1 MiB; None if neither exists"""
+    for ext in (".gz", ".xz"):
+        path = os.path.join(GOLD, "check", "%s.%s.dat%s" % (size, name, ext))
+        if os.path.exists(path):
+            return path
+    return None
+
+
+def savez_lzma(path, **arrays):
+    """np.savez with LZMA-compressed members (np.load reads them as it reads any .npz): the fixtures stay below 1 MiB"""
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for key, value in arrays.items():
+            buf = io.BytesIO()
+            np.save(buf, value)
+            z.writestr(key + ".npy", buf.getvalue())
 
 
 def max_pcnt(ref, sim):
@@ -51,13 +71,13 @@ def main():
         av = orc.run(p, cells, obst, p.max_iters)
         dt = time.time() - t0
         ux, uy, u, pr = orc.final_fields(p, cells, obst)
-        ref_av = load_gz_cols(os.path.join(GOLD, "check", "%s.av_vels.dat.gz" % size), [1])
+        ref_av = load_gz_cols(shipped_golden(size, "av_vels"), [1])
         # %.12E print precision of the golden files bounds the agreement at ~5e-11 relative
         e_av = max_pcnt(ref_av, av)
         assert e_av < 1e-8, (size, e_av)
         msg = "%s: %d steps in %.1f s, av_vels max %.2e %%" % (size, p.max_iters, dt, e_av)
-        fs = os.path.join(GOLD, "check", "%s.final_state.dat.gz" % size)
-        if os.path.exists(fs):
+        fs = shipped_golden(size, "final_state")
+        if fs is not None:
             ref_p = load_gz_cols(fs, [5]).reshape(p.ny, p.nx)
             e_p = max_pcnt(ref_p, pr)
             assert e_p < 1e-8, (size, e_p)
@@ -66,11 +86,11 @@ def main():
             out = os.path.join(GOLD, "generated", "%s.final_state.npz" % size)
             if pr.size > (1 << 18):
                 # 1024²: pressure only, rounded to f32 (6e-8 relative, the gate is 1 %), mask as bits
-                np.savez_compressed(out, pressure=pr.astype(np.float32), obstacles=np.packbits(obst.astype(np.uint8)),
-                                    shape=np.array(pr.shape))
+                savez_lzma(out, pressure=pr.astype(np.float32), obstacles=np.packbits(obst.astype(np.uint8)),
+                           shape=np.array(pr.shape))
             else:
-                np.savez_compressed(out, pressure=pr, u_x=ux.astype(np.float32), u_y=uy.astype(np.float32),
-                                    u=u.astype(np.float32), obstacles=obst.astype(np.uint8))
+                savez_lzma(out, pressure=pr, u_x=ux.astype(np.float32), u_y=uy.astype(np.float32),
+                           u=u.astype(np.float32), obstacles=obst.astype(np.uint8))
             msg += ", final_state stored"
         print(msg, flush=True)
         scalars[size] = {

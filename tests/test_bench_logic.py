@@ -127,6 +127,53 @@ def test_band_oracle_equals_the_oracle_of_the_whole_grid(oracle_f32_omp):
     assert np.array_equal(got, cells[:, 10:115])
 
 
+def test_dump_outputs_sample_and_rank_merge(tmp_path, monkeypatch):
+    """--dump-outputs: the whole state up to DUMP_CELLS values, beyond that the same seeded positions in every run; with ranks each
+    rank contributes the values of its own rows, whatever else its read-back holds, and their sum is the undivided grid's; the
+    files are float32"""
+    bench = load_bench()
+    assert bench.dump_positions((9, 16, 8)) is None
+    shape = (9, 1024, 1024)
+    pos = bench.dump_positions(shape)
+    assert np.array_equal(pos, bench.dump_positions(shape)) and np.all(np.diff(pos) > 0)
+    assert pos[0] >= 0 and pos[-1] < np.prod(shape) and 0.6 * bench.DUMP_CELLS < pos.size <= bench.DUMP_CELLS
+
+    class Sim:
+        def __init__(self, cells):
+            self.cells = cells
+
+        def download(self, cells=True, av_vels=True):
+            return self.cells.copy(), None
+
+    class One:
+        dist, device = None, None
+
+    class Rank:
+        dist, device = object(), None
+
+    monkeypatch.setattr(bench, "sum_over_ranks", lambda dist, values, device: np.asarray(values, dtype=np.float64))
+    rng = np.random.default_rng(1)
+    for whole, want in ((rng.random((9, 40, 24), dtype=np.float32), None), (rng.random(shape, dtype=np.float32), pos)):
+        ny = whole.shape[1]
+        want = whole if want is None else whole.reshape(-1)[want]
+        assert np.array_equal(bench.output_sample(One, Sim(whole), 0, ny), want)
+        got = 0
+        for y0, y1 in ((0, 17), (17, ny)):
+            held = np.full_like(whole, 7.0)      # the rows of the other rank: not this rank's to report
+            held[:, y0:y1] = whole[:, y0:y1]
+            got = got + bench.output_sample(Rank, Sim(held), y0, y1)
+        assert got.dtype == np.float32 and np.array_equal(got, want)
+    info = bench.write_outputs(str(tmp_path / "d"), {"cells": whole[:, :4], "av_vels": np.arange(5, dtype=np.float64)})
+    assert info == {"cells.npy": [9, 4, 1024], "av_vels.npy": [5]}
+    assert np.load(tmp_path / "d" / "av_vels.npy").dtype == np.float32 and np.load(tmp_path / "d" / "cells.npy").shape == (9, 4, 1024)
+
+
+def test_steps_must_be_positive():
+    """--steps sets the number of timed steps: zero of them is refused before anything starts"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
 def test_self_launch_without_gpu_fails_in_the_child():
     """`python bench.py --gpus 2` with no launcher around it starts torch.distributed.run as a child process; on this
     CPU-only box the child ranks refuse ("needs a GPU"), the parent relays that and exits non-zero without a result line"""

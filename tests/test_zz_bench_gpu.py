@@ -56,7 +56,7 @@ def test_bench_json_contract():
     """bench.py prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline` (small grid here)"""
     import json
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "8", "--nx", "1024",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "40", "--warmup", "8", "--nx", "1024",
                         "--ny", "1024", "--no-extra"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, _bench_failure(r)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -95,6 +95,43 @@ def test_bench_json_contract():
     assert j["library"].startswith("lbm-hip") and "src " in j["library"] and j["launcher"].startswith("none")
 
 
+def test_bench_plain_run_dumps_the_timed_outputs(lbm, tmp_path):
+    """a plain run (no --full) measures the headline and nothing else, and --dump-outputs writes what the timed context holds
+    after its last step: av_vels of every step run and the state at the seeded positions — the same in two runs, and what the
+    library computes for the same steps of the same grid"""
+    import importlib.util
+    import sys
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    nx, ny, warmup, steps = 2048, 1024, 8, 40
+    for k in range(2):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--nx", str(nx),
+                            "--ny", str(ny), "--dump-outputs", str(tmp_path / str(k))], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, _bench_failure(r)
+        j = _records(r, False)
+        assert j["steps"] == steps and j["warmup"] == warmup and j["result_ok"] is True and j["dtype"] == "f32"
+        assert abs(j["value"] - nx * ny / (j["ms_per_step"] * 1e-3) / 1e6) / j["value"] < 0.01
+        assert j["value_cold"] is None and j["pre_warmup"]["first_context"] == {"warmup": warmup, "steps": steps}
+        assert j["result_check"]["compared_steps"] == 0
+        assert not {"cpu_baseline", "also", "reference_rule"} & set(j)
+        assert j["outputs"]["cells_sampled"] is True and j["outputs"]["av_vels.npy"] == [warmup + steps]
+    av = [np.load(tmp_path / str(k) / "av_vels.npy") for k in range(2)]
+    cells = [np.load(tmp_path / str(k) / "cells.npy") for k in range(2)]
+    assert av[0].dtype == cells[0].dtype == np.float32 and cells[0].ndim == 1 and cells[0].nbytes + av[0].nbytes <= 64e6
+    assert np.array_equal(cells[0], cells[1]) and bench.max_rel(av[1], av[0]) < 2e-6
+    ob = bench.cavity(nx, ny)
+    p = lbm.make_params(nx, ny, warmup + steps + 256, 10, 0.1, 0.005, 1.85, ob)
+    with lbm.LBM(p, ob) as sim:
+        sim.upload(None)
+        sim.run(warmup)
+        sim.run(steps)
+        ref, av_ref = sim.download()
+    assert np.array_equal(cells[0], ref.reshape(-1)[bench.dump_positions(ref.shape)])
+    assert bench.max_rel(av[0], av_ref) < 2e-6
+
+
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus N` without a launcher around it: bench.py starts torch.distributed.run itself as a child
     process (the parent never touches the GPU) and relays rank 0's line.  With --gpus 2 on this one-GPU box the CHILD
@@ -108,7 +145,7 @@ def test_bench_starts_its_own_ranks():
     assert r.returncode != 0 and "2 GPUs needed, 1 visible" in r.stderr, r.stderr[-2000:]
     assert "needs a torch.distributed launch" not in r.stderr
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--launcher", "torchrun", "--steps", "60",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--launcher", "torchrun", "--steps", "60",
                         "--warmup", "12", "--nx", "2048", "--ny", "1024", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, _bench_failure(r)
@@ -133,7 +170,7 @@ def test_bench_rehearsal_of_the_multi_rank_path(nranks):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LBM_BENCH_RANK_MODE", "LBM_BENCH_CHILD")}
     env["LBM_BENCH_REHEARSAL"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nranks), "--steps", "24", "--warmup", "8",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(nranks), "--steps", "24", "--warmup", "8",
                         "--nx", "2048", "--ny", "1024", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, _bench_failure(r)
     j = _records(r, True)
@@ -194,7 +231,7 @@ def test_bench_falls_back_from_staged_to_two_stream_rccl_sets():
     env = dict(os.environ, LBM_BENCH_RANK_MODE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", LBM_BENCH_FAULT="stale_halo@deep:rccl")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--steps", "24", "--warmup", "8", "--nx", "8192", "--ny", "1024", "--transport", "rccl",
+                        "--full", "--gpus", "1", "--steps", "24", "--warmup", "8", "--nx", "8192", "--ny", "1024", "--transport", "rccl",
                         "--no-cpu-baseline", "--no-extra", "--no-cold"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, _bench_failure(r)
     j = _records(r, True)
@@ -211,7 +248,7 @@ def test_bench_one_process_form_rehearsal():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LBM_BENCH_RANK_MODE", "LBM_BENCH_CHILD")}
     env["LBM_BENCH_REHEARSAL"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--launcher", "one-process", "--steps", "24",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--launcher", "one-process", "--steps", "24",
                         "--warmup", "8", "--nx", "2048", "--ny", "1024", "--no-cpu-baseline", "--no-extra"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, _bench_failure(r)
@@ -233,7 +270,7 @@ def test_bench_one_process_per_gpu_path_single_rank():
     env = dict(os.environ, LBM_BENCH_RANK_MODE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--steps", "60", "--warmup", "12", "--nx", "2048", "--ny", "1024",
+                        "--full", "--gpus", "1", "--steps", "60", "--warmup", "12", "--nx", "2048", "--ny", "1024",
                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, _bench_failure(r)
     j = _records(r, True)

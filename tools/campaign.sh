@@ -7,8 +7,8 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 cd $REPO
-python bench.py > $OUT/bench_400.json 2> $OUT/bench_400.err; echo "bench 400: $(cut -c1-120 $OUT/bench_400.json)"
-python bench.py --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench driver: $(cut -c1-120 $OUT/bench_driver.json)"
+python bench.py --full > $OUT/bench_400.json 2> $OUT/bench_400.err; echo "bench 400: $(cut -c1-120 $OUT/bench_400.json)"
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench driver: $(cut -c1-120 $OUT/bench_driver.json)"
 bash tools/prof.sh ${TAG}b $REPO/bench.py --no-cpu-baseline --no-extra --no-cold 2>&1 | tail -6
 bash tools/prof.sh ${TAG}c3 $REPO/bench.py --nx 1024 --ny 1024 --workload tiled --steps 2560 --warmup 256 --no-cpu-baseline --no-extra --no-cold 2>&1 | tail -6   # (d2q9_resident: ten launches of 256 steps)
 cd $REPO
