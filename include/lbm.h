@@ -307,6 +307,66 @@ int lbm_host_free(void *ptr);
 /* Release everything.  Replaces the clRelease* block of finalise (d2q9-bgk.c:729-741). */
 void lbm_destroy(lbm_ctx *ctx);
 
+/*
+ * ---- Ensembles: N independent grids of one size, advanced together ------------------------------------------------
+ *
+ * Grids of a few hundred cells a side (the sizes the reference ships) cannot fill the device and every launch on one of
+ * them is mostly latency; they are run in numbers — a sweep over omega / accel (a Reynolds-number sweep), over obstacle
+ * maps, over initial states.  An ensemble holds N such simulations ("members") on the current device, each with its own
+ * run constants, obstacle map and state, and advances all of them with one launch per (up to) eight timesteps.  The members
+ * never interact, and every member computes, bit for bit, the cells an ordinary context (lbm_create) computes for the same
+ * inputs; its av_vels agree up to summation order.  The reference has no counterpart: one grid, one in-order queue
+ * (d2q9-bgk.c:221-239); each entry point below stands beside the ordinary one of the same name and says which call sites
+ * that one replaces.  Conventions as at the top of this file; one host thread drives an ensemble; arrays carry the member
+ * index first: cells = float[n][9][ny][nx], obstacles = int32[n][ny][nx], fields = float[n][ny][nx].
+ */
+typedef struct lbm_ens lbm_ens; /* opaque */
+
+/*
+ * Create an ensemble of n members on the current HIP device (beside lbm_create: d2q9-bgk.c:600-710, and the obstacle
+ * upload, :205-209).  params[n]: nx, ny and max_iters are the same in all members; reynolds_dim, density, accel, omega,
+ * free_cells_inv are each member's own.  obstacles = int32[n][ny][nx], borrowed for the duration of the call.
+ * Refused with LBM_ERR_ARG before any device is touched: n < 1 or n > 65535, NULL pointers, members that differ in nx, ny or
+ * max_iters, a grid under 3x3, and members of more than 300 x 1024 cells — above that size a grid is no longer bound by
+ * launch latency: use ordinary contexts.  An ensemble that does not fit the device's free memory is refused with LBM_ERR_HIP.
+ * On failure *out is NULL.
+ */
+int lbm_ens_create(lbm_ens **out, const lbm_params *params, const int32_t *obstacles, int n);
+
+/* Host -> device copy of all members' initial states, float[n][9][ny][nx] (beside lbm_upload: d2q9-bgk.c:200-203).
+ * cells == NULL initialises every member's rest state from its own density on the device (d2q9-bgk.c:529-550).  Resets the
+ * step counter.  Synchronises. */
+int lbm_ens_upload(lbm_ens *e, const float *cells);
+
+/* Advance every member by nsteps timesteps (accelerate_flow on row ny-2 + timestep + av_vels reduction each, per member);
+ * asynchronous, repeatable (beside lbm_run: the loop body d2q9-bgk.c:221-238).  A run is cut into the fewest launches of
+ * equal depth, at most 8 steps each (20 = 7 + 7 + 6).  steps_done + nsteps may not exceed max_iters (LBM_ERR_STATE). */
+int lbm_ens_run(lbm_ens *e, int nsteps);
+
+/* lbm_ens_run + device-side timing: *ms = elapsed time of the whole step loop (prologue included) measured with HIP events
+ * on the stream the kernels run on (beside lbm_run_timed).  Synchronises. */
+int lbm_ens_run_timed(lbm_ens *e, int nsteps, double *ms);
+
+/* Wait for all queued work (beside lbm_sync: clFinish, d2q9-bgk.c:239). */
+int lbm_ens_sync(lbm_ens *e);
+
+/* Device -> host (beside lbm_download: d2q9-bgk.c:251-260).  cells_out = float[n][9][ny][nx], the CURRENT state whatever the
+ * step parity; av_vels_out = float[n][steps_done], member m's record times its own free_cells_inv.  Either may be NULL.
+ * Synchronises. */
+int lbm_ens_download(lbm_ens *e, float *cells_out, float *av_vels_out);
+
+/* Output stage per member (beside lbm_final_state / lbm_reynolds: d2q9-bgk.c:787-832, 396-442, 747-752): each field is
+ * float[n][ny][nx] and may be NULL; reynolds_out = float[n].  Synchronise. */
+int lbm_ens_final_state(lbm_ens *e, float *u_x, float *u_y, float *u, float *pressure);
+int lbm_ens_reynolds(lbm_ens *e, float *reynolds_out);
+
+/* Steps applied since the last lbm_ens_upload / number of members; -1 for a NULL ensemble. */
+int lbm_ens_steps_done(const lbm_ens *e);
+int lbm_ens_members(const lbm_ens *e);
+
+/* Release everything (beside lbm_destroy: d2q9-bgk.c:729-741). */
+void lbm_ens_destroy(lbm_ens *e);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

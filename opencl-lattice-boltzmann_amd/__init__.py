@@ -26,6 +26,8 @@ ABI_SYMBOLS = [
     "lbm_reynolds", "lbm_set_option", "lbm_get_option", "lbm_copy_bandwidth", "lbm_valu_rate", "lbm_destroy",
     "lbm_last_error", "lbm_version", "lbm_set_default", "lbm_peer_info_size", "lbm_peer_info", "lbm_connect_peers",
     "lbm_run_profiled", "lbm_upload_obstacles", "lbm_disconnect_peers", "lbm_host_alloc", "lbm_host_free",
+    "lbm_ens_create", "lbm_ens_upload", "lbm_ens_run", "lbm_ens_run_timed", "lbm_ens_sync", "lbm_ens_download",
+    "lbm_ens_final_state", "lbm_ens_reynolds", "lbm_ens_steps_done", "lbm_ens_members", "lbm_ens_destroy",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -89,6 +91,18 @@ def load_library():
     L.lbm_host_free.argtypes = [vp]
     L.lbm_destroy.argtypes = [vp]
     L.lbm_destroy.restype = None
+    L.lbm_ens_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(Params), vp, ci]
+    L.lbm_ens_upload.argtypes = [vp, vp]
+    L.lbm_ens_run.argtypes = [vp, ci]
+    L.lbm_ens_run_timed.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_double)]
+    L.lbm_ens_sync.argtypes = [vp]
+    L.lbm_ens_download.argtypes = [vp, vp, vp]
+    L.lbm_ens_final_state.argtypes = [vp, vp, vp, vp, vp]
+    L.lbm_ens_reynolds.argtypes = [vp, vp]
+    L.lbm_ens_steps_done.argtypes = [vp]
+    L.lbm_ens_members.argtypes = [vp]
+    L.lbm_ens_destroy.argtypes = [vp]
+    L.lbm_ens_destroy.restype = None
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -350,6 +364,106 @@ class LBM:
         if self.ctx:
             self.lib.lbm_destroy(self.ctx)
             self.ctx = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sweep_params(base, omega=None, accel=None):
+    """The members of a parameter sweep: copies of `base` with omega and / or accel replaced from lists of equal length."""
+    count = len(omega if omega is not None else accel)
+    members = []
+    for i in range(count):
+        p = Params.from_buffer_copy(base)
+        if omega is not None:
+            p.omega = omega[i]
+        if accel is not None:
+            p.accel = accel[i]
+        members.append(p)
+    return members
+
+
+class Ensemble:
+    """N independent simulations of one grid size, advanced together (lbm_ens): one launch per (up to) eight timesteps for
+    all members.  Mirrors LBM with the member index as the first axis of every array.  `params`: a list of Params that share
+    nx, ny and max_iters; `obstacles`: int32[n, ny, nx], or one [ny, nx] map for all members."""
+
+    def __init__(self, params, obstacles):
+        self.lib = load_library()
+        self.params = list(params)
+        self.n = len(self.params)
+        if self.n < 1:
+            raise LBMError("an ensemble needs at least one member")
+        self.nx, self.ny = self.params[0].nx, self.params[0].ny
+        obst = np.asarray(obstacles, dtype=np.int32)
+        if obst.ndim == 2:
+            obst = np.broadcast_to(obst, (self.n,) + obst.shape)
+        obst = np.ascontiguousarray(obst)
+        assert obst.shape == (self.n, self.ny, self.nx)
+        self.obstacles = obst
+        self._params = (Params * self.n)(*self.params)
+        self.ens = ctypes.c_void_p()
+        _check(self.lib.lbm_ens_create(ctypes.byref(self.ens), self._params, obst.ctypes.data, self.n), "lbm_ens_create")
+
+    def upload(self, cells=None):
+        """cells float32[n, 9, ny, nx]; None = every member's rest state from its own density, on the device"""
+        if cells is None:
+            _check(self.lib.lbm_ens_upload(self.ens, None), "lbm_ens_upload")
+        else:
+            c = np.ascontiguousarray(cells, dtype=np.float32)
+            assert c.shape == (self.n, 9, self.ny, self.nx)
+            _check(self.lib.lbm_ens_upload(self.ens, c.ctypes.data), "lbm_ens_upload")
+
+    def run(self, nsteps):
+        _check(self.lib.lbm_ens_run(self.ens, nsteps), "lbm_ens_run")
+
+    def run_timed(self, nsteps):
+        """Runs nsteps and returns the HIP-event time of the step loop in milliseconds."""
+        ms = ctypes.c_double()
+        _check(self.lib.lbm_ens_run_timed(self.ens, nsteps, ctypes.byref(ms)), "lbm_ens_run_timed")
+        return ms.value
+
+    def sync(self):
+        _check(self.lib.lbm_ens_sync(self.ens), "lbm_ens_sync")
+
+    @property
+    def steps_done(self):
+        return self.lib.lbm_ens_steps_done(self.ens)
+
+    def download(self, cells=True, av_vels=True):
+        """Returns (cells float32[n,9,ny,nx] or None, av_vels float32[n,steps_done] or None)."""
+        steps = self.steps_done
+        c = np.zeros((self.n, 9, self.ny, self.nx), dtype=np.float32) if cells else None
+        a = np.zeros((self.n, steps), dtype=np.float32) if av_vels else None
+        _check(self.lib.lbm_ens_download(self.ens, c.ctypes.data if cells else None,
+                                         a.ctypes.data if av_vels and steps else None), "lbm_ens_download")
+        return c, a
+
+    def final_state(self):
+        """(u_x, u_y, u, pressure), each float32[n,ny,nx] — per member the columns of final_state.dat."""
+        outs = [np.zeros((self.n, self.ny, self.nx), dtype=np.float32) for _ in range(4)]
+        _check(self.lib.lbm_ens_final_state(self.ens, *[o.ctypes.data for o in outs]), "lbm_ens_final_state")
+        return outs
+
+    def reynolds(self):
+        """float32[n]: every member's Reynolds number of the current state"""
+        r = np.zeros(self.n, dtype=np.float32)
+        _check(self.lib.lbm_ens_reynolds(self.ens, r.ctypes.data), "lbm_ens_reynolds")
+        return r
+
+    def close(self):
+        if self.ens:
+            self.lib.lbm_ens_destroy(self.ens)
+            self.ens = ctypes.c_void_p()
 
     def __enter__(self):
         return self

@@ -1,0 +1,402 @@
+// Third translation unit of liblbm_hip.so: the host side of the ensemble entry points (include/lbm.h: lbm_ens_*).
+//
+// An ensemble is N independent grids of one size on one device, each with its own run constants, obstacle map and
+// state.  All members live in one pair of arrays (member m at m * member_stride in the layout of an ordinary context:
+// row-interleaved planes padded to 256-B lines), one mask array and one table of per-member constants; every entry
+// point is one launch (or one transfer) for all members.  The step loop is the KIND_MULTI case of lbm_hip.cpp reduced to
+// one slab: a prologue accelerate_flow, launches of up to 8 steps of d2q9_ensemble with the next step's acceleration
+// fused into all but the last, a ring of buffered per-step partial sums flushed by the batched second reduction stage.
+// The reference has no counterpart: one grid, one in-order queue (d2q9-bgk.c:221-239).
+#include "../../include/lbm.h"
+#include "ensemble_kernels.h"
+#include "lbm_error.h"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+using namespace lbm;
+
+namespace {
+
+#define HIP_TRY(expr)                                                                               \
+  do {                                                                                              \
+    hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess)                                                                           \
+      return lbm_fail(LBM_ERR_HIP, "HIP error during '%s' (%s:%d): %s", #expr, __FILE__, __LINE__, \
+                      hipGetErrorString(e_));                                                       \
+  } while (0)
+
+constexpr int kEnsRingMax = 256;           // most steps of per-tile partial sums buffered between reductions
+constexpr long kEnsMaxCells = 300L * 1024; // the library's bound for "launch-bound" (multistep_effective, lbm_hip.cpp)
+constexpr int kEnsMaxMembers = 65535;      // member index = blockIdx.y
+
+inline long div_up(long a, long b) { return (a + b - 1) / b; }
+
+}  // namespace
+
+struct lbm_ens {
+  int n = 0;
+  int nx = 0, ny = 0, max_iters = 0;
+  std::vector<lbm_params> p;
+  int dev = 0;
+  int cus = 256;
+  hipStream_t st = nullptr;
+  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+  size_t plane_stride = 0, member_stride = 0;  // floats
+  float *cells[2] = {nullptr, nullptr};
+  uint8_t *mask = nullptr;       // [n][ny][nx]
+  EnsMember *members = nullptr;  // [n]
+  float *partials = nullptr;     // [ring][n][tiles]
+  double *av_sum = nullptr;      // [n][max(1, max_iters)]
+  float *fin_partials = nullptr; // [n][fin_blocks]
+  int fin_blocks = 1;
+  int tx = 16, ty = 16, tiles_x = 1, tiles = 1;
+  int ring = 8, ring_fill = 0;
+  int cur = 0, steps_done = 0;
+  bool failed = false;
+};
+
+namespace {
+
+void free_ens(lbm_ens *e) {
+  if (e->st) (void)hipStreamSynchronize(e->st);
+  for (float *c : e->cells)
+    if (c) (void)hipFree(c);
+  if (e->mask) (void)hipFree(e->mask);
+  if (e->members) (void)hipFree(e->members);
+  if (e->partials) (void)hipFree(e->partials);
+  if (e->av_sum) (void)hipFree(e->av_sum);
+  if (e->fin_partials) (void)hipFree(e->fin_partials);
+  if (e->ev_t0) (void)hipEventDestroy(e->ev_t0);
+  if (e->ev_t1) (void)hipEventDestroy(e->ev_t1);
+  if (e->st) (void)hipStreamDestroy(e->st);
+  delete e;
+}
+
+int build_ens(lbm_ens *e, const int32_t *obstacles) {
+  const int n = e->n, nx = e->nx, ny = e->ny;
+  const size_t cells_per = (size_t)nx * ny;
+  HIP_TRY(hipGetDevice(&e->dev));
+  {
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->dev));
+    if (cus > 0) e->cus = cus;
+  }
+  // Tile shape.  d2q9_multi's cost model (lbm_hip.cpp, slab_geometry: ceil(tiles / CUs) x cell updates per tile) holds while
+  // every tile has a CU to itself: there the smallest tile wins (one grid, us/step for 32x16 / 16x16 / 16x8: 128x128 1.85 /
+  // 1.55 / 1.38).  An ensemble soon has several rounds of tiles per CU, and then the workgroups that fit a CU together
+  // decide: two of 16x16 (75 KB of LDS each, 52 VGPRs) or of 16x8 overlap one's loads and stores with the other's sub-steps,
+  // one of 32x16 (113 KB) cannot.  Measured (tools/ensemble_ab.py, us/step 32x16 / 16x16 / 16x8): 64 x 128x128 15.05 / 13.26 /
+  // 21.50, 16 x 256x256 13.45 / 13.07 / 21.33 - so 16x8 while its tiles fit one per CU, 16x16 from there on, and no 32x16 form.
+  {
+    const long tiles_16x8 = (long)n * div_up(nx, 16) * div_up(ny, 8);
+    e->tx = 16;
+    e->ty = tiles_16x8 <= e->cus ? 8 : 16;
+  }
+  e->tiles_x = (int)div_up(nx, e->tx);
+  e->tiles = e->tiles_x * (int)div_up(ny, e->ty);
+  e->plane_stride = ((size_t)(nx + 63) / 64) * 64;
+  e->member_stride = 9 * e->plane_stride * ny;
+  e->fin_blocks = (int)std::max(1L, std::min(div_up((long)cells_per, kBlock), 2048L));
+  // ring of per-step partial sums: at most 16 MiB, at least 8 steps (one launch)
+  const size_t per_step = (size_t)n * e->tiles;
+  e->ring = (int)std::max<size_t>(kMultiMaxT, std::min<size_t>(kEnsRingMax, ((size_t)4 << 20) / per_step));
+
+  // what the ensemble needs against what the device has free: refuse here rather than fail half-way through
+  const size_t cells_bytes = ((size_t)n * e->member_stride + 64) * sizeof(float);
+  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + (size_t)n * sizeof(EnsMember) +
+                      (size_t)e->ring * per_step * sizeof(float) + (size_t)n * std::max(1, e->max_iters) * sizeof(double) +
+                      (size_t)n * e->fin_blocks * sizeof(float);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (need > free_b)
+    return lbm_fail(LBM_ERR_HIP, "an ensemble of %d members of %dx%d with max_iters=%d needs %.1f MiB of device memory, %.1f MiB are free",
+                    n, nx, ny, e->max_iters, (double)need / 1048576.0, (double)free_b / 1048576.0);
+
+  HIP_TRY(hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreate(&e->ev_t0));
+  HIP_TRY(hipEventCreate(&e->ev_t1));
+  for (int i = 0; i < 2; i++) {
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->cells[i]), cells_bytes));
+    HIP_TRY(hipMemset(e->cells[i], 0, cells_bytes));
+  }
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->mask), (size_t)n * cells_per + 64));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), (size_t)n * sizeof(EnsMember)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->partials), (size_t)e->ring * per_step * sizeof(float)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->av_sum), (size_t)n * std::max(1, e->max_iters) * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->fin_partials), (size_t)n * e->fin_blocks * sizeof(float)));
+  {
+    // the members' byte masks from the caller's int32[n][ny][nx] (d2q9-bgk.c:205-209: the obstacle transfer)
+    std::vector<uint8_t> m((size_t)n * cells_per);
+    for (size_t i = 0; i < m.size(); i++) m[i] = obstacles[i] != 0;
+    HIP_TRY(hipMemcpy(e->mask, m.data(), m.size(), hipMemcpyHostToDevice));
+  }
+  {
+    std::vector<EnsMember> t(n);
+    for (int i = 0; i < n; i++) {
+      const lbm_params &p = e->p[i];
+      t[i].omega = p.omega;
+      t[i].aw1 = p.density * p.accel / 9.0f;   // kernels.cl:14-15
+      t[i].aw2 = p.density * p.accel / 36.0f;
+      t[i].density = p.density;
+      t[i].w0 = p.density * 4.0f / 9.0f;       // d2q9-bgk.c:529-531
+      t[i].w1 = p.density / 9.0f;
+      t[i].w2 = p.density / 36.0f;
+      t[i].pad = 0.0f;
+    }
+    HIP_TRY(hipMemcpy(e->members, t.data(), t.size() * sizeof(EnsMember), hipMemcpyHostToDevice));
+  }
+  return LBM_OK;
+}
+
+void launch_ensemble(const lbm_ens *e, const EnsArgs &a) {
+  const dim3 grid(e->tiles, e->n), block(kMultiThreads);
+  if (e->ty == 16) hipLaunchKernelGGL((d2q9_ensemble<16, 16>), grid, block, 0, e->st, a);
+  else hipLaunchKernelGGL((d2q9_ensemble<16, 8>), grid, block, 0, e->st, a);
+}
+
+int run_ens_impl(lbm_ens *e, int nsteps, bool timed, double *ms, bool *launched) {
+  if (nsteps < 0) return lbm_fail(LBM_ERR_ARG, "nsteps must be >= 0");
+  if (e->failed) return lbm_fail(LBM_ERR_STATE, "an earlier run failed after its launches had begun; destroy the ensemble");
+  if (e->steps_done + nsteps > e->max_iters)
+    return lbm_fail(LBM_ERR_STATE, "av_vels record holds max_iters=%d steps; %d done, %d more requested", e->max_iters,
+                    e->steps_done, nsteps);
+  if (timed && ms) *ms = 0.0;
+  if (nsteps == 0) return LBM_OK;
+  HIP_TRY(hipSetDevice(e->dev));
+  *launched = true;
+  if (timed) HIP_TRY(hipEventRecord(e->ev_t0, e->st));
+  // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
+  // into the previous launch's write of row ny-2
+  hipLaunchKernelGGL(ens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->st, e->cells[e->cur], e->plane_stride,
+                     e->member_stride, e->mask, e->members, e->nx, e->ny);
+  HIP_TRY(hipGetLastError());
+
+  int batch_first = e->steps_done;
+  // second reduction stage over the buffered steps (kernels.cl:234-290 counterpart)
+  auto flush = [&]() -> int {
+    if (e->ring_fill == 0) return LBM_OK;
+    hipLaunchKernelGGL(ens_reduce_partials, dim3(e->n, e->ring_fill), dim3(kBlock), 0, e->st, e->partials, e->tiles, e->av_sum,
+                       (unsigned long long)std::max(1, e->max_iters), batch_first);
+    HIP_TRY(hipGetLastError());
+    batch_first += e->ring_fill;
+    e->ring_fill = 0;
+    return LBM_OK;
+  };
+  int i = 0;
+  while (i < nsteps) {
+    // the remaining steps in as few launches as possible, of equal depth (20 steps = 7 + 7 + 6)
+    const int rem = nsteps - i;
+    const int adv = (int)div_up(rem, div_up(rem, kMultiMaxT));
+    if (e->ring_fill + adv > e->ring)
+      if (int rc = flush()) return rc;
+    EnsArgs a{};
+    a.src = e->cells[e->cur];
+    a.dst = e->cells[e->cur ^ 1];
+    a.mask = e->mask;
+    a.members = e->members;
+    a.partials = e->partials + (size_t)e->ring_fill * e->n * e->tiles;
+    a.plane_stride = e->plane_stride;
+    a.member_stride = e->member_stride;
+    a.nx = e->nx;
+    a.ny = e->ny;
+    a.tiles_x = e->tiles_x;
+    a.T = adv;
+    a.accel_next = (i + adv < nsteps) ? 1 : 0;
+    launch_ensemble(e, a);
+    HIP_TRY(hipGetLastError());
+    e->cur ^= 1;
+    e->ring_fill += adv;
+    i += adv;
+  }
+  if (int rc = flush()) return rc;
+  e->steps_done += nsteps;
+  if (timed) {
+    HIP_TRY(hipEventRecord(e->ev_t1, e->st));
+    HIP_TRY(hipEventSynchronize(e->ev_t1));
+    float t = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&t, e->ev_t0, e->ev_t1));
+    if (ms) *ms = t;
+  }
+  return LBM_OK;
+}
+
+// A failure after launches have begun: let what was enqueued finish and refuse further work (as run_steps, lbm_hip.cpp)
+int run_ens(lbm_ens *e, int nsteps, bool timed, double *ms) {
+  bool launched = false;
+  const int rc = run_ens_impl(e, nsteps, timed, ms, &launched);
+  if (rc != LBM_OK && launched) {
+    const std::string keep = lbm_last_error();
+    (void)hipStreamSynchronize(e->st);
+    (void)hipGetLastError();
+    e->failed = true;
+    lbm_fail(rc, "%s", keep.c_str());
+  }
+  return rc;
+}
+
+int sync_ens(lbm_ens *e) {
+  HIP_TRY(hipSetDevice(e->dev));
+  HIP_TRY(hipStreamSynchronize(e->st));
+  return LBM_OK;
+}
+
+}  // namespace
+
+// =================================================================================================
+extern "C" {
+
+int lbm_ens_create(lbm_ens **out, const lbm_params *params, const int32_t *obstacles, int n) {
+  // every argument error is reported before a device is touched
+  if (!out) return lbm_fail(LBM_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  if (!params) return lbm_fail(LBM_ERR_ARG, "params is NULL");
+  if (!obstacles) return lbm_fail(LBM_ERR_ARG, "obstacles is NULL");
+  if (n < 1 || n > kEnsMaxMembers) return lbm_fail(LBM_ERR_ARG, "an ensemble has 1 to %d members (got %d)", kEnsMaxMembers, n);
+  const lbm_params &p0 = params[0];
+  if (p0.nx < 3 || p0.ny < 3) return lbm_fail(LBM_ERR_ARG, "grid must be at least 3x3 (got %dx%d)", p0.nx, p0.ny);
+  if (p0.max_iters < 0) return lbm_fail(LBM_ERR_ARG, "max_iters must be >= 0");
+  for (int i = 1; i < n; i++)
+    if (params[i].nx != p0.nx || params[i].ny != p0.ny || params[i].max_iters != p0.max_iters)
+      return lbm_fail(LBM_ERR_ARG, "member %d is %dx%d with max_iters=%d, member 0 %dx%d with max_iters=%d: the members of an ensemble "
+                      "share nx, ny and max_iters", i, params[i].nx, params[i].ny, params[i].max_iters, p0.nx, p0.ny, p0.max_iters);
+  if ((long)p0.nx * p0.ny > kEnsMaxCells)
+    return lbm_fail(LBM_ERR_ARG, "a member of %dx%d cells is not launch-bound (the ensemble path takes members of at most %ld cells): "
+                    "use ordinary contexts (lbm_create)", p0.nx, p0.ny, kEnsMaxCells);
+  int ndev_visible = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev_visible));
+  if (ndev_visible < 1) return lbm_fail(LBM_ERR_HIP, "no HIP device visible");
+
+  lbm_ens *e = new lbm_ens();
+  e->n = n;
+  e->nx = p0.nx;
+  e->ny = p0.ny;
+  e->max_iters = p0.max_iters;
+  e->p.assign(params, params + n);
+  if (int rc = build_ens(e, obstacles)) {
+    const std::string keep = lbm_last_error();
+    free_ens(e);
+    (void)hipGetLastError();
+    return lbm_fail(rc, "%s", keep.c_str());
+  }
+  *out = e;
+  return LBM_OK;
+}
+
+int lbm_ens_upload(lbm_ens *e, const float *cells) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (int rc = sync_ens(e)) return rc;
+  const size_t per = (size_t)e->nx * e->ny;
+  const dim3 grid((unsigned)std::min(div_up((long)per, 256), 1024L), e->n);
+  if (cells) {
+    // one transfer of the caller's float[n][9][ny][nx] into the second grid array (9 nx ny <= member_stride), then one
+    // launch that scatters every member's planes into the first (d2q9-bgk.c:200-203 for all members)
+    HIP_TRY(hipMemcpyAsync(e->cells[1], cells, (size_t)e->n * 9 * per * sizeof(float), hipMemcpyHostToDevice, e->st));
+    hipLaunchKernelGGL(ens_pack_planes<true>, grid, dim3(256), 0, e->st, e->cells[0], e->plane_stride, e->member_stride, e->nx, per,
+                       e->cells[1]);
+  } else {
+    hipLaunchKernelGGL(ens_init_cells, grid, dim3(256), 0, e->st, e->cells[0], e->plane_stride, e->member_stride, e->members, e->nx,
+                       per);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->st));
+  e->cur = 0;
+  e->steps_done = 0;
+  e->ring_fill = 0;
+  return LBM_OK;
+}
+
+int lbm_ens_run(lbm_ens *e, int nsteps) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  return run_ens(e, nsteps, false, nullptr);
+}
+
+int lbm_ens_run_timed(lbm_ens *e, int nsteps, double *ms) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  return run_ens(e, nsteps, true, ms);
+}
+
+int lbm_ens_sync(lbm_ens *e) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  return sync_ens(e);
+}
+
+int lbm_ens_steps_done(const lbm_ens *e) { return e ? e->steps_done : -1; }
+int lbm_ens_members(const lbm_ens *e) { return e ? e->n : -1; }
+
+int lbm_ens_download(lbm_ens *e, float *cells_out, float *av_vels_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (int rc = sync_ens(e)) return rc;
+  const size_t per = (size_t)e->nx * e->ny;
+  if (cells_out) {
+    // the grid array that is not current is scratch between runs: repack every member into the caller's layout there,
+    // then one contiguous transfer
+    float *stage = e->cells[e->cur ^ 1];
+    hipLaunchKernelGGL(ens_pack_planes<false>, dim3((unsigned)std::min(div_up((long)per, 256), 1024L), e->n), dim3(256), 0, e->st,
+                       e->cells[e->cur], e->plane_stride, e->member_stride, e->nx, per, stage);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cells_out, stage, (size_t)e->n * 9 * per * sizeof(float), hipMemcpyDeviceToHost, e->st));
+    HIP_TRY(hipStreamSynchronize(e->st));
+  }
+  if (av_vels_out && e->steps_done > 0) {
+    const int T = e->steps_done;
+    std::vector<double> sums((size_t)e->n * T);
+    HIP_TRY(hipMemcpy2D(sums.data(), (size_t)T * sizeof(double), e->av_sum, (size_t)std::max(1, e->max_iters) * sizeof(double),
+                        (size_t)T * sizeof(double), e->n, hipMemcpyDeviceToHost));
+    // kernels.cl:202: sum * FREE_CELLS_INV, the member's own
+    for (int m = 0; m < e->n; m++)
+      for (int t = 0; t < T; t++)
+        av_vels_out[(size_t)m * T + t] = (float)(sums[(size_t)m * T + t] * (double)e->p[m].free_cells_inv);
+  }
+  return LBM_OK;
+}
+
+int lbm_ens_final_state(lbm_ens *e, float *u_x, float *u_y, float *u, float *pressure) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (int rc = sync_ens(e)) return rc;
+  const size_t per = (size_t)e->nx * e->ny, all = per * e->n;
+  float *outs[4] = {u_x, u_y, u, pressure};
+  // the four columns of all members go to the grid array that is not current (4 n nx ny floats of its 9 n nx ny)
+  float *d[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 4; i++)
+    if (outs[i]) d[i] = e->cells[e->cur ^ 1] + (size_t)i * all;
+  hipLaunchKernelGGL(ens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->st, e->cells[e->cur], e->plane_stride,
+                     e->member_stride, e->nx, e->mask, per, e->members, d[0], d[1], d[2], d[3], e->fin_partials);
+  HIP_TRY(hipGetLastError());
+  for (int i = 0; i < 4; i++)
+    if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], d[i], all * sizeof(float), hipMemcpyDeviceToHost, e->st));
+  HIP_TRY(hipStreamSynchronize(e->st));
+  return LBM_OK;
+}
+
+int lbm_ens_reynolds(lbm_ens *e, float *reynolds_out) {
+  if (!e || !reynolds_out) return lbm_fail(LBM_ERR_ARG, "NULL argument");
+  if (int rc = sync_ens(e)) return rc;
+  const size_t per = (size_t)e->nx * e->ny;
+  hipLaunchKernelGGL(ens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->st, e->cells[e->cur], e->plane_stride,
+                     e->member_stride, e->nx, e->mask, per, e->members, (float *)nullptr, (float *)nullptr, (float *)nullptr,
+                     (float *)nullptr, e->fin_partials);
+  HIP_TRY(hipGetLastError());
+  std::vector<float> part((size_t)e->n * e->fin_blocks);
+  HIP_TRY(hipMemcpyAsync(part.data(), e->fin_partials, part.size() * sizeof(float), hipMemcpyDeviceToHost, e->st));
+  HIP_TRY(hipStreamSynchronize(e->st));
+  for (int m = 0; m < e->n; m++) {
+    double tot = 0.0;
+    for (int b = 0; b < e->fin_blocks; b++) tot += part[(size_t)m * e->fin_blocks + b];
+    // d2q9-bgk.c:747-752
+    const lbm_params &p = e->p[m];
+    const float viscosity = 1.0f / 6.0f * (2.0f / p.omega - 1.0f);
+    const float av = (float)(tot * (double)p.free_cells_inv);
+    reynolds_out[m] = av * p.reynolds_dim / viscosity;
+  }
+  return LBM_OK;
+}
+
+void lbm_ens_destroy(lbm_ens *e) {
+  if (!e) return;
+  (void)hipSetDevice(e->dev);
+  free_ens(e);
+}
+
+}  // extern "C"

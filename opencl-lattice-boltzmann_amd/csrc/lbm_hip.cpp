@@ -20,6 +20,7 @@
 #include "d2q9_kernels.h"
 #include "deep_instances.h"
 #include "halo_exchange.h"
+#include "lbm_error.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -2374,6 +2375,17 @@ int connect_local_ring(lbm_ctx *c) {
 }
 
 }  // namespace
+
+// lbm_error.h: the same channel for the library's other translation units (lbm_ensemble.cpp)
+int lbm_fail(int code, const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
 
 // =================================================================================================
 extern "C" {
