@@ -367,6 +367,86 @@ int lbm_ens_members(const lbm_ens *e);
 /* Release everything (beside lbm_destroy: d2q9-bgk.c:729-741). */
 void lbm_ens_destroy(lbm_ens *e);
 
+/*
+ * ---- Double precision: one grid in fp64 ------------------------------------------------------------------------------
+ *
+ * The reference's golden files (check/SIZE.av_vels.dat, check/SIZE.final_state.dat) and the Reynolds numbers of its README come
+ * from its fp64 ancestor, which held every distribution in double and parsed density, accel and omega as double.  An
+ * ordinary context computes in fp32 and lands a few tenths of a percent away from those files over a full-length run; a
+ * double-precision context computes in fp64 and reproduces them to print precision.  It is a family of its own beside
+ * lbm_create: one grid on the current device, no row slabs, ranks or halo transports.  Each entry point stands beside the
+ * ordinary one of the same name and says which call sites that one replaces.  Conventions as at the top of this file, with
+ * double in place of float: cells = double[9][ny][nx], fields = double[ny][nx], obstacles = int32[ny][nx].
+ */
+typedef struct lbm_dparams {
+  int nx;                /* cells in x */
+  int ny;                /* cells in y */
+  int max_iters;         /* capacity of the av_vels record (steps that can be run) */
+  int reynolds_dim;      /* dimension for the Reynolds number */
+  double density;        /* density per link: the fp64 literal of the parameter file, not a widened float */
+  double accel;          /* density redistribution */
+  double omega;          /* relaxation parameter */
+  double free_cells_inv; /* 1.0 / number of non-blocked cells, in double (d2q9-bgk.c:591) */
+} lbm_dparams;
+
+typedef struct lbm_dp lbm_dp; /* opaque */
+
+/*
+ * Create a double-precision context on the current HIP device (beside lbm_create: d2q9-bgk.c:600-710, and the obstacle
+ * upload, :205-209).  Any nx, ny >= 3 that fits device memory (8192 x 8192: about 9.7 GB for the two grids).  obstacles is
+ * borrowed for the duration of the call.  Refused with LBM_ERR_ARG before any device is touched: NULL pointers, nx or ny
+ * under 3, max_iters under 1, omega or density not finite and positive, accel not finite.  A grid that does not fit the
+ * device's free memory is refused with LBM_ERR_HIP.  On failure *out is NULL.
+ */
+int lbm_dp_create(lbm_dp **out, const lbm_dparams *params, const int32_t *obstacles);
+
+/* Host -> device copy of the initial state, double[9][ny][nx] (beside lbm_upload: d2q9-bgk.c:200-203).  cells == NULL
+ * initialises the rest state from params.density on the device (d2q9-bgk.c:529-550).  Resets the step counter.
+ * Synchronises. */
+int lbm_dp_upload(lbm_dp *d, const double *cells);
+
+/* Host -> device copy of the obstacle map, int32[ny][nx] (beside lbm_upload_obstacles: d2q9-bgk.c:205-209); same nx, ny;
+ * free_cells_inv stays the caller's to keep consistent.  Synchronises. */
+int lbm_dp_upload_obstacles(lbm_dp *d, const int32_t *obstacles);
+
+/* Advance nsteps timesteps (accelerate_flow on row ny-2 + timestep + av_vels reduction each); asynchronous, repeatable
+ * (beside lbm_run: the loop body d2q9-bgk.c:221-238).  steps_done + nsteps may not exceed max_iters (LBM_ERR_STATE). */
+int lbm_dp_run(lbm_dp *d, int nsteps);
+
+/* lbm_dp_run + device-side timing: *ms = elapsed time of the step loop (prologue and reductions included) measured with
+ * HIP events on the stream the kernels run on (beside lbm_run_timed).  Synchronises. */
+int lbm_dp_run_timed(lbm_dp *d, int nsteps, double *ms);
+
+/* Wait for all queued work (beside lbm_sync: clFinish, d2q9-bgk.c:239). */
+int lbm_dp_sync(lbm_dp *d);
+
+/* Device -> host (beside lbm_download: d2q9-bgk.c:251-260).  cells_out = double[9][ny][nx], the CURRENT state whatever the
+ * step parity; av_vels_out = double[steps_done], each step's sum of |u| over the fluid cells times free_cells_inv, in
+ * double.  Either may be NULL.  Synchronises. */
+int lbm_dp_download(lbm_dp *d, double *cells_out, double *av_vels_out);
+
+/* Output stage on the device in double (beside lbm_final_state / lbm_reynolds: d2q9-bgk.c:787-832, 396-442, 747-752):
+ * u_x, u_y, u, pressure, each double[ny][nx] and may be NULL, obstacle cells give 0, 0, 0, density/3; the Reynolds number
+ * av_velocity * reynolds_dim / (1/6 (2/omega - 1)).  Synchronise. */
+int lbm_dp_final_state(lbm_dp *d, double *u_x, double *u_y, double *u, double *pressure);
+int lbm_dp_reynolds(lbm_dp *d, double *reynolds_out);
+
+/* Steps applied since the last lbm_dp_upload; -1 for a NULL context. */
+int lbm_dp_steps_done(const lbm_dp *d);
+
+/*
+ * One option (beside lbm_set_option / lbm_get_option):
+ *   "multistep"   -1 = auto (the LDS-tile form up to 300K cells, else one step per launch), 0 = one step per launch
+ *                 (d2q9_dp_step), 1..8 = that many steps per launch on LDS-resident tiles (d2q9_dp_multi); a run is cut
+ *                 into the fewest launches of equal depth.  Both forms give the same cells, av_vels and fields bit for bit.
+ * lbm_dp_get_option("multistep") reads back the steps per launch in force (0 = one step per launch).
+ */
+int lbm_dp_set_option(lbm_dp *d, const char *key, long value);
+int lbm_dp_get_option(const lbm_dp *d, const char *key, long *value);
+
+/* Release everything (beside lbm_destroy: d2q9-bgk.c:729-741).  NULL is a no-op. */
+void lbm_dp_destroy(lbm_dp *d);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

@@ -28,6 +28,9 @@ ABI_SYMBOLS = [
     "lbm_run_profiled", "lbm_upload_obstacles", "lbm_disconnect_peers", "lbm_host_alloc", "lbm_host_free",
     "lbm_ens_create", "lbm_ens_upload", "lbm_ens_run", "lbm_ens_run_timed", "lbm_ens_sync", "lbm_ens_download",
     "lbm_ens_final_state", "lbm_ens_reynolds", "lbm_ens_steps_done", "lbm_ens_members", "lbm_ens_destroy",
+    "lbm_dp_create", "lbm_dp_upload", "lbm_dp_upload_obstacles", "lbm_dp_run", "lbm_dp_run_timed", "lbm_dp_sync",
+    "lbm_dp_download", "lbm_dp_final_state", "lbm_dp_reynolds", "lbm_dp_steps_done", "lbm_dp_set_option",
+    "lbm_dp_get_option", "lbm_dp_destroy",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -42,6 +45,13 @@ class Params(ctypes.Structure):
     _fields_ = [("nx", ctypes.c_int), ("ny", ctypes.c_int), ("max_iters", ctypes.c_int),
                 ("reynolds_dim", ctypes.c_int), ("density", ctypes.c_float), ("accel", ctypes.c_float),
                 ("omega", ctypes.c_float), ("free_cells_inv", ctypes.c_float)]
+
+
+class DParams(ctypes.Structure):
+    """lbm_dparams: the fields of Params with the four reals in double, as the reference's fp64 ancestor held them."""
+    _fields_ = [("nx", ctypes.c_int), ("ny", ctypes.c_int), ("max_iters", ctypes.c_int),
+                ("reynolds_dim", ctypes.c_int), ("density", ctypes.c_double), ("accel", ctypes.c_double),
+                ("omega", ctypes.c_double), ("free_cells_inv", ctypes.c_double)]
 
 
 def build_library(verbose=False):
@@ -103,6 +113,20 @@ def load_library():
     L.lbm_ens_members.argtypes = [vp]
     L.lbm_ens_destroy.argtypes = [vp]
     L.lbm_ens_destroy.restype = None
+    L.lbm_dp_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(DParams), vp]
+    L.lbm_dp_upload.argtypes = [vp, vp]
+    L.lbm_dp_upload_obstacles.argtypes = [vp, vp]
+    L.lbm_dp_run.argtypes = [vp, ci]
+    L.lbm_dp_run_timed.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_double)]
+    L.lbm_dp_sync.argtypes = [vp]
+    L.lbm_dp_download.argtypes = [vp, vp, vp]
+    L.lbm_dp_final_state.argtypes = [vp, vp, vp, vp, vp]
+    L.lbm_dp_reynolds.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+    L.lbm_dp_steps_done.argtypes = [vp]
+    L.lbm_dp_set_option.argtypes = [vp, cp, ctypes.c_long]
+    L.lbm_dp_get_option.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_long)]
+    L.lbm_dp_destroy.argtypes = [vp]
+    L.lbm_dp_destroy.restype = None
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -124,8 +148,9 @@ def make_params(nx, ny, max_iters, reynolds_dim=10, density=0.1, accel=0.005, om
     return p
 
 
-def read_inputs(paramfile, obstaclefile):
-    """Parse the reference's two input files (d2q9-bgk.c:466-492, 553-591) into (Params, mask)."""
+def _parse_inputs(paramfile, obstaclefile):
+    """the reference's two input files (d2q9-bgk.c:466-492, 553-591): (nx, ny, max_iters, reynolds_dim), the three reals as
+    Python floats (double), and the mask"""
     with open(paramfile) as f:
         tok = f.read().split()
     if len(tok) < 7:
@@ -147,7 +172,43 @@ def read_inputs(paramfile, obstaclefile):
         if np.any(tri[:, 2] != 1):
             raise ValueError("obstacle blocked value should be 1")
         obstacles[tri[:, 1], tri[:, 0]] = 1
-    return make_params(nx, ny, max_iters, reynolds_dim, density, accel, omega, obstacles), obstacles
+    return (nx, ny, max_iters, reynolds_dim), (density, accel, omega), obstacles
+
+
+def read_inputs(paramfile, obstaclefile):
+    """Parse the reference's two input files (d2q9-bgk.c:466-492, 553-591) into (Params, mask)."""
+    ints, reals, obstacles = _parse_inputs(paramfile, obstaclefile)
+    return make_params(*ints, *reals, obstacles), obstacles
+
+
+def make_dparams(nx, ny, max_iters, reynolds_dim=10, density=0.1, accel=0.005, omega=1.85, obstacles=None):
+    """Run constants of a double-precision context: the reals as given (the fp64 literals, never widened floats),
+    free_cells_inv = 1.0 / free_cells in double (inf for a grid without a free cell, as the reference's division gives)."""
+    p = DParams()
+    p.nx, p.ny, p.max_iters, p.reynolds_dim = nx, ny, max_iters, reynolds_dim
+    p.density, p.accel, p.omega = float(density), float(accel), float(omega)
+    free_cells = nx * ny if obstacles is None else int(obstacles.size - np.count_nonzero(obstacles))
+    p.free_cells_inv = 1.0 / free_cells if free_cells else float("inf")
+    return p
+
+
+def read_inputs_double(paramfile, obstaclefile):
+    """The reference's two input files as its fp64 ancestor read them: (DParams, mask) with density, accel and omega parsed
+    as double and free_cells_inv = 1.0 / free_cells in double."""
+    ints, reals, obstacles = _parse_inputs(paramfile, obstaclefile)
+    return make_dparams(*ints, *reals, obstacles), obstacles
+
+
+def _write_values(final_state_path, av_vels_path, obstacles, fields, av):
+    """final_state.dat and av_vels.dat in the reference's formats (d2q9-bgk.c:835, 848-851)"""
+    ny, nx = obstacles.shape
+    ux, uy, u, pr = fields
+    yy, xx = np.mgrid[0:ny, 0:nx]
+    cols = np.stack([xx.ravel(), yy.ravel(), ux.ravel(), uy.ravel(), u.ravel(), pr.ravel(), obstacles.ravel()], axis=1)
+    np.savetxt(final_state_path, cols, fmt=["%d", "%d", "%.12E", "%.12E", "%.12E", "%.12E", "%d"])
+    with open(av_vels_path, "w") as f:
+        for i, v in enumerate(av):
+            f.write("%d:\t%.12E\n" % (i, v))
 
 
 # ---- row partition: the host-side geometry of csrc/lbm_hip.cpp (split_rows, build_slab, exchange_halos) ----
@@ -464,6 +525,107 @@ class Ensemble:
         if self.ens:
             self.lib.lbm_ens_destroy(self.ens)
             self.ens = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LBMDouble:
+    """A double-precision context (lbm_dp): one grid on the current device in fp64, the precision of the reference's golden
+    files.  Mirrors LBM with double in place of float: create -> upload -> run -> sync -> download -> destroy.  `params`:
+    DParams (make_dparams, read_inputs_double); `obstacles`: int32[ny, nx]."""
+
+    def __init__(self, params, obstacles):
+        self.lib = load_library()
+        if not isinstance(params, DParams):
+            raise LBMError("LBMDouble takes DParams (make_dparams / read_inputs_double), not %s" % type(params).__name__)
+        self.params = params
+        self.nx, self.ny = params.nx, params.ny
+        obst = np.ascontiguousarray(obstacles, dtype=np.int32)
+        assert obst.shape == (params.ny, params.nx)
+        self.obstacles = obst
+        self.ctx = ctypes.c_void_p()
+        _check(self.lib.lbm_dp_create(ctypes.byref(self.ctx), ctypes.byref(params), obst.ctypes.data), "lbm_dp_create")
+
+    def upload(self, cells=None):
+        """cells float64[9, ny, nx]; None = the rest state from params.density, on the device"""
+        if cells is None:
+            _check(self.lib.lbm_dp_upload(self.ctx, None), "lbm_dp_upload")
+        else:
+            c = np.ascontiguousarray(cells, dtype=np.float64)
+            assert c.shape == (9, self.ny, self.nx)
+            _check(self.lib.lbm_dp_upload(self.ctx, c.ctypes.data), "lbm_dp_upload")
+
+    def upload_obstacles(self, obstacles):
+        """the obstacle map once more (d2q9-bgk.c:205-209); same shape as at creation"""
+        ob = np.ascontiguousarray(obstacles, dtype=np.int32)
+        assert ob.shape == (self.ny, self.nx)
+        _check(self.lib.lbm_dp_upload_obstacles(self.ctx, ob.ctypes.data), "lbm_dp_upload_obstacles")
+        self.obstacles = ob
+
+    def run(self, nsteps):
+        _check(self.lib.lbm_dp_run(self.ctx, nsteps), "lbm_dp_run")
+
+    def run_timed(self, nsteps):
+        """Runs nsteps and returns the HIP-event time of the step loop in milliseconds."""
+        ms = ctypes.c_double()
+        _check(self.lib.lbm_dp_run_timed(self.ctx, nsteps, ctypes.byref(ms)), "lbm_dp_run_timed")
+        return ms.value
+
+    def sync(self):
+        _check(self.lib.lbm_dp_sync(self.ctx), "lbm_dp_sync")
+
+    @property
+    def steps_done(self):
+        return self.lib.lbm_dp_steps_done(self.ctx)
+
+    def download(self, cells=True, av_vels=True):
+        """Returns (cells float64[9,ny,nx] or None, av_vels float64[steps_done] or None)."""
+        steps = self.steps_done
+        c = np.zeros((9, self.ny, self.nx), dtype=np.float64) if cells else None
+        a = np.zeros(max(steps, 1), dtype=np.float64) if av_vels else None
+        _check(self.lib.lbm_dp_download(self.ctx, c.ctypes.data if cells else None,
+                                        a.ctypes.data if av_vels else None), "lbm_dp_download")
+        return c, (a[:steps] if av_vels else None)
+
+    def final_state(self):
+        """(u_x, u_y, u, pressure), each float64[ny,nx] — the columns of final_state.dat."""
+        outs = [np.zeros((self.ny, self.nx), dtype=np.float64) for _ in range(4)]
+        _check(self.lib.lbm_dp_final_state(self.ctx, *[o.ctypes.data for o in outs]), "lbm_dp_final_state")
+        return outs
+
+    def reynolds(self):
+        r = ctypes.c_double()
+        _check(self.lib.lbm_dp_reynolds(self.ctx, ctypes.byref(r)), "lbm_dp_reynolds")
+        return r.value
+
+    def set_option(self, key, value):
+        _check(self.lib.lbm_dp_set_option(self.ctx, key.encode(), int(value)), "lbm_dp_set_option(%s)" % key)
+
+    def get_option(self, key):
+        v = ctypes.c_long()
+        _check(self.lib.lbm_dp_get_option(self.ctx, key.encode(), ctypes.byref(v)), "lbm_dp_get_option(%s)" % key)
+        return v.value
+
+    def write_values(self, final_state_path="final_state.dat", av_vels_path="av_vels.dat"):
+        """The two output files in the reference's %.12E formats (d2q9-bgk.c:835,848-851), as check/check.py reads them."""
+        fields = self.final_state()
+        _, av = self.download(cells=False)
+        _write_values(final_state_path, av_vels_path, self.obstacles, fields, av)
+
+    def close(self):
+        if self.ctx:
+            self.lib.lbm_dp_destroy(self.ctx)
+            self.ctx = ctypes.c_void_p()
 
     def __enter__(self):
         return self

@@ -1,0 +1,372 @@
+// Device side of the DOUBLE-PRECISION contexts (include/lbm.h: lbm_dp_*): the reference's accelerate_flow + timestep
+// (kernels.cl:9-53, 56-231) with every distribution, density, momentum and velocity in fp64, as in the fp64 ancestor that
+// wrote the reference's golden files (check/*.dat).
+//
+// Layout: the row-interleaved SoA of d2q9_kernels.h in double — f_k(x, y) at y*9*plane_stride + k*plane_stride + x, plane_stride
+// a multiple of 32 doubles (256 B).  A lane holds two neighbouring cells (x0 even, one 16-B load per plane), so the nine loads
+// and nine stores of a wave are whole 1-KiB segments as in the fp32 kernels.  The mask is one byte per cell.
+//
+// Two kernel forms, both built on dp_collide_cell / dp_accelerate_cell (bit-identical cells):
+//   d2q9_dp_step    one timestep per launch, lane = 2 cells; the bandwidth-bound form (144 B per lattice update)
+//   d2q9_dp_multi   T <= 8 timesteps per launch on an LDS-resident tile with redundant halo (d2q9_multi's scheme);
+//                   launch-bound small grids
+// and one reduction that does not depend on the form: every kernel writes the sum of |u| over each 16-cell row segment
+// (x = 16s .. 16s+15 of row y) in one fixed tree, ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)) with p_i the sum of cells 2i, 2i+1,
+// and dp_reduce adds the segments of a step in a fixed order.  So av_vels, too, are bit-identical between the forms and
+// between runs.
+#pragma once
+#include "d2q9_kernels.h"
+
+namespace lbm {
+
+constexpr int kDpSeg = 16;  // cells per row segment of the velocity sum
+
+typedef double v2d __attribute__((ext_vector_type(2)));
+
+// BGK collision of one cell in fp64 (kernels.cl:119-198).  The statements of the fp64 oracle (oracle/d2q9_oracle.c,
+// timestep_row) with pairwise momenta, contraction off: every kernel that inlines this rounds identically, and the cell
+// equals the oracle's pairwise no-FMA build bit for bit.  Returns |u| = sqrt(j^2)/rho of a fluid cell, 0 for an obstacle.
+__device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obstacle, double omega, double (&out)[9]) {
+#pragma clang fp contract(off)
+  if (obstacle) {
+    // bounce-back: the un-relaxed value leaves through the opposite speed (kernels.cl:69, 187-197)
+    out[0] = g[0]; out[1] = g[3]; out[2] = g[4]; out[3] = g[1]; out[4] = g[2];
+    out[5] = g[7]; out[6] = g[8]; out[7] = g[5]; out[8] = g[6];
+    return 0.0;
+  }
+  const double ic_sq = 3.0;
+  const double w0 = 4.0 / 9.0, w1 = 1.0 / 9.0, w2 = 1.0 / 36.0;
+  double dens = g[0];
+#pragma unroll
+  for (int k = 1; k < 9; k++) dens += g[k];
+  const double densinv = 1.0 / dens;
+  const double diag_a = g[5] - g[7], diag_b = g[8] - g[6];
+  const double u_x = (g[1] - g[3]) + (diag_a + diag_b);
+  const double u_y = (g[2] - g[4]) + (diag_a - diag_b);
+  const double u_sq = u_x * u_x + u_y * u_y;
+  double uvec[9];
+  uvec[0] = 0.0;
+  uvec[1] = u_x;        uvec[2] = u_y;
+  uvec[3] = -u_x;       uvec[4] = -u_y;
+  uvec[5] = u_x + u_y;  uvec[6] = -u_x + u_y;
+  uvec[7] = -u_x - u_y; uvec[8] = u_x - u_y;
+  const double half_densinv_icsq = 0.5 * densinv * ic_sq;
+  double eq[9];
+  eq[0] = w0 * (dens - half_densinv_icsq * u_sq);
+#pragma unroll
+  for (int k = 1; k < 9; k++) {
+    const double t = uvec[k] * ic_sq;
+    const double tsq = t * uvec[k];
+    eq[k] = ((k < 5) ? w1 : w2) * (dens + t + half_densinv_icsq * (tsq - u_sq));
+  }
+#pragma unroll
+  for (int k = 0; k < 9; k++) out[k] = g[k] + omega * (eq[k] - g[k]);
+  return __builtin_sqrt(u_sq) * densinv;
+}
+
+// accelerate_flow on one cell (kernels.cl:24-42): fluid, and none of the three west-side densities would go negative
+__device__ __forceinline__ void dp_accelerate_cell(double (&f)[9], bool obstacle, double aw1, double aw2) {
+#pragma clang fp contract(off)
+  if (!obstacle && (f[3] - aw1) > 0.0 && (f[6] - aw2) > 0.0 && (f[7] - aw2) > 0.0) {
+    f[1] += aw1; f[5] += aw2; f[8] += aw2;
+    f[3] -= aw1; f[6] -= aw2; f[7] -= aw2;
+  }
+}
+
+struct DpStepArgs {
+  const double *src;
+  double *dst;
+  const uint8_t *mask;       // [ny][nx]
+  double *seg;               // [ny][nseg] segment sums of this step
+  unsigned long long plane_stride;
+  int nx, ny;
+  int lanes_per_row;         // ceil(nx / 2) rounded up to a multiple of 8: eight lanes = one 16-cell segment
+  int accel_row;             // row that gets the NEXT step's accelerate_flow, or -1
+  double omega, aw1, aw2;
+};
+
+// One timestep, lane = cells x0, x0+1 of one row.  x-1 / x+1 neighbours: aligned 16-B loads plus one scalar load per
+// streamed plane at the wrap column (an L1 hit).  A lane past the row's end (x0 >= nx) only joins the segment sum with 0.
+__global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a) {
+  const unsigned t = blockIdx.x * kBlock + threadIdx.x;
+  const unsigned lpr = (unsigned)a.lanes_per_row;
+  const int y = (int)(t / lpr);
+  const int x0 = 2 * (int)(t - (unsigned)y * lpr);
+  double tot = 0.0;
+  const bool live = y < a.ny && x0 < a.nx;
+  if (live) {
+    const bool has_b = x0 + 1 < a.nx;
+    const size_t ps = a.plane_stride, rs = 9 * ps;
+    const int ys = (y == 0) ? a.ny - 1 : y - 1, yn = (y + 1 == a.ny) ? 0 : y + 1;  // kernels.cl:91-93
+    const int xw = (x0 == 0) ? a.nx - 1 : x0 - 1;                                  // kernels.cl:99-102
+    const int xe = (x0 + 2 < a.nx) ? x0 + 2 : 0;  // east of cell x0+1, or of x0 when x0 is the row's last cell
+    const double *rc = a.src + (size_t)y * rs, *rsth = a.src + (size_t)ys * rs, *rnth = a.src + (size_t)yn * rs;
+    const v2d c0 = *reinterpret_cast<const v2d *>(rc + x0);
+    const v2d c1 = *reinterpret_cast<const v2d *>(rc + ps + x0);
+    const v2d c3 = *reinterpret_cast<const v2d *>(rc + 3 * ps + x0);
+    const v2d c2 = *reinterpret_cast<const v2d *>(rsth + 2 * ps + x0);
+    const v2d c5 = *reinterpret_cast<const v2d *>(rsth + 5 * ps + x0);
+    const v2d c6 = *reinterpret_cast<const v2d *>(rsth + 6 * ps + x0);
+    const v2d c4 = *reinterpret_cast<const v2d *>(rnth + 4 * ps + x0);
+    const v2d c7 = *reinterpret_cast<const v2d *>(rnth + 7 * ps + x0);
+    const v2d c8 = *reinterpret_cast<const v2d *>(rnth + 8 * ps + x0);
+    const double w1 = rc[ps + xw], w5 = rsth[5 * ps + xw], w8 = rnth[8 * ps + xw];
+    const double e3 = rc[3 * ps + xe], e6 = rsth[6 * ps + xe], e7 = rnth[7 * ps + xe];
+    const uint8_t *m = a.mask + (size_t)y * a.nx + x0;
+    const bool ob_a = m[0] != 0, ob_b = has_b && m[1] != 0;
+    double ga[9] = {c0.x, w1, c2.x, has_b ? c3.y : e3, c4.x, w5, has_b ? c6.y : e6, has_b ? c7.y : e7, w8};
+    double gb[9] = {c0.y, c1.x, c2.y, e3, c4.y, c5.x, e6, e7, c8.x};
+    double oa[9], ob[9];
+    const double ta = dp_collide_cell(ga, ob_a, a.omega, oa);
+    const double tb = dp_collide_cell(gb, ob_b, a.omega, ob);
+    if (y == a.accel_row) {
+      dp_accelerate_cell(oa, ob_a, a.aw1, a.aw2);
+      dp_accelerate_cell(ob, ob_b, a.aw1, a.aw2);
+    }
+    double *d = a.dst + (size_t)y * rs + x0;
+    if (has_b) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) {
+        v2d v = {oa[k], ob[k]};
+        *reinterpret_cast<v2d *>(d + k * ps) = v;
+      }
+      tot = ta + tb;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 9; k++) d[k * ps] = oa[k];
+      tot = ta + 0.0;
+    }
+  }
+  // the segment's tree: pairs, then xor 1, 2, 4 across its eight lanes (IEEE addition commutes: every lane of the
+  // segment ends with the same bits, the d2q9_dp_multi tree's)
+  tot += __shfl_xor(tot, 1, 64);
+  tot += __shfl_xor(tot, 2, 64);
+  tot += __shfl_xor(tot, 4, 64);
+  if (y < a.ny && ((t - (unsigned)y * lpr) & 7u) == 0) a.seg[(size_t)y * (lpr >> 3) + ((t - (unsigned)y * lpr) >> 3)] = tot;
+}
+
+struct DpMultiArgs {
+  const double *src;
+  double *dst;
+  const uint8_t *mask;
+  double *seg;              // [T][ny][nseg]: the segment sums of each of the T steps
+  unsigned long long plane_stride, seg_step;   // seg_step = ny * nseg
+  int nx, ny, nseg;
+  int tiles_x;
+  int T;                    // steps in this launch
+  int accel_next;           // apply the following step's accelerate_flow to the final state
+  double omega, aw1, aw2;
+};
+
+// T <= TMAX timesteps per launch: a (TX + 2T) x (TY + 2T) region around the TX x TY output tile is loaded into LDS,
+// advanced T times LDS -> LDS on a region that shrinks by one cell per step (halo cells computed redundantly by the
+// neighbouring tiles), and the central tile is stored (d2q9_multi, d2q9_kernels.h).  Each step's |u| of the tile's cells
+// goes to an LDS tile of its own; one lane per 16-cell segment adds it up in the segment tree while the next step runs.
+//
+// Tile shape and depth, measured (tools/dp_throughput.py, one call, us/step at 128^2 / 256^2 / 512^2; profiles/dp_throughput.txt):
+//   16x16, T <= 8 (149 KB of LDS, one workgroup per CU)  1.98 / 2.53 / 8.07   <- instantiated
+//   16x8,  T <= 8 (113 KB)                               1.71 / 3.60 / 12.09  (wins only where every tile has a CU of its own)
+//   16x16, T <= 4 (85 KB)                                2.13 / 2.99 / 8.43
+// and one step per launch (d2q9_dp_step) 3.78 / 4.45 / 9.53, at 1024^2 23.8 against this kernel's 28.2: auto up to 300K cells.
+template <int TX, int TY, int TMAX>
+__global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs a) {
+  static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
+  constexpr int kRX = TX + 2 * TMAX, kRY = TY + 2 * TMAX;
+  __shared__ double lds[2][9][kRY * kRX];
+  __shared__ uint8_t lmask[kRY * kRX];
+  __shared__ double tval[2][TY][TX];
+  const int tid = threadIdx.x;
+  const int T = a.T;
+  const int RX = TX + 2 * T, RY = TY + 2 * T;
+  const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
+  const int gx0 = tile_x * TX - T, gy0 = tile_y * TY - T;  // region cell (0,0)
+  const size_t ps = a.plane_stride, rs = 9 * ps;
+  auto grid_row = [&](int ry) {
+    int r = (gy0 + ry) % a.ny;
+    return r < 0 ? r + a.ny : r;
+  };
+  // segment sums of step s (1-based) from tval[s & 1]
+  auto store_segments = [&](int s) {
+    constexpr int kSegs = TY * (TX / kDpSeg);
+    if (tid < kSegs) {
+      const int oy = tid / (TX / kDpSeg), sx = tid - oy * (TX / kDpSeg);
+      const int gy = tile_y * TY + oy;
+      const double *v = &tval[s & 1][oy][sx * kDpSeg];
+      double p[8];
+#pragma unroll
+      for (int i = 0; i < 8; i++) p[i] = v[2 * i] + v[2 * i + 1];
+      const double tot = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+      const int seg = tile_x * (TX / kDpSeg) + sx;
+      if (gy < a.ny && seg < a.nseg) a.seg[(size_t)(s - 1) * a.seg_step + (size_t)gy * a.nseg + seg] = tot;
+    }
+  };
+
+  // region -> LDS (periodic wrap in x, kernels.cl:99-102)
+  const float rinv = 1.0f / (float)RX;
+  for (int i = tid; i < RX * RY; i += kMultiThreads) {
+    const int ry = (int)(((float)i + 0.5f) * rinv), rx = i - ry * RX;
+    int gx = (gx0 + rx) % a.nx;
+    if (gx < 0) gx += a.nx;
+    const int gy = grid_row(ry);
+    const double *p = a.src + (size_t)gy * rs + gx;
+#pragma unroll
+    for (int k = 0; k < 9; k++) lds[0][k][ry * kRX + rx] = p[k * ps];
+    lmask[ry * kRX + rx] = a.mask[(size_t)gy * a.nx + gx];
+  }
+  __syncthreads();
+
+  for (int s = 1; s <= T; s++) {
+    if (s > 1) store_segments(s - 1);
+    const int in = (s - 1) & 1, out = s & 1;
+    const int w = RX - 2 * s, h = RY - 2 * s;
+    const bool accel_step = (s < T) || a.accel_next;
+    const float inv = 1.0f / (float)w;
+    for (int i = tid; i < w * h; i += kMultiThreads) {
+      const int q = (int)(((float)i + 0.5f) * inv);
+      const int rx = s + (i - q * w), ry = s + q;
+      const int c = ry * kRX + rx;
+      double g[9], o[9];
+      g[0] = lds[in][0][c];
+      g[1] = lds[in][1][c - 1];
+      g[2] = lds[in][2][c - kRX];
+      g[3] = lds[in][3][c + 1];
+      g[4] = lds[in][4][c + kRX];
+      g[5] = lds[in][5][c - kRX - 1];
+      g[6] = lds[in][6][c - kRX + 1];
+      g[7] = lds[in][7][c + kRX + 1];
+      g[8] = lds[in][8][c + kRX - 1];
+      const bool obst = lmask[c] != 0;
+      const double t = dp_collide_cell(g, obst, a.omega, o);
+      if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, a.aw1, a.aw2);
+#pragma unroll
+      for (int k = 0; k < 9; k++) lds[out][k][c] = o[k];
+      // the tile's own cells: every one is inside the region of every step; cells past the grid's edge count 0
+      const int ox = rx - T, oy = ry - T;
+      if (ox >= 0 && ox < TX && oy >= 0 && oy < TY)
+        tval[s & 1][oy][ox] = (tile_x * TX + ox < a.nx && tile_y * TY + oy < a.ny) ? t : 0.0;
+    }
+    __syncthreads();
+  }
+  store_segments(T);
+
+  // central tile -> global
+  const int fin = T & 1;
+  for (int i = tid; i < TX * TY; i += kMultiThreads) {
+    const int oy = i / TX, ox = i - oy * TX;
+    const int gx = tile_x * TX + ox, gy = tile_y * TY + oy;
+    if (gx < a.nx && gy < a.ny) {
+      const int c = (oy + T) * kRX + ox + T;
+      double *d = a.dst + (size_t)gy * rs + gx;
+#pragma unroll
+      for (int k = 0; k < 9; k++) d[k * ps] = lds[fin][k][c];
+    }
+  }
+}
+
+// ---- second reduction stage: fixed order, no atomics ---------------------------------------------------------------
+// grid = (blocks, steps): block b of step r adds in[r * in_stride + i] for i in its contiguous chunk (lane-strided, then the
+// wave butterfly, then the four waves in order) into out[r * out_stride + b].  Run once into av_sum, or twice (partials
+// per block, then one block per step) where a step has many segments.
+static __global__ __launch_bounds__(kBlock) void dp_reduce(const double *in, unsigned long long in_stride, long n, double *out,
+                                                           unsigned long long out_stride) {
+  const long chunk = (n + gridDim.x - 1) / gridDim.x;
+  const long i0 = (long)blockIdx.x * chunk, i1 = i0 + chunk < n ? i0 + chunk : n;
+  const double *p = in + (size_t)blockIdx.y * in_stride;
+  double acc = 0.0;
+  for (long i = i0 + threadIdx.x; i < i1; i += kBlock) acc += p[i];
+  __shared__ double wsum[kBlock / 64];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = wsum[0];
+    for (int i = 1; i < kBlock / 64; i++) t += wsum[i];
+    out[(size_t)blockIdx.y * out_stride + blockIdx.x] = t;
+  }
+}
+
+// accelerate_flow of row ny-2 (kernels.cl:9-53): prologue of a run
+static __global__ void dp_accelerate_row(double *cells, unsigned long long plane_stride, const uint8_t *mask, int nx, int row,
+                                         double aw1, double aw2) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= nx) return;
+  double f[9];
+  double *c = cells + (size_t)row * 9 * plane_stride + x;
+#pragma unroll
+  for (int k = 0; k < 9; k++) f[k] = c[k * plane_stride];
+  dp_accelerate_cell(f, mask[(size_t)row * nx + x] != 0, aw1, aw2);
+#pragma unroll
+  for (int k = 0; k < 9; k++) c[k * plane_stride] = f[k];
+}
+
+// the rest state (values of d2q9-bgk.c:529-550, computed on the host in double)
+static __global__ void dp_init_cells(double *cells, unsigned long long plane_stride, int nx, size_t n, double w0, double w1,
+                                     double w2) {
+  for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
+    const size_t y = c / nx;
+    const size_t i = y * 9 * plane_stride + (c - y * nx);
+    cells[i] = w0;
+#pragma unroll
+    for (int k = 1; k <= 4; k++) cells[k * plane_stride + i] = w1;
+#pragma unroll
+    for (int k = 5; k <= 8; k++) cells[k * plane_stride + i] = w2;
+  }
+}
+
+// device layout <-> the caller's double[9][ny][nx] (staged in the grid that is not current).  TO_DEVICE: flat -> cells.
+template <bool TO_DEVICE>
+static __global__ void dp_pack_planes(double *cells, unsigned long long plane_stride, int nx, size_t n, double *flat) {
+  for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
+    const size_t y = c / nx;
+    const size_t i = y * 9 * plane_stride + (c - y * nx);
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+      if (TO_DEVICE) cells[k * plane_stride + i] = flat[k * n + c];
+      else flat[k * n + c] = cells[k * plane_stride + i];
+    }
+  }
+}
+
+// output stage: the columns of final_state.dat and the velocity sum (d2q9-bgk.c:787-832, 396-442) in double, the oracle's
+// statements (cell_moments); obstacle cells give 0, 0, 0, density/3.  partials[gridDim.x]: per-block sums of u.
+static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *cells, unsigned long long plane_stride, int nx,
+                                                                 const uint8_t *mask, size_t n, double density, double *u_x,
+                                                                 double *u_y, double *u, double *pressure, double *partials) {
+#pragma clang fp contract(off)
+  const double c_sq = 1.0 / 3.0;
+  double tot_u = 0.0;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+    double ux = 0.0, uy = 0.0, uu = 0.0, pr = density * c_sq;
+    if (mask[i] == 0) {
+      double f[9];
+      double local_density = 0.0;
+      const size_t y = i / nx;
+      const size_t cell = y * 9 * plane_stride + (i - y * nx);
+#pragma unroll
+      for (int k = 0; k < 9; k++) {
+        f[k] = cells[k * plane_stride + cell];
+        local_density += f[k];
+      }
+      ux = (f[1] + f[5] + f[8] - f[3] - f[6] - f[7]) / local_density;
+      uy = (f[2] + f[5] + f[6] - f[4] - f[7] - f[8]) / local_density;
+      uu = __builtin_sqrt(ux * ux + uy * uy);
+      pr = local_density * c_sq;
+      tot_u += uu;
+    }
+    if (u_x) u_x[i] = ux;
+    if (u_y) u_y[i] = uy;
+    if (u) u[i] = uu;
+    if (pressure) pressure[i] = pr;
+  }
+  __shared__ double wsum[kBlock / 64];
+  tot_u = wave_sum(tot_u);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = tot_u;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = wsum[0];
+    for (int i = 1; i < kBlock / 64; i++) t += wsum[i];
+    partials[blockIdx.x] = t;
+  }
+}
+
+}  // namespace lbm
