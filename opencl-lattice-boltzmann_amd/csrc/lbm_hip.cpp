@@ -476,7 +476,6 @@ int fuse_level(const lbm_ctx *c) {
   if (lvl == 3 && c->halo_mode && c->halo_depth < 3) lvl = 2;
   return lvl;
 }
-bool fuse_effective(const lbm_ctx *c) { return fuse_level(c) != 0; }
 
 // d2q9_resident: one slab without halo rows whose grid decomposes into bands of BH full-width rows x W = nx/128 <= 8 waves that are
 // all resident at once (two waves per SIMD: 8 / W workgroups per CU); res_* are set by resident_geometry.
@@ -1126,6 +1125,90 @@ int effective_mode(const lbm_ctx *c) {
   return m;
 }
 
+// ---- The launch plan: what a context does, stated once.  resolve_plan() is the only caller of the policy predicates above
+// outside the geometry builders; the step loop, the launchers and lbm_get_option read the plan.  It is resolved from a context
+// whose geometry is built (deep_twin_effective reads f6_twin.paired, which the builders set — and the builders ask compact_sets,
+// staged_sets, slab_twin5 and twin_cap) and is not kept across lbm_set_option calls: several options change it without a rebuild.
+enum { KIND_NONE = 0, KIND_SINGLE = 1, KIND_FUSED2 = 2, KIND_MULTI = 3, KIND_FUSED3 = 4, KIND_FUSED4 = 5, KIND_DEEP = 6, KIND_RESIDENT = 7 };
+// form of a launch set: one slab without halo rows / edge launch + interior launch on two streams / ONE launch whose edge units push
+// the halo rows into the ring neighbours (peer stores) / ... into local staging blocks that RCCL sends (see compact_sets, staged_sets)
+enum { FORM_ONE_SLAB = 0, FORM_TWO_STREAM = 1, FORM_COMPACT = 2, FORM_STAGED = 3 };
+
+struct LaunchPlan {
+  int kind = KIND_SINGLE;         // kernel family of a launch set while enough steps remain
+  int cap = 1;                    // most timesteps one launch set of it advances (option "launch_steps")
+  int window_kind = KIND_SINGLE;  // the family option "fuse" resolves to (KIND_SINGLE, KIND_FUSED2..4, KIND_DEEP): == kind unless the
+                                  // LDS tiles or the resident kernel have the context
+  int fuse_lvl = 0;               // fuse_level(): 0, 2, 3, 4, 5 (twin5 only), 6..8
+  int form = FORM_ONE_SLAB;
+  bool multi = false;             // the slabs carry halo rows
+  bool pairs = false;             // option "pair": the window family runs as chunk pairs on the first slab (levels below 3, which have no
+                                  // pair kernel, report the three-step schedule's form)
+  bool twin = false;              // KIND_DEEP on one slab runs d2q9_deep_twin over Slab::f6_twin
+  bool twin5 = false;             // KIND_DEEP is the slab form of the five-step chunk pairs (slab_twin5)
+  // per-launch constants of the deep window kernels
+  bool nt = false, paths = true, steady = true;  // non-temporal stores; second collision path (obst_paths); per-depth kernels
+  int twin_depth = kDeepTwinDefault;             // D of the one-slab pairs: kDeepTwinDefault (caps up to five steps) or kDeepTwinSteps
+  bool compact() const { return form >= FORM_COMPACT; }
+  bool staged() const { return form == FORM_STAGED; }
+};
+
+LaunchPlan resolve_plan(const lbm_ctx *c) {
+  LaunchPlan p;
+  const int lvl = fuse_level(c), ms = multistep_effective(c), tcap = twin_cap(c);
+  p.multi = c->halo_mode;
+  p.fuse_lvl = lvl;
+  p.twin5 = slab_twin5(c);
+  p.twin = lvl >= kDeepMin && deep_twin_effective(c);
+  p.twin_depth = tcap <= kDeepTwinDefault ? kDeepTwinDefault : kDeepTwinSteps;
+  p.form = !c->halo_mode ? FORM_ONE_SLAB : staged_sets(c) ? FORM_STAGED : compact_sets(c) ? FORM_COMPACT : FORM_TWO_STREAM;
+  const bool deep = lvl >= kDeepMin || p.twin5, res = resident_effective(c);
+  p.window_kind = deep ? KIND_DEEP : lvl == 4 ? KIND_FUSED4 : lvl >= 3 ? KIND_FUSED3 : lvl ? KIND_FUSED2 : KIND_SINGLE;
+  const int wcap = deep ? (p.twin ? std::min(lvl, tcap) : lvl) : lvl >= 3 ? lvl : (lvl ? 2 : 1);
+  // (the resident kernel: all remaining steps in one launch, as far as the ring of per-step partial sums reaches)
+  p.kind = res ? KIND_RESIDENT : ms > 0 ? KIND_MULTI : p.window_kind;
+  p.cap = res ? c->ring : ms > 0 ? ms : wcap;
+  if (!c->slabs.empty()) {
+    const Slab &s0 = c->slabs[0];
+    p.pairs = p.twin5 ? true : lvl >= kDeepMin ? (c->halo_mode ? p.compact() && s0.f6_main.paired : p.twin) : lvl == 4 ? s0.f4_main.paired : s0.f3_main.paired;
+    p.nt = nt_effective(c);
+  }
+  p.paths = c->obst_paths != 0;  // (-1 auto = on)
+  p.steady = c->steady != 0;
+  return p;
+}
+
+// Kernel and timesteps of the next launch set with `rem` steps left in the run.  The tail of a run falls back: deep window kernels
+// -> any depth >= 2, four -> three -> two -> single step; the LDS tiles and the resident kernel take whatever is left.
+struct SetChoice { int kind, adv; };
+SetChoice plan_set(const LaunchPlan &p, int rem) {
+  if (p.kind == KIND_RESIDENT || p.kind == KIND_MULTI) return {p.kind, std::min(p.cap, rem)};
+  // the remaining steps in as few launches as possible, of equal depth (every launch moves the whole grid once:
+  // 20 steps = 7+7+6, not 8+8+4)
+  if (p.kind == KIND_DEEP && rem >= 2) return {KIND_DEEP, div_up(rem, div_up(rem, p.cap))};
+  if (p.cap >= 4 && rem >= 4) return {KIND_FUSED4, 4};
+  if (p.cap >= 3 && rem >= 3) return {KIND_FUSED3, 3};
+  if (p.cap >= 2 && rem >= 2) return {KIND_FUSED2, 2};
+  return {KIND_SINGLE, 1};
+}
+
+// Per kind: which schedule of a slab is the interior one, which the edge one, and how many ring slots a step of it occupies.
+// (KIND_SINGLE / KIND_MULTI / KIND_RESIDENT launch no unit schedule: main / edge are the two-step kernel's, for "fuse_units".)
+struct SetGeom { const FuseGeom *main, *edge; int used; };
+SetGeom set_geom(const LaunchPlan &p, const Slab &s, int kind) {
+  SetGeom g{&s.f_main, &s.f_edge, s.nb_main + s.nb_edge};
+  if (kind == KIND_FUSED3) g.main = &s.f3_main;
+  if (kind == KIND_FUSED4) g.main = &s.f4_main;
+  if (kind == KIND_DEEP) {
+    g.main = p.twin ? &s.f6_twin : &s.f6_main;
+    g.edge = &s.f6_edge;
+  }
+  if (kind == KIND_FUSED2 || kind == KIND_FUSED3 || kind == KIND_FUSED4 || kind == KIND_DEEP) g.used = g.main->units + (p.multi ? g.edge->units : 0);
+  if (kind == KIND_MULTI) g.used = s.m_tiles_x * s.m_tiles_y;
+  if (kind == KIND_RESIDENT) g.used = s.res_bands * s.res_w;
+  return g;
+}
+
 template <int LM>
 void launch_step_lm(bool nt, const StepArgs &a, int nblocks, hipStream_t st) {
   if (nt) hipLaunchKernelGGL((d2q9_step<4, true, LM>), dim3(nblocks), dim3(kBlock), 0, st, a);
@@ -1201,8 +1284,7 @@ Step2Args base_args2(const lbm_ctx *c, const Slab &s, int src, bool accel_next, 
 // d2q9_step3p = its chunk pairs.  (Round 4 removed the register-window form, the form with two row-sets of loads in flight and the
 // non-temporal-load variants — nine instantiations at 253-256 registers that no policy selected: LDS windows 230 against 188 GLUPS on
 // 8192x8192, plain loads 227.6 against 221.4 hybrid / 202.3 non-temporal, tools/ab.py, rounds 1-2.)
-void launch_step3(const lbm_ctx *c, const Step2Args &a0, float *partials3, int units, hipStream_t st, bool paired = false) {
-  (void)c;
+void launch_step3(const Step2Args &a0, float *partials3, int units, hipStream_t st, bool paired = false) {
   if (paired) {
     // one workgroup of two waves per pair of chunks: a.units_per_band counts pairs x strips
     Step2Args a = a0;
@@ -1213,11 +1295,9 @@ void launch_step3(const lbm_ctx *c, const Step2Args &a0, float *partials3, int u
   hipLaunchKernelGGL((d2q9_step3<true, 0, true, 1>), dim3(units), dim3(64), 0, st, a0, partials3);
 }
 
-void launch_step4(const lbm_ctx *c, const Step2Args &a0, float *partials3, float *partials4, int units, hipStream_t st,
-                  bool paired = false) {
+void launch_step4(const Step2Args &a0, float *partials3, float *partials4, int units, hipStream_t st, bool paired = false) {
   // source loads are always plain here: the kernel sits at the 256-VGPR limit and its non-temporal forms spill (6 and
   // 8 registers to scratch) — option "nt_loads" applies to the two- and three-step kernels only (lbm_set_option)
-  (void)c;
   if (paired) {
     Step2Args a = a0;
     a.units_per_band = a0.units_per_band / 2;  // chunk pairs x strips
@@ -1227,104 +1307,103 @@ void launch_step4(const lbm_ctx *c, const Step2Args &a0, float *partials3, float
   hipLaunchKernelGGL((d2q9_step4<true, 0>), dim3(units), dim3(64), 0, st, a0, partials3, partials4);
 }
 
-// compact launch set of the three- / four-step kernels: edge units first, then the interior units, one launch
-void launch_deep(const lbm_ctx *c, const Slab &s, const FuseGeom &g, const Step2Args &a0, int units, float *partials, int nlev, hipStream_t st) {
+// The ONE selection among the instantiations of deep_instances.h (every instance has this signature).  A family is a kernel with
+// its D and PUSH arguments fixed; within it the launch picks NT, OBST_PATHS and LT = the depth the row loop is instantiated for
+// (steady form, see deep_sweep) or 0 = the any-depth kernel.  The depths whole runs are cut into have a kernel of their own in
+// the default configuration only — both collision paths, option steady on and, for the eight-step families, non-temporal
+// stores; every other combination of options runs the any-depth kernel.
+using DeepKernel = void (*)(const Step2Args, float *, int, int);
+enum DeepFamily {
+  DEEP_LONE,        // d2q9_deep<8, .., PUSH = false>: one slab without pairs, two-stream launch sets
+  DEEP_LONE_PUSH,   // d2q9_deep<8, .., PUSH = true>: compact launch sets, lone interior
+  DEEP_TWIN8,       // d2q9_deep_twin<8, .., PUSH = false>: one slab, up to eight steps per launch
+  DEEP_TWIN8_PUSH,  // d2q9_deep_twin<8, .., PUSH = true>: compact launch sets, interior chunk pairs
+  DEEP_TWIN5,       // d2q9_deep_twin<5, .., PUSH = false>: one slab, up to five steps; its steady form exists with plain stores too
+  DEEP_TWIN5_PUSH   // d2q9_deep_twin<5, false, .., PUSH = true>: slab_twin5; plain stores only (both grids of a slab of this size fit
+                    // the Infinity Cache up to 2.8M cells), so no non-temporal instantiations
+};
+DeepKernel deep_kernel(DeepFamily f, const LaunchPlan &p, int nlev) {
+  // the tables are deep_instances.h, family by family, in its order: the per-depth forms, then the any-depth forms by (NT, OBST_PATHS)
+  static const DeepKernel lone[7] = {d2q9_deep<8, true, true, false, 8>, d2q9_deep<8, true, true, false, 7>, d2q9_deep<8, true, true, false, 6>, d2q9_deep<8, true, true, false, 0>,
+                                     d2q9_deep<8, true, false, false, 0>, d2q9_deep<8, false, true, false, 0>, d2q9_deep<8, false, false, false, 0>};
+  static const DeepKernel lone_push[7] = {d2q9_deep<8, true, true, true, 8>, d2q9_deep<8, true, true, true, 7>, d2q9_deep<8, true, true, true, 6>, d2q9_deep<8, true, true, true, 0>,
+                                          d2q9_deep<8, true, false, true, 0>, d2q9_deep<8, false, true, true, 0>, d2q9_deep<8, false, false, true, 0>};
+  static const DeepKernel twin8[7] = {d2q9_deep_twin<8, true, true, 8, false>, d2q9_deep_twin<8, true, true, 7, false>, d2q9_deep_twin<8, true, true, 6, false>, d2q9_deep_twin<8, true, true, 0, false>,
+                                      d2q9_deep_twin<8, true, false, 0, false>, d2q9_deep_twin<8, false, true, 0, false>, d2q9_deep_twin<8, false, false, 0, false>};
+  static const DeepKernel twin8_push[7] = {d2q9_deep_twin<8, true, true, 8, true>, d2q9_deep_twin<8, true, true, 7, true>, d2q9_deep_twin<8, true, true, 6, true>, d2q9_deep_twin<8, true, true, 0, true>,
+                                           d2q9_deep_twin<8, true, false, 0, true>, d2q9_deep_twin<8, false, true, 0, true>, d2q9_deep_twin<8, false, false, 0, true>};
+  static const DeepKernel twin5[6] = {d2q9_deep_twin<5, true, true, 5, false>, d2q9_deep_twin<5, false, true, 5, false>, d2q9_deep_twin<5, true, true, 0, false>,
+                                      d2q9_deep_twin<5, true, false, 0, false>, d2q9_deep_twin<5, false, true, 0, false>, d2q9_deep_twin<5, false, false, 0, false>};
+  static const DeepKernel twin5_push[3] = {d2q9_deep_twin<5, false, true, 5, true>, d2q9_deep_twin<5, false, true, 0, true>, d2q9_deep_twin<5, false, false, 0, true>};
+  const bool five = f == DEEP_TWIN5 || f == DEEP_TWIN5_PUSH;
+  const bool nt = p.nt && f != DEEP_TWIN5_PUSH, paths = p.paths;
+  const bool own_depth = five ? nlev == kDeepTwinDefault : (nt && nlev >= kDeepMin && nlev <= kDeepSteps);
+  const bool lt = paths && p.steady && own_depth;    // the launch runs the kernel instantiated for its depth (LT = nlev)
+  const int any = (nt ? 0 : 2) + (paths ? 0 : 1);    // any-depth forms: {NT + paths, NT, paths, neither}
+  if (f == DEEP_TWIN5) return twin5[lt ? (nt ? 0 : 1) : 2 + any];
+  if (f == DEEP_TWIN5_PUSH) return twin5_push[lt ? 0 : (paths ? 1 : 2)];
+  const DeepKernel *t = f == DEEP_LONE ? lone : f == DEEP_LONE_PUSH ? lone_push : f == DEEP_TWIN8 ? twin8 : twin8_push;
+  return t[lt ? kDeepSteps - nlev : 3 + any];
+}
+
+// one launch of d2q9_deep over schedule g (one slab without pairs; the edge and the interior launch of a two-stream set)
+void launch_deep(const lbm_ctx *c, const LaunchPlan &p, const Slab &s, const FuseGeom &g, const Step2Args &a0, float *partials, int nlev, hipStream_t st) {
   Step2Args a = a0;
   a.strips = g.vstrips > 0 ? g.vstrips : s.strips2;
   a.strips_edge = s.strips2;
   a.lanes_out = s.lanes2;
   a.clean_bits = clean_bits_for(c, s, s.f6_main);  // (an edge launch beside the interior launch follows the interior's policy)
   a.clean_words = s.clean_words;
-  const dim3 grid(units), block(64);
-  const bool nt = nt_effective(c), paths = c->obst_paths != 0;  // (-1 auto = on)
-  // the depths whole runs are cut into have a kernel of their own (steady form of the row loop, see deep_sweep); the
-  // default configuration only — every other combination of options runs the any-depth kernel
-  if (nt && paths && c->steady != 0 && nlev == 8) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, true, true, false, 8>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt && paths && c->steady != 0 && nlev == 7) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, true, true, false, 7>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt && paths && c->steady != 0 && nlev == 6) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, true, true, false, 6>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt && paths) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, true, true>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, true, false>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (paths) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, false, true>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else hipLaunchKernelGGL((d2q9_deep<kDeepSteps, false, false>), grid, block, 0, st, a, partials, s.nb_total, nlev);
+  hipLaunchKernelGGL(deep_kernel(DEEP_LONE, p, nlev), dim3(g.units), dim3(64), 0, st, a, partials, s.nb_total, nlev);
 }
 
-// compact launch set of d2q9_deep: the edge units first, then the interior units, ONE launch
-void launch_deep_compact(const lbm_ctx *c, const Slab &s, const Step2Args &a0, float *partials, int nlev, hipStream_t st) {
+// compact launch set of the deep window kernels: the edge units first, then the interior units, ONE launch
+void launch_deep_compact(const lbm_ctx *c, const LaunchPlan &p, const Slab &s, const Step2Args &a0, float *partials, int nlev, hipStream_t st) {
   Step2Args a = a0;
   a.strips = s.f6_main.vstrips > 0 ? s.f6_main.vstrips : s.strips2;
   a.strips_edge = s.strips2;
   a.lanes_out = s.lanes2;
   a.clean_bits = clean_bits_for(c, s, s.f6_main);
   a.clean_words = s.clean_words;
-  const bool nt = nt_effective(c), paths = c->obst_paths != 0;
-  if (slab_twin5(c)) {
-    // five halo rows: interior chunk pairs + two edge chunk pairs per strip, d2q9_deep_twin<5, ..., PUSH> (twin5_slab_geometry)
+  DeepFamily f = DEEP_LONE_PUSH;
+  dim3 grid(a0.edge_units + s.f6_main.units), block(64);
+  if (p.twin5) {
+    // five halo rows: interior chunk pairs + two edge chunk pairs per strip (twin5_slab_geometry)
+    f = DEEP_TWIN5_PUSH;
     a.strips = a.strips_edge = s.strips_tw;
     a.lanes_out = s.lanes_tw;
     a.clean_bits = nullptr;
-    a.units_per_band = a0.units_per_band / 2;  // chunk pairs x strips
     a.edge_units = 4 * s.strips_tw;            // edge WAVES
-    const dim3 pgrid(2 * s.strips_tw + s.f6_main.units / 2), pblock(128);
-    constexpr int D5 = kDeepTwinDefault;
-    // (plain stores only: both grids of a slab of this size fit the Infinity Cache up to 2.8M cells; no non-temporal instantiations)
-    if (paths && c->steady != 0 && nlev == D5) hipLaunchKernelGGL((d2q9_deep_twin<D5, false, true, D5, true>), pgrid, pblock, 0, st, a, partials, s.nb_total, nlev);
-    else if (paths) hipLaunchKernelGGL((d2q9_deep_twin<D5, false, true, 0, true>), pgrid, pblock, 0, st, a, partials, s.nb_total, nlev);
-    else hipLaunchKernelGGL((d2q9_deep_twin<D5, false, false, 0, true>), pgrid, pblock, 0, st, a, partials, s.nb_total, nlev);
-    return;
+    grid = dim3(2 * s.strips_tw + s.f6_main.units / 2);
+  } else if (s.f6_main.paired) {
+    // interior chunk pairs + one edge workgroup per strip (bottom and top edge rows on its two waves)
+    f = DEEP_TWIN8_PUSH;
+    a.edge_units = 2 * s.strips2;              // edge WAVES (what the last of them counts up to); edge workgroups = half
+    grid = dim3(s.strips2 + s.f6_main.units / 2);
   }
-  if (s.f6_main.paired) {
-    // interior chunk pairs + one edge workgroup per strip (bottom and top edge rows on its two waves): d2q9_deep_twin<..., PUSH>
-    a.units_per_band = a0.units_per_band / 2;     // chunk pairs x strips
-    a.edge_units = 2 * s.strips2;                 // edge WAVES (what the last of them counts up to); edge workgroups = half
-    const dim3 pgrid(s.strips2 + s.f6_main.units / 2), pblock(128);
-    if (nt && paths && c->steady != 0 && nlev == 8) hipLaunchKernelGGL((d2q9_deep_twin<kDeepSteps, true, true, 8, true>), pgrid, pblock, 0, st, a, partials, s.nb_total, nlev);
-    else if (nt && paths && c->steady != 0 && nlev == 7) hipLaunchKernelGGL((d2q9_deep_twin<kDeepSteps, true, true, 7, true>), pgrid, pblock, 0, st, a, partials, s.nb_total, nlev);
-    else if (nt && paths && c->steady != 0 && nlev == 6) hipLaunchKernelGGL((d2q9_deep_twin<kDeepSteps, true, true, 6, true>), pgrid, pblock, 0, st, a, partials, s.nb_total, nlev);
-    else if (nt && paths) hipLaunchKernelGGL((d2q9_deep_twin<kDeepSteps, true, true, 0, true>), pgrid, pblock, 0, st, a, partials, s.nb_total, nlev);
-    else if (nt) hipLaunchKernelGGL((d2q9_deep_twin<kDeepSteps, true, false, 0, true>), pgrid, pblock, 0, st, a, partials, s.nb_total, nlev);
-    else if (paths) hipLaunchKernelGGL((d2q9_deep_twin<kDeepSteps, false, true, 0, true>), pgrid, pblock, 0, st, a, partials, s.nb_total, nlev);
-    else hipLaunchKernelGGL((d2q9_deep_twin<kDeepSteps, false, false, 0, true>), pgrid, pblock, 0, st, a, partials, s.nb_total, nlev);
-    return;
+  if (f != DEEP_LONE_PUSH) {
+    a.units_per_band = a0.units_per_band / 2;  // chunk pairs x strips
+    block = dim3(128);
   }
-  const dim3 grid(a0.edge_units + s.f6_main.units), block(64);
-  if (nt && paths && c->steady != 0 && nlev == 8) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, true, true, true, 8>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt && paths && c->steady != 0 && nlev == 7) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, true, true, true, 7>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt && paths && c->steady != 0 && nlev == 6) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, true, true, true, 6>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt && paths) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, true, true, true>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, true, false, true>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (paths) hipLaunchKernelGGL((d2q9_deep<kDeepSteps, false, true, true>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else hipLaunchKernelGGL((d2q9_deep<kDeepSteps, false, false, true>), grid, block, 0, st, a, partials, s.nb_total, nlev);
+  hipLaunchKernelGGL(deep_kernel(f, p, nlev), grid, block, 0, st, a, partials, s.nb_total, nlev);
 }
 
-void launch_deep_twin(const lbm_ctx *c, const Slab &s, const Step2Args &a0, float *partials, int nlev, hipStream_t st) {
+// one slab: d2q9_deep as chunk pairs over Slab::f6_twin
+void launch_deep_twin(const lbm_ctx *c, const LaunchPlan &p, const Slab &s, const Step2Args &a0, float *partials, int nlev, hipStream_t st) {
   Step2Args a = a0;
   a.strips = s.f6_twin.vstrips > 0 ? s.f6_twin.vstrips : s.strips_tw;
   a.strips_edge = s.strips_tw;
   a.lanes_out = s.lanes_tw;
   a.units_per_band = a0.units_per_band / 2;  // chunk pairs x strips
-  const dim3 grid(s.f6_twin.units / 2), block(128);
-  const bool nt = nt_effective(c), paths = c->obst_paths != 0;
-  if (twin_cap(c) <= kDeepTwinDefault) {
-    // all windows in LDS, no mailbox, 2 halo lanes per side
-    if (nt && paths && c->steady != 0 && nlev == kDeepTwinDefault) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinDefault, true, true, kDeepTwinDefault>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-    else if (!nt && paths && c->steady != 0 && nlev == kDeepTwinDefault) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinDefault, false, true, kDeepTwinDefault>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-    else if (nt && paths) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinDefault, true, true>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-    else if (nt) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinDefault, true, false>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-    else if (paths) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinDefault, false, true>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-    else hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinDefault, false, false>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-    return;
+  if (p.twin_depth > kDeepTwinDefault) {  // (up to five steps: all windows in LDS, no mailbox, 2 halo lanes per side — and no map)
+    a.clean_bits = clean_bits_for(c, s, s.f6_twin);  // (eight-step twins run d2q9_deep's strips: strips_tw == strips2)
+    a.clean_words = s.clean_words;
   }
-  a.clean_bits = clean_bits_for(c, s, s.f6_twin);  // (eight-step twins run d2q9_deep's strips: strips_tw == strips2)
-  a.clean_words = s.clean_words;
-  if (nt && paths && c->steady != 0 && nlev == kDeepTwinSteps) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinSteps, true, true, kDeepTwinSteps>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt && paths && c->steady != 0 && nlev == 7) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinSteps, true, true, 7>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt && paths && c->steady != 0 && nlev == 6) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinSteps, true, true, 6>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt && paths) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinSteps, true, true>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (nt) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinSteps, true, false>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else if (paths) hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinSteps, false, true>), grid, block, 0, st, a, partials, s.nb_total, nlev);
-  else hipLaunchKernelGGL((d2q9_deep_twin<kDeepTwinSteps, false, false>), grid, block, 0, st, a, partials, s.nb_total, nlev);
+  hipLaunchKernelGGL(deep_kernel(p.twin_depth > kDeepTwinDefault ? DEEP_TWIN8 : DEEP_TWIN5, p, nlev), dim3(s.f6_twin.units / 2), dim3(128), 0, st, a,
+                     partials, s.nb_total, nlev);
 }
 
+// compact launch set of the three- / four-step kernels: edge units first, then the interior units, one launch
 void launch_compact(int level, bool paired, const Step2Args &a0, float *partials3, float *partials4, int main_units, hipStream_t st) {
   Step2Args a = a0;
   if (paired) {
@@ -1549,6 +1628,304 @@ int exchange_halos(lbm_ctx *c, int buf, int evq, bool on_main = false, bool stag
   return LBM_OK;
 }
 
+// ---- the step loop: run_steps_impl drives these pieces, each a function of (context, plan, set, slab) ----
+// one launch set of a run
+struct SetState {
+  int src = 0;               // grid the set reads (it writes src ^ 1)
+  int kind = KIND_SINGLE, adv = 1;
+  bool last = false;         // the run ends with this set: no exchange, no acceleration of the next step
+  int q = 0, qp = 1;         // event parity of this launch set / of the previous one
+  bool compact_set = false;  // issued as ONE launch per slab (a compact context's leftover two- and single-step sets are not)
+  bool stale_set = false;    // test hook: its exchange is the stale one — no fused push; a flags-only launch follows it
+};
+// the steps buffered in the ring of partial sums
+struct RunState {
+  int batch_first;             // first step of the batch
+  int batch_kind = KIND_NONE;  // launch kind of the batch (the slot occupancy differs)
+  int last_q = 1;
+};
+
+// lbm_run_profiled: timing events around the launches of the first local slab
+int mark(lbm_ctx *c, const Slab &s, int which, hipStream_t st) {
+  if (c->prof_sets < 0 || c->prof_sets >= kProfSets || &s != &c->slabs[0]) return LBM_OK;
+  HIP_TRY(hipEventRecord(c->prof_ev[(size_t)c->prof_sets * kProfEvents + which], st));
+  return LBM_OK;
+}
+
+// second reduction stage over the buffered steps of all slabs (kernels.cl:234-290 counterpart)
+int flush(lbm_ctx *c, const LaunchPlan &p, RunState &run) {
+  const int fill = c->ring_fill;
+  if (fill == 0) return LBM_OK;
+  const bool two_stream = p.form == FORM_TWO_STREAM;
+  for (Slab &s : c->slabs) {
+    if (set_dev(s)) return LBM_ERR_HIP;
+    if (two_stream) HIP_TRY(hipStreamWaitEvent(s.s_main, s.ev_edgek[run.last_q], 0));
+    hipLaunchKernelGGL(reduce_partials, dim3(fill), dim3(kBlock), 0, s.s_main, s.partials, s.nb_total, set_geom(p, s, run.batch_kind).used,
+                       s.av_sum + run.batch_first);
+    HIP_TRY(hipGetLastError());
+    if (two_stream) {
+      // the next batch's edge launches overwrite ring slots: order them after this reduction
+      HIP_TRY(hipEventRecord(s.ev_aux, s.s_main));
+      HIP_TRY(hipStreamWaitEvent(s.s_edge, s.ev_aux, 0));
+    }
+  }
+  run.batch_first += fill;
+  c->ring_fill = 0;
+  return LBM_OK;
+}
+
+// prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53; later steps get theirs fused into the
+// previous launch's write of row ny-2), the halos of the initial state, the start of the clock
+int run_prologue(lbm_ctx *c, const LaunchPlan &p, bool timed) {
+  const float aw1 = c->p.density * c->p.accel / 9.0f, aw2 = c->p.density * c->p.accel / 36.0f;
+  const int nx = c->p.nx;
+  for (Slab &s : c->slabs) {
+    if (set_dev(s)) return LBM_ERR_HIP;
+    if (p.multi) HIP_TRY(hipStreamSynchronize(s.s_edge));
+    if (s.accel_own >= 0) {
+      hipLaunchKernelGGL(accelerate_row, dim3(div_up(nx, 128)), dim3(128), 0, s.s_main, s.cells[c->cur], s.plane_stride,
+                         s.row_stride, s.mask, nx, s.accel_own, aw1, aw2);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (p.multi) {
+    // halos of the initial state ("launch set -1", event parity 1)
+    for (Slab &s : c->slabs) {
+      if (set_dev(s)) return LBM_ERR_HIP;
+      HIP_TRY(hipEventRecord(s.ev_main[1], s.s_main));
+      HIP_TRY(hipEventRecord(s.ev_edgek[1], s.s_main));
+      HIP_TRY(hipStreamWaitEvent(s.s_edge, s.ev_main[1], 0));
+    }
+    if (int rc = exchange_halos(c, c->cur, 1, p.compact())) return rc;  // (compact launch sets: everything on the main stream)
+    if (p.staged())  // the first launch is ordered behind this exchange as every later one behind its predecessor's
+      for (Slab &s : c->slabs) {
+        if (set_dev(s)) return LBM_ERR_HIP;
+        HIP_TRY(hipEventRecord(s.ev_edgek[1], s.s_edge));
+      }
+  }
+  if (timed)
+    for (Slab &s : c->slabs) {
+      if (set_dev(s)) return LBM_ERR_HIP;
+      if (p.multi && (!p.compact() || p.staged())) {
+        // start the clock on the main stream once the initial halos have landed
+        HIP_TRY(hipEventRecord(s.ev_aux, s.s_edge));
+        HIP_TRY(hipStreamWaitEvent(s.s_main, s.ev_aux, 0));
+      }
+      HIP_TRY(hipEventRecord(s.ev_t0, s.s_main));
+    }
+  return LBM_OK;
+}
+
+// One launch of a window kernel — two-, three-, four-step or deep (lone form, or the pairs of one slab) — over schedule g, whose
+// units' ring slots start `off` slots behind the set's first.  `paired`: launch form of the three- / four-step kernels (an edge
+// launch takes it from the interior schedule); `skip`: the chunk of an edge schedule that does nothing.
+void launch_window(const lbm_ctx *c, const LaunchPlan &p, const Slab &s, const SetState &t, const FuseGeom &g, bool paired, int skip, float *slot1,
+                   int off, hipStream_t st) {
+  Step2Args a = base_args2(c, s, t.src, !t.last, g);
+  a.skip_chunk = skip;
+  float *s1 = slot1 + off, *s2 = s1 + s.nb_total, *s3 = s2 + s.nb_total, *s4 = s3 + s.nb_total;
+  if (t.kind == KIND_DEEP) {
+    if (p.twin) launch_deep_twin(c, p, s, a, s1, t.adv, st);
+    else launch_deep(c, p, s, g, a, s1, t.adv, st);
+    return;
+  }
+  a.partials1 = s1;
+  a.partials2 = s2;
+  if (t.kind == KIND_FUSED4) launch_step4(a, s3, s4, g.units, st, paired);
+  else if (t.kind == KIND_FUSED3) launch_step3(a, s3, g.units, st, paired);
+  else launch_step2(c, a, g.units, st);
+}
+
+// d2q9_multi with halo rows: edge = the tile rows that hold the halo_depth bottom and top rows (what the neighbours receive) —
+// tile row 0 and the tile rows from t_top up; interior = tile rows 1 .. t_top-1
+struct TileSplit { int t_top, edge_trows, int_trows; };
+TileSplit multi_split(const Slab &s) {
+  const int m = s.m_tiles_y, t_top = std::max(1, std::min(m, (s.rows - s.edge_rows) / s.m_ty));
+  return {t_top, 1 + (m - t_top), t_top - 1};
+}
+
+// a slab without halo rows: one launch on the main stream
+int issue_one_slab(lbm_ctx *c, const LaunchPlan &p, const SetState &t, Slab &s, float *slot1) {
+  if (int rc = mark(c, s, 3, s.s_main)) return rc;
+  if (t.kind == KIND_RESIDENT) {
+    launch_resident(c, s, t.src, t.adv, !t.last, slot1, s.s_main);
+  } else if (t.kind == KIND_MULTI) {
+    MultiArgs a = base_args_multi(c, s, t.src, t.adv, !t.last);
+    a.partials = slot1;
+    a.ty_begin = 0; a.ty_split = s.m_tiles_y; a.ty_begin2 = 0;
+    launch_multi(s, a, s.m_tiles_y, s.s_main);
+  } else if (t.kind == KIND_SINGLE) {
+    StepArgs a = base_args(c, s, t.src, !t.last);
+    a.y_begin = 0; a.y_count = s.rows; a.y_split = s.rows; a.y_begin2 = 0;
+    a.partials = slot1;
+    launch_step(c, a, s.nb_main, s.s_main);
+  } else {
+    const FuseGeom &g = *set_geom(p, s, t.kind).main;
+    launch_window(c, p, s, t, g, g.paired, -1, slot1, 0, s.s_main);
+  }
+  HIP_TRY(hipGetLastError());
+  return mark(c, s, 4, s.s_main);
+}
+
+// the peer fields MultiArgs and Step2Args share: where the edge units push, whether the launch itself waits for the latest
+// exchange (halo_sync 2), and — unless the run ends here or the set's exchange is the stale one — the push of this set's halo rows
+template <class Args>
+void arm_peer(Args &a, const lbm_ctx *c, const SetState &t, HaloPeer *peer, bool wait_in_kernel) {
+  a.peer = peer;
+  if (wait_in_kernel) {
+    a.peer_mode |= 2;
+    a.wait_seq = c->halo_seq;
+  }
+  if (!t.last && !t.stale_set) {
+    a.peer_mode |= 1;
+    a.peer_buf = t.src ^ 1;
+    a.seq = c->halo_seq + 1;
+  }
+}
+
+// Compact launch set: wait for the neighbours' rows of the latest exchange, then ONE launch on the main stream — the edge tile
+// rows / edge chunks first (they push this set's halo rows and raise the flags), then the interior.  Staged sets (RCCL) wait for
+// the previous set's exchange on the edge stream instead of the flag words — its received rows are this launch's halo rows, its
+// sent blocks the ones this launch's edge units overwrite — push into the local staging blocks, and never publish flags-only.
+int issue_compact(lbm_ctx *c, const LaunchPlan &p, const SetState &t, Slab &s, float *slot1) {
+  const bool staged = p.staged();
+  if (staged) HIP_TRY(hipStreamWaitEvent(s.s_main, s.ev_edgek[t.qp], 0));
+  else if (c->halo_sync != 2)
+    if (int rc = wait_halos(c, s, s.s_main, c->halo_seq)) return rc;
+  HaloPeer *peer = staged ? s.d_stage_peer : s.d_peer;
+  const bool wait_in_kernel = c->halo_sync == 2 && !staged;
+  if (int rc = mark(c, s, 3, s.s_main)) return rc;
+  if (t.kind == KIND_MULTI) {
+    const TileSplit ts = multi_split(s);
+    MultiArgs a = base_args_multi(c, s, t.src, t.adv, !t.last);
+    a.partials = slot1;
+    a.ty_begin = 0; a.ty_split = 1; a.ty_begin2 = ts.t_top;   // workgroup rows 1 .. edge_trows-1: tile rows t_top ..
+    a.ty_split2 = ts.edge_trows; a.ty_begin3 = 1;             // then the interior tile rows 1 .. t_top-1
+    a.edge_blocks = ts.edge_trows * s.m_tiles_x;
+    arm_peer(a, c, t, peer, wait_in_kernel);
+    launch_multi(s, a, s.m_tiles_y, s.s_main, true);
+  } else {
+    const SetGeom g = set_geom(p, s, t.kind);
+    Step2Args a = base_args2(c, s, t.src, !t.last, *g.main);
+    a.edge_chunk_start = g.edge->chunk_start;
+    a.edge_nchunks = g.edge->nchunks;
+    a.edge_units = g.edge->units;
+    a.edge_skip = g.edge->skip;
+    a.edge_partial_off = g.main->units;
+    arm_peer(a, c, t, peer, wait_in_kernel);
+    if (t.kind == KIND_DEEP) {
+      launch_deep_compact(c, p, s, a, slot1, t.adv, s.s_main);
+    } else {
+      float *slot2 = slot1 + s.nb_total, *slot3 = slot2 + s.nb_total;
+      a.partials1 = slot1;
+      a.partials2 = slot2;
+      launch_compact(t.kind == KIND_FUSED4 ? 4 : 3, g.main->paired, a, slot3, slot3 + s.nb_total, g.main->units, s.s_main);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  if (t.stale_set && !staged)
+    if (int rc = publish_flags_only(c, s, c->halo_seq + 1, s.s_main)) return rc;
+  return mark(c, s, 4, s.s_main);
+}
+
+// Slab mode on two streams: edge rows first (they feed the neighbours), interior meanwhile.  The edge launch's ring slots lie
+// behind the interior's.  (A compact run gets here with the leftover steps at its end only: no exchange follows, both launches
+// go to the main stream one after the other.)
+int issue_two_stream(lbm_ctx *c, const LaunchPlan &p, const SetState &t, Slab &s, float *slot1) {
+  const bool compact = p.compact();
+  const hipStream_t s_edge = compact ? s.s_main : s.s_edge;
+  // edge launch: needs the previous set's halos (edge stream order; with the peer transport the neighbours'
+  // pushes of the latest exchange, announced in this slab's flag words) and interior (event)
+  if (c->transport_eff == TRANSPORT_PEER)
+    if (int rc = wait_halos(c, s, s_edge, c->halo_seq)) return rc;
+  if (p.staged()) HIP_TRY(hipStreamWaitEvent(s.s_main, s.ev_edgek[t.qp], 0));  // (the previous set's exchange ran on the edge stream)
+  if (!compact) {
+    HIP_TRY(hipStreamWaitEvent(s.s_edge, s.ev_main[t.qp], 0));
+    // interior launch: needs the previous set's edge rows
+    HIP_TRY(hipStreamWaitEvent(s.s_main, s.ev_edgek[t.qp], 0));
+  }
+  if (int rc = mark(c, s, 0, s_edge)) return rc;
+  if (!compact)
+    if (int rc = mark(c, s, 3, s.s_main)) return rc;
+  if (t.kind == KIND_MULTI) {
+    const TileSplit ts = multi_split(s);
+    MultiArgs e = base_args_multi(c, s, t.src, t.adv, !t.last);
+    e.partials = slot1 + (size_t)ts.int_trows * s.m_tiles_x;
+    e.ty_begin = 0; e.ty_split = 1; e.ty_begin2 = ts.t_top;
+    launch_multi(s, e, ts.edge_trows, s_edge);
+    HIP_TRY(hipGetLastError());
+    if (ts.int_trows > 0) {
+      MultiArgs mm = base_args_multi(c, s, t.src, t.adv, !t.last);
+      mm.partials = slot1;
+      mm.ty_begin = 1; mm.ty_split = ts.int_trows; mm.ty_begin2 = 0;
+      launch_multi(s, mm, ts.int_trows, s.s_main);
+      HIP_TRY(hipGetLastError());
+    }
+  } else if (t.kind == KIND_SINGLE) {
+    StepArgs e = base_args(c, s, t.src, !t.last);
+    e.y_begin = s.row0; e.y_count = 2 * s.edge_rows; e.y_split = s.edge_rows; e.y_begin2 = s.row0 + s.rows - s.edge_rows;
+    e.partials = slot1 + s.nb_main;
+    launch_step(c, e, s.nb_edge, s_edge);
+    HIP_TRY(hipGetLastError());
+    if (s.rows > 2 * s.edge_rows) {
+      StepArgs m = base_args(c, s, t.src, !t.last);
+      m.y_begin = s.row0 + s.edge_rows; m.y_count = s.rows - 2 * s.edge_rows; m.y_split = m.y_count; m.y_begin2 = 0;
+      m.partials = slot1;
+      launch_step(c, m, s.nb_main, s.s_main);
+      HIP_TRY(hipGetLastError());
+    } else {
+      HIP_TRY(hipMemsetAsync(slot1, 0, sizeof(float) * s.nb_main, s.s_main));
+    }
+  } else {
+    // the window kernels: the edge schedule's chunk table is {bottom edge rows, (interior), top edge rows}
+    const SetGeom g = set_geom(p, s, t.kind);
+    launch_window(c, p, s, t, *g.edge, g.main->paired, g.edge->skip, slot1, g.main->units, s_edge);
+    HIP_TRY(hipGetLastError());
+    if (g.main->units > 0) {
+      launch_window(c, p, s, t, *g.main, g.main->paired, -1, slot1, 0, s.s_main);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (!compact) {
+    HIP_TRY(hipEventRecord(s.ev_edgek[t.q], s.s_edge));
+    HIP_TRY(hipEventRecord(s.ev_main[t.q], s.s_main));
+  }
+  if (int rc = mark(c, s, 1, s_edge)) return rc;
+  return mark(c, s, 4, s.s_main);
+}
+
+// what follows the launches of a set on every slab: its halo exchange and the count of exchanges
+int finish_set(lbm_ctx *c, const LaunchPlan &p, const SetState &t) {
+  if (t.compact_set && p.staged()) {
+    // the exchange of a staged set: the edge stream waits for the words the set's last edge wave raises, then RCCL sends the
+    // staging blocks and receives into the halo rows of the grid the set has written — beside the set's interior units
+    if (!t.last) {
+      c->halo_seq++;
+      if (!t.stale_set) {  // (test hook: no push, no exchange — the next set reads what its halo rows held before)
+        for (Slab &s : c->slabs) {
+          if (set_dev(s)) return LBM_ERR_HIP;
+          HIP_TRY(hipStreamWaitValue32(s.s_edge, s.halo_flags + 4, c->halo_seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
+          HIP_TRY(hipStreamWaitValue32(s.s_edge, s.halo_flags + 5, c->halo_seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
+        }
+        if (int rc = exchange_halos(c, t.src ^ 1, t.q, false, true)) return rc;
+      }
+      for (Slab &s : c->slabs) {
+        if (set_dev(s)) return LBM_ERR_HIP;
+        HIP_TRY(hipEventRecord(s.ev_edgek[t.q], s.s_edge));
+      }
+    }
+    return mark(c, c->slabs[0], 2, c->slabs[0].s_edge);
+  }
+  if (t.compact_set) {
+    if (!t.last) c->halo_seq++;  // the edge units of this set's launches have pushed exchange number halo_seq
+    return LBM_OK;
+  }
+  if (!p.multi) return LBM_OK;
+  if (!t.last)
+    if (int rc = exchange_halos(c, t.src ^ 1, t.q, p.compact())) return rc;
+  return mark(c, c->slabs[0], 2, p.compact() ? c->slabs[0].s_main : c->slabs[0].s_edge);
+}
+
 int run_steps_impl(lbm_ctx *c, int nsteps, bool timed, double *ms, bool *launched) {
   if (nsteps < 0) return fail(LBM_ERR_ARG, "nsteps must be >= 0");
   if (c->failed) return fail(LBM_ERR_STATE, "an earlier run failed after its launches had begun; destroy the context");
@@ -1559,415 +1936,38 @@ int run_steps_impl(lbm_ctx *c, int nsteps, bool timed, double *ms, bool *launche
                 c->steps_done, nsteps);
   if (timed && ms) *ms = 0.0;
   if (nsteps == 0) return LBM_OK;
-  const bool multi = c->halo_mode;
-  const int fuse_lvl = fuse_level(c);
-  const bool fuse = fuse_lvl != 0;
-  const float aw1 = c->p.density * c->p.accel / 9.0f, aw2 = c->p.density * c->p.accel / 36.0f;
-  const int nx = c->p.nx;
-
-  // prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53); later
-  // steps get theirs fused into the previous launch's write of row ny-2
+  const LaunchPlan plan = resolve_plan(c);
   *launched = true;
-  for (Slab &s : c->slabs) {
-    if (set_dev(s)) return LBM_ERR_HIP;
-    if (multi) HIP_TRY(hipStreamSynchronize(s.s_edge));
-    if (s.accel_own >= 0) {
-      hipLaunchKernelGGL(accelerate_row, dim3(div_up(nx, 128)), dim3(128), 0, s.s_main, s.cells[c->cur], s.plane_stride,
-                         s.row_stride, s.mask, nx, s.accel_own, aw1, aw2);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  // compact launch sets (small slabs, peer transport): everything on the main stream
-  const bool compact = compact_sets(c);
-  const bool staged = staged_sets(c);  // (a compact form: the pushes go to local staging blocks, the exchange is RCCL's on the edge stream)
-  if (multi) {
-    // halos of the initial state ("launch set -1", event parity 1)
-    for (Slab &s : c->slabs) {
-      if (set_dev(s)) return LBM_ERR_HIP;
-      HIP_TRY(hipEventRecord(s.ev_main[1], s.s_main));
-      HIP_TRY(hipEventRecord(s.ev_edgek[1], s.s_main));
-      HIP_TRY(hipStreamWaitEvent(s.s_edge, s.ev_main[1], 0));
-    }
-    if (int rc = exchange_halos(c, c->cur, 1, compact)) return rc;
-    if (staged)  // the first launch is ordered behind this exchange as every later one behind its predecessor's
-      for (Slab &s : c->slabs) {
-        if (set_dev(s)) return LBM_ERR_HIP;
-        HIP_TRY(hipEventRecord(s.ev_edgek[1], s.s_edge));
-      }
-  }
-  if (timed)
-    for (Slab &s : c->slabs) {
-      if (set_dev(s)) return LBM_ERR_HIP;
-      if (multi && (!compact || staged)) {
-        // start the clock on the main stream once the initial halos have landed
-        HIP_TRY(hipEventRecord(s.ev_aux, s.s_edge));
-        HIP_TRY(hipStreamWaitEvent(s.s_main, s.ev_aux, 0));
-      }
-      HIP_TRY(hipEventRecord(s.ev_t0, s.s_main));
-    }
+  if (int rc = run_prologue(c, plan, timed)) return rc;
 
-  // d2q9_deep as chunk pairs: one slab without halo rows whose pair schedule is one round of units (all slabs alike)
-  const bool deep_lvl = fuse_lvl >= kDeepMin || slab_twin5(c);  // the deep window kernels (slab_twin5: their five-step pairs in compact launch sets)
-  const bool deep_twin = fuse_lvl >= kDeepMin && deep_twin_effective(c);
-  int batch_first = c->steps_done;
-  enum { KIND_NONE = 0, KIND_SINGLE = 1, KIND_FUSED2 = 2, KIND_MULTI = 3, KIND_FUSED3 = 4, KIND_FUSED4 = 5, KIND_DEEP = 6, KIND_RESIDENT = 7 };
-  const bool resident = resident_effective(c);
-  int batch_kind = KIND_NONE;  // launch kind of the steps buffered in the ring (their slot occupancy differs)
-  int last_q = 1;
-  const int multi_T = multistep_effective(c);
-  // second reduction stage over the buffered steps of all slabs (kernels.cl:234-290 counterpart)
-  auto flush = [&]() -> int {
-    const int fill = c->ring_fill;
-    if (fill == 0) return LBM_OK;
-    for (Slab &s : c->slabs) {
-      if (set_dev(s)) return LBM_ERR_HIP;
-      if (multi && !compact) HIP_TRY(hipStreamWaitEvent(s.s_main, s.ev_edgek[last_q], 0));
-      int used = s.nb_main + s.nb_edge;
-      if (batch_kind == KIND_FUSED2) used = s.f_main.units + (multi ? s.f_edge.units : 0);
-      if (batch_kind == KIND_FUSED3) used = s.f3_main.units + (multi ? s.f_edge.units : 0);
-      if (batch_kind == KIND_FUSED4) used = s.f4_main.units + (multi ? s.f_edge.units : 0);
-      if (batch_kind == KIND_DEEP) used = deep_twin ? s.f6_twin.units : s.f6_main.units + (multi ? s.f6_edge.units : 0);
-      if (batch_kind == KIND_MULTI) used = s.m_tiles_x * s.m_tiles_y;
-      if (batch_kind == KIND_RESIDENT) used = s.res_bands * s.res_w;
-      hipLaunchKernelGGL(reduce_partials, dim3(fill), dim3(kBlock), 0, s.s_main, s.partials, s.nb_total, used,
-                         s.av_sum + batch_first);
-      HIP_TRY(hipGetLastError());
-      if (multi && !compact) {
-        // the next batch's edge launches overwrite ring slots: order them after this reduction
-        HIP_TRY(hipEventRecord(s.ev_aux, s.s_main));
-        HIP_TRY(hipStreamWaitEvent(s.s_edge, s.ev_aux, 0));
-      }
-    }
-    batch_first += fill;
-    c->ring_fill = 0;
-    return LBM_OK;
-  };
-
-  // lbm_run_profiled: timing events around the launches of the first local slab
-  auto mark = [&](const Slab &s, int which, hipStream_t st) -> int {
-    if (c->prof_sets < 0 || c->prof_sets >= kProfSets || &s != &c->slabs[0]) return LBM_OK;
-    HIP_TRY(hipEventRecord(c->prof_ev[(size_t)c->prof_sets * kProfEvents + which], st));
-    return LBM_OK;
-  };
+  RunState run{c->steps_done};
   int i = 0, set = 0;
   while (i < nsteps) {
-    const int src = c->cur;
     // timesteps advanced by this launch set, and with which kernel
-    int kind = KIND_SINGLE, adv = 1;
-    if (resident) {
-      // all remaining steps in one launch, as far as the ring of per-step partial sums reaches
-      kind = KIND_RESIDENT;
-      adv = std::min(nsteps - i, c->ring);
-    } else if (multi_T > 0) {
-      kind = KIND_MULTI;
-      adv = std::min(multi_T, nsteps - i);
-    } else if (deep_lvl && nsteps - i >= 2) {
-      // the remaining steps in as few launches as possible, of equal depth (every launch moves the whole grid once:
-      // 20 steps = 7+7+6, not 8+8+4)
-      kind = KIND_DEEP;
-      const int cap = deep_twin ? std::min(fuse_lvl, twin_cap(c)) : fuse_lvl;
-      adv = div_up(nsteps - i, div_up(nsteps - i, cap));
-    } else if (fuse_lvl == 4 && nsteps - i >= 4) {
-      kind = KIND_FUSED4;
-      adv = 4;
-    } else if (fuse_lvl >= 3 && nsteps - i >= 3) {
-      kind = KIND_FUSED3;
-      adv = 3;
-    } else if (fuse && nsteps - i >= 2) {
-      kind = KIND_FUSED2;
-      adv = 2;
-    }
-    const bool last = (i + adv == nsteps);
-    const int q = set & 1, qp = q ^ 1;  // event parity of this launch set / of the previous one
-    // (test hook: a compact launch set whose exchange is the stale one runs without the fused push; a flags-only launch follows it)
-    const bool compact_set = multi && compact && (kind == KIND_MULTI || kind == KIND_FUSED3 || kind == KIND_FUSED4 || kind == KIND_DEEP);
-    const bool stale_set = compact_set && !last && stale_exchange_now(c);
-    if (batch_kind != kind || c->ring_fill + adv > c->ring)
-      if (int rc = flush()) return rc;
-    batch_kind = kind;
+    const SetChoice choice = plan_set(plan, nsteps - i);
+    SetState t{c->cur, choice.kind, choice.adv, i + choice.adv == nsteps, set & 1, (set & 1) ^ 1};
+    t.compact_set = plan.compact() && (t.kind == KIND_MULTI || t.kind == KIND_FUSED3 || t.kind == KIND_FUSED4 || t.kind == KIND_DEEP);
+    t.stale_set = t.compact_set && !t.last && stale_exchange_now(c);
+    if (run.batch_kind != t.kind || c->ring_fill + t.adv > c->ring)
+      if (int rc = flush(c, plan, run)) return rc;
+    run.batch_kind = t.kind;
     for (Slab &s : c->slabs) {
-      if (multi && set_dev(s)) return LBM_ERR_HIP;
+      if (plan.multi && set_dev(s)) return LBM_ERR_HIP;
       float *slot1 = s.partials + (size_t)c->ring_fill * s.nb_total;
-      float *slot2 = slot1 + s.nb_total;
-      if (!multi) {
-        if (int rc = mark(s, 3, s.s_main)) return rc;
-        if (kind == KIND_RESIDENT) {
-          launch_resident(c, s, src, adv, !last, slot1, s.s_main);
-        } else if (kind == KIND_MULTI) {
-          MultiArgs a = base_args_multi(c, s, src, adv, !last);
-          a.partials = slot1;
-          a.ty_begin = 0; a.ty_split = s.m_tiles_y; a.ty_begin2 = 0;
-          launch_multi(s, a, s.m_tiles_y, s.s_main);
-        } else if (kind == KIND_DEEP) {
-          if (deep_twin) launch_deep_twin(c, s, base_args2(c, s, src, !last, s.f6_twin), slot1, adv, s.s_main);
-          else launch_deep(c, s, s.f6_main, base_args2(c, s, src, !last, s.f6_main), s.f6_main.units, slot1, adv, s.s_main);
-        } else if (kind == KIND_FUSED4) {
-          Step2Args a = base_args2(c, s, src, !last, s.f4_main);
-          a.partials1 = slot1;
-          a.partials2 = slot2;
-          float *slot3 = slot2 + s.nb_total;
-          launch_step4(c, a, slot3, slot3 + s.nb_total, s.f4_main.units, s.s_main, s.f4_main.paired);
-        } else if (kind == KIND_FUSED3) {
-          Step2Args a = base_args2(c, s, src, !last, s.f3_main);
-          a.partials1 = slot1;
-          a.partials2 = slot2;
-          launch_step3(c, a, slot2 + s.nb_total, s.f3_main.units, s.s_main, s.f3_main.paired);
-        } else if (kind == KIND_FUSED2) {
-          Step2Args a = base_args2(c, s, src, !last, s.f_main);
-          a.partials1 = slot1;
-          a.partials2 = slot2;
-          launch_step2(c, a, s.f_main.units, s.s_main);
-        } else {
-          StepArgs a = base_args(c, s, src, !last);
-          a.y_begin = 0; a.y_count = s.rows; a.y_split = s.rows; a.y_begin2 = 0;
-          a.partials = slot1;
-          launch_step(c, a, s.nb_main, s.s_main);
-        }
-        HIP_TRY(hipGetLastError());
-        if (int rc = mark(s, 4, s.s_main)) return rc;
-        continue;
-      }
-      if (compact && kind == KIND_MULTI) {
-        // ---- compact launch set: wait for the neighbours' rows of the latest exchange, then ONE launch of all tile
-        // rows, the edge tile rows (tile row 0 and the tile rows from t_top up) first; they push this set's halo rows
-        if (c->halo_sync != 2)
-          if (int rc = wait_halos(c, s, s.s_main, c->halo_seq)) return rc;
-        const int m = s.m_tiles_y;
-        const int t_top = std::max(1, std::min(m, (s.rows - s.edge_rows) / s.m_ty));
-        const int edge_trows = 1 + (m - t_top);
-        MultiArgs a = base_args_multi(c, s, src, adv, !last);
-        a.partials = slot1;
-        a.ty_begin = 0; a.ty_split = 1; a.ty_begin2 = t_top;     // workgroup rows 1 .. edge_trows-1: tile rows t_top ..
-        a.ty_split2 = edge_trows; a.ty_begin3 = 1;               // then the interior tile rows 1 .. t_top-1
-        a.edge_blocks = edge_trows * s.m_tiles_x;
-        a.peer = s.d_peer;
-        if (c->halo_sync == 2) {
-          a.peer_mode |= 2;
-          a.wait_seq = c->halo_seq;
-        }
-        if (!last && !stale_set) {
-          a.peer_mode |= 1;
-          a.peer_buf = src ^ 1;
-          a.seq = c->halo_seq + 1;
-        }
-        if (int rc = mark(s, 3, s.s_main)) return rc;
-        launch_multi(s, a, m, s.s_main, true);
-        HIP_TRY(hipGetLastError());
-        if (stale_set)
-          if (int rc = publish_flags_only(c, s, c->halo_seq + 1, s.s_main)) return rc;
-        if (int rc = mark(s, 4, s.s_main)) return rc;
-        continue;
-      }
-      if (compact && kind == KIND_DEEP) {
-        // ---- compact launch set of d2q9_deep: as for the three- / four-step kernels below
-        // (staged: behind the previous set's exchange on the edge stream — its received rows are this launch's halo rows, its
-        // sent blocks the ones this launch's edge units overwrite)
-        if (staged) HIP_TRY(hipStreamWaitEvent(s.s_main, s.ev_edgek[qp], 0));
-        else if (c->halo_sync != 2)
-          if (int rc = wait_halos(c, s, s.s_main, c->halo_seq)) return rc;
-        Step2Args a = base_args2(c, s, src, !last, s.f6_main);
-        a.edge_chunk_start = s.f6_edge.chunk_start;
-        a.edge_nchunks = s.f6_edge.nchunks;
-        a.edge_units = s.f6_edge.units;
-        a.edge_skip = s.f6_edge.skip;
-        a.edge_partial_off = s.f6_main.units;
-        a.peer = staged ? s.d_stage_peer : s.d_peer;
-        if (c->halo_sync == 2 && !staged) {
-          a.peer_mode |= 2;
-          a.wait_seq = c->halo_seq;
-        }
-        if (!last && !stale_set) {
-          a.peer_mode |= 1;
-          a.peer_buf = src ^ 1;
-          a.seq = c->halo_seq + 1;
-        }
-        if (int rc = mark(s, 3, s.s_main)) return rc;
-        launch_deep_compact(c, s, a, slot1, adv, s.s_main);
-        HIP_TRY(hipGetLastError());
-        if (stale_set && !staged)
-          if (int rc = publish_flags_only(c, s, c->halo_seq + 1, s.s_main)) return rc;
-        if (int rc = mark(s, 4, s.s_main)) return rc;
-        continue;
-      }
-      if (compact && (kind == KIND_FUSED4 || kind == KIND_FUSED3)) {
-        // ---- compact launch set of the window kernels: wait for the neighbours' rows of the latest exchange, then ONE
-        // launch — the edge chunks first (they push this set's halo rows and raise the flags), then the interior chunks
-        if (c->halo_sync != 2)
-          if (int rc = wait_halos(c, s, s.s_main, c->halo_seq)) return rc;
-        const int level = kind == KIND_FUSED4 ? 4 : 3;
-        const FuseGeom &g = level == 4 ? s.f4_main : s.f3_main;
-        Step2Args a = base_args2(c, s, src, !last, g);
-        a.partials1 = slot1;
-        a.partials2 = slot2;
-        float *slot3 = slot2 + s.nb_total, *slot4 = slot3 + s.nb_total;
-        a.edge_chunk_start = s.f_edge.chunk_start;
-        a.edge_nchunks = s.f_edge.nchunks;
-        a.edge_units = s.f_edge.units;
-        a.edge_skip = s.f_edge.skip;
-        a.edge_partial_off = g.units;
-        a.peer = s.d_peer;
-        if (c->halo_sync == 2) {
-          a.peer_mode |= 2;
-          a.wait_seq = c->halo_seq;
-        }
-        if (!last && !stale_set) {
-          a.peer_mode |= 1;
-          a.peer_buf = src ^ 1;
-          a.seq = c->halo_seq + 1;
-        }
-        if (int rc = mark(s, 3, s.s_main)) return rc;
-        launch_compact(level, g.paired, a, slot3, slot4, g.units, s.s_main);
-        HIP_TRY(hipGetLastError());
-        if (stale_set)
-          if (int rc = publish_flags_only(c, s, c->halo_seq + 1, s.s_main)) return rc;
-        if (int rc = mark(s, 4, s.s_main)) return rc;
-        continue;
-      }
-      // ---- slab mode: edge rows first (they feed the neighbours), interior meanwhile ----
-      // (a compact run gets here with the leftover steps at its end only: no exchange follows, both launches go to
-      // the main stream one after the other)
-      const hipStream_t s_edge = compact ? s.s_main : s.s_edge;
-      // edge launch: needs the previous set's halos (edge stream order; with the peer transport the neighbours'
-      // pushes of the latest exchange, announced in this slab's flag words) and interior (event)
-      if (c->transport_eff == TRANSPORT_PEER)
-        if (int rc = wait_halos(c, s, s_edge, c->halo_seq)) return rc;
-      if (staged) HIP_TRY(hipStreamWaitEvent(s.s_main, s.ev_edgek[qp], 0));  // (the previous set's exchange ran on the edge stream)
-      if (!compact) {
-        HIP_TRY(hipStreamWaitEvent(s.s_edge, s.ev_main[qp], 0));
-        // interior launch: needs the previous set's edge rows
-        HIP_TRY(hipStreamWaitEvent(s.s_main, s.ev_edgek[qp], 0));
-      }
-      if (int rc = mark(s, 0, s_edge)) return rc;
-      if (!compact)
-        if (int rc = mark(s, 3, s.s_main)) return rc;
-      if (kind == KIND_MULTI) {
-        // edge = the tile rows that hold the halo_depth bottom and top rows (what the neighbours receive):
-        // tile row 0 and the tile rows from t_top up; interior = tile rows 1 .. t_top-1
-        const int m = s.m_tiles_y;
-        const int t_top = std::max(1, std::min(m, (s.rows - s.edge_rows) / s.m_ty));
-        const int edge_trows = 1 + (m - t_top), int_trows = t_top - 1;
-        MultiArgs e = base_args_multi(c, s, src, adv, !last);
-        e.partials = slot1 + (size_t)int_trows * s.m_tiles_x;
-        e.ty_begin = 0; e.ty_split = 1; e.ty_begin2 = t_top;
-        launch_multi(s, e, edge_trows, s_edge);
-        HIP_TRY(hipGetLastError());
-        if (int_trows > 0) {
-          MultiArgs mm = base_args_multi(c, s, src, adv, !last);
-          mm.partials = slot1;
-          mm.ty_begin = 1; mm.ty_split = int_trows; mm.ty_begin2 = 0;
-          launch_multi(s, mm, int_trows, s.s_main);
-          HIP_TRY(hipGetLastError());
-        }
-      } else if (kind == KIND_DEEP) {
-        Step2Args e = base_args2(c, s, src, !last, s.f6_edge);
-        e.skip_chunk = s.f6_edge.skip;  // chunk table {bottom edge rows, (interior), top edge rows}
-        launch_deep(c, s, s.f6_edge, e, s.f6_edge.units, slot1 + s.f6_main.units, adv, s_edge);
-        HIP_TRY(hipGetLastError());
-        if (s.f6_main.units > 0) {
-          launch_deep(c, s, s.f6_main, base_args2(c, s, src, !last, s.f6_main), s.f6_main.units, slot1, adv, s.s_main);
-          HIP_TRY(hipGetLastError());
-        }
-      } else if (kind == KIND_FUSED4) {
-        float *slot3 = slot2 + s.nb_total, *slot4 = slot3 + s.nb_total;
-        Step2Args e = base_args2(c, s, src, !last, s.f_edge);
-        e.skip_chunk = s.f_edge.skip;  // chunk table {bottom edge rows, (interior), top edge rows}
-        e.partials1 = slot1 + s.f4_main.units;
-        e.partials2 = slot2 + s.f4_main.units;
-        launch_step4(c, e, slot3 + s.f4_main.units, slot4 + s.f4_main.units, s.f_edge.units, s_edge, s.f4_main.paired);
-        HIP_TRY(hipGetLastError());
-        if (s.f4_main.units > 0) {
-          Step2Args m = base_args2(c, s, src, !last, s.f4_main);
-          m.partials1 = slot1;
-          m.partials2 = slot2;
-          launch_step4(c, m, slot3, slot4, s.f4_main.units, s.s_main, s.f4_main.paired);
-          HIP_TRY(hipGetLastError());
-        }
-      } else if (kind == KIND_FUSED3) {
-        float *slot3 = slot2 + s.nb_total;
-        Step2Args e = base_args2(c, s, src, !last, s.f_edge);
-        e.skip_chunk = s.f_edge.skip;  // chunk table {bottom edge rows, (interior), top edge rows}
-        e.partials1 = slot1 + s.f3_main.units;
-        e.partials2 = slot2 + s.f3_main.units;
-        launch_step3(c, e, slot3 + s.f3_main.units, s.f_edge.units, s_edge, s.f3_main.paired);
-        HIP_TRY(hipGetLastError());
-        if (s.f3_main.units > 0) {
-          Step2Args m = base_args2(c, s, src, !last, s.f3_main);
-          m.partials1 = slot1;
-          m.partials2 = slot2;
-          launch_step3(c, m, slot3, s.f3_main.units, s.s_main, s.f3_main.paired);
-          HIP_TRY(hipGetLastError());
-        }
-      } else if (kind == KIND_FUSED2) {
-        Step2Args e = base_args2(c, s, src, !last, s.f_edge);
-        e.skip_chunk = s.f_edge.skip;  // chunk table {bottom edge rows, (interior), top edge rows}
-        e.partials1 = slot1 + s.f_main.units;
-        e.partials2 = slot2 + s.f_main.units;
-        launch_step2(c, e, s.f_edge.units, s_edge);
-        HIP_TRY(hipGetLastError());
-        if (s.f_main.units > 0) {
-          Step2Args m = base_args2(c, s, src, !last, s.f_main);
-          m.partials1 = slot1;
-          m.partials2 = slot2;
-          launch_step2(c, m, s.f_main.units, s.s_main);
-          HIP_TRY(hipGetLastError());
-        }
-      } else {
-        StepArgs e = base_args(c, s, src, !last);
-        e.y_begin = s.row0; e.y_count = 2 * s.edge_rows; e.y_split = s.edge_rows; e.y_begin2 = s.row0 + s.rows - s.edge_rows;
-        e.partials = slot1 + s.nb_main;
-        launch_step(c, e, s.nb_edge, s_edge);
-        HIP_TRY(hipGetLastError());
-        if (s.rows > 2 * s.edge_rows) {
-          StepArgs m = base_args(c, s, src, !last);
-          m.y_begin = s.row0 + s.edge_rows; m.y_count = s.rows - 2 * s.edge_rows; m.y_split = m.y_count; m.y_begin2 = 0;
-          m.partials = slot1;
-          launch_step(c, m, s.nb_main, s.s_main);
-          HIP_TRY(hipGetLastError());
-        } else {
-          HIP_TRY(hipMemsetAsync(slot1, 0, sizeof(float) * s.nb_main, s.s_main));
-        }
-      }
-      if (!compact) {
-        HIP_TRY(hipEventRecord(s.ev_edgek[q], s.s_edge));
-        HIP_TRY(hipEventRecord(s.ev_main[q], s.s_main));
-      }
-      if (int rc = mark(s, 1, s_edge)) return rc;
-      if (int rc = mark(s, 4, s.s_main)) return rc;
+      if (int rc = !plan.multi ? issue_one_slab(c, plan, t, s, slot1)
+                   : t.compact_set ? issue_compact(c, plan, t, s, slot1)
+                                   : issue_two_stream(c, plan, t, s, slot1))
+        return rc;
     }
-    if (compact_set && staged) {
-      // the exchange of a staged set: the edge stream waits for the words the set's last edge wave raises, then RCCL sends the
-      // staging blocks and receives into the halo rows of the grid the set has written — beside the set's interior units
-      if (!last) {
-        c->halo_seq++;
-        if (!stale_set) {  // (test hook: no push, no exchange — the next set reads what its halo rows held before)
-          for (Slab &s : c->slabs) {
-            if (set_dev(s)) return LBM_ERR_HIP;
-            HIP_TRY(hipStreamWaitValue32(s.s_edge, s.halo_flags + 4, c->halo_seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
-            HIP_TRY(hipStreamWaitValue32(s.s_edge, s.halo_flags + 5, c->halo_seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
-          }
-          if (int rc = exchange_halos(c, src ^ 1, q, false, true)) return rc;
-        }
-        for (Slab &s : c->slabs) {
-          if (set_dev(s)) return LBM_ERR_HIP;
-          HIP_TRY(hipEventRecord(s.ev_edgek[q], s.s_edge));
-        }
-      }
-      if (int rc = mark(c->slabs[0], 2, c->slabs[0].s_edge)) return rc;
-    } else if (compact_set) {
-      if (!last) c->halo_seq++;     // the edge units of this set's launches have pushed exchange number halo_seq
-    } else if (multi) {
-      if (!last)
-        if (int rc = exchange_halos(c, src ^ 1, q, compact)) return rc;
-      if (int rc = mark(c->slabs[0], 2, compact ? c->slabs[0].s_main : c->slabs[0].s_edge)) return rc;
-    }
+    if (int rc = finish_set(c, plan, t)) return rc;
     if (c->prof_sets >= 0) c->prof_sets++;
     c->cur ^= 1;
-    c->ring_fill += adv;
-    i += adv;
+    c->ring_fill += t.adv;
+    i += t.adv;
     set++;
-    last_q = q;
+    run.last_q = t.q;
   }
-  if (int rc = flush()) return rc;
+  if (int rc = flush(c, plan, run)) return rc;
   c->steps_done += nsteps;
 
   if (timed) {
@@ -3052,46 +3052,36 @@ int lbm_set_option(lbm_ctx *c, const char *key, long value) {
 
 int lbm_get_option(const lbm_ctx *c, const char *key, long *value) {
   if (!c || !key || !value) return fail(LBM_ERR_ARG, "NULL argument");
+  // what the context does is read from its launch plan (a few dozen integer comparisons)
+  const LaunchPlan p = resolve_plan(c);
+  const Slab *s0 = c->slabs.empty() ? nullptr : &c->slabs[0];
   if (!strcmp(key, "variant")) *value = effective_mode(c) + 1;
-  else if (!strcmp(key, "grid_blocks")) *value = c->slabs.empty() ? 0 : c->slabs[0].nb_main;
+  else if (!strcmp(key, "grid_blocks")) *value = s0 ? s0->nb_main : 0;
   else if (!strcmp(key, "nt_stores")) *value = nt_effective(c);
-  else if (!strcmp(key, "fuse")) *value = fuse_level(c) >= 3 ? fuse_level(c) : (fuse_level(c) ? 1 : 0);
-  else if (!strcmp(key, "multistep")) *value = resident_effective(c) ? 0 : multistep_effective(c);
-  else if (!strcmp(key, "resident")) *value = resident_effective(c) ? c->slabs[0].res_bh : 0;  // rows per band, 0 = not in use
+  else if (!strcmp(key, "fuse")) *value = p.fuse_lvl >= 3 ? p.fuse_lvl : (p.fuse_lvl ? 1 : 0);
+  else if (!strcmp(key, "multistep")) *value = p.kind == KIND_MULTI ? p.cap : 0;
+  else if (!strcmp(key, "resident")) *value = p.kind == KIND_RESIDENT ? s0->res_bh : 0;  // rows per band, 0 = not in use
   else if (!strcmp(key, "chunk_rows")) *value = c->chunk_rows;
   else if (!strcmp(key, "windows")) *value = windows_in_lds(c);
-  else if (!strcmp(key, "pair")) *value = c->slabs.empty() ? 0 : slab_twin5(c) ? 1 : (fuse_level(c) >= kDeepMin ? (c->halo_mode ? (compact_sets(c) && c->slabs[0].f6_main.paired) : deep_twin_effective(c)) : fuse_level(c) == 4 ? c->slabs[0].f4_main.paired : c->slabs[0].f3_main.paired);
+  else if (!strcmp(key, "pair")) *value = p.pairs;
   else if (!strcmp(key, "load_bufs")) *value = step3_load_bufs(c);
-  else if (!strcmp(key, "launch_steps")) {
-    // most timesteps one launch (launch set) of the context's main kernel advances
-    const int ms = multistep_effective(c), lvl = fuse_level(c);
-    *value = resident_effective(c) ? c->ring : ms > 0 ? ms : slab_twin5(c) ? kDeepTwinDefault : (lvl >= kDeepMin ? (deep_twin_effective(c) ? std::min(lvl, twin_cap(c)) : lvl) : (lvl >= 3 ? lvl : (lvl ? 2 : 1)));
-  }
-  else if (!strcmp(key, "fuse_units")) *value = c->slabs.empty() ? 0 : ((fuse_level(c) >= kDeepMin || slab_twin5(c)) ? c->slabs[0].f6_main.units + c->slabs[0].f6_edge.units - c->slabs[0].f_edge.units : fuse_level(c) == 4 ? c->slabs[0].f4_main.units : (fuse_level(c) == 3 ? c->slabs[0].f3_main.units : c->slabs[0].f_main.units)) + c->slabs[0].f_edge.units;
+  else if (!strcmp(key, "launch_steps")) *value = p.cap;  // most timesteps one launch (launch set) of the context's main kernel advances
+  else if (!strcmp(key, "fuse_units"))  // interior + edge units of the window family's schedule (the lone kernel's also where its pairs run)
+    *value = !s0 ? 0 : (p.twin ? s0->f6_main.units : set_geom(p, *s0, p.window_kind).main->units) + set_geom(p, *s0, p.window_kind).edge->units;
   else if (!strcmp(key, "transport")) *value = c->transport_eff;
   else if (!strcmp(key, "steady")) *value = c->steady != 0;
   else if (!strcmp(key, "balance")) {
     // strips of the context's deep window kernel that got a second (virtual) strip
-    *value = 0;
-    if (!c->slabs.empty() && fuse_level(c) >= kDeepMin) {
-      const Slab &s0 = c->slabs[0];
-      const FuseGeom &g = (!c->halo_mode && deep_twin_effective(c)) ? s0.f6_twin : s0.f6_main;
-      *value = g.vstrips > 0 ? g.vstrips - s0.strips2 : 0;
-    }
+    const int vstrips = s0 && p.fuse_lvl >= kDeepMin ? set_geom(p, *s0, KIND_DEEP).main->vstrips : 0;
+    *value = vstrips > 0 ? vstrips - s0->strips2 : 0;
   }
-  else if (!strcmp(key, "free_sweeps")) {
-    // are the launches of the context's deep window kernel given the map?
-    *value = 0;
-    if (!c->slabs.empty() && fuse_level(c) >= kDeepMin) {
-      const Slab &s0 = c->slabs[0];
-      *value = clean_bits_for(c, s0, (!c->halo_mode && deep_twin_effective(c)) ? s0.f6_twin : s0.f6_main) != nullptr;
-    }
-  }
+  else if (!strcmp(key, "free_sweeps"))  // are the launches of the context's deep window kernel given the map?
+    *value = s0 && p.fuse_lvl >= kDeepMin && clean_bits_for(c, *s0, *set_geom(p, *s0, KIND_DEEP).main) != nullptr;
   else if (!strcmp(key, "halo_sync")) *value = c->halo_sync;
   else if (!strcmp(key, "halo_timeout_ms")) *value = (long)c->halo_timeout_ms;
   else if (!strcmp(key, "push_release")) *value = c->slabs.empty() ? 0 : push_release_effective(c, c->slabs[0]);
   else if (!strcmp(key, "debug_stale_exchange")) *value = c->stale_exchange;
-  else if (!strcmp(key, "compact")) *value = compact_sets(c);
+  else if (!strcmp(key, "compact")) *value = p.compact();
   else if (!strcmp(key, "halo_depth")) *value = c->halo_mode ? c->halo_depth : 0;
   else if (!strcmp(key, "nslabs")) *value = c->nslabs_global;
   else return fail(LBM_ERR_ARG, "unknown option '%s'", key);
