@@ -39,7 +39,13 @@ $(PKG)/csrc/lbm_ensemble.o: $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/ensemble_ke
 $(PKG)/csrc/lbm_dp.o: $(PKG)/csrc/lbm_dp.cpp $(PKG)/csrc/dp_kernels.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h include/lbm.h
 	$(HIPCC) $(HIPFLAGS) $(LBM_DP_FLAGS) -c $(PKG)/csrc/lbm_dp.cpp -o $@
 
-$(LIB): $(PKG)/csrc/lbm_hip.o $(PKG)/csrc/lbm_deep.o $(PKG)/csrc/lbm_ensemble.o $(PKG)/csrc/lbm_dp.o
+# The double-precision ensembles (lbm_dens_*) are a fifth unit: the member axis of ensemble_kernels.h over the arithmetic of
+# dp_kernels.h, which it includes.  Out of CSRC for the same reason.  LBM_DENS_FLAGS: a measurement build that forces one
+# tile shape (csrc/lbm_dens.cpp, LBM_DENS_TY / LBM_DENS_TMAX / LBM_DENS_THREADS; tools/dp_ensemble_ab.py).
+$(PKG)/csrc/lbm_dens.o: $(PKG)/csrc/lbm_dens.cpp $(PKG)/csrc/dp_ensemble_kernels.h $(PKG)/csrc/dp_kernels.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h include/lbm.h
+	$(HIPCC) $(HIPFLAGS) $(LBM_DENS_FLAGS) -c $(PKG)/csrc/lbm_dens.cpp -o $@
+
+$(LIB): $(PKG)/csrc/lbm_hip.o $(PKG)/csrc/lbm_deep.o $(PKG)/csrc/lbm_ensemble.o $(PKG)/csrc/lbm_dp.o $(PKG)/csrc/lbm_dens.o
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -Wl,-z,defs $^ -o $@ -ldl   # -z defs: a launch of a deep kernel instance that LBM_DEEP_INSTANCES lacks fails HERE
 
 $(EXE): $(PKG)/host/d2q9-bgk.c include/lbm.h $(LIB)

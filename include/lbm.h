@@ -447,6 +447,68 @@ int lbm_dp_get_option(const lbm_dp *d, const char *key, long *value);
 /* Release everything (beside lbm_destroy: d2q9-bgk.c:729-741).  NULL is a no-op. */
 void lbm_dp_destroy(lbm_dp *d);
 
+/*
+ * ---- Double-precision ensembles: N independent fp64 grids of one size, advanced together ------------------------------
+ *
+ * The two families above composed ("dens" = double ensemble): the small grids that are run in numbers, in the precision of
+ * the golden files — a Reynolds-number sweep that has to land on fp64 results.  An ensemble holds N members on the current
+ * device, each with its own run constants (lbm_dparams), obstacle map and state, and advances all of them with one launch
+ * per several timesteps.  The members never interact, and every member computes, bit for bit, what a double-precision
+ * context (lbm_dp_create) computes for the same inputs: cells, av_vels, fields and Reynolds number.  No options, row slabs
+ * or ranks.  The reference has no counterpart: one grid, one in-order queue (d2q9-bgk.c:221-239); each entry point below
+ * stands beside the lbm_ens_ / lbm_dp_ one of the same name and says which call sites that one replaces.  Conventions as at
+ * the top of this file; one host thread drives an ensemble; arrays carry the member index first: cells =
+ * double[n][9][ny][nx], obstacles = int32[n][ny][nx], fields = double[n][ny][nx].
+ */
+typedef struct lbm_dens lbm_dens; /* opaque */
+
+/*
+ * Create a double-precision ensemble of n members on the current HIP device (beside lbm_ens_create / lbm_dp_create:
+ * d2q9-bgk.c:600-710, and the obstacle upload, :205-209).  params[n]: nx, ny and max_iters are the same in all members;
+ * reynolds_dim, density, accel, omega, free_cells_inv are each member's own, in double.  obstacles = int32[n][ny][nx],
+ * borrowed for the duration of the call.  Refused with LBM_ERR_ARG before any device is touched: n < 1 or n > 65535, NULL
+ * pointers, members that differ in nx, ny or max_iters, a grid under 3x3, max_iters under 1, a member's omega or density not
+ * finite and positive or its accel not finite, and members of more than 300 x 1024 cells — up to that size a
+ * double-precision context itself is bound by launch latency; above it use lbm_dp_create.  An ensemble that does not fit the
+ * device's free memory is refused with LBM_ERR_HIP.  On failure *out is NULL.
+ */
+int lbm_dens_create(lbm_dens **out, const lbm_dparams *params, const int32_t *obstacles, int n);
+
+/* Host -> device copy of all members' initial states, double[n][9][ny][nx] (beside lbm_ens_upload / lbm_dp_upload:
+ * d2q9-bgk.c:200-203).  cells == NULL initialises every member's rest state from its own density on the device
+ * (d2q9-bgk.c:529-550).  Resets the step counter.  Synchronises. */
+int lbm_dens_upload(lbm_dens *e, const double *cells);
+
+/* Advance every member by nsteps timesteps (accelerate_flow on row ny-2 + timestep + av_vels reduction each, per member);
+ * asynchronous, repeatable (beside lbm_ens_run / lbm_dp_run: the loop body d2q9-bgk.c:221-238).  A run is cut into the
+ * fewest launches of equal depth.  steps_done + nsteps may not exceed max_iters (LBM_ERR_STATE). */
+int lbm_dens_run(lbm_dens *e, int nsteps);
+
+/* lbm_dens_run + device-side timing: *ms = elapsed time of the whole step loop (prologue and reductions included) measured
+ * with HIP events on the stream the kernels run on (beside lbm_ens_run_timed / lbm_dp_run_timed).  Synchronises. */
+int lbm_dens_run_timed(lbm_dens *e, int nsteps, double *ms);
+
+/* Wait for all queued work (beside lbm_ens_sync / lbm_dp_sync: clFinish, d2q9-bgk.c:239). */
+int lbm_dens_sync(lbm_dens *e);
+
+/* Device -> host (beside lbm_ens_download / lbm_dp_download: d2q9-bgk.c:251-260).  cells_out = double[n][9][ny][nx], the
+ * CURRENT state whatever the step parity; av_vels_out = double[n][steps_done], member m's per-step sum of |u| over its fluid
+ * cells times its own free_cells_inv, in double.  Either may be NULL.  Synchronises. */
+int lbm_dens_download(lbm_dens *e, double *cells_out, double *av_vels_out);
+
+/* Output stage per member on the device in double (beside lbm_ens_final_state / lbm_dp_final_state and lbm_ens_reynolds /
+ * lbm_dp_reynolds: d2q9-bgk.c:787-832, 396-442, 747-752): each field is double[n][ny][nx] and may be NULL, obstacle cells
+ * give 0, 0, 0, density/3; reynolds_out = double[n].  Synchronise. */
+int lbm_dens_final_state(lbm_dens *e, double *u_x, double *u_y, double *u, double *pressure);
+int lbm_dens_reynolds(lbm_dens *e, double *reynolds_out);
+
+/* Steps applied since the last lbm_dens_upload / number of members; -1 for a NULL ensemble. */
+int lbm_dens_steps_done(const lbm_dens *e);
+int lbm_dens_members(const lbm_dens *e);
+
+/* Release everything (beside lbm_ens_destroy / lbm_dp_destroy: d2q9-bgk.c:729-741).  NULL is a no-op. */
+void lbm_dens_destroy(lbm_dens *e);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

@@ -31,6 +31,8 @@ ABI_SYMBOLS = [
     "lbm_dp_create", "lbm_dp_upload", "lbm_dp_upload_obstacles", "lbm_dp_run", "lbm_dp_run_timed", "lbm_dp_sync",
     "lbm_dp_download", "lbm_dp_final_state", "lbm_dp_reynolds", "lbm_dp_steps_done", "lbm_dp_set_option",
     "lbm_dp_get_option", "lbm_dp_destroy",
+    "lbm_dens_create", "lbm_dens_upload", "lbm_dens_run", "lbm_dens_run_timed", "lbm_dens_sync", "lbm_dens_download",
+    "lbm_dens_final_state", "lbm_dens_reynolds", "lbm_dens_steps_done", "lbm_dens_members", "lbm_dens_destroy",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -127,6 +129,18 @@ def load_library():
     L.lbm_dp_get_option.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_long)]
     L.lbm_dp_destroy.argtypes = [vp]
     L.lbm_dp_destroy.restype = None
+    L.lbm_dens_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(DParams), vp, ci]
+    L.lbm_dens_upload.argtypes = [vp, vp]
+    L.lbm_dens_run.argtypes = [vp, ci]
+    L.lbm_dens_run_timed.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_double)]
+    L.lbm_dens_sync.argtypes = [vp]
+    L.lbm_dens_download.argtypes = [vp, vp, vp]
+    L.lbm_dens_final_state.argtypes = [vp, vp, vp, vp, vp]
+    L.lbm_dens_reynolds.argtypes = [vp, vp]
+    L.lbm_dens_steps_done.argtypes = [vp]
+    L.lbm_dens_members.argtypes = [vp]
+    L.lbm_dens_destroy.argtypes = [vp]
+    L.lbm_dens_destroy.restype = None
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -626,6 +640,110 @@ class LBMDouble:
         if self.ctx:
             self.lib.lbm_dp_destroy(self.ctx)
             self.ctx = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sweep_dparams(base, omega=None, accel=None):
+    """The members of a double-precision parameter sweep: copies of the DParams `base` with omega and / or accel replaced
+    from lists of equal length, as Python floats (the fp64 literals, never widened floats)."""
+    count = len(omega if omega is not None else accel)
+    members = []
+    for i in range(count):
+        p = DParams.from_buffer_copy(base)
+        if omega is not None:
+            p.omega = float(omega[i])
+        if accel is not None:
+            p.accel = float(accel[i])
+        members.append(p)
+    return members
+
+
+class EnsembleDouble:
+    """N independent double-precision simulations of one grid size, advanced together (lbm_dens): one launch per several
+    timesteps for all members, every member bit-identical to an LBMDouble on the same inputs.  Mirrors Ensemble with double
+    in place of float.  `params`: a list of DParams that share nx, ny and max_iters (sweep_dparams); `obstacles`:
+    int32[n, ny, nx], or one [ny, nx] map for all members."""
+
+    def __init__(self, params, obstacles):
+        self.lib = load_library()
+        self.params = list(params)
+        self.n = len(self.params)
+        if self.n < 1:
+            raise LBMError("an ensemble needs at least one member")
+        if not all(isinstance(p, DParams) for p in self.params):
+            raise LBMError("EnsembleDouble takes DParams (make_dparams / read_inputs_double / sweep_dparams)")
+        self.nx, self.ny = self.params[0].nx, self.params[0].ny
+        obst = np.asarray(obstacles, dtype=np.int32)
+        if obst.ndim == 2:
+            obst = np.broadcast_to(obst, (self.n,) + obst.shape)
+        obst = np.ascontiguousarray(obst)
+        assert obst.shape == (self.n, self.ny, self.nx)
+        self.obstacles = obst
+        self._params = (DParams * self.n)(*self.params)
+        self.ens = ctypes.c_void_p()
+        _check(self.lib.lbm_dens_create(ctypes.byref(self.ens), self._params, obst.ctypes.data, self.n), "lbm_dens_create")
+
+    def upload(self, cells=None):
+        """cells float64[n, 9, ny, nx]; None = every member's rest state from its own density, on the device"""
+        if cells is None:
+            _check(self.lib.lbm_dens_upload(self.ens, None), "lbm_dens_upload")
+        else:
+            c = np.ascontiguousarray(cells, dtype=np.float64)
+            assert c.shape == (self.n, 9, self.ny, self.nx)
+            _check(self.lib.lbm_dens_upload(self.ens, c.ctypes.data), "lbm_dens_upload")
+
+    def run(self, nsteps):
+        _check(self.lib.lbm_dens_run(self.ens, nsteps), "lbm_dens_run")
+
+    def run_timed(self, nsteps):
+        """Runs nsteps and returns the HIP-event time of the step loop in milliseconds."""
+        ms = ctypes.c_double()
+        _check(self.lib.lbm_dens_run_timed(self.ens, nsteps, ctypes.byref(ms)), "lbm_dens_run_timed")
+        return ms.value
+
+    def sync(self):
+        _check(self.lib.lbm_dens_sync(self.ens), "lbm_dens_sync")
+
+    @property
+    def steps_done(self):
+        return self.lib.lbm_dens_steps_done(self.ens)
+
+    def download(self, cells=True, av_vels=True):
+        """Returns (cells float64[n,9,ny,nx] or None, av_vels float64[n,steps_done] or None)."""
+        steps = self.steps_done
+        c = np.zeros((self.n, 9, self.ny, self.nx), dtype=np.float64) if cells else None
+        a = np.zeros((self.n, steps), dtype=np.float64) if av_vels else None
+        _check(self.lib.lbm_dens_download(self.ens, c.ctypes.data if cells else None,
+                                          a.ctypes.data if av_vels and steps else None), "lbm_dens_download")
+        return c, a
+
+    def final_state(self):
+        """(u_x, u_y, u, pressure), each float64[n,ny,nx] — per member the columns of final_state.dat."""
+        outs = [np.zeros((self.n, self.ny, self.nx), dtype=np.float64) for _ in range(4)]
+        _check(self.lib.lbm_dens_final_state(self.ens, *[o.ctypes.data for o in outs]), "lbm_dens_final_state")
+        return outs
+
+    def reynolds(self):
+        """float64[n]: every member's Reynolds number of the current state"""
+        r = np.zeros(self.n, dtype=np.float64)
+        _check(self.lib.lbm_dens_reynolds(self.ens, r.ctypes.data), "lbm_dens_reynolds")
+        return r
+
+    def close(self):
+        if self.ens:
+            self.lib.lbm_dens_destroy(self.ens)
+            self.ens = ctypes.c_void_p()
 
     def __enter__(self):
         return self

@@ -1,0 +1,286 @@
+// Device side of a DOUBLE-PRECISION ENSEMBLE (include/lbm.h: lbm_dens_*): N independent fp64 grids of one size, each with
+// its own run constants, obstacle map and state, advanced by one launch per (up to) TMAX timesteps.
+//
+// d2q9_dp_ensemble is d2q9_dp_multi (dp_kernels.h) with a member axis, the way d2q9_ensemble (ensemble_kernels.h) is
+// d2q9_multi's: member = blockIdx.y, tile = blockIdx.x; a member's two grids, mask and segment sums lie a member stride
+// apart, in the layout of dp_kernels.h (row-interleaved SoA in double, planes padded to 32 doubles).  x and y wrap inside
+// the member: members never interact.  The per-cell arithmetic is dp_collide_cell / dp_accelerate_cell of dp_kernels.h, so a
+// member's cells are bit-identical to an lbm_dp context on the same inputs; the velocity sum keeps that header's scheme
+// (every 16-cell row segment in one fixed tree, a step's segments added per member by dens_reduce in dp_reduce's order), so
+// a member's av_vels are bit-identical too.
+#pragma once
+#include "dp_kernels.h"
+
+namespace lbm {
+
+// What differs from member to member, in device memory, read by member index (a wave-uniform load), as EnsMember
+struct DensMember {
+  double omega, aw1, aw2;  // aw1 = density*accel/9, aw2 = density*accel/36 (kernels.cl:14-15), in double
+  double density;
+  double w0, w1, w2;       // rest state (d2q9-bgk.c:529-531)
+  double pad;
+};
+
+struct DensArgs {
+  const double *src;         // member m: src + m * member_stride
+  double *dst;
+  const uint8_t *mask;       // member m: mask + m * nx * ny
+  const DensMember *members;
+  double *seg;               // [T][members][ny][nseg]: the segment sums of each of the T steps
+  unsigned long long plane_stride, member_stride;   // row_stride = 9 * plane_stride
+  unsigned long long seg_step;                      // = members * ny * nseg
+  int nx, ny, nseg;
+  int tiles_x;
+  int T;                     // steps in this launch
+  int accel_next;            // apply the following step's accelerate_flow to the final state
+};
+
+// grid = (tiles per member, members), NT threads.  TX x TY output tile, T <= TMAX steps LDS -> LDS on a region that shrinks
+// by one cell per step (d2q9_dp_multi's scheme; halo cells are computed redundantly by the member's neighbouring tiles).
+// Each step's |u| of the tile's cells goes to an LDS tile of its own; one lane per 16-cell segment adds it up in the
+// segment tree of dp_kernels.h while the next step runs.  The body is d2q9_dp_multi's with member offsets, the DensMember
+// load and NT: a change to that kernel's loops has to be mirrored here (tests/test_dp_ensemble_gpu.py pins the bits).
+//
+// Tile shape and depth, measured (tools/dp_ensemble_ab.py, one MI355X, one call; us/step for all members together at
+// 64 x 128x128 / 16 x 256x256, medians of 5 repeats of 2000 steps; as 64 / 16 lbm_dp contexts in the same runs: 37.9 / 30.2;
+// profiles/dp_ensemble_throughput.txt):
+//   16x16, T <= 8, 1024 threads (149 KB of LDS, one workgroup per CU)   28.82 / 28.61
+//   16x8,  T <= 8, 1024 threads (111 KB, one per CU)                    46.29 / 46.08
+//   16x16, T <= 3, 1024 threads ( 73 KB, two per CU, 62 VGPRs)          20.25 / 19.92   <- instantiated
+//   16x16, T <= 3,  512 threads ( 73 KB, two per CU)                    20.61 / 20.22
+//   16x8,  T <= 5,  512 threads ( 68 KB, two per CU)                    27.43 / 27.28
+//   16x8,  T <= 4,  512 threads ( 56 KB, two per CU)                    28.11 / 27.86
+//   16x8,  T <= 3,  512 threads ( 46 KB, three per CU)                  23.53 / 23.20
+// Two workgroups per CU win at either height (one's loads and stores run under the other's sub-steps, and a shallow region
+// recomputes 1.28 x the tile per step against 2.15 x at T = 8); 16x16 at T <= 2 / 1: 25.85 / 51.75 on the first case.  One form
+// serves both sizes.  Ensembles whose tiles all get a CU of their own (<= 256 tiles) run 19-30 % faster at T <= 8 (1 x 128x128
+// 1.95 against 2.40); that form is not instantiated.  0 scratch, 0 spills in all.
+template <int TX, int TY, int TMAX, int NT = kMultiThreads>
+__global__ __launch_bounds__(NT) void d2q9_dp_ensemble(const DensArgs a) {
+  static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
+  static_assert(TY * (TX / kDpSeg) <= NT, "one lane per segment of the tile");
+  constexpr int kRX = TX + 2 * TMAX, kRY = TY + 2 * TMAX;
+  __shared__ double lds[2][9][kRY * kRX];
+  __shared__ uint8_t lmask[kRY * kRX];
+  __shared__ double tval[2][TY][TX];
+  const int tid = threadIdx.x;
+  const int T = a.T;
+  const int RX = TX + 2 * T, RY = TY + 2 * T;
+  const int member = blockIdx.y;
+  const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
+  const int gx0 = tile_x * TX - T, gy0 = tile_y * TY - T;  // region cell (0,0)
+  const size_t ps = a.plane_stride, rs = 9 * ps;
+  const double *const src = a.src + (size_t)member * a.member_stride;
+  double *const dst = a.dst + (size_t)member * a.member_stride;
+  const uint8_t *const mask = a.mask + (size_t)member * ((size_t)a.nx * a.ny);
+  double *const seg_out = a.seg + (size_t)member * ((size_t)a.ny * a.nseg);
+  const DensMember mc = a.members[member];
+  // grid row of region row ry: periodic wrap inside the member (kernels.cl:91-93)
+  auto grid_row = [&](int ry) {
+    int r = (gy0 + ry) % a.ny;
+    return r < 0 ? r + a.ny : r;
+  };
+  // segment sums of step s (1-based) from tval[s & 1]
+  auto store_segments = [&](int s) {
+    constexpr int kSegs = TY * (TX / kDpSeg);
+    if (tid < kSegs) {
+      const int oy = tid / (TX / kDpSeg), sx = tid - oy * (TX / kDpSeg);
+      const int gy = tile_y * TY + oy;
+      const double *v = &tval[s & 1][oy][sx * kDpSeg];
+      double p[8];
+#pragma unroll
+      for (int i = 0; i < 8; i++) p[i] = v[2 * i] + v[2 * i + 1];
+      const double tot = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+      const int seg = tile_x * (TX / kDpSeg) + sx;
+      if (gy < a.ny && seg < a.nseg) seg_out[(size_t)(s - 1) * a.seg_step + (size_t)gy * a.nseg + seg] = tot;
+    }
+  };
+
+  // region -> LDS (periodic wrap in x, kernels.cl:99-102)
+  const float rinv = 1.0f / (float)RX;
+  for (int i = tid; i < RX * RY; i += NT) {
+    const int ry = (int)(((float)i + 0.5f) * rinv), rx = i - ry * RX;
+    int gx = (gx0 + rx) % a.nx;
+    if (gx < 0) gx += a.nx;
+    const int gy = grid_row(ry);
+    const double *p = src + (size_t)gy * rs + gx;
+#pragma unroll
+    for (int k = 0; k < 9; k++) lds[0][k][ry * kRX + rx] = p[k * ps];
+    lmask[ry * kRX + rx] = mask[(size_t)gy * a.nx + gx];
+  }
+  __syncthreads();
+
+  for (int s = 1; s <= T; s++) {
+    if (s > 1) store_segments(s - 1);
+    const int in = (s - 1) & 1, out = s & 1;
+    const int w = RX - 2 * s, h = RY - 2 * s;
+    const bool accel_step = (s < T) || a.accel_next;
+    const float inv = 1.0f / (float)w;
+    for (int i = tid; i < w * h; i += NT) {
+      const int q = (int)(((float)i + 0.5f) * inv);
+      const int rx = s + (i - q * w), ry = s + q;
+      const int c = ry * kRX + rx;
+      double g[9], o[9];
+      g[0] = lds[in][0][c];
+      g[1] = lds[in][1][c - 1];
+      g[2] = lds[in][2][c - kRX];
+      g[3] = lds[in][3][c + 1];
+      g[4] = lds[in][4][c + kRX];
+      g[5] = lds[in][5][c - kRX - 1];
+      g[6] = lds[in][6][c - kRX + 1];
+      g[7] = lds[in][7][c + kRX + 1];
+      g[8] = lds[in][8][c + kRX - 1];
+      const bool obst = lmask[c] != 0;
+      const double t = dp_collide_cell(g, obst, mc.omega, o);
+      if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, mc.aw1, mc.aw2);
+#pragma unroll
+      for (int k = 0; k < 9; k++) lds[out][k][c] = o[k];
+      // the tile's own cells: every one is inside the region of every step; cells past the grid's edge count 0
+      const int ox = rx - T, oy = ry - T;
+      if (ox >= 0 && ox < TX && oy >= 0 && oy < TY)
+        tval[s & 1][oy][ox] = (tile_x * TX + ox < a.nx && tile_y * TY + oy < a.ny) ? t : 0.0;
+    }
+    __syncthreads();
+  }
+  store_segments(T);
+
+  // central tile -> global
+  const int fin = T & 1;
+  for (int i = tid; i < TX * TY; i += NT) {
+    const int oy = i / TX, ox = i - oy * TX;
+    const int gx = tile_x * TX + ox, gy = tile_y * TY + oy;
+    if (gx < a.nx && gy < a.ny) {
+      const int c = (oy + T) * kRX + ox + T;
+      double *d = dst + (size_t)gy * rs + gx;
+#pragma unroll
+      for (int k = 0; k < 9; k++) d[k * ps] = lds[fin][k][c];
+    }
+  }
+}
+
+// ---- second reduction stage with a member axis: dp_reduce's partition and order, fixed, no atomics -------------------
+// grid = (blocks, steps, members): block b of step r of member m adds in[r * in_stride + m * in_member + i] for i in its
+// contiguous chunk (lane-strided, then the wave butterfly, then the four waves in order) into
+// out[m * out_member + r * out_stride + b].  With the block count lbm_dp takes for a grid of the member's ny * nseg this
+// adds a step's segments in the order dp_reduce adds them there: once into av_sum, or twice (partials per block, then one
+// block per step and member).
+static __global__ __launch_bounds__(kBlock) void dens_reduce(const double *in, unsigned long long in_stride,
+                                                             unsigned long long in_member, long n, double *out,
+                                                             unsigned long long out_stride, unsigned long long out_member) {
+  const long chunk = (n + gridDim.x - 1) / gridDim.x;
+  const long i0 = (long)blockIdx.x * chunk, i1 = i0 + chunk < n ? i0 + chunk : n;
+  const double *p = in + (size_t)blockIdx.y * in_stride + (size_t)blockIdx.z * in_member;
+  double acc = 0.0;
+  for (long i = i0 + threadIdx.x; i < i1; i += kBlock) acc += p[i];
+  __shared__ double wsum[kBlock / 64];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = wsum[0];
+    for (int i = 1; i < kBlock / 64; i++) t += wsum[i];
+    out[(size_t)blockIdx.z * out_member + (size_t)blockIdx.y * out_stride + blockIdx.x] = t;
+  }
+}
+
+// ---- the helper kernels of dp_kernels.h with a member axis (blockIdx.y), same per-cell arithmetic --------------------
+
+// accelerate_flow of row ny-2 of every member (kernels.cl:9-53): prologue of a run
+static __global__ void dens_accelerate_row(double *cells, unsigned long long plane_stride, unsigned long long member_stride,
+                                           const uint8_t *mask, const DensMember *members, int nx, int ny) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= nx) return;
+  const DensMember mc = members[blockIdx.y];
+  const int row = ny - 2;
+  double f[9];
+  double *c = cells + (size_t)blockIdx.y * member_stride + (size_t)row * 9 * plane_stride + x;
+#pragma unroll
+  for (int k = 0; k < 9; k++) f[k] = c[k * plane_stride];
+  dp_accelerate_cell(f, mask[(size_t)blockIdx.y * ((size_t)nx * ny) + (size_t)row * nx + x] != 0, mc.aw1, mc.aw2);
+#pragma unroll
+  for (int k = 0; k < 9; k++) c[k * plane_stride] = f[k];
+}
+
+// every member's rest state from its own density (values of d2q9-bgk.c:529-550, computed on the host in double)
+static __global__ void dens_init_cells(double *cells, unsigned long long plane_stride, unsigned long long member_stride,
+                                       const DensMember *members, int nx, size_t n) {
+  const DensMember mc = members[blockIdx.y];
+  cells += (size_t)blockIdx.y * member_stride;
+  for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
+    const size_t y = c / nx;
+    const size_t i = y * 9 * plane_stride + (c - y * nx);
+    cells[i] = mc.w0;
+#pragma unroll
+    for (int k = 1; k <= 4; k++) cells[k * plane_stride + i] = mc.w1;
+#pragma unroll
+    for (int k = 5; k <= 8; k++) cells[k * plane_stride + i] = mc.w2;
+  }
+}
+
+// device layout <-> the caller's double[members][9][ny][nx] (staged in the grid array that is not current, one transfer
+// for the whole ensemble).  TO_DEVICE: flat -> cells, else cells -> flat.
+template <bool TO_DEVICE>
+static __global__ void dens_pack_planes(double *cells, unsigned long long plane_stride, unsigned long long member_stride, int nx,
+                                        size_t n, double *flat) {
+  cells += (size_t)blockIdx.y * member_stride;
+  flat += (size_t)blockIdx.y * 9 * n;
+  for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
+    const size_t y = c / nx;
+    const size_t i = y * 9 * plane_stride + (c - y * nx);
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+      if (TO_DEVICE) cells[k * plane_stride + i] = flat[k * n + c];
+      else flat[k * n + c] = cells[k * plane_stride + i];
+    }
+  }
+}
+
+// output stage per member (dp_final_fields: d2q9-bgk.c:787-832, 396-442, in double, the oracle's statements): outputs are
+// double[members][ny][nx], partials double[members][gridDim.x] — with dp_final_fields' block count the per-block sums of u
+// are those of an lbm_dp context of the member's size, bit for bit
+static __global__ __launch_bounds__(kBlock) void dens_final_fields(const double *cells, unsigned long long plane_stride,
+                                                                   unsigned long long member_stride, int nx, const uint8_t *mask,
+                                                                   size_t n, const DensMember *members, double *u_x, double *u_y,
+                                                                   double *u, double *pressure, double *partials) {
+#pragma clang fp contract(off)
+  const double c_sq = 1.0 / 3.0;
+  const double density = members[blockIdx.y].density;
+  cells += (size_t)blockIdx.y * member_stride;
+  mask += (size_t)blockIdx.y * n;
+  const size_t off = (size_t)blockIdx.y * n;
+  double tot_u = 0.0;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+    double ux = 0.0, uy = 0.0, uu = 0.0, pr = density * c_sq;
+    if (mask[i] == 0) {
+      double f[9];
+      double local_density = 0.0;
+      const size_t y = i / nx;
+      const size_t cell = y * 9 * plane_stride + (i - y * nx);
+#pragma unroll
+      for (int k = 0; k < 9; k++) {
+        f[k] = cells[k * plane_stride + cell];
+        local_density += f[k];
+      }
+      ux = (f[1] + f[5] + f[8] - f[3] - f[6] - f[7]) / local_density;
+      uy = (f[2] + f[5] + f[6] - f[4] - f[7] - f[8]) / local_density;
+      uu = __builtin_sqrt(ux * ux + uy * uy);
+      pr = local_density * c_sq;
+      tot_u += uu;
+    }
+    if (u_x) u_x[off + i] = ux;
+    if (u_y) u_y[off + i] = uy;
+    if (u) u[off + i] = uu;
+    if (pressure) pressure[off + i] = pr;
+  }
+  __shared__ double wsum[kBlock / 64];
+  tot_u = wave_sum(tot_u);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = tot_u;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = wsum[0];
+    for (int i = 1; i < kBlock / 64; i++) t += wsum[i];
+    partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
+  }
+}
+
+}  // namespace lbm

@@ -87,7 +87,8 @@ struct DpStepArgs {
 
 // One timestep, lane = cells x0, x0+1 of one row.  x-1 / x+1 neighbours: aligned 16-B loads plus one scalar load per
 // streamed plane at the wrap column (an L1 hit).  A lane past the row's end (x0 >= nx) only joins the segment sum with 0.
-__global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a) {
+// static, like the helper kernels below: two translation units include this header (lbm_dp.cpp, lbm_dens.cpp).
+static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a) {
   const unsigned t = blockIdx.x * kBlock + threadIdx.x;
   const unsigned lpr = (unsigned)a.lanes_per_row;
   const int y = (int)(t / lpr);
