@@ -19,18 +19,18 @@ all: $(LIB) $(EXE) $(EXE).exe oracle
 # lbm_version() carries a digest of the device + host sources the library was built from: a committed profile
 # (profiles/traffic.json) names the build it measured, and bench.py refuses its counters for any other build
 CSRC   = $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/deep_instances.h $(PKG)/csrc/halo_exchange.h $(PKG)/csrc/lbm_hip.cpp $(PKG)/csrc/lbm_deep.cpp \
-         $(PKG)/csrc/ensemble_kernels.h $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/lbm_error.h
+         $(PKG)/csrc/ensemble_kernels.h $(PKG)/csrc/steady_kernels.h $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/lbm_error.h
 SRC_ID = $(shell cat $(CSRC) | sha256sum | cut -c1-12)
 
 # Three translation units: the deep window kernels get the compiler's max-ILP scheduling strategy (csrc/deep_instances.h says
-# why), everything else the default one; the ensemble entry points (lbm_ens_*) and their kernel are the third.  The objects are build products next to the library (*.o is git-ignored).
+# why), everything else the default one; the ensemble entry points (lbm_ens_*, lbm_steady_*) and their kernels are the third.  The objects are build products next to the library (*.o is git-ignored).
 $(PKG)/csrc/lbm_hip.o: $(CSRC) include/lbm.h
 	$(HIPCC) $(HIPFLAGS) -DLBM_SRC_ID=\"$(SRC_ID)\" -c $(PKG)/csrc/lbm_hip.cpp -o $@
 
 $(PKG)/csrc/lbm_deep.o: $(PKG)/csrc/lbm_deep.cpp $(PKG)/csrc/deep_instances.h $(PKG)/csrc/d2q9_kernels.h
 	$(HIPCC) $(HIPFLAGS) -mllvm -amdgpu-sched-strategy=max-ilp -c $(PKG)/csrc/lbm_deep.cpp -o $@
 
-$(PKG)/csrc/lbm_ensemble.o: $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/ensemble_kernels.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h include/lbm.h
+$(PKG)/csrc/lbm_ensemble.o: $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/ensemble_kernels.h $(PKG)/csrc/steady_kernels.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h include/lbm.h
 	$(HIPCC) $(HIPFLAGS) -c $(PKG)/csrc/lbm_ensemble.cpp -o $@
 
 # The double-precision entry points (lbm_dp_*) and their kernels are a fourth unit.  They stay out of CSRC: the digest names

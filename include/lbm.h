@@ -368,6 +368,57 @@ int lbm_ens_members(const lbm_ens *e);
 void lbm_ens_destroy(lbm_ens *e);
 
 /*
+ * ---- Steady runs: every member of an ensemble to its own steady state, in one call ------------------------------------
+ *
+ * A sweep over omega or accel is run for each member's steady state, and the members reach theirs at very different step
+ * counts.  A steady run advances an ensemble in legs of `window` steps and, after each leg, stops every member whose own
+ * av_vels record has settled.  The decision is taken on the device: a stopped member's workgroups return before they touch
+ * its cells, its state is never written again, and no host round trip separates the legs.  The reference has no
+ * counterpart (one grid, a fixed maxIters: d2q9-bgk.c:221-239).
+ *
+ * Check points.  With s0 = lbm_ens_steps_done(e) at the call, a check point is a step count s = s0 + k * window, k = 1, 2,
+ * ..., with s <= s0 + max_steps and s - window >= 1.  Between check points the members still active advance by `window`
+ * steps exactly as lbm_ens_run(e, window) advances them: the accelerate prologue, the fewest launches of equal depth (at
+ * most 8 steps each), no fused acceleration on the last launch, the partial sums reduced into the record.  If max_steps is
+ * not a multiple of window the last leg is shorter and no check follows it.
+ *
+ * Criterion.  Let A(s) be the float that lbm_ens_download returns for the s-th step of a member,
+ * (float)(av_sum[s - 1] * (double)free_cells_inv).  A member stops at check point s if
+ *     fabs((double)A(s) - (double)A(s - window)) <= rel_tol * fabs((double)A(s)),
+ * evaluated on the device in IEEE double with exactly these operations, the difference and the product as separate
+ * statements without contraction: the host can reproduce every decision from the downloaded record.  A NaN never stops a
+ * member.  A member without a free cell (A = 0 throughout) stops at its first check point.
+ *
+ * The host reads one word back every few legs, the count of active members, and stops enqueuing when it is 0; what a
+ * member computes does not depend on that.  The call returns after a final synchronisation.
+ *
+ * Afterwards lbm_ens_steps_done returns the largest member count; lbm_ens_download, lbm_ens_final_state and
+ * lbm_ens_reynolds return each member's own last state (the two grid arrays are double-buffered and a leg may be an odd
+ * number of launches, so which array holds a member's state is the member's own from then on), and av_vels_out is
+ * float[n][steps_done] with exactly 0.0f at and beyond a member's own count.  If all members ended at the same count the
+ * ensemble is an ordinary one again and lbm_ens_run continues it.  Otherwise lbm_ens_run, lbm_ens_run_timed and
+ * lbm_steady_run answer LBM_ERR_STATE until lbm_ens_upload, which resets counts, parities and flags.
+ *
+ * Limits: fp32 ensembles only (lbm_dens_* has no steady run yet); the record of a step is the launch split's (a leg of 7
+ * steps sums its tiles in another order than a launch of 8, so A(s) agrees with an uninterrupted lbm_ens_run up to
+ * summation order and bit for bit with lbm_ens_run(e, window) repeated); the stopped members' workgroups are still
+ * launched, and return at once.
+ */
+
+/*
+ * Advance every member until ITS OWN av_vels record has settled, at most max_steps steps (beside lbm_ens_run).
+ * Synchronises.  Refused with LBM_ERR_ARG before the ensemble or a device is touched: a NULL ensemble, max_steps < 0,
+ * window < 1, rel_tol negative or not finite.  s0 + max_steps > max_iters, and an ensemble whose members are at different
+ * counts, are answered with LBM_ERR_STATE.  max_steps == 0 is a no-op.  A failure after launches began is handled as in
+ * lbm_ens_run: what was enqueued is drained, and the ensemble accepts only lbm_ens_destroy.
+ */
+int lbm_steady_run(lbm_ens *e, int max_steps, int window, double rel_tol);
+
+/* Per member: steps applied since the last lbm_ens_upload, and whether it met the criterion of the last lbm_steady_run
+ * since then (beside lbm_ens_steps_done).  steps_out = int[n], converged_out = int[n] (1 / 0); either may be NULL. */
+int lbm_steady_steps(lbm_ens *e, int *steps_out /*[n]*/, int *converged_out /*[n]*/);
+
+/*
  * ---- Double precision: one grid in fp64 ------------------------------------------------------------------------------
  *
  * The reference's golden files (check/SIZE.av_vels.dat, check/SIZE.final_state.dat) and the Reynolds numbers of its README come

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "lbm_run_profiled", "lbm_upload_obstacles", "lbm_disconnect_peers", "lbm_host_alloc", "lbm_host_free",
     "lbm_ens_create", "lbm_ens_upload", "lbm_ens_run", "lbm_ens_run_timed", "lbm_ens_sync", "lbm_ens_download",
     "lbm_ens_final_state", "lbm_ens_reynolds", "lbm_ens_steps_done", "lbm_ens_members", "lbm_ens_destroy",
+    "lbm_steady_run", "lbm_steady_steps",
     "lbm_dp_create", "lbm_dp_upload", "lbm_dp_upload_obstacles", "lbm_dp_run", "lbm_dp_run_timed", "lbm_dp_sync",
     "lbm_dp_download", "lbm_dp_final_state", "lbm_dp_reynolds", "lbm_dp_steps_done", "lbm_dp_set_option",
     "lbm_dp_get_option", "lbm_dp_destroy",
@@ -115,6 +116,8 @@ def load_library():
     L.lbm_ens_members.argtypes = [vp]
     L.lbm_ens_destroy.argtypes = [vp]
     L.lbm_ens_destroy.restype = None
+    L.lbm_steady_run.argtypes = [vp, ci, ci, ctypes.c_double]
+    L.lbm_steady_steps.argtypes = [vp, vp, vp]
     L.lbm_dp_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(DParams), vp]
     L.lbm_dp_upload.argtypes = [vp, vp]
     L.lbm_dp_upload_obstacles.argtypes = [vp, vp]
@@ -506,6 +509,22 @@ class Ensemble:
         ms = ctypes.c_double()
         _check(self.lib.lbm_ens_run_timed(self.ens, nsteps, ctypes.byref(ms)), "lbm_ens_run_timed")
         return ms.value
+
+    def run_until(self, max_steps, window=64, rel_tol=1e-4):
+        """Every member to its own steady state (lbm_steady_run): legs of `window` steps, a member stops at the first check
+        point s where |A(s) - A(s - window)| <= rel_tol |A(s)| on its own av_vels record, at most max_steps steps.  Returns
+        (steps int32[n], converged bool[n]).  Members that stopped at different counts leave the ensemble ragged: download(),
+        final_state() and reynolds() return every member's own last state, run() is refused until the next upload()."""
+        _check(self.lib.lbm_steady_run(self.ens, max_steps, window, rel_tol), "lbm_steady_run")
+        return self.member_steps()
+
+    def member_steps(self):
+        """(steps int32[n], converged bool[n]): per member the steps applied since the last upload, and whether it met the
+        criterion of the last run_until since then"""
+        steps = np.zeros(self.n, dtype=np.int32)
+        conv = np.zeros(self.n, dtype=np.int32)
+        _check(self.lib.lbm_steady_steps(self.ens, steps.ctypes.data, conv.ctypes.data), "lbm_steady_steps")
+        return steps, conv.astype(bool)
 
     def sync(self):
         _check(self.lib.lbm_ens_sync(self.ens), "lbm_ens_sync")

@@ -37,10 +37,12 @@ struct EnsArgs {
 
 // grid = (tiles per member, members).  TX x TY output tile, T <= kMultiMaxT steps LDS -> LDS on a region that shrinks by
 // one cell per step (d2q9_multi's scheme; halo cells are computed redundantly by the member's neighbouring tiles).
-// Instantiated for 16x16 (75 KB of LDS) and 16x8 (57 KB) tiles, 52 VGPRs: two workgroups share a CU, so one's loads and
+// Instantiated for 16x16 (75 KB of LDS) and 16x8 (57 KB) tiles, 50 VGPRs: two workgroups share a CU, so one's loads and
 // stores overlap the other's sub-steps (lbm_ensemble.cpp, build_ens: the measurements behind the choice).
+// The tile body is a function of its own so that the gated kernel of a steady run (steady_kernels.h) advances a member with
+// the very same instructions.
 template <int TX, int TY>
-__global__ __launch_bounds__(kMultiThreads) void d2q9_ensemble(const EnsArgs a) {
+__device__ __forceinline__ void ens_tile(const EnsArgs a) {
   constexpr int kRX = TX + 2 * kMultiMaxT, kRY = TY + 2 * kMultiMaxT;
   __shared__ float lds[2][9][kRY * kRX];
   __shared__ uint8_t lmask[kRY * kRX];
@@ -133,11 +135,18 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_ensemble(const EnsArgs a) 
   }
 }
 
+template <int TX, int TY>
+__global__ __launch_bounds__(kMultiThreads) void d2q9_ensemble(const EnsArgs a) {
+  ens_tile<TX, TY>(a);
+}
+
 // ---- second reduction stage, batched: one workgroup per (buffered step, member) -------------------
 // partials = [steps][members][tiles]; sums a member's tiles of one step in a fixed order (fp64) into
-// av_sum[member * record + first + step].  grid = (members, steps).
+// av_sum[member * record + first + step].  grid = (members, steps).  active: NULL, or one word per member; a member whose
+// word is 0 has stopped (steady_kernels.h), its tiles wrote no partial sums and its record is left alone.
 static __global__ __launch_bounds__(kBlock) void ens_reduce_partials(const float *partials, int tiles, double *av_sum,
-                                                                     unsigned long long record, int first) {
+                                                                     unsigned long long record, int first, const int *active) {
+  if (active && active[blockIdx.x] == 0) return;
   const float *p = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * tiles;
   double acc = 0.0;
   for (int i = threadIdx.x; i < tiles; i += kBlock) acc += (double)p[i];
@@ -154,11 +163,11 @@ static __global__ __launch_bounds__(kBlock) void ens_reduce_partials(const float
 
 // ---- the helper kernels of d2q9_kernels.h with a member axis (blockIdx.y), same per-cell arithmetic ----------------
 
-// accelerate_flow of row ny-2 of every member (kernels.cl:9-53): prologue of a run
+// accelerate_flow of row ny-2 of every member (kernels.cl:9-53): prologue of a run.  active: as ens_reduce_partials
 static __global__ void ens_accelerate_row(float *cells, unsigned long long plane_stride, unsigned long long member_stride,
-                                          const uint8_t *mask, const EnsMember *members, int nx, int ny) {
+                                          const uint8_t *mask, const EnsMember *members, int nx, int ny, const int *active) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
-  if (x >= nx) return;
+  if (x >= nx || (active && active[blockIdx.y] == 0)) return;
   const EnsMember mc = members[blockIdx.y];
   cells += (size_t)blockIdx.y * member_stride;
   mask += (size_t)blockIdx.y * ((size_t)nx * ny);
@@ -192,10 +201,13 @@ static __global__ void ens_init_cells(float *cells, unsigned long long plane_str
 }
 
 // device layout <-> the caller's float[members][9][ny][nx] (staged in the grid that is not current, one transfer for
-// the whole ensemble).  TO_DEVICE: flat -> cells, else cells -> flat.
+// the whole ensemble).  TO_DEVICE: flat -> cells, else cells -> flat.  par: NULL, or one word per member that says which
+// of the two grid arrays holds that member's current state (0: cells, 1: cells_alt) once members have stopped on different
+// launch parities (steady_kernels.h).
 template <bool TO_DEVICE>
-static __global__ void ens_pack_planes(float *cells, unsigned long long plane_stride, unsigned long long member_stride, int nx,
-                                       size_t n, float *flat) {
+static __global__ void ens_pack_planes(float *cells, float *cells_alt, const int *par, unsigned long long plane_stride,
+                                       unsigned long long member_stride, int nx, size_t n, float *flat) {
+  if (par && par[blockIdx.y]) cells = cells_alt;
   cells += (size_t)blockIdx.y * member_stride;
   flat += (size_t)blockIdx.y * 9 * n;
   for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
@@ -210,13 +222,15 @@ static __global__ void ens_pack_planes(float *cells, unsigned long long plane_st
 }
 
 // output stage per member (final_fields of d2q9_kernels.h: d2q9-bgk.c:787-832, 396-442): outputs are
-// float[members][ny][nx], partials float[members][gridDim.x]
-static __global__ __launch_bounds__(kBlock) void ens_final_fields(const float *cells, unsigned long long plane_stride,
+// float[members][ny][nx], partials float[members][gridDim.x].  cells_alt, par: as ens_pack_planes
+static __global__ __launch_bounds__(kBlock) void ens_final_fields(const float *cells, const float *cells_alt, const int *par,
+                                                                  unsigned long long plane_stride,
                                                                   unsigned long long member_stride, int nx, const uint8_t *mask,
                                                                   size_t n, const EnsMember *members, float *u_x, float *u_y,
                                                                   float *u, float *pressure, float *partials) {
   const float c_sq = 1.0f / 3.0f;
   const float density = members[blockIdx.y].density;
+  if (par && par[blockIdx.y]) cells = cells_alt;
   cells += (size_t)blockIdx.y * member_stride;
   mask += (size_t)blockIdx.y * n;
   const size_t off = (size_t)blockIdx.y * n;

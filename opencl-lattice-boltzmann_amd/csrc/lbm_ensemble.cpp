@@ -7,11 +7,16 @@
 // one slab: a prologue accelerate_flow, launches of up to 8 steps of d2q9_ensemble with the next step's acceleration
 // fused into all but the last, a ring of buffered per-step partial sums flushed by the batched second reduction stage.
 // The reference has no counterpart: one grid, one in-order queue (d2q9-bgk.c:221-239).
+//
+// A steady run (lbm_steady_*) is the same loop cut into legs of `window` steps behind a per-member `active` word that a
+// criterion kernel clears on the device (steady_kernels.h).  Members may then stop on different launch parities, so from
+// the end of such a run until the next upload the array that holds a member's state is the member's own (`par`).
 #include "../../include/lbm.h"
-#include "ensemble_kernels.h"
+#include "steady_kernels.h"
 #include "lbm_error.h"
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -30,6 +35,7 @@ namespace {
 constexpr int kEnsRingMax = 256;           // most steps of per-tile partial sums buffered between reductions
 constexpr long kEnsMaxCells = 300L * 1024; // the library's bound for "launch-bound" (multistep_effective, lbm_hip.cpp)
 constexpr int kEnsMaxMembers = 65535;      // member index = blockIdx.y
+constexpr int kSteadyPollChecks = 4;       // a steady run reads the count of active members back after every so many checks
 
 inline long div_up(long a, long b) { return (a + b - 1) / b; }
 
@@ -55,6 +61,13 @@ struct lbm_ens {
   int ring = 8, ring_fill = 0;
   int cur = 0, steps_done = 0;
   bool failed = false;
+  // steady runs (allocated by the first lbm_steady_run)
+  int *steady_words = nullptr;       // device: active[n], par[n], steps[n], conv[n], count
+  float *steady_inv = nullptr;       // device: free_cells_inv[n]
+  int *steady_count_host = nullptr;  // page-locked: where the count of active members is read back to
+  float *stage = nullptr;            // device, float[n][9][ny][nx]: staging of downloads while the ensemble is ragged
+  std::vector<int> m_steps, m_conv;  // host copies of the words after the last steady run (empty: none since the upload)
+  bool ragged = false;               // members stopped at different step counts: download and output only, until an upload
 };
 
 namespace {
@@ -68,6 +81,10 @@ void free_ens(lbm_ens *e) {
   if (e->partials) (void)hipFree(e->partials);
   if (e->av_sum) (void)hipFree(e->av_sum);
   if (e->fin_partials) (void)hipFree(e->fin_partials);
+  if (e->steady_words) (void)hipFree(e->steady_words);
+  if (e->steady_inv) (void)hipFree(e->steady_inv);
+  if (e->steady_count_host) (void)hipHostFree(e->steady_count_host);
+  if (e->stage) (void)hipFree(e->stage);
   if (e->ev_t0) (void)hipEventDestroy(e->ev_t0);
   if (e->ev_t1) (void)hipEventDestroy(e->ev_t1);
   if (e->st) (void)hipStreamDestroy(e->st);
@@ -86,7 +103,7 @@ int build_ens(lbm_ens *e, const int32_t *obstacles) {
   // Tile shape.  d2q9_multi's cost model (lbm_hip.cpp, slab_geometry: ceil(tiles / CUs) x cell updates per tile) holds while
   // every tile has a CU to itself: there the smallest tile wins (one grid, us/step for 32x16 / 16x16 / 16x8: 128x128 1.85 /
   // 1.55 / 1.38).  An ensemble soon has several rounds of tiles per CU, and then the workgroups that fit a CU together
-  // decide: two of 16x16 (75 KB of LDS each, 52 VGPRs) or of 16x8 overlap one's loads and stores with the other's sub-steps,
+  // decide: two of 16x16 (75 KB of LDS each, 50 VGPRs) or of 16x8 overlap one's loads and stores with the other's sub-steps,
   // one of 32x16 (113 KB) cannot.  Measured (tools/ensemble_ab.py, us/step 32x16 / 16x16 / 16x8): 64 x 128x128 15.05 / 13.26 /
   // 21.50, 16 x 256x256 13.45 / 13.07 / 21.33 - so 16x8 while its tiles fit one per CU, 16x16 from there on, and no 32x16 form.
   {
@@ -150,35 +167,33 @@ int build_ens(lbm_ens *e, const int32_t *obstacles) {
   return LBM_OK;
 }
 
-void launch_ensemble(const lbm_ens *e, const EnsArgs &a) {
+// active: NULL for an ordinary run, the members' words for a leg of a steady run
+void launch_ensemble(const lbm_ens *e, const EnsArgs &a, const int *active) {
   const dim3 grid(e->tiles, e->n), block(kMultiThreads);
-  if (e->ty == 16) hipLaunchKernelGGL((d2q9_ensemble<16, 16>), grid, block, 0, e->st, a);
-  else hipLaunchKernelGGL((d2q9_ensemble<16, 8>), grid, block, 0, e->st, a);
+  if (!active) {
+    if (e->ty == 16) hipLaunchKernelGGL((d2q9_ensemble<16, 16>), grid, block, 0, e->st, a);
+    else hipLaunchKernelGGL((d2q9_ensemble<16, 8>), grid, block, 0, e->st, a);
+  } else {
+    if (e->ty == 16) hipLaunchKernelGGL((d2q9_ensemble_gated<16, 16>), grid, block, 0, e->st, a, active);
+    else hipLaunchKernelGGL((d2q9_ensemble_gated<16, 8>), grid, block, 0, e->st, a, active);
+  }
 }
 
-int run_ens_impl(lbm_ens *e, int nsteps, bool timed, double *ms, bool *launched) {
-  if (nsteps < 0) return lbm_fail(LBM_ERR_ARG, "nsteps must be >= 0");
-  if (e->failed) return lbm_fail(LBM_ERR_STATE, "an earlier run failed after its launches had begun; destroy the ensemble");
-  if (e->steps_done + nsteps > e->max_iters)
-    return lbm_fail(LBM_ERR_STATE, "av_vels record holds max_iters=%d steps; %d done, %d more requested", e->max_iters,
-                    e->steps_done, nsteps);
-  if (timed && ms) *ms = 0.0;
-  if (nsteps == 0) return LBM_OK;
-  HIP_TRY(hipSetDevice(e->dev));
-  *launched = true;
-  if (timed) HIP_TRY(hipEventRecord(e->ev_t0, e->st));
+// nsteps steps from step count `first` on, enqueued: the prologue, the launches, the reductions into the record.  Flips
+// e->cur per launch; the caller counts the steps.  active: as launch_ensemble.
+int enqueue_steps(lbm_ens *e, int nsteps, int first, const int *active) {
   // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
   // into the previous launch's write of row ny-2
   hipLaunchKernelGGL(ens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->st, e->cells[e->cur], e->plane_stride,
-                     e->member_stride, e->mask, e->members, e->nx, e->ny);
+                     e->member_stride, e->mask, e->members, e->nx, e->ny, active);
   HIP_TRY(hipGetLastError());
 
-  int batch_first = e->steps_done;
+  int batch_first = first;
   // second reduction stage over the buffered steps (kernels.cl:234-290 counterpart)
   auto flush = [&]() -> int {
     if (e->ring_fill == 0) return LBM_OK;
     hipLaunchKernelGGL(ens_reduce_partials, dim3(e->n, e->ring_fill), dim3(kBlock), 0, e->st, e->partials, e->tiles, e->av_sum,
-                       (unsigned long long)std::max(1, e->max_iters), batch_first);
+                       (unsigned long long)std::max(1, e->max_iters), batch_first, active);
     HIP_TRY(hipGetLastError());
     batch_first += e->ring_fill;
     e->ring_fill = 0;
@@ -204,13 +219,33 @@ int run_ens_impl(lbm_ens *e, int nsteps, bool timed, double *ms, bool *launched)
     a.tiles_x = e->tiles_x;
     a.T = adv;
     a.accel_next = (i + adv < nsteps) ? 1 : 0;
-    launch_ensemble(e, a);
+    launch_ensemble(e, a, active);
     HIP_TRY(hipGetLastError());
     e->cur ^= 1;
     e->ring_fill += adv;
     i += adv;
   }
-  if (int rc = flush()) return rc;
+  return flush();
+}
+
+int refuse_ragged(const lbm_ens *e) {
+  return lbm_fail(LBM_ERR_STATE, "the members of this ensemble stopped at different step counts (lbm_steady_run; %d is the "
+                  "largest): download them, then lbm_ens_upload before the next run", e->steps_done);
+}
+
+int run_ens_impl(lbm_ens *e, int nsteps, bool timed, double *ms, bool *launched) {
+  if (nsteps < 0) return lbm_fail(LBM_ERR_ARG, "nsteps must be >= 0");
+  if (e->failed) return lbm_fail(LBM_ERR_STATE, "an earlier run failed after its launches had begun; destroy the ensemble");
+  if (e->ragged) return refuse_ragged(e);
+  if (e->steps_done + nsteps > e->max_iters)
+    return lbm_fail(LBM_ERR_STATE, "av_vels record holds max_iters=%d steps; %d done, %d more requested", e->max_iters,
+                    e->steps_done, nsteps);
+  if (timed && ms) *ms = 0.0;
+  if (nsteps == 0) return LBM_OK;
+  HIP_TRY(hipSetDevice(e->dev));
+  *launched = true;
+  if (timed) HIP_TRY(hipEventRecord(e->ev_t0, e->st));
+  if (int rc = enqueue_steps(e, nsteps, e->steps_done, nullptr)) return rc;
   e->steps_done += nsteps;
   if (timed) {
     HIP_TRY(hipEventRecord(e->ev_t1, e->st));
@@ -223,9 +258,7 @@ int run_ens_impl(lbm_ens *e, int nsteps, bool timed, double *ms, bool *launched)
 }
 
 // A failure after launches have begun: let what was enqueued finish and refuse further work (as run_steps, lbm_hip.cpp)
-int run_ens(lbm_ens *e, int nsteps, bool timed, double *ms) {
-  bool launched = false;
-  const int rc = run_ens_impl(e, nsteps, timed, ms, &launched);
+int after_launches(lbm_ens *e, int rc, bool launched) {
   if (rc != LBM_OK && launched) {
     const std::string keep = lbm_last_error();
     (void)hipStreamSynchronize(e->st);
@@ -234,6 +267,88 @@ int run_ens(lbm_ens *e, int nsteps, bool timed, double *ms) {
     lbm_fail(rc, "%s", keep.c_str());
   }
   return rc;
+}
+
+int run_ens(lbm_ens *e, int nsteps, bool timed, double *ms) {
+  bool launched = false;
+  return after_launches(e, run_ens_impl(e, nsteps, timed, ms, &launched), launched);
+}
+
+SteadyWords steady_words(const lbm_ens *e) {
+  int *w = e->steady_words;
+  const size_t n = (size_t)e->n;
+  return SteadyWords{w, w + n, w + 2 * n, w + 3 * n, w + 4 * n};
+}
+
+// which array holds member m, for the kernels that read a state: the members' own words while the ensemble is ragged
+const int *member_parity(const lbm_ens *e) { return e->ragged ? steady_words(e).par : nullptr; }
+
+// what a steady run needs beyond an ordinary one, allocated by the first
+int steady_alloc(lbm_ens *e) {
+  if (e->steady_words) return LBM_OK;
+  const size_t n = (size_t)e->n;
+  if (!e->steady_count_host)
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->steady_count_host), sizeof(int), hipHostMallocDefault));
+  if (!e->steady_inv) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->steady_inv), n * sizeof(float)));
+  std::vector<float> inv(n);
+  for (size_t m = 0; m < n; m++) inv[m] = e->p[m].free_cells_inv;
+  HIP_TRY(hipMemcpy(e->steady_inv, inv.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->steady_words), (4 * n + 1) * sizeof(int)));
+  return LBM_OK;
+}
+
+int steady_impl(lbm_ens *e, int max_steps, int window, double rel_tol, bool *launched) {
+  if (e->failed) return lbm_fail(LBM_ERR_STATE, "an earlier run failed after its launches had begun; destroy the ensemble");
+  if (e->ragged) return refuse_ragged(e);
+  if (e->steps_done + max_steps > e->max_iters)
+    return lbm_fail(LBM_ERR_STATE, "av_vels record holds max_iters=%d steps; %d done, up to %d more requested", e->max_iters,
+                    e->steps_done, max_steps);
+  if (max_steps == 0) return LBM_OK;
+  HIP_TRY(hipSetDevice(e->dev));
+  if (int rc = steady_alloc(e)) return rc;
+  const int n = e->n, s0 = e->steps_done;
+  const SteadyWords w = steady_words(e);
+  const dim3 mgrid((unsigned)div_up(n, 256)), mblock(256);
+  *launched = true;
+  hipLaunchKernelGGL(ens_steady_begin, mgrid, mblock, 0, e->st, w, n, e->cur, s0);
+  HIP_TRY(hipGetLastError());
+  int done = 0, checks = 0;
+  while (done < max_steps) {
+    const int leg = std::min(window, max_steps - done);
+    if (int rc = enqueue_steps(e, leg, s0 + done, w.active)) return rc;
+    done += leg;
+    const int s = s0 + done;
+    // a check point: a whole leg, with a record entry one window back (step counts start at 1)
+    const int check = (leg == window && s - window >= 1) ? 1 : 0;
+    hipLaunchKernelGGL(ens_steady_check, mgrid, mblock, 0, e->st, w, n, e->av_sum, (unsigned long long)std::max(1, e->max_iters),
+                       e->steady_inv, s, window, rel_tol, check, e->cur);
+    HIP_TRY(hipGetLastError());
+    // Every few checks: is anyone left?  Only how much is enqueued depends on the answer; what a member computes does not,
+    // the workgroups of a stopped member return at once.
+    if (check && ++checks % kSteadyPollChecks == 0 && done < max_steps) {
+      HIP_TRY(hipMemcpyAsync(e->steady_count_host, w.count, sizeof(int), hipMemcpyDeviceToHost, e->st));
+      HIP_TRY(hipStreamSynchronize(e->st));
+      if (*e->steady_count_host == 0) break;
+    }
+  }
+  // the members' words: on which parity each one is, at which count, and whether it met the criterion
+  std::vector<int> words(3 * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(words.data(), w.par, words.size() * sizeof(int), hipMemcpyDeviceToHost, e->st));
+  HIP_TRY(hipStreamSynchronize(e->st));
+  e->m_steps.assign(words.begin() + n, words.begin() + 2 * (size_t)n);
+  e->m_conv.assign(words.begin() + 2 * (size_t)n, words.end());
+  e->steps_done = *std::max_element(e->m_steps.begin(), e->m_steps.end());
+  e->ragged = *std::min_element(e->m_steps.begin(), e->m_steps.end()) != e->steps_done;
+  // all at one count: they stopped after the same launch, and the ensemble is an ordinary one on that parity
+  if (!e->ragged) e->cur = words[0];
+  return LBM_OK;
+}
+
+// the staging array of downloads while both grid arrays hold members' states
+int stage_alloc(lbm_ens *e) {
+  if (e->stage) return LBM_OK;
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->stage), (size_t)e->n * 9 * e->nx * e->ny * sizeof(float)));
+  return LBM_OK;
 }
 
 int sync_ens(lbm_ens *e) {
@@ -293,8 +408,8 @@ int lbm_ens_upload(lbm_ens *e, const float *cells) {
     // one transfer of the caller's float[n][9][ny][nx] into the second grid array (9 nx ny <= member_stride), then one
     // launch that scatters every member's planes into the first (d2q9-bgk.c:200-203 for all members)
     HIP_TRY(hipMemcpyAsync(e->cells[1], cells, (size_t)e->n * 9 * per * sizeof(float), hipMemcpyHostToDevice, e->st));
-    hipLaunchKernelGGL(ens_pack_planes<true>, grid, dim3(256), 0, e->st, e->cells[0], e->plane_stride, e->member_stride, e->nx, per,
-                       e->cells[1]);
+    hipLaunchKernelGGL(ens_pack_planes<true>, grid, dim3(256), 0, e->st, e->cells[0], (float *)nullptr, (const int *)nullptr,
+                       e->plane_stride, e->member_stride, e->nx, per, e->cells[1]);
   } else {
     hipLaunchKernelGGL(ens_init_cells, grid, dim3(256), 0, e->st, e->cells[0], e->plane_stride, e->member_stride, e->members, e->nx,
                        per);
@@ -304,6 +419,9 @@ int lbm_ens_upload(lbm_ens *e, const float *cells) {
   e->cur = 0;
   e->steps_done = 0;
   e->ring_fill = 0;
+  e->ragged = false;
+  e->m_steps.clear();
+  e->m_conv.clear();
   return LBM_OK;
 }
 
@@ -331,10 +449,16 @@ int lbm_ens_download(lbm_ens *e, float *cells_out, float *av_vels_out) {
   const size_t per = (size_t)e->nx * e->ny;
   if (cells_out) {
     // the grid array that is not current is scratch between runs: repack every member into the caller's layout there,
-    // then one contiguous transfer
+    // then one contiguous transfer.  A ragged ensemble has no scratch array: every member from the array that holds it,
+    // into a staging array of its own
     float *stage = e->cells[e->cur ^ 1];
+    if (e->ragged) {
+      if (int rc = stage_alloc(e)) return rc;
+      stage = e->stage;
+    }
     hipLaunchKernelGGL(ens_pack_planes<false>, dim3((unsigned)std::min(div_up((long)per, 256), 1024L), e->n), dim3(256), 0, e->st,
-                       e->cells[e->cur], e->plane_stride, e->member_stride, e->nx, per, stage);
+                       e->cells[e->ragged ? 0 : e->cur], e->cells[1], member_parity(e), e->plane_stride, e->member_stride, e->nx,
+                       per, stage);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(cells_out, stage, (size_t)e->n * 9 * per * sizeof(float), hipMemcpyDeviceToHost, e->st));
     HIP_TRY(hipStreamSynchronize(e->st));
@@ -348,6 +472,10 @@ int lbm_ens_download(lbm_ens *e, float *cells_out, float *av_vels_out) {
     for (int m = 0; m < e->n; m++)
       for (int t = 0; t < T; t++)
         av_vels_out[(size_t)m * T + t] = (float)(sums[(size_t)m * T + t] * (double)e->p[m].free_cells_inv);
+    // a member that stopped earlier has no record from its own count on
+    if (e->ragged)
+      for (int m = 0; m < e->n; m++)
+        for (int t = e->m_steps[m]; t < T; t++) av_vels_out[(size_t)m * T + t] = 0.0f;
   }
   return LBM_OK;
 }
@@ -358,11 +486,18 @@ int lbm_ens_final_state(lbm_ens *e, float *u_x, float *u_y, float *u, float *pre
   const size_t per = (size_t)e->nx * e->ny, all = per * e->n;
   float *outs[4] = {u_x, u_y, u, pressure};
   // the four columns of all members go to the grid array that is not current (4 n nx ny floats of its 9 n nx ny)
+  // (a ragged ensemble: to its staging array, as lbm_ens_download)
   float *d[4] = {nullptr, nullptr, nullptr, nullptr};
+  float *stage = e->cells[e->cur ^ 1];
+  if (e->ragged) {
+    if (int rc = stage_alloc(e)) return rc;
+    stage = e->stage;
+  }
   for (int i = 0; i < 4; i++)
-    if (outs[i]) d[i] = e->cells[e->cur ^ 1] + (size_t)i * all;
-  hipLaunchKernelGGL(ens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->st, e->cells[e->cur], e->plane_stride,
-                     e->member_stride, e->nx, e->mask, per, e->members, d[0], d[1], d[2], d[3], e->fin_partials);
+    if (outs[i]) d[i] = stage + (size_t)i * all;
+  hipLaunchKernelGGL(ens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->st, e->cells[e->ragged ? 0 : e->cur],
+                     e->cells[1], member_parity(e), e->plane_stride, e->member_stride, e->nx, e->mask, per, e->members, d[0], d[1],
+                     d[2], d[3], e->fin_partials);
   HIP_TRY(hipGetLastError());
   for (int i = 0; i < 4; i++)
     if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], d[i], all * sizeof(float), hipMemcpyDeviceToHost, e->st));
@@ -374,9 +509,9 @@ int lbm_ens_reynolds(lbm_ens *e, float *reynolds_out) {
   if (!e || !reynolds_out) return lbm_fail(LBM_ERR_ARG, "NULL argument");
   if (int rc = sync_ens(e)) return rc;
   const size_t per = (size_t)e->nx * e->ny;
-  hipLaunchKernelGGL(ens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->st, e->cells[e->cur], e->plane_stride,
-                     e->member_stride, e->nx, e->mask, per, e->members, (float *)nullptr, (float *)nullptr, (float *)nullptr,
-                     (float *)nullptr, e->fin_partials);
+  hipLaunchKernelGGL(ens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->st, e->cells[e->ragged ? 0 : e->cur],
+                     e->cells[1], member_parity(e), e->plane_stride, e->member_stride, e->nx, e->mask, per, e->members,
+                     (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr, e->fin_partials);
   HIP_TRY(hipGetLastError());
   std::vector<float> part((size_t)e->n * e->fin_blocks);
   HIP_TRY(hipMemcpyAsync(part.data(), e->fin_partials, part.size() * sizeof(float), hipMemcpyDeviceToHost, e->st));
@@ -389,6 +524,26 @@ int lbm_ens_reynolds(lbm_ens *e, float *reynolds_out) {
     const float viscosity = 1.0f / 6.0f * (2.0f / p.omega - 1.0f);
     const float av = (float)(tot * (double)p.free_cells_inv);
     reynolds_out[m] = av * p.reynolds_dim / viscosity;
+  }
+  return LBM_OK;
+}
+
+int lbm_steady_run(lbm_ens *e, int max_steps, int window, double rel_tol) {
+  // every argument error is reported before the ensemble or a device is touched
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (max_steps < 0) return lbm_fail(LBM_ERR_ARG, "max_steps must be >= 0 (got %d)", max_steps);
+  if (window < 1) return lbm_fail(LBM_ERR_ARG, "window must be >= 1 (got %d)", window);
+  if (!std::isfinite(rel_tol) || rel_tol < 0.0) return lbm_fail(LBM_ERR_ARG, "rel_tol must be finite and >= 0 (got %g)", rel_tol);
+  bool launched = false;
+  return after_launches(e, steady_impl(e, max_steps, window, rel_tol, &launched), launched);
+}
+
+int lbm_steady_steps(lbm_ens *e, int *steps_out, int *converged_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  for (int m = 0; m < e->n; m++) {
+    // the members of an ensemble that is not ragged are all at its count, whatever ran since the last steady run
+    if (steps_out) steps_out[m] = e->ragged ? e->m_steps[m] : e->steps_done;
+    if (converged_out) converged_out[m] = e->m_conv.empty() ? 0 : e->m_conv[m];
   }
   return LBM_OK;
 }
