@@ -155,14 +155,21 @@ def _check(rc, what):
         raise LBMError("%s failed (code %d): %s" % (what, rc, load_library().lbm_last_error().decode()))
 
 
+def _make_params(ptype, real, nx, ny, max_iters, reynolds_dim, density, accel, omega, obstacles):
+    """a `ptype` (Params / DParams) of these run constants; free_cells_inv = 1 / free_cells in `real`, the numpy type of
+    ptype's reals (inf for a grid without a free cell, as the reference's division gives)"""
+    p = ptype()
+    p.nx, p.ny, p.max_iters, p.reynolds_dim = nx, ny, max_iters, reynolds_dim
+    p.density, p.accel, p.omega = float(density), float(accel), float(omega)
+    free_cells = nx * ny if obstacles is None else int(obstacles.size - np.count_nonzero(obstacles))
+    with np.errstate(divide="ignore"):
+        p.free_cells_inv = real(1.0) / real(free_cells)
+    return p
+
+
 def make_params(nx, ny, max_iters, reynolds_dim=10, density=0.1, accel=0.005, omega=1.85, obstacles=None):
     """Run constants; free_cells_inv from the mask as in d2q9-bgk.c:583-591."""
-    p = Params()
-    p.nx, p.ny, p.max_iters, p.reynolds_dim = nx, ny, max_iters, reynolds_dim
-    p.density, p.accel, p.omega = density, accel, omega
-    free_cells = nx * ny if obstacles is None else int(obstacles.size - np.count_nonzero(obstacles))
-    p.free_cells_inv = np.float32(1.0) / np.float32(free_cells)
-    return p
+    return _make_params(Params, np.float32, nx, ny, max_iters, reynolds_dim, density, accel, omega, obstacles)
 
 
 def _parse_inputs(paramfile, obstaclefile):
@@ -201,12 +208,7 @@ def read_inputs(paramfile, obstaclefile):
 def make_dparams(nx, ny, max_iters, reynolds_dim=10, density=0.1, accel=0.005, omega=1.85, obstacles=None):
     """Run constants of a double-precision context: the reals as given (the fp64 literals, never widened floats),
     free_cells_inv = 1.0 / free_cells in double (inf for a grid without a free cell, as the reference's division gives)."""
-    p = DParams()
-    p.nx, p.ny, p.max_iters, p.reynolds_dim = nx, ny, max_iters, reynolds_dim
-    p.density, p.accel, p.omega = float(density), float(accel), float(omega)
-    free_cells = nx * ny if obstacles is None else int(obstacles.size - np.count_nonzero(obstacles))
-    p.free_cells_inv = 1.0 / free_cells if free_cells else float("inf")
-    return p
+    return _make_params(DParams, np.float64, nx, ny, max_iters, reynolds_dim, density, accel, omega, obstacles)
 
 
 def read_inputs_double(paramfile, obstaclefile):
@@ -309,9 +311,56 @@ def comm_id():
     return buf.raw
 
 
-class LBM:
+class _Handle:
+    """What the four families of include/lbm.h have in common beyond their names: a handle that `<prefix>_destroy` frees, and
+    `<prefix>_run`, `_run_timed`, `_sync` and `_steps_done` on it.  A class names its family in `_prefix` and the attribute
+    that holds its handle in `_handle` (contexts keep theirs in `ctx`, ensembles in `ens`)."""
+    _prefix = None
+    _handle = None
+
+    def _call(self, name, *args):
+        """<prefix>_<name>(handle, *args), raising LBMError on a non-zero return code"""
+        symbol = "%s_%s" % (self._prefix, name)
+        _check(getattr(self.lib, symbol)(getattr(self, self._handle), *args), symbol)
+
+    def run(self, nsteps):
+        self._call("run", nsteps)
+
+    def run_timed(self, nsteps):
+        """Runs nsteps and returns the HIP-event time of the step loop in milliseconds."""
+        ms = ctypes.c_double()
+        self._call("run_timed", nsteps, ctypes.byref(ms))
+        return ms.value
+
+    def sync(self):
+        self._call("sync")
+
+    @property
+    def steps_done(self):
+        return getattr(self.lib, self._prefix + "_steps_done")(getattr(self, self._handle))
+
+    def close(self):
+        if getattr(self, self._handle):
+            getattr(self.lib, self._prefix + "_destroy")(getattr(self, self._handle))
+            setattr(self, self._handle, ctypes.c_void_p())
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LBM(_Handle):
     """A simulation context (lbm_ctx).  Mirrors the call sequence of the reference's main()
     (d2q9-bgk.c:194-277): create -> upload -> run -> sync -> download -> destroy."""
+    _prefix, _handle = "lbm", "ctx"
 
     def __init__(self, params, obstacles, devices=None, rank=None, nranks=None, device=0, comm=None):
         self.lib = load_library()
@@ -348,15 +397,6 @@ class LBM:
         _check(self.lib.lbm_upload_obstacles(self.ctx, ob.ctypes.data), "lbm_upload_obstacles")
         self.obstacles = ob
 
-    def run(self, nsteps):
-        _check(self.lib.lbm_run(self.ctx, nsteps), "lbm_run")
-
-    def run_timed(self, nsteps):
-        """Runs nsteps and returns the HIP-event time of the step loop in milliseconds."""
-        ms = ctypes.c_double()
-        _check(self.lib.lbm_run_timed(self.ctx, nsteps, ctypes.byref(ms)), "lbm_run_timed")
-        return ms.value
-
     def run_profiled(self, nsteps):
         """Runs nsteps with timing events around every launch of the first slab; dict of mean microseconds."""
         st = (ctypes.c_double * 8)()
@@ -364,13 +404,6 @@ class LBM:
         return {"sets": int(st[0]), "steps_per_set": st[1], "edge_us": st[2], "exchange_us": st[3], "interior_us": st[4],
                 "set_period_us": st[5], "interior_start_lag_us": st[6],
                 "transport": {0: "none", 1: "rccl", 2: "copy", 3: "peer"}.get(int(st[7]), "?")}
-
-    def sync(self):
-        _check(self.lib.lbm_sync(self.ctx), "lbm_sync")
-
-    @property
-    def steps_done(self):
-        return self.lib.lbm_steps_done(self.ctx)
 
     def row_range(self):
         y0, y1 = ctypes.c_int(), ctypes.c_int()
@@ -438,144 +471,12 @@ class LBM:
             for i, v in enumerate(av):
                 f.write("%d:\t%.12E\n" % (i, v))
 
-    def close(self):
-        if self.ctx:
-            self.lib.lbm_destroy(self.ctx)
-            self.ctx = ctypes.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def sweep_params(base, omega=None, accel=None):
-    """The members of a parameter sweep: copies of `base` with omega and / or accel replaced from lists of equal length."""
-    count = len(omega if omega is not None else accel)
-    members = []
-    for i in range(count):
-        p = Params.from_buffer_copy(base)
-        if omega is not None:
-            p.omega = omega[i]
-        if accel is not None:
-            p.accel = accel[i]
-        members.append(p)
-    return members
-
-
-class Ensemble:
-    """N independent simulations of one grid size, advanced together (lbm_ens): one launch per (up to) eight timesteps for
-    all members.  Mirrors LBM with the member index as the first axis of every array.  `params`: a list of Params that share
-    nx, ny and max_iters; `obstacles`: int32[n, ny, nx], or one [ny, nx] map for all members."""
-
-    def __init__(self, params, obstacles):
-        self.lib = load_library()
-        self.params = list(params)
-        self.n = len(self.params)
-        if self.n < 1:
-            raise LBMError("an ensemble needs at least one member")
-        self.nx, self.ny = self.params[0].nx, self.params[0].ny
-        obst = np.asarray(obstacles, dtype=np.int32)
-        if obst.ndim == 2:
-            obst = np.broadcast_to(obst, (self.n,) + obst.shape)
-        obst = np.ascontiguousarray(obst)
-        assert obst.shape == (self.n, self.ny, self.nx)
-        self.obstacles = obst
-        self._params = (Params * self.n)(*self.params)
-        self.ens = ctypes.c_void_p()
-        _check(self.lib.lbm_ens_create(ctypes.byref(self.ens), self._params, obst.ctypes.data, self.n), "lbm_ens_create")
-
-    def upload(self, cells=None):
-        """cells float32[n, 9, ny, nx]; None = every member's rest state from its own density, on the device"""
-        if cells is None:
-            _check(self.lib.lbm_ens_upload(self.ens, None), "lbm_ens_upload")
-        else:
-            c = np.ascontiguousarray(cells, dtype=np.float32)
-            assert c.shape == (self.n, 9, self.ny, self.nx)
-            _check(self.lib.lbm_ens_upload(self.ens, c.ctypes.data), "lbm_ens_upload")
-
-    def run(self, nsteps):
-        _check(self.lib.lbm_ens_run(self.ens, nsteps), "lbm_ens_run")
-
-    def run_timed(self, nsteps):
-        """Runs nsteps and returns the HIP-event time of the step loop in milliseconds."""
-        ms = ctypes.c_double()
-        _check(self.lib.lbm_ens_run_timed(self.ens, nsteps, ctypes.byref(ms)), "lbm_ens_run_timed")
-        return ms.value
-
-    def run_until(self, max_steps, window=64, rel_tol=1e-4):
-        """Every member to its own steady state (lbm_steady_run): legs of `window` steps, a member stops at the first check
-        point s where |A(s) - A(s - window)| <= rel_tol |A(s)| on its own av_vels record, at most max_steps steps.  Returns
-        (steps int32[n], converged bool[n]).  Members that stopped at different counts leave the ensemble ragged: download(),
-        final_state() and reynolds() return every member's own last state, run() is refused until the next upload()."""
-        _check(self.lib.lbm_steady_run(self.ens, max_steps, window, rel_tol), "lbm_steady_run")
-        return self.member_steps()
-
-    def member_steps(self):
-        """(steps int32[n], converged bool[n]): per member the steps applied since the last upload, and whether it met the
-        criterion of the last run_until since then"""
-        steps = np.zeros(self.n, dtype=np.int32)
-        conv = np.zeros(self.n, dtype=np.int32)
-        _check(self.lib.lbm_steady_steps(self.ens, steps.ctypes.data, conv.ctypes.data), "lbm_steady_steps")
-        return steps, conv.astype(bool)
-
-    def sync(self):
-        _check(self.lib.lbm_ens_sync(self.ens), "lbm_ens_sync")
-
-    @property
-    def steps_done(self):
-        return self.lib.lbm_ens_steps_done(self.ens)
-
-    def download(self, cells=True, av_vels=True):
-        """Returns (cells float32[n,9,ny,nx] or None, av_vels float32[n,steps_done] or None)."""
-        steps = self.steps_done
-        c = np.zeros((self.n, 9, self.ny, self.nx), dtype=np.float32) if cells else None
-        a = np.zeros((self.n, steps), dtype=np.float32) if av_vels else None
-        _check(self.lib.lbm_ens_download(self.ens, c.ctypes.data if cells else None,
-                                         a.ctypes.data if av_vels and steps else None), "lbm_ens_download")
-        return c, a
-
-    def final_state(self):
-        """(u_x, u_y, u, pressure), each float32[n,ny,nx] — per member the columns of final_state.dat."""
-        outs = [np.zeros((self.n, self.ny, self.nx), dtype=np.float32) for _ in range(4)]
-        _check(self.lib.lbm_ens_final_state(self.ens, *[o.ctypes.data for o in outs]), "lbm_ens_final_state")
-        return outs
-
-    def reynolds(self):
-        """float32[n]: every member's Reynolds number of the current state"""
-        r = np.zeros(self.n, dtype=np.float32)
-        _check(self.lib.lbm_ens_reynolds(self.ens, r.ctypes.data), "lbm_ens_reynolds")
-        return r
-
-    def close(self):
-        if self.ens:
-            self.lib.lbm_ens_destroy(self.ens)
-            self.ens = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class LBMDouble:
+class LBMDouble(_Handle):
     """A double-precision context (lbm_dp): one grid on the current device in fp64, the precision of the reference's golden
     files.  Mirrors LBM with double in place of float: create -> upload -> run -> sync -> download -> destroy.  `params`:
     DParams (make_dparams, read_inputs_double); `obstacles`: int32[ny, nx]."""
+    _prefix, _handle = "lbm_dp", "ctx"
 
     def __init__(self, params, obstacles):
         self.lib = load_library()
@@ -604,22 +505,6 @@ class LBMDouble:
         assert ob.shape == (self.ny, self.nx)
         _check(self.lib.lbm_dp_upload_obstacles(self.ctx, ob.ctypes.data), "lbm_dp_upload_obstacles")
         self.obstacles = ob
-
-    def run(self, nsteps):
-        _check(self.lib.lbm_dp_run(self.ctx, nsteps), "lbm_dp_run")
-
-    def run_timed(self, nsteps):
-        """Runs nsteps and returns the HIP-event time of the step loop in milliseconds."""
-        ms = ctypes.c_double()
-        _check(self.lib.lbm_dp_run_timed(self.ctx, nsteps, ctypes.byref(ms)), "lbm_dp_run_timed")
-        return ms.value
-
-    def sync(self):
-        _check(self.lib.lbm_dp_sync(self.ctx), "lbm_dp_sync")
-
-    @property
-    def steps_done(self):
-        return self.lib.lbm_dp_steps_done(self.ctx)
 
     def download(self, cells=True, av_vels=True):
         """Returns (cells float64[9,ny,nx] or None, av_vels float64[steps_done] or None)."""
@@ -655,31 +540,13 @@ class LBMDouble:
         _, av = self.download(cells=False)
         _write_values(final_state_path, av_vels_path, self.obstacles, fields, av)
 
-    def close(self):
-        if self.ctx:
-            self.lib.lbm_dp_destroy(self.ctx)
-            self.ctx = ctypes.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def sweep_dparams(base, omega=None, accel=None):
-    """The members of a double-precision parameter sweep: copies of the DParams `base` with omega and / or accel replaced
-    from lists of equal length, as Python floats (the fp64 literals, never widened floats)."""
+def _sweep(ptype, base, omega, accel):
+    """copies of `base` as `ptype` (Params / DParams) with omega and / or accel replaced, each given as a Python float"""
     count = len(omega if omega is not None else accel)
     members = []
     for i in range(count):
-        p = DParams.from_buffer_copy(base)
+        p = ptype.from_buffer_copy(base)
         if omega is not None:
             p.omega = float(omega[i])
         if accel is not None:
@@ -688,11 +555,23 @@ def sweep_dparams(base, omega=None, accel=None):
     return members
 
 
-class EnsembleDouble:
-    """N independent double-precision simulations of one grid size, advanced together (lbm_dens): one launch per several
-    timesteps for all members, every member bit-identical to an LBMDouble on the same inputs.  Mirrors Ensemble with double
-    in place of float.  `params`: a list of DParams that share nx, ny and max_iters (sweep_dparams); `obstacles`:
-    int32[n, ny, nx], or one [ny, nx] map for all members."""
+def sweep_params(base, omega=None, accel=None):
+    """The members of a parameter sweep: copies of `base` with omega and / or accel replaced from lists of equal length."""
+    return _sweep(Params, base, omega, accel)
+
+
+def sweep_dparams(base, omega=None, accel=None):
+    """The members of a double-precision parameter sweep: copies of the DParams `base` with omega and / or accel replaced
+    from lists of equal length, as Python floats (the fp64 literals, never widened floats)."""
+    return _sweep(DParams, base, omega, accel)
+
+
+class _EnsembleOf(_Handle):
+    """The body of Ensemble and EnsembleDouble.  A class names its family in `_prefix`, the numpy type of its arrays in
+    `_dtype` and the ctypes type of its members' parameters in `_ptype`."""
+    _handle = "ens"
+    _dtype = None
+    _ptype = None
 
     def __init__(self, params, obstacles):
         self.lib = load_library()
@@ -700,8 +579,6 @@ class EnsembleDouble:
         self.n = len(self.params)
         if self.n < 1:
             raise LBMError("an ensemble needs at least one member")
-        if not all(isinstance(p, DParams) for p in self.params):
-            raise LBMError("EnsembleDouble takes DParams (make_dparams / read_inputs_double / sweep_dparams)")
         self.nx, self.ny = self.params[0].nx, self.params[0].ny
         obst = np.asarray(obstacles, dtype=np.int32)
         if obst.ndim == 2:
@@ -709,69 +586,75 @@ class EnsembleDouble:
         obst = np.ascontiguousarray(obst)
         assert obst.shape == (self.n, self.ny, self.nx)
         self.obstacles = obst
-        self._params = (DParams * self.n)(*self.params)
+        self._params = (self._ptype * self.n)(*self.params)
         self.ens = ctypes.c_void_p()
-        _check(self.lib.lbm_dens_create(ctypes.byref(self.ens), self._params, obst.ctypes.data, self.n), "lbm_dens_create")
+        create = self._prefix + "_create"
+        _check(getattr(self.lib, create)(ctypes.byref(self.ens), self._params, obst.ctypes.data, self.n), create)
 
     def upload(self, cells=None):
-        """cells float64[n, 9, ny, nx]; None = every member's rest state from its own density, on the device"""
+        """cells float32[n, 9, ny, nx] (an EnsembleDouble: float64); None = every member's rest state from its own density, on
+        the device"""
         if cells is None:
-            _check(self.lib.lbm_dens_upload(self.ens, None), "lbm_dens_upload")
+            self._call("upload", None)
         else:
-            c = np.ascontiguousarray(cells, dtype=np.float64)
+            c = np.ascontiguousarray(cells, dtype=self._dtype)
             assert c.shape == (self.n, 9, self.ny, self.nx)
-            _check(self.lib.lbm_dens_upload(self.ens, c.ctypes.data), "lbm_dens_upload")
-
-    def run(self, nsteps):
-        _check(self.lib.lbm_dens_run(self.ens, nsteps), "lbm_dens_run")
-
-    def run_timed(self, nsteps):
-        """Runs nsteps and returns the HIP-event time of the step loop in milliseconds."""
-        ms = ctypes.c_double()
-        _check(self.lib.lbm_dens_run_timed(self.ens, nsteps, ctypes.byref(ms)), "lbm_dens_run_timed")
-        return ms.value
-
-    def sync(self):
-        _check(self.lib.lbm_dens_sync(self.ens), "lbm_dens_sync")
-
-    @property
-    def steps_done(self):
-        return self.lib.lbm_dens_steps_done(self.ens)
+            self._call("upload", c.ctypes.data)
 
     def download(self, cells=True, av_vels=True):
-        """Returns (cells float64[n,9,ny,nx] or None, av_vels float64[n,steps_done] or None)."""
+        """Returns (cells float32[n,9,ny,nx] or None, av_vels float32[n,steps_done] or None); an EnsembleDouble: float64."""
         steps = self.steps_done
-        c = np.zeros((self.n, 9, self.ny, self.nx), dtype=np.float64) if cells else None
-        a = np.zeros((self.n, steps), dtype=np.float64) if av_vels else None
-        _check(self.lib.lbm_dens_download(self.ens, c.ctypes.data if cells else None,
-                                          a.ctypes.data if av_vels and steps else None), "lbm_dens_download")
+        c = np.zeros((self.n, 9, self.ny, self.nx), dtype=self._dtype) if cells else None
+        a = np.zeros((self.n, steps), dtype=self._dtype) if av_vels else None
+        self._call("download", c.ctypes.data if cells else None, a.ctypes.data if av_vels and steps else None)
         return c, a
 
     def final_state(self):
-        """(u_x, u_y, u, pressure), each float64[n,ny,nx] — per member the columns of final_state.dat."""
-        outs = [np.zeros((self.n, self.ny, self.nx), dtype=np.float64) for _ in range(4)]
-        _check(self.lib.lbm_dens_final_state(self.ens, *[o.ctypes.data for o in outs]), "lbm_dens_final_state")
+        """(u_x, u_y, u, pressure), each float32[n,ny,nx] (an EnsembleDouble: float64) — per member the columns of
+        final_state.dat."""
+        outs = [np.zeros((self.n, self.ny, self.nx), dtype=self._dtype) for _ in range(4)]
+        self._call("final_state", *[o.ctypes.data for o in outs])
         return outs
 
     def reynolds(self):
-        """float64[n]: every member's Reynolds number of the current state"""
-        r = np.zeros(self.n, dtype=np.float64)
-        _check(self.lib.lbm_dens_reynolds(self.ens, r.ctypes.data), "lbm_dens_reynolds")
+        """float32[n] (an EnsembleDouble: float64[n]): every member's Reynolds number of the current state"""
+        r = np.zeros(self.n, dtype=self._dtype)
+        self._call("reynolds", r.ctypes.data)
         return r
 
-    def close(self):
-        if self.ens:
-            self.lib.lbm_dens_destroy(self.ens)
-            self.ens = ctypes.c_void_p()
 
-    def __enter__(self):
-        return self
+class Ensemble(_EnsembleOf):
+    """N independent simulations of one grid size, advanced together (lbm_ens): one launch per (up to) eight timesteps for
+    all members.  Mirrors LBM with the member index as the first axis of every array.  `params`: a list of Params that share
+    nx, ny and max_iters; `obstacles`: int32[n, ny, nx], or one [ny, nx] map for all members."""
+    _prefix, _dtype, _ptype = "lbm_ens", np.float32, Params
 
-    def __exit__(self, *exc):
-        self.close()
+    def run_until(self, max_steps, window=64, rel_tol=1e-4):
+        """Every member to its own steady state (lbm_steady_run): legs of `window` steps, a member stops at the first check
+        point s where |A(s) - A(s - window)| <= rel_tol |A(s)| on its own av_vels record, at most max_steps steps.  Returns
+        (steps int32[n], converged bool[n]).  Members that stopped at different counts leave the ensemble ragged: download(),
+        final_state() and reynolds() return every member's own last state, run() is refused until the next upload()."""
+        _check(self.lib.lbm_steady_run(self.ens, max_steps, window, rel_tol), "lbm_steady_run")
+        return self.member_steps()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def member_steps(self):
+        """(steps int32[n], converged bool[n]): per member the steps applied since the last upload, and whether it met the
+        criterion of the last run_until since then"""
+        steps = np.zeros(self.n, dtype=np.int32)
+        conv = np.zeros(self.n, dtype=np.int32)
+        _check(self.lib.lbm_steady_steps(self.ens, steps.ctypes.data, conv.ctypes.data), "lbm_steady_steps")
+        return steps, conv.astype(bool)
+
+
+class EnsembleDouble(_EnsembleOf):
+    """N independent double-precision simulations of one grid size, advanced together (lbm_dens): one launch per several
+    timesteps for all members, every member bit-identical to an LBMDouble on the same inputs.  Mirrors Ensemble with double
+    in place of float.  `params`: a list of DParams that share nx, ny and max_iters (sweep_dparams); `obstacles`:
+    int32[n, ny, nx], or one [ny, nx] map for all members."""
+    _prefix, _dtype, _ptype = "lbm_dens", np.float64, DParams
+
+    def __init__(self, params, obstacles):
+        params = list(params)
+        if not all(isinstance(p, DParams) for p in params):
+            raise LBMError("EnsembleDouble takes DParams (make_dparams / read_inputs_double / sweep_dparams)")
+        super().__init__(params, obstacles)

@@ -10,7 +10,7 @@
 // The reference has no counterpart: one grid, one in-order queue (d2q9-bgk.c:221-239).
 #include "../../include/lbm.h"
 #include "dp_ensemble_kernels.h"
-#include "lbm_error.h"
+#include "host_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -18,24 +18,15 @@
 #include <vector>
 
 using namespace lbm;
+using namespace lbm_host;
 
 namespace {
-
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess)                                                                           \
-      return lbm_fail(LBM_ERR_HIP, "HIP error during '%s' (%s:%d): %s", #expr, __FILE__, __LINE__, \
-                      hipGetErrorString(e_));                                                       \
-  } while (0)
 
 constexpr long kDensMaxCells = 300L * 1024;   // up to here lbm_dp itself takes the LDS-tile form (multistep_effective, lbm_dp.cpp)
 constexpr int kDensMaxMembers = 65535;        // member index = blockIdx.y (blockIdx.z in dens_reduce)
 constexpr size_t kDensRingBytes = 32u << 20;  // per-step segment sums of all members buffered between reductions
 constexpr int kDensRingMax = 256;
 constexpr long kDensSegsPerBlock = 4096;      // segments per block of the first reduction stage: lbm_dp.cpp's kDpSegsPerBlock
-
-inline long div_up(long a, long b) { return (a + b - 1) / b; }
 
 // The instantiated form of d2q9_dp_ensemble<16, TY, TMAX, threads>: 16 x 16 at T <= 3 with 1024 threads, two workgroups per
 // CU (dp_ensemble_kernels.h holds the measurements behind the choice).  A measurement build takes another form:
@@ -57,9 +48,7 @@ struct lbm_dens {
   int n = 0;
   int nx = 0, ny = 0, max_iters = 0;
   std::vector<lbm_dparams> p;
-  int dev = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+  Queue q;
   size_t plane_stride = 0, member_stride = 0;  // doubles
   double *cells[2] = {nullptr, nullptr};
   uint8_t *mask = nullptr;         // [n][ny][nx]
@@ -78,7 +67,7 @@ struct lbm_dens {
 namespace {
 
 void free_dens(lbm_dens *e) {
-  if (e->st) (void)hipStreamSynchronize(e->st);
+  queue_drain(e->q);
   for (double *c : e->cells)
     if (c) (void)hipFree(c);
   if (e->mask) (void)hipFree(e->mask);
@@ -87,16 +76,14 @@ void free_dens(lbm_dens *e) {
   if (e->red) (void)hipFree(e->red);
   if (e->av_sum) (void)hipFree(e->av_sum);
   if (e->fin_partials) (void)hipFree(e->fin_partials);
-  if (e->ev_t0) (void)hipEventDestroy(e->ev_t0);
-  if (e->ev_t1) (void)hipEventDestroy(e->ev_t1);
-  if (e->st) (void)hipStreamDestroy(e->st);
+  queue_destroy(e->q);
   delete e;
 }
 
 int build_dens(lbm_dens *e, const int32_t *obstacles) {
   const int n = e->n, nx = e->nx, ny = e->ny;
   const size_t cells_per = (size_t)nx * ny;
-  HIP_TRY(hipGetDevice(&e->dev));
+  HIP_TRY(hipGetDevice(&e->q.dev));
   e->tiles_x = (int)div_up(nx, kDensTX);
   e->tiles = e->tiles_x * (int)div_up(ny, kDensTY);
   // the sizes of build_dp (lbm_dp.cpp), from the member's nx and ny alone: they fix the order of every sum
@@ -120,9 +107,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
     return lbm_fail(LBM_ERR_HIP, "a double-precision ensemble of %d members of %dx%d with max_iters=%d needs %.1f MiB of device memory, "
                     "%.1f MiB are free", n, nx, ny, e->max_iters, (double)need / 1048576.0, (double)free_b / 1048576.0);
 
-  HIP_TRY(hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreate(&e->ev_t0));
-  HIP_TRY(hipEventCreate(&e->ev_t1));
+  if (int rc = queue_create(e->q)) return rc;
   for (int i = 0; i < 2; i++) {
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->cells[i]), cells_bytes));
     HIP_TRY(hipMemset(e->cells[i], 0, cells_bytes));
@@ -133,46 +118,27 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->red), (size_t)e->ring * n * e->red_blocks * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->av_sum), (size_t)n * e->max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->fin_partials), (size_t)n * e->fin_blocks * sizeof(double)));
-  {
-    // the members' byte masks from the caller's int32[n][ny][nx] (d2q9-bgk.c:205-209: the obstacle transfer)
-    std::vector<uint8_t> m((size_t)n * cells_per);
-    for (size_t i = 0; i < m.size(); i++) m[i] = obstacles[i] != 0;
-    HIP_TRY(hipMemcpy(e->mask, m.data(), m.size(), hipMemcpyHostToDevice));
-  }
-  {
-    // the statements of lbm_dp.cpp (run_dp_impl, lbm_dp_upload), in double
-    std::vector<DensMember> t(n);
-    for (int i = 0; i < n; i++) {
-      const lbm_dparams &p = e->p[i];
-      t[i].omega = p.omega;
-      t[i].aw1 = p.density * p.accel / 9.0;   // kernels.cl:14-15
-      t[i].aw2 = p.density * p.accel / 36.0;
-      t[i].density = p.density;
-      t[i].w0 = p.density * 4.0 / 9.0;        // d2q9-bgk.c:529-531
-      t[i].w1 = p.density / 9.0;
-      t[i].w2 = p.density / 36.0;
-      t[i].pad = 0.0;
-    }
-    HIP_TRY(hipMemcpy(e->members, t.data(), t.size() * sizeof(DensMember), hipMemcpyHostToDevice));
-  }
+  // the members' byte masks from the caller's int32[n][ny][nx]
+  if (int rc = upload_mask(e->mask, obstacles, (size_t)n * cells_per)) return rc;
+  // in double these are lbm_dp.cpp's own statements (run_dp_impl, lbm_dp_upload): a member's constants are a context's
+  std::vector<DensMember> t(n);
+  for (int i = 0; i < n; i++) t[i] = member_constants<DensMember>(e->p[i]);
+  HIP_TRY(hipMemcpy(e->members, t.data(), t.size() * sizeof(DensMember), hipMemcpyHostToDevice));
   return LBM_OK;
 }
 
 int run_dens_impl(lbm_dens *e, int nsteps, bool timed, double *ms, bool *launched) {
-  if (nsteps < 0) return lbm_fail(LBM_ERR_ARG, "nsteps must be >= 0");
-  if (e->failed) return lbm_fail(LBM_ERR_STATE, "an earlier run failed after its launches had begun; destroy the ensemble");
-  if (e->steps_done + nsteps > e->max_iters)
-    return lbm_fail(LBM_ERR_STATE, "av_vels record holds max_iters=%d steps; %d done, %d more requested", e->max_iters,
-                    e->steps_done, nsteps);
+  if (int rc = check_runnable(nsteps, e->failed, "ensemble")) return rc;
+  if (int rc = check_record(e->max_iters, e->steps_done, nsteps, "")) return rc;
   if (timed && ms) *ms = 0.0;
   if (nsteps == 0) return LBM_OK;
-  HIP_TRY(hipSetDevice(e->dev));
+  HIP_TRY(hipSetDevice(e->q.dev));
   *launched = true;
   const size_t per_step = (size_t)e->ny * e->nseg, all_step = (size_t)e->n * per_step;
-  if (timed) HIP_TRY(hipEventRecord(e->ev_t0, e->st));
+  if (int rc = timed_begin(e->q, timed)) return rc;
   // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
   // into the previous launch's write of row ny-2
-  hipLaunchKernelGGL(dens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->st, e->cells[e->cur], e->plane_stride,
+  hipLaunchKernelGGL(dens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
                      e->member_stride, (const uint8_t *)e->mask, (const DensMember *)e->members, e->nx, e->ny);
   HIP_TRY(hipGetLastError());
 
@@ -182,15 +148,15 @@ int run_dens_impl(lbm_dens *e, int nsteps, bool timed, double *ms, bool *launche
     if (e->ring_fill == 0) return LBM_OK;
     const unsigned long long record = (unsigned long long)e->max_iters;
     if (e->red_blocks > 1) {
-      hipLaunchKernelGGL(dens_reduce, dim3(e->red_blocks, e->ring_fill, e->n), dim3(kBlock), 0, e->st, (const double *)e->seg,
+      hipLaunchKernelGGL(dens_reduce, dim3(e->red_blocks, e->ring_fill, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->seg,
                          (unsigned long long)all_step, (unsigned long long)per_step, (long)per_step, e->red,
                          (unsigned long long)e->n * e->red_blocks, (unsigned long long)e->red_blocks);
       HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(dens_reduce, dim3(1, e->ring_fill, e->n), dim3(kBlock), 0, e->st, (const double *)e->red,
+      hipLaunchKernelGGL(dens_reduce, dim3(1, e->ring_fill, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->red,
                          (unsigned long long)e->n * e->red_blocks, (unsigned long long)e->red_blocks, (long)e->red_blocks,
                          e->av_sum + batch_first, 1ull, record);
     } else {
-      hipLaunchKernelGGL(dens_reduce, dim3(1, e->ring_fill, e->n), dim3(kBlock), 0, e->st, (const double *)e->seg,
+      hipLaunchKernelGGL(dens_reduce, dim3(1, e->ring_fill, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->seg,
                          (unsigned long long)all_step, (unsigned long long)per_step, (long)per_step, e->av_sum + batch_first, 1ull,
                          record);
     }
@@ -203,7 +169,7 @@ int run_dens_impl(lbm_dens *e, int nsteps, bool timed, double *ms, bool *launche
   while (i < nsteps) {
     // the remaining steps in as few launches as possible, of equal depth (8 steps at 3 a launch: 3 + 3 + 2)
     const int rem = nsteps - i;
-    const int adv = (int)div_up(rem, div_up(rem, kDensTMax));
+    const int adv = equal_depth(rem, kDensTMax);
     if (e->ring_fill + adv > e->ring)
       if (int rc = flush()) return rc;
     DensArgs a{};
@@ -222,7 +188,7 @@ int run_dens_impl(lbm_dens *e, int nsteps, bool timed, double *ms, bool *launche
     a.T = adv;
     a.accel_next = (i + adv < nsteps) ? 1 : 0;
     hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads>), dim3(e->tiles, e->n), dim3(kDensThreads), 0,
-                       e->st, a);
+                       e->q.st, a);
     HIP_TRY(hipGetLastError());
     e->cur ^= 1;
     e->ring_fill += adv;
@@ -230,46 +196,23 @@ int run_dens_impl(lbm_dens *e, int nsteps, bool timed, double *ms, bool *launche
   }
   if (int rc = flush()) return rc;
   e->steps_done += nsteps;
-  if (timed) {
-    HIP_TRY(hipEventRecord(e->ev_t1, e->st));
-    HIP_TRY(hipEventSynchronize(e->ev_t1));
-    float t = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&t, e->ev_t0, e->ev_t1));
-    if (ms) *ms = t;
-  }
-  return LBM_OK;
+  return timed_end(e->q, timed, ms);
 }
 
-// A failure after launches have begun: let what was enqueued finish and refuse further work (as run_steps, lbm_hip.cpp)
 int run_dens(lbm_dens *e, int nsteps, bool timed, double *ms) {
   bool launched = false;
   const int rc = run_dens_impl(e, nsteps, timed, ms, &launched);
-  if (rc != LBM_OK && launched) {
-    const std::string keep = lbm_last_error();
-    (void)hipStreamSynchronize(e->st);
-    (void)hipGetLastError();
-    e->failed = true;
-    lbm_fail(rc, "%s", keep.c_str());
-  }
-  return rc;
-}
-
-int sync_dens(lbm_dens *e) {
-  HIP_TRY(hipSetDevice(e->dev));
-  HIP_TRY(hipStreamSynchronize(e->st));
-  return LBM_OK;
+  return latch_failure(rc, launched, e->q.st, &e->failed);
 }
 
 // the output stage of all members into `d[0..3]` (any may be NULL) and the per-block sums of u
 int final_fields_dens(lbm_dens *e, double *const (&d)[4]) {
-  hipLaunchKernelGGL(dens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->st, (const double *)e->cells[e->cur],
+  hipLaunchKernelGGL(dens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->cells[e->cur],
                      e->plane_stride, e->member_stride, e->nx, (const uint8_t *)e->mask, (size_t)e->nx * e->ny,
                      (const DensMember *)e->members, d[0], d[1], d[2], d[3], e->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
 }
-
-bool positive_finite(double v) { return std::isfinite(v) && v > 0.0; }
 
 }  // namespace
 
@@ -286,10 +229,7 @@ int lbm_dens_create(lbm_dens **out, const lbm_dparams *params, const int32_t *ob
   const lbm_dparams &p0 = params[0];
   if (p0.nx < 3 || p0.ny < 3) return lbm_fail(LBM_ERR_ARG, "grid must be at least 3x3 (got %dx%d)", p0.nx, p0.ny);
   if (p0.max_iters < 1) return lbm_fail(LBM_ERR_ARG, "max_iters must be >= 1 (got %d)", p0.max_iters);
-  for (int i = 1; i < n; i++)
-    if (params[i].nx != p0.nx || params[i].ny != p0.ny || params[i].max_iters != p0.max_iters)
-      return lbm_fail(LBM_ERR_ARG, "member %d is %dx%d with max_iters=%d, member 0 %dx%d with max_iters=%d: the members of an ensemble "
-                      "share nx, ny and max_iters", i, params[i].nx, params[i].ny, params[i].max_iters, p0.nx, p0.ny, p0.max_iters);
+  if (int rc = check_members_alike(params, n)) return rc;
   for (int i = 0; i < n; i++) {
     const lbm_dparams &p = params[i];
     if (!positive_finite(p.omega)) return lbm_fail(LBM_ERR_ARG, "member %d: omega must be finite and positive (got %g)", i, p.omega);
@@ -313,8 +253,7 @@ int lbm_dens_create(lbm_dens **out, const lbm_dparams *params, const int32_t *ob
   if (int rc = build_dens(e, obstacles)) {
     const std::string keep = lbm_last_error();
     free_dens(e);
-    (void)hipGetLastError();
-    return lbm_fail(rc, "%s", keep.c_str());
+    return fail_again(rc, keep);
   }
   *out = e;
   return LBM_OK;
@@ -322,21 +261,21 @@ int lbm_dens_create(lbm_dens **out, const lbm_dparams *params, const int32_t *ob
 
 int lbm_dens_upload(lbm_dens *e, const double *cells) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  if (int rc = sync_dens(e)) return rc;
+  if (int rc = queue_sync(e->q)) return rc;
   const size_t per = (size_t)e->nx * e->ny;
   const dim3 grid((unsigned)std::min(div_up((long)per, 256), 1024L), e->n);
   if (cells) {
     // one transfer of the caller's double[n][9][ny][nx] into the second grid array (9 nx ny <= member_stride), then one
     // launch that scatters every member's planes into the first (d2q9-bgk.c:200-203 for all members)
-    HIP_TRY(hipMemcpyAsync(e->cells[1], cells, (size_t)e->n * 9 * per * sizeof(double), hipMemcpyHostToDevice, e->st));
-    hipLaunchKernelGGL(dens_pack_planes<true>, grid, dim3(256), 0, e->st, e->cells[0], e->plane_stride, e->member_stride, e->nx, per,
+    HIP_TRY(hipMemcpyAsync(e->cells[1], cells, (size_t)e->n * 9 * per * sizeof(double), hipMemcpyHostToDevice, e->q.st));
+    hipLaunchKernelGGL(dens_pack_planes<true>, grid, dim3(256), 0, e->q.st, e->cells[0], e->plane_stride, e->member_stride, e->nx, per,
                        e->cells[1]);
   } else {
-    hipLaunchKernelGGL(dens_init_cells, grid, dim3(256), 0, e->st, e->cells[0], e->plane_stride, e->member_stride,
+    hipLaunchKernelGGL(dens_init_cells, grid, dim3(256), 0, e->q.st, e->cells[0], e->plane_stride, e->member_stride,
                        (const DensMember *)e->members, e->nx, per);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(hipStreamSynchronize(e->q.st));
   e->cur = 0;
   e->steps_done = 0;
   e->ring_fill = 0;
@@ -355,7 +294,7 @@ int lbm_dens_run_timed(lbm_dens *e, int nsteps, double *ms) {
 
 int lbm_dens_sync(lbm_dens *e) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  return sync_dens(e);
+  return queue_sync(e->q);
 }
 
 int lbm_dens_steps_done(const lbm_dens *e) { return e ? e->steps_done : -1; }
@@ -363,17 +302,17 @@ int lbm_dens_members(const lbm_dens *e) { return e ? e->n : -1; }
 
 int lbm_dens_download(lbm_dens *e, double *cells_out, double *av_vels_out) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  if (int rc = sync_dens(e)) return rc;
+  if (int rc = queue_sync(e->q)) return rc;
   const size_t per = (size_t)e->nx * e->ny;
   if (cells_out) {
     // the grid array that is not current is scratch between runs: repack every member into the caller's layout there,
     // then one contiguous transfer
     double *stage = e->cells[e->cur ^ 1];
-    hipLaunchKernelGGL(dens_pack_planes<false>, dim3((unsigned)std::min(div_up((long)per, 256), 1024L), e->n), dim3(256), 0, e->st,
+    hipLaunchKernelGGL(dens_pack_planes<false>, dim3((unsigned)std::min(div_up((long)per, 256), 1024L), e->n), dim3(256), 0, e->q.st,
                        e->cells[e->cur], e->plane_stride, e->member_stride, e->nx, per, stage);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(cells_out, stage, (size_t)e->n * 9 * per * sizeof(double), hipMemcpyDeviceToHost, e->st));
-    HIP_TRY(hipStreamSynchronize(e->st));
+    HIP_TRY(hipMemcpyAsync(cells_out, stage, (size_t)e->n * 9 * per * sizeof(double), hipMemcpyDeviceToHost, e->q.st));
+    HIP_TRY(hipStreamSynchronize(e->q.st));
   }
   if (av_vels_out && e->steps_done > 0) {
     const int T = e->steps_done;
@@ -389,7 +328,7 @@ int lbm_dens_download(lbm_dens *e, double *cells_out, double *av_vels_out) {
 
 int lbm_dens_final_state(lbm_dens *e, double *u_x, double *u_y, double *u, double *pressure) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  if (int rc = sync_dens(e)) return rc;
+  if (int rc = queue_sync(e->q)) return rc;
   const size_t all = (size_t)e->nx * e->ny * e->n;
   double *outs[4] = {u_x, u_y, u, pressure};
   // the four columns of all members go to the grid array that is not current (4 n nx ny doubles of its 9 n nx ny)
@@ -398,19 +337,19 @@ int lbm_dens_final_state(lbm_dens *e, double *u_x, double *u_y, double *u, doubl
     if (outs[i]) d[i] = e->cells[e->cur ^ 1] + (size_t)i * all;
   if (int rc = final_fields_dens(e, d)) return rc;
   for (int i = 0; i < 4; i++)
-    if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], d[i], all * sizeof(double), hipMemcpyDeviceToHost, e->st));
-  HIP_TRY(hipStreamSynchronize(e->st));
+    if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], d[i], all * sizeof(double), hipMemcpyDeviceToHost, e->q.st));
+  HIP_TRY(hipStreamSynchronize(e->q.st));
   return LBM_OK;
 }
 
 int lbm_dens_reynolds(lbm_dens *e, double *reynolds_out) {
   if (!e || !reynolds_out) return lbm_fail(LBM_ERR_ARG, "NULL argument");
-  if (int rc = sync_dens(e)) return rc;
+  if (int rc = queue_sync(e->q)) return rc;
   double *none[4] = {nullptr, nullptr, nullptr, nullptr};
   if (int rc = final_fields_dens(e, none)) return rc;
   std::vector<double> part((size_t)e->n * e->fin_blocks);
-  HIP_TRY(hipMemcpyAsync(part.data(), e->fin_partials, part.size() * sizeof(double), hipMemcpyDeviceToHost, e->st));
-  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(hipMemcpyAsync(part.data(), e->fin_partials, part.size() * sizeof(double), hipMemcpyDeviceToHost, e->q.st));
+  HIP_TRY(hipStreamSynchronize(e->q.st));
   for (int m = 0; m < e->n; m++) {
     double tot = 0.0;
     for (int b = 0; b < e->fin_blocks; b++) tot += part[(size_t)m * e->fin_blocks + b];
@@ -424,7 +363,7 @@ int lbm_dens_reynolds(lbm_dens *e, double *reynolds_out) {
 
 void lbm_dens_destroy(lbm_dens *e) {
   if (!e) return;
-  (void)hipSetDevice(e->dev);
+  (void)hipSetDevice(e->q.dev);
   free_dens(e);
 }
 

@@ -8,7 +8,7 @@
 // in-order queue (d2q9-bgk.c:221-239), in the precision of its fp64 ancestor.
 #include "../../include/lbm.h"
 #include "dp_kernels.h"
-#include "lbm_error.h"
+#include "host_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -17,6 +17,7 @@
 #include <vector>
 
 using namespace lbm;
+using namespace lbm_host;
 
 // The LDS-tile form's tile height and most steps per launch (16 x 16 at T <= 8 unless a measurement build asks for
 // another shape: tools/dp_throughput.py, DESIGN.md "Double precision")
@@ -29,29 +30,17 @@ using namespace lbm;
 
 namespace {
 
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess)                                                                           \
-      return lbm_fail(LBM_ERR_HIP, "HIP error during '%s' (%s:%d): %s", #expr, __FILE__, __LINE__, \
-                      hipGetErrorString(e_));                                                       \
-  } while (0)
-
 constexpr int kDpTX = 16, kDpTY = LBM_DP_TY, kDpTMax = LBM_DP_TMAX;
 constexpr long kDpAutoMultiCells = 300L * 1024;  // the library's bound for "launch-bound" (multistep_effective, lbm_hip.cpp)
 constexpr size_t kDpRingBytes = 32u << 20;       // per-step segment sums buffered between reductions
 constexpr int kDpRingMax = 256;
 constexpr long kDpSegsPerBlock = 4096;           // segments per block of the first reduction stage
 
-inline long div_up(long a, long b) { return (a + b - 1) / b; }
-
 }  // namespace
 
 struct lbm_dp {
   lbm_dparams p{};
-  int dev = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+  Queue q;
   size_t plane_stride = 0;        // doubles
   double *cells[2] = {nullptr, nullptr};
   uint8_t *mask = nullptr;        // [ny][nx]
@@ -76,7 +65,7 @@ int multistep_effective(const lbm_dp *d) {
 }
 
 void free_dp(lbm_dp *d) {
-  if (d->st) (void)hipStreamSynchronize(d->st);
+  queue_drain(d->q);
   for (double *c : d->cells)
     if (c) (void)hipFree(c);
   if (d->mask) (void)hipFree(d->mask);
@@ -84,24 +73,14 @@ void free_dp(lbm_dp *d) {
   if (d->red) (void)hipFree(d->red);
   if (d->av_sum) (void)hipFree(d->av_sum);
   if (d->fin_partials) (void)hipFree(d->fin_partials);
-  if (d->ev_t0) (void)hipEventDestroy(d->ev_t0);
-  if (d->ev_t1) (void)hipEventDestroy(d->ev_t1);
-  if (d->st) (void)hipStreamDestroy(d->st);
+  queue_destroy(d->q);
   delete d;
-}
-
-int copy_mask(lbm_dp *d, const int32_t *obstacles) {
-  const size_t n = (size_t)d->p.nx * d->p.ny;
-  std::vector<uint8_t> m(n);
-  for (size_t i = 0; i < n; i++) m[i] = obstacles[i] != 0;
-  HIP_TRY(hipMemcpy(d->mask, m.data(), n, hipMemcpyHostToDevice));
-  return LBM_OK;
 }
 
 int build_dp(lbm_dp *d, const int32_t *obstacles) {
   const int nx = d->p.nx, ny = d->p.ny;
   const size_t cells = (size_t)nx * ny;
-  HIP_TRY(hipGetDevice(&d->dev));
+  HIP_TRY(hipGetDevice(&d->q.dev));
   d->plane_stride = ((size_t)(nx + 31) / 32) * 32;   // 256-B lines, >= nx + 1 for odd nx: a lane's second cell stays inside
   d->lanes_per_row = (int)(div_up(div_up(nx, 2), 8) * 8);
   d->nseg = d->lanes_per_row / 8;                    // = ceil(nx / 16)
@@ -124,9 +103,7 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
     return lbm_fail(LBM_ERR_HIP, "a double-precision grid of %dx%d with max_iters=%d needs %.1f MiB of device memory, %.1f MiB are free",
                     nx, ny, d->p.max_iters, (double)need / 1048576.0, (double)free_b / 1048576.0);
 
-  HIP_TRY(hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreate(&d->ev_t0));
-  HIP_TRY(hipEventCreate(&d->ev_t1));
+  if (int rc = queue_create(d->q)) return rc;
   for (int i = 0; i < 2; i++) {
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->cells[i]), grid_bytes));
     HIP_TRY(hipMemset(d->cells[i], 0, grid_bytes));
@@ -136,28 +113,25 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->red), (size_t)d->ring * d->red_blocks * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->av_sum), (size_t)d->p.max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->fin_partials), (size_t)d->fin_blocks * sizeof(double)));
-  return copy_mask(d, obstacles);
+  return upload_mask(d->mask, obstacles, cells);
 }
 
 int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
-  if (nsteps < 0) return lbm_fail(LBM_ERR_ARG, "nsteps must be >= 0");
-  if (d->failed) return lbm_fail(LBM_ERR_STATE, "an earlier run failed after its launches had begun; destroy the context");
-  if (d->steps_done + nsteps > d->p.max_iters)
-    return lbm_fail(LBM_ERR_STATE, "av_vels record holds max_iters=%d steps; %d done, %d more requested", d->p.max_iters,
-                    d->steps_done, nsteps);
+  if (int rc = check_runnable(nsteps, d->failed, "context")) return rc;
+  if (int rc = check_record(d->p.max_iters, d->steps_done, nsteps, "")) return rc;
   if (timed && ms) *ms = 0.0;
   if (nsteps == 0) return LBM_OK;
-  HIP_TRY(hipSetDevice(d->dev));
+  HIP_TRY(hipSetDevice(d->q.dev));
   *launched = true;
   const int nx = d->p.nx, ny = d->p.ny;
   const double aw1 = d->p.density * d->p.accel / 9.0;   // kernels.cl:14-15
   const double aw2 = d->p.density * d->p.accel / 36.0;
   const size_t per_step = (size_t)ny * d->nseg;
   const int T = multistep_effective(d);
-  if (timed) HIP_TRY(hipEventRecord(d->ev_t0, d->st));
+  if (int rc = timed_begin(d->q, timed)) return rc;
   // prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53); later steps get theirs fused into
   // the previous launch's write of row ny-2
-  hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(nx, 128)), dim3(128), 0, d->st, d->cells[d->cur], d->plane_stride, d->mask,
+  hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(nx, 128)), dim3(128), 0, d->q.st, d->cells[d->cur], d->plane_stride, d->mask,
                      nx, ny - 2, aw1, aw2);
   HIP_TRY(hipGetLastError());
 
@@ -166,13 +140,13 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   auto flush = [&]() -> int {
     if (d->ring_fill == 0) return LBM_OK;
     if (d->red_blocks > 1) {
-      hipLaunchKernelGGL(dp_reduce, dim3(d->red_blocks, d->ring_fill), dim3(kBlock), 0, d->st, (const double *)d->seg,
+      hipLaunchKernelGGL(dp_reduce, dim3(d->red_blocks, d->ring_fill), dim3(kBlock), 0, d->q.st, (const double *)d->seg,
                          (unsigned long long)per_step, (long)per_step, d->red, (unsigned long long)d->red_blocks);
       HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(dp_reduce, dim3(1, d->ring_fill), dim3(kBlock), 0, d->st, (const double *)d->red,
+      hipLaunchKernelGGL(dp_reduce, dim3(1, d->ring_fill), dim3(kBlock), 0, d->q.st, (const double *)d->red,
                          (unsigned long long)d->red_blocks, (long)d->red_blocks, d->av_sum + batch_first, 1ull);
     } else {
-      hipLaunchKernelGGL(dp_reduce, dim3(1, d->ring_fill), dim3(kBlock), 0, d->st, (const double *)d->seg,
+      hipLaunchKernelGGL(dp_reduce, dim3(1, d->ring_fill), dim3(kBlock), 0, d->q.st, (const double *)d->seg,
                          (unsigned long long)per_step, (long)per_step, d->av_sum + batch_first, 1ull);
     }
     HIP_TRY(hipGetLastError());
@@ -184,7 +158,7 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   while (i < nsteps) {
     // the LDS-tile form: the remaining steps in as few launches as possible, of equal depth (20 steps at T = 8: 7 + 7 + 6)
     const int rem = nsteps - i;
-    const int adv = T > 0 ? (int)div_up(rem, div_up(rem, T)) : 1;
+    const int adv = T > 0 ? equal_depth(rem, T) : 1;
     if (d->ring_fill + adv > d->ring)
       if (int rc = flush()) return rc;
     const bool accel_next = i + adv < nsteps;
@@ -206,7 +180,7 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.omega = d->p.omega;
       a.aw1 = aw1;
       a.aw2 = aw2;
-      hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax>), dim3(d->tiles), dim3(kMultiThreads), 0, d->st, a);
+      hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
     } else {
       DpStepArgs a{};
       a.src = d->cells[d->cur];
@@ -221,7 +195,7 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.omega = d->p.omega;
       a.aw1 = aw1;
       a.aw2 = aw2;
-      hipLaunchKernelGGL(d2q9_dp_step, dim3((unsigned)div_up((long)d->lanes_per_row * ny, kBlock)), dim3(kBlock), 0, d->st, a);
+      hipLaunchKernelGGL(d2q9_dp_step, dim3((unsigned)div_up((long)d->lanes_per_row * ny, kBlock)), dim3(kBlock), 0, d->q.st, a);
     }
     HIP_TRY(hipGetLastError());
     d->cur ^= 1;
@@ -230,46 +204,23 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   }
   if (int rc = flush()) return rc;
   d->steps_done += nsteps;
-  if (timed) {
-    HIP_TRY(hipEventRecord(d->ev_t1, d->st));
-    HIP_TRY(hipEventSynchronize(d->ev_t1));
-    float t = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&t, d->ev_t0, d->ev_t1));
-    if (ms) *ms = t;
-  }
-  return LBM_OK;
+  return timed_end(d->q, timed, ms);
 }
 
-// A failure after launches have begun: let what was enqueued finish and refuse further work (as run_steps, lbm_hip.cpp)
 int run_dp(lbm_dp *d, int nsteps, bool timed, double *ms) {
   bool launched = false;
   const int rc = run_dp_impl(d, nsteps, timed, ms, &launched);
-  if (rc != LBM_OK && launched) {
-    const std::string keep = lbm_last_error();
-    (void)hipStreamSynchronize(d->st);
-    (void)hipGetLastError();
-    d->failed = true;
-    lbm_fail(rc, "%s", keep.c_str());
-  }
-  return rc;
-}
-
-int sync_dp(lbm_dp *d) {
-  HIP_TRY(hipSetDevice(d->dev));
-  HIP_TRY(hipStreamSynchronize(d->st));
-  return LBM_OK;
+  return latch_failure(rc, launched, d->q.st, &d->failed);
 }
 
 // the output stage into `d[0..3]` (any may be NULL) and the per-block sums of u
 int final_fields_dp(lbm_dp *d, double *const (&dst)[4]) {
   const size_t n = (size_t)d->p.nx * d->p.ny;
-  hipLaunchKernelGGL(dp_final_fields, dim3(d->fin_blocks), dim3(kBlock), 0, d->st, (const double *)d->cells[d->cur], d->plane_stride,
+  hipLaunchKernelGGL(dp_final_fields, dim3(d->fin_blocks), dim3(kBlock), 0, d->q.st, (const double *)d->cells[d->cur], d->plane_stride,
                      d->p.nx, (const uint8_t *)d->mask, n, d->p.density, dst[0], dst[1], dst[2], dst[3], d->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
 }
-
-bool positive_finite(double v) { return std::isfinite(v) && v > 0.0; }
 
 }  // namespace
 
@@ -296,8 +247,7 @@ int lbm_dp_create(lbm_dp **out, const lbm_dparams *p, const int32_t *obstacles) 
   if (int rc = build_dp(d, obstacles)) {
     const std::string keep = lbm_last_error();
     free_dp(d);
-    (void)hipGetLastError();
-    return lbm_fail(rc, "%s", keep.c_str());
+    return fail_again(rc, keep);
   }
   *out = d;
   return LBM_OK;
@@ -305,21 +255,21 @@ int lbm_dp_create(lbm_dp **out, const lbm_dparams *p, const int32_t *obstacles) 
 
 int lbm_dp_upload(lbm_dp *d, const double *cells) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
-  if (int rc = sync_dp(d)) return rc;
+  if (int rc = queue_sync(d->q)) return rc;
   const size_t n = (size_t)d->p.nx * d->p.ny;
   const dim3 grid((unsigned)std::min(div_up((long)n, 256), 4096L));
   if (cells) {
     // one transfer of the caller's double[9][ny][nx] into the second grid array (9 nx ny <= its size), then one launch that
     // scatters the planes into the first (d2q9-bgk.c:200-203)
-    HIP_TRY(hipMemcpyAsync(d->cells[1], cells, 9 * n * sizeof(double), hipMemcpyHostToDevice, d->st));
-    hipLaunchKernelGGL(dp_pack_planes<true>, grid, dim3(256), 0, d->st, d->cells[0], d->plane_stride, d->p.nx, n, d->cells[1]);
+    HIP_TRY(hipMemcpyAsync(d->cells[1], cells, 9 * n * sizeof(double), hipMemcpyHostToDevice, d->q.st));
+    hipLaunchKernelGGL(dp_pack_planes<true>, grid, dim3(256), 0, d->q.st, d->cells[0], d->plane_stride, d->p.nx, n, d->cells[1]);
   } else {
     // d2q9-bgk.c:529-550 in double
     const double w0 = d->p.density * 4.0 / 9.0, w1 = d->p.density / 9.0, w2 = d->p.density / 36.0;
-    hipLaunchKernelGGL(dp_init_cells, grid, dim3(256), 0, d->st, d->cells[0], d->plane_stride, d->p.nx, n, w0, w1, w2);
+    hipLaunchKernelGGL(dp_init_cells, grid, dim3(256), 0, d->q.st, d->cells[0], d->plane_stride, d->p.nx, n, w0, w1, w2);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(d->st));
+  HIP_TRY(hipStreamSynchronize(d->q.st));
   d->cur = 0;
   d->steps_done = 0;
   d->ring_fill = 0;
@@ -328,8 +278,8 @@ int lbm_dp_upload(lbm_dp *d, const double *cells) {
 
 int lbm_dp_upload_obstacles(lbm_dp *d, const int32_t *obstacles) {
   if (!d || !obstacles) return lbm_fail(LBM_ERR_ARG, "NULL argument");
-  if (int rc = sync_dp(d)) return rc;
-  return copy_mask(d, obstacles);
+  if (int rc = queue_sync(d->q)) return rc;
+  return upload_mask(d->mask, obstacles, (size_t)d->p.nx * d->p.ny);
 }
 
 int lbm_dp_run(lbm_dp *d, int nsteps) {
@@ -344,23 +294,23 @@ int lbm_dp_run_timed(lbm_dp *d, int nsteps, double *ms) {
 
 int lbm_dp_sync(lbm_dp *d) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
-  return sync_dp(d);
+  return queue_sync(d->q);
 }
 
 int lbm_dp_steps_done(const lbm_dp *d) { return d ? d->steps_done : -1; }
 
 int lbm_dp_download(lbm_dp *d, double *cells_out, double *av_vels_out) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
-  if (int rc = sync_dp(d)) return rc;
+  if (int rc = queue_sync(d->q)) return rc;
   const size_t n = (size_t)d->p.nx * d->p.ny;
   if (cells_out) {
     // the grid array that is not current is scratch between runs: repack there, then one contiguous transfer
     double *stage = d->cells[d->cur ^ 1];
-    hipLaunchKernelGGL(dp_pack_planes<false>, dim3((unsigned)std::min(div_up((long)n, 256), 4096L)), dim3(256), 0, d->st,
+    hipLaunchKernelGGL(dp_pack_planes<false>, dim3((unsigned)std::min(div_up((long)n, 256), 4096L)), dim3(256), 0, d->q.st,
                        d->cells[d->cur], d->plane_stride, d->p.nx, n, stage);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(cells_out, stage, 9 * n * sizeof(double), hipMemcpyDeviceToHost, d->st));
-    HIP_TRY(hipStreamSynchronize(d->st));
+    HIP_TRY(hipMemcpyAsync(cells_out, stage, 9 * n * sizeof(double), hipMemcpyDeviceToHost, d->q.st));
+    HIP_TRY(hipStreamSynchronize(d->q.st));
   }
   if (av_vels_out && d->steps_done > 0) {
     std::vector<double> sums(d->steps_done);
@@ -373,7 +323,7 @@ int lbm_dp_download(lbm_dp *d, double *cells_out, double *av_vels_out) {
 
 int lbm_dp_final_state(lbm_dp *d, double *u_x, double *u_y, double *u, double *pressure) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
-  if (int rc = sync_dp(d)) return rc;
+  if (int rc = queue_sync(d->q)) return rc;
   const size_t n = (size_t)d->p.nx * d->p.ny;
   double *outs[4] = {u_x, u_y, u, pressure};
   // the four columns go to the grid array that is not current (4 nx ny of its 9 plane_stride ny doubles)
@@ -382,19 +332,19 @@ int lbm_dp_final_state(lbm_dp *d, double *u_x, double *u_y, double *u, double *p
     if (outs[i]) dst[i] = d->cells[d->cur ^ 1] + (size_t)i * n;
   if (int rc = final_fields_dp(d, dst)) return rc;
   for (int i = 0; i < 4; i++)
-    if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], dst[i], n * sizeof(double), hipMemcpyDeviceToHost, d->st));
-  HIP_TRY(hipStreamSynchronize(d->st));
+    if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], dst[i], n * sizeof(double), hipMemcpyDeviceToHost, d->q.st));
+  HIP_TRY(hipStreamSynchronize(d->q.st));
   return LBM_OK;
 }
 
 int lbm_dp_reynolds(lbm_dp *d, double *reynolds_out) {
   if (!d || !reynolds_out) return lbm_fail(LBM_ERR_ARG, "NULL argument");
-  if (int rc = sync_dp(d)) return rc;
+  if (int rc = queue_sync(d->q)) return rc;
   double *none[4] = {nullptr, nullptr, nullptr, nullptr};
   if (int rc = final_fields_dp(d, none)) return rc;
   std::vector<double> part(d->fin_blocks);
-  HIP_TRY(hipMemcpyAsync(part.data(), d->fin_partials, part.size() * sizeof(double), hipMemcpyDeviceToHost, d->st));
-  HIP_TRY(hipStreamSynchronize(d->st));
+  HIP_TRY(hipMemcpyAsync(part.data(), d->fin_partials, part.size() * sizeof(double), hipMemcpyDeviceToHost, d->q.st));
+  HIP_TRY(hipStreamSynchronize(d->q.st));
   double tot = 0.0;
   for (double v : part) tot += v;
   // av_velocity + calc_reynolds, d2q9-bgk.c:396-442, 747-752, in double
@@ -424,7 +374,7 @@ int lbm_dp_get_option(const lbm_dp *d, const char *key, long *value) {
 
 void lbm_dp_destroy(lbm_dp *d) {
   if (!d) return;
-  (void)hipSetDevice(d->dev);
+  (void)hipSetDevice(d->q.dev);
   free_dp(d);
 }
 

@@ -13,7 +13,7 @@
 // the end of such a run until the next upload the array that holds a member's state is the member's own (`par`).
 #include "../../include/lbm.h"
 #include "steady_kernels.h"
-#include "lbm_error.h"
+#include "host_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -21,23 +21,14 @@
 #include <vector>
 
 using namespace lbm;
+using namespace lbm_host;
 
 namespace {
-
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess)                                                                           \
-      return lbm_fail(LBM_ERR_HIP, "HIP error during '%s' (%s:%d): %s", #expr, __FILE__, __LINE__, \
-                      hipGetErrorString(e_));                                                       \
-  } while (0)
 
 constexpr int kEnsRingMax = 256;           // most steps of per-tile partial sums buffered between reductions
 constexpr long kEnsMaxCells = 300L * 1024; // the library's bound for "launch-bound" (multistep_effective, lbm_hip.cpp)
 constexpr int kEnsMaxMembers = 65535;      // member index = blockIdx.y
 constexpr int kSteadyPollChecks = 4;       // a steady run reads the count of active members back after every so many checks
-
-inline long div_up(long a, long b) { return (a + b - 1) / b; }
 
 }  // namespace
 
@@ -45,10 +36,8 @@ struct lbm_ens {
   int n = 0;
   int nx = 0, ny = 0, max_iters = 0;
   std::vector<lbm_params> p;
-  int dev = 0;
+  Queue q;
   int cus = 256;
-  hipStream_t st = nullptr;
-  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
   size_t plane_stride = 0, member_stride = 0;  // floats
   float *cells[2] = {nullptr, nullptr};
   uint8_t *mask = nullptr;       // [n][ny][nx]
@@ -73,7 +62,7 @@ struct lbm_ens {
 namespace {
 
 void free_ens(lbm_ens *e) {
-  if (e->st) (void)hipStreamSynchronize(e->st);
+  queue_drain(e->q);
   for (float *c : e->cells)
     if (c) (void)hipFree(c);
   if (e->mask) (void)hipFree(e->mask);
@@ -85,19 +74,17 @@ void free_ens(lbm_ens *e) {
   if (e->steady_inv) (void)hipFree(e->steady_inv);
   if (e->steady_count_host) (void)hipHostFree(e->steady_count_host);
   if (e->stage) (void)hipFree(e->stage);
-  if (e->ev_t0) (void)hipEventDestroy(e->ev_t0);
-  if (e->ev_t1) (void)hipEventDestroy(e->ev_t1);
-  if (e->st) (void)hipStreamDestroy(e->st);
+  queue_destroy(e->q);
   delete e;
 }
 
 int build_ens(lbm_ens *e, const int32_t *obstacles) {
   const int n = e->n, nx = e->nx, ny = e->ny;
   const size_t cells_per = (size_t)nx * ny;
-  HIP_TRY(hipGetDevice(&e->dev));
+  HIP_TRY(hipGetDevice(&e->q.dev));
   {
     int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->q.dev));
     if (cus > 0) e->cus = cus;
   }
   // Tile shape.  d2q9_multi's cost model (lbm_hip.cpp, slab_geometry: ceil(tiles / CUs) x cell updates per tile) holds while
@@ -131,9 +118,7 @@ int build_ens(lbm_ens *e, const int32_t *obstacles) {
     return lbm_fail(LBM_ERR_HIP, "an ensemble of %d members of %dx%d with max_iters=%d needs %.1f MiB of device memory, %.1f MiB are free",
                     n, nx, ny, e->max_iters, (double)need / 1048576.0, (double)free_b / 1048576.0);
 
-  HIP_TRY(hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreate(&e->ev_t0));
-  HIP_TRY(hipEventCreate(&e->ev_t1));
+  if (int rc = queue_create(e->q)) return rc;
   for (int i = 0; i < 2; i++) {
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->cells[i]), cells_bytes));
     HIP_TRY(hipMemset(e->cells[i], 0, cells_bytes));
@@ -143,27 +128,11 @@ int build_ens(lbm_ens *e, const int32_t *obstacles) {
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->partials), (size_t)e->ring * per_step * sizeof(float)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->av_sum), (size_t)n * std::max(1, e->max_iters) * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->fin_partials), (size_t)n * e->fin_blocks * sizeof(float)));
-  {
-    // the members' byte masks from the caller's int32[n][ny][nx] (d2q9-bgk.c:205-209: the obstacle transfer)
-    std::vector<uint8_t> m((size_t)n * cells_per);
-    for (size_t i = 0; i < m.size(); i++) m[i] = obstacles[i] != 0;
-    HIP_TRY(hipMemcpy(e->mask, m.data(), m.size(), hipMemcpyHostToDevice));
-  }
-  {
-    std::vector<EnsMember> t(n);
-    for (int i = 0; i < n; i++) {
-      const lbm_params &p = e->p[i];
-      t[i].omega = p.omega;
-      t[i].aw1 = p.density * p.accel / 9.0f;   // kernels.cl:14-15
-      t[i].aw2 = p.density * p.accel / 36.0f;
-      t[i].density = p.density;
-      t[i].w0 = p.density * 4.0f / 9.0f;       // d2q9-bgk.c:529-531
-      t[i].w1 = p.density / 9.0f;
-      t[i].w2 = p.density / 36.0f;
-      t[i].pad = 0.0f;
-    }
-    HIP_TRY(hipMemcpy(e->members, t.data(), t.size() * sizeof(EnsMember), hipMemcpyHostToDevice));
-  }
+  // the members' byte masks from the caller's int32[n][ny][nx]
+  if (int rc = upload_mask(e->mask, obstacles, (size_t)n * cells_per)) return rc;
+  std::vector<EnsMember> t(n);
+  for (int i = 0; i < n; i++) t[i] = member_constants<EnsMember>(e->p[i]);
+  HIP_TRY(hipMemcpy(e->members, t.data(), t.size() * sizeof(EnsMember), hipMemcpyHostToDevice));
   return LBM_OK;
 }
 
@@ -171,11 +140,11 @@ int build_ens(lbm_ens *e, const int32_t *obstacles) {
 void launch_ensemble(const lbm_ens *e, const EnsArgs &a, const int *active) {
   const dim3 grid(e->tiles, e->n), block(kMultiThreads);
   if (!active) {
-    if (e->ty == 16) hipLaunchKernelGGL((d2q9_ensemble<16, 16>), grid, block, 0, e->st, a);
-    else hipLaunchKernelGGL((d2q9_ensemble<16, 8>), grid, block, 0, e->st, a);
+    if (e->ty == 16) hipLaunchKernelGGL((d2q9_ensemble<16, 16>), grid, block, 0, e->q.st, a);
+    else hipLaunchKernelGGL((d2q9_ensemble<16, 8>), grid, block, 0, e->q.st, a);
   } else {
-    if (e->ty == 16) hipLaunchKernelGGL((d2q9_ensemble_gated<16, 16>), grid, block, 0, e->st, a, active);
-    else hipLaunchKernelGGL((d2q9_ensemble_gated<16, 8>), grid, block, 0, e->st, a, active);
+    if (e->ty == 16) hipLaunchKernelGGL((d2q9_ensemble_gated<16, 16>), grid, block, 0, e->q.st, a, active);
+    else hipLaunchKernelGGL((d2q9_ensemble_gated<16, 8>), grid, block, 0, e->q.st, a, active);
   }
 }
 
@@ -184,7 +153,7 @@ void launch_ensemble(const lbm_ens *e, const EnsArgs &a, const int *active) {
 int enqueue_steps(lbm_ens *e, int nsteps, int first, const int *active) {
   // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
   // into the previous launch's write of row ny-2
-  hipLaunchKernelGGL(ens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->st, e->cells[e->cur], e->plane_stride,
+  hipLaunchKernelGGL(ens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
                      e->member_stride, e->mask, e->members, e->nx, e->ny, active);
   HIP_TRY(hipGetLastError());
 
@@ -192,7 +161,7 @@ int enqueue_steps(lbm_ens *e, int nsteps, int first, const int *active) {
   // second reduction stage over the buffered steps (kernels.cl:234-290 counterpart)
   auto flush = [&]() -> int {
     if (e->ring_fill == 0) return LBM_OK;
-    hipLaunchKernelGGL(ens_reduce_partials, dim3(e->n, e->ring_fill), dim3(kBlock), 0, e->st, e->partials, e->tiles, e->av_sum,
+    hipLaunchKernelGGL(ens_reduce_partials, dim3(e->n, e->ring_fill), dim3(kBlock), 0, e->q.st, e->partials, e->tiles, e->av_sum,
                        (unsigned long long)std::max(1, e->max_iters), batch_first, active);
     HIP_TRY(hipGetLastError());
     batch_first += e->ring_fill;
@@ -203,7 +172,7 @@ int enqueue_steps(lbm_ens *e, int nsteps, int first, const int *active) {
   while (i < nsteps) {
     // the remaining steps in as few launches as possible, of equal depth (20 steps = 7 + 7 + 6)
     const int rem = nsteps - i;
-    const int adv = (int)div_up(rem, div_up(rem, kMultiMaxT));
+    const int adv = equal_depth(rem, kMultiMaxT);
     if (e->ring_fill + adv > e->ring)
       if (int rc = flush()) return rc;
     EnsArgs a{};
@@ -234,44 +203,23 @@ int refuse_ragged(const lbm_ens *e) {
 }
 
 int run_ens_impl(lbm_ens *e, int nsteps, bool timed, double *ms, bool *launched) {
-  if (nsteps < 0) return lbm_fail(LBM_ERR_ARG, "nsteps must be >= 0");
-  if (e->failed) return lbm_fail(LBM_ERR_STATE, "an earlier run failed after its launches had begun; destroy the ensemble");
+  if (int rc = check_runnable(nsteps, e->failed, "ensemble")) return rc;
   if (e->ragged) return refuse_ragged(e);
-  if (e->steps_done + nsteps > e->max_iters)
-    return lbm_fail(LBM_ERR_STATE, "av_vels record holds max_iters=%d steps; %d done, %d more requested", e->max_iters,
-                    e->steps_done, nsteps);
+  if (int rc = check_record(e->max_iters, e->steps_done, nsteps, "")) return rc;
   if (timed && ms) *ms = 0.0;
   if (nsteps == 0) return LBM_OK;
-  HIP_TRY(hipSetDevice(e->dev));
+  HIP_TRY(hipSetDevice(e->q.dev));
   *launched = true;
-  if (timed) HIP_TRY(hipEventRecord(e->ev_t0, e->st));
+  if (int rc = timed_begin(e->q, timed)) return rc;
   if (int rc = enqueue_steps(e, nsteps, e->steps_done, nullptr)) return rc;
   e->steps_done += nsteps;
-  if (timed) {
-    HIP_TRY(hipEventRecord(e->ev_t1, e->st));
-    HIP_TRY(hipEventSynchronize(e->ev_t1));
-    float t = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&t, e->ev_t0, e->ev_t1));
-    if (ms) *ms = t;
-  }
-  return LBM_OK;
-}
-
-// A failure after launches have begun: let what was enqueued finish and refuse further work (as run_steps, lbm_hip.cpp)
-int after_launches(lbm_ens *e, int rc, bool launched) {
-  if (rc != LBM_OK && launched) {
-    const std::string keep = lbm_last_error();
-    (void)hipStreamSynchronize(e->st);
-    (void)hipGetLastError();
-    e->failed = true;
-    lbm_fail(rc, "%s", keep.c_str());
-  }
-  return rc;
+  return timed_end(e->q, timed, ms);
 }
 
 int run_ens(lbm_ens *e, int nsteps, bool timed, double *ms) {
   bool launched = false;
-  return after_launches(e, run_ens_impl(e, nsteps, timed, ms, &launched), launched);
+  const int rc = run_ens_impl(e, nsteps, timed, ms, &launched);
+  return latch_failure(rc, launched, e->q.st, &e->failed);
 }
 
 SteadyWords steady_words(const lbm_ens *e) {
@@ -298,19 +246,17 @@ int steady_alloc(lbm_ens *e) {
 }
 
 int steady_impl(lbm_ens *e, int max_steps, int window, double rel_tol, bool *launched) {
-  if (e->failed) return lbm_fail(LBM_ERR_STATE, "an earlier run failed after its launches had begun; destroy the ensemble");
+  if (int rc = check_runnable(max_steps, e->failed, "ensemble")) return rc;  // max_steps >= 0 here (lbm_steady_run)
   if (e->ragged) return refuse_ragged(e);
-  if (e->steps_done + max_steps > e->max_iters)
-    return lbm_fail(LBM_ERR_STATE, "av_vels record holds max_iters=%d steps; %d done, up to %d more requested", e->max_iters,
-                    e->steps_done, max_steps);
+  if (int rc = check_record(e->max_iters, e->steps_done, max_steps, "up to ")) return rc;
   if (max_steps == 0) return LBM_OK;
-  HIP_TRY(hipSetDevice(e->dev));
+  HIP_TRY(hipSetDevice(e->q.dev));
   if (int rc = steady_alloc(e)) return rc;
   const int n = e->n, s0 = e->steps_done;
   const SteadyWords w = steady_words(e);
   const dim3 mgrid((unsigned)div_up(n, 256)), mblock(256);
   *launched = true;
-  hipLaunchKernelGGL(ens_steady_begin, mgrid, mblock, 0, e->st, w, n, e->cur, s0);
+  hipLaunchKernelGGL(ens_steady_begin, mgrid, mblock, 0, e->q.st, w, n, e->cur, s0);
   HIP_TRY(hipGetLastError());
   int done = 0, checks = 0;
   while (done < max_steps) {
@@ -320,21 +266,21 @@ int steady_impl(lbm_ens *e, int max_steps, int window, double rel_tol, bool *lau
     const int s = s0 + done;
     // a check point: a whole leg, with a record entry one window back (step counts start at 1)
     const int check = (leg == window && s - window >= 1) ? 1 : 0;
-    hipLaunchKernelGGL(ens_steady_check, mgrid, mblock, 0, e->st, w, n, e->av_sum, (unsigned long long)std::max(1, e->max_iters),
+    hipLaunchKernelGGL(ens_steady_check, mgrid, mblock, 0, e->q.st, w, n, e->av_sum, (unsigned long long)std::max(1, e->max_iters),
                        e->steady_inv, s, window, rel_tol, check, e->cur);
     HIP_TRY(hipGetLastError());
     // Every few checks: is anyone left?  Only how much is enqueued depends on the answer; what a member computes does not,
     // the workgroups of a stopped member return at once.
     if (check && ++checks % kSteadyPollChecks == 0 && done < max_steps) {
-      HIP_TRY(hipMemcpyAsync(e->steady_count_host, w.count, sizeof(int), hipMemcpyDeviceToHost, e->st));
-      HIP_TRY(hipStreamSynchronize(e->st));
+      HIP_TRY(hipMemcpyAsync(e->steady_count_host, w.count, sizeof(int), hipMemcpyDeviceToHost, e->q.st));
+      HIP_TRY(hipStreamSynchronize(e->q.st));
       if (*e->steady_count_host == 0) break;
     }
   }
   // the members' words: on which parity each one is, at which count, and whether it met the criterion
   std::vector<int> words(3 * (size_t)n);
-  HIP_TRY(hipMemcpyAsync(words.data(), w.par, words.size() * sizeof(int), hipMemcpyDeviceToHost, e->st));
-  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(hipMemcpyAsync(words.data(), w.par, words.size() * sizeof(int), hipMemcpyDeviceToHost, e->q.st));
+  HIP_TRY(hipStreamSynchronize(e->q.st));
   e->m_steps.assign(words.begin() + n, words.begin() + 2 * (size_t)n);
   e->m_conv.assign(words.begin() + 2 * (size_t)n, words.end());
   e->steps_done = *std::max_element(e->m_steps.begin(), e->m_steps.end());
@@ -348,12 +294,6 @@ int steady_impl(lbm_ens *e, int max_steps, int window, double rel_tol, bool *lau
 int stage_alloc(lbm_ens *e) {
   if (e->stage) return LBM_OK;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->stage), (size_t)e->n * 9 * e->nx * e->ny * sizeof(float)));
-  return LBM_OK;
-}
-
-int sync_ens(lbm_ens *e) {
-  HIP_TRY(hipSetDevice(e->dev));
-  HIP_TRY(hipStreamSynchronize(e->st));
   return LBM_OK;
 }
 
@@ -372,10 +312,7 @@ int lbm_ens_create(lbm_ens **out, const lbm_params *params, const int32_t *obsta
   const lbm_params &p0 = params[0];
   if (p0.nx < 3 || p0.ny < 3) return lbm_fail(LBM_ERR_ARG, "grid must be at least 3x3 (got %dx%d)", p0.nx, p0.ny);
   if (p0.max_iters < 0) return lbm_fail(LBM_ERR_ARG, "max_iters must be >= 0");
-  for (int i = 1; i < n; i++)
-    if (params[i].nx != p0.nx || params[i].ny != p0.ny || params[i].max_iters != p0.max_iters)
-      return lbm_fail(LBM_ERR_ARG, "member %d is %dx%d with max_iters=%d, member 0 %dx%d with max_iters=%d: the members of an ensemble "
-                      "share nx, ny and max_iters", i, params[i].nx, params[i].ny, params[i].max_iters, p0.nx, p0.ny, p0.max_iters);
+  if (int rc = check_members_alike(params, n)) return rc;
   if ((long)p0.nx * p0.ny > kEnsMaxCells)
     return lbm_fail(LBM_ERR_ARG, "a member of %dx%d cells is not launch-bound (the ensemble path takes members of at most %ld cells): "
                     "use ordinary contexts (lbm_create)", p0.nx, p0.ny, kEnsMaxCells);
@@ -392,8 +329,7 @@ int lbm_ens_create(lbm_ens **out, const lbm_params *params, const int32_t *obsta
   if (int rc = build_ens(e, obstacles)) {
     const std::string keep = lbm_last_error();
     free_ens(e);
-    (void)hipGetLastError();
-    return lbm_fail(rc, "%s", keep.c_str());
+    return fail_again(rc, keep);
   }
   *out = e;
   return LBM_OK;
@@ -401,21 +337,21 @@ int lbm_ens_create(lbm_ens **out, const lbm_params *params, const int32_t *obsta
 
 int lbm_ens_upload(lbm_ens *e, const float *cells) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  if (int rc = sync_ens(e)) return rc;
+  if (int rc = queue_sync(e->q)) return rc;
   const size_t per = (size_t)e->nx * e->ny;
   const dim3 grid((unsigned)std::min(div_up((long)per, 256), 1024L), e->n);
   if (cells) {
     // one transfer of the caller's float[n][9][ny][nx] into the second grid array (9 nx ny <= member_stride), then one
     // launch that scatters every member's planes into the first (d2q9-bgk.c:200-203 for all members)
-    HIP_TRY(hipMemcpyAsync(e->cells[1], cells, (size_t)e->n * 9 * per * sizeof(float), hipMemcpyHostToDevice, e->st));
-    hipLaunchKernelGGL(ens_pack_planes<true>, grid, dim3(256), 0, e->st, e->cells[0], (float *)nullptr, (const int *)nullptr,
+    HIP_TRY(hipMemcpyAsync(e->cells[1], cells, (size_t)e->n * 9 * per * sizeof(float), hipMemcpyHostToDevice, e->q.st));
+    hipLaunchKernelGGL(ens_pack_planes<true>, grid, dim3(256), 0, e->q.st, e->cells[0], (float *)nullptr, (const int *)nullptr,
                        e->plane_stride, e->member_stride, e->nx, per, e->cells[1]);
   } else {
-    hipLaunchKernelGGL(ens_init_cells, grid, dim3(256), 0, e->st, e->cells[0], e->plane_stride, e->member_stride, e->members, e->nx,
+    hipLaunchKernelGGL(ens_init_cells, grid, dim3(256), 0, e->q.st, e->cells[0], e->plane_stride, e->member_stride, e->members, e->nx,
                        per);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(hipStreamSynchronize(e->q.st));
   e->cur = 0;
   e->steps_done = 0;
   e->ring_fill = 0;
@@ -437,7 +373,7 @@ int lbm_ens_run_timed(lbm_ens *e, int nsteps, double *ms) {
 
 int lbm_ens_sync(lbm_ens *e) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  return sync_ens(e);
+  return queue_sync(e->q);
 }
 
 int lbm_ens_steps_done(const lbm_ens *e) { return e ? e->steps_done : -1; }
@@ -445,7 +381,7 @@ int lbm_ens_members(const lbm_ens *e) { return e ? e->n : -1; }
 
 int lbm_ens_download(lbm_ens *e, float *cells_out, float *av_vels_out) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  if (int rc = sync_ens(e)) return rc;
+  if (int rc = queue_sync(e->q)) return rc;
   const size_t per = (size_t)e->nx * e->ny;
   if (cells_out) {
     // the grid array that is not current is scratch between runs: repack every member into the caller's layout there,
@@ -456,12 +392,12 @@ int lbm_ens_download(lbm_ens *e, float *cells_out, float *av_vels_out) {
       if (int rc = stage_alloc(e)) return rc;
       stage = e->stage;
     }
-    hipLaunchKernelGGL(ens_pack_planes<false>, dim3((unsigned)std::min(div_up((long)per, 256), 1024L), e->n), dim3(256), 0, e->st,
+    hipLaunchKernelGGL(ens_pack_planes<false>, dim3((unsigned)std::min(div_up((long)per, 256), 1024L), e->n), dim3(256), 0, e->q.st,
                        e->cells[e->ragged ? 0 : e->cur], e->cells[1], member_parity(e), e->plane_stride, e->member_stride, e->nx,
                        per, stage);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(cells_out, stage, (size_t)e->n * 9 * per * sizeof(float), hipMemcpyDeviceToHost, e->st));
-    HIP_TRY(hipStreamSynchronize(e->st));
+    HIP_TRY(hipMemcpyAsync(cells_out, stage, (size_t)e->n * 9 * per * sizeof(float), hipMemcpyDeviceToHost, e->q.st));
+    HIP_TRY(hipStreamSynchronize(e->q.st));
   }
   if (av_vels_out && e->steps_done > 0) {
     const int T = e->steps_done;
@@ -482,7 +418,7 @@ int lbm_ens_download(lbm_ens *e, float *cells_out, float *av_vels_out) {
 
 int lbm_ens_final_state(lbm_ens *e, float *u_x, float *u_y, float *u, float *pressure) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  if (int rc = sync_ens(e)) return rc;
+  if (int rc = queue_sync(e->q)) return rc;
   const size_t per = (size_t)e->nx * e->ny, all = per * e->n;
   float *outs[4] = {u_x, u_y, u, pressure};
   // the four columns of all members go to the grid array that is not current (4 n nx ny floats of its 9 n nx ny)
@@ -495,27 +431,27 @@ int lbm_ens_final_state(lbm_ens *e, float *u_x, float *u_y, float *u, float *pre
   }
   for (int i = 0; i < 4; i++)
     if (outs[i]) d[i] = stage + (size_t)i * all;
-  hipLaunchKernelGGL(ens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->st, e->cells[e->ragged ? 0 : e->cur],
+  hipLaunchKernelGGL(ens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->q.st, e->cells[e->ragged ? 0 : e->cur],
                      e->cells[1], member_parity(e), e->plane_stride, e->member_stride, e->nx, e->mask, per, e->members, d[0], d[1],
                      d[2], d[3], e->fin_partials);
   HIP_TRY(hipGetLastError());
   for (int i = 0; i < 4; i++)
-    if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], d[i], all * sizeof(float), hipMemcpyDeviceToHost, e->st));
-  HIP_TRY(hipStreamSynchronize(e->st));
+    if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], d[i], all * sizeof(float), hipMemcpyDeviceToHost, e->q.st));
+  HIP_TRY(hipStreamSynchronize(e->q.st));
   return LBM_OK;
 }
 
 int lbm_ens_reynolds(lbm_ens *e, float *reynolds_out) {
   if (!e || !reynolds_out) return lbm_fail(LBM_ERR_ARG, "NULL argument");
-  if (int rc = sync_ens(e)) return rc;
+  if (int rc = queue_sync(e->q)) return rc;
   const size_t per = (size_t)e->nx * e->ny;
-  hipLaunchKernelGGL(ens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->st, e->cells[e->ragged ? 0 : e->cur],
+  hipLaunchKernelGGL(ens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->q.st, e->cells[e->ragged ? 0 : e->cur],
                      e->cells[1], member_parity(e), e->plane_stride, e->member_stride, e->nx, e->mask, per, e->members,
                      (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr, e->fin_partials);
   HIP_TRY(hipGetLastError());
   std::vector<float> part((size_t)e->n * e->fin_blocks);
-  HIP_TRY(hipMemcpyAsync(part.data(), e->fin_partials, part.size() * sizeof(float), hipMemcpyDeviceToHost, e->st));
-  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(hipMemcpyAsync(part.data(), e->fin_partials, part.size() * sizeof(float), hipMemcpyDeviceToHost, e->q.st));
+  HIP_TRY(hipStreamSynchronize(e->q.st));
   for (int m = 0; m < e->n; m++) {
     double tot = 0.0;
     for (int b = 0; b < e->fin_blocks; b++) tot += part[(size_t)m * e->fin_blocks + b];
@@ -535,7 +471,8 @@ int lbm_steady_run(lbm_ens *e, int max_steps, int window, double rel_tol) {
   if (window < 1) return lbm_fail(LBM_ERR_ARG, "window must be >= 1 (got %d)", window);
   if (!std::isfinite(rel_tol) || rel_tol < 0.0) return lbm_fail(LBM_ERR_ARG, "rel_tol must be finite and >= 0 (got %g)", rel_tol);
   bool launched = false;
-  return after_launches(e, steady_impl(e, max_steps, window, rel_tol, &launched), launched);
+  const int rc = steady_impl(e, max_steps, window, rel_tol, &launched);
+  return latch_failure(rc, launched, e->q.st, &e->failed);
 }
 
 int lbm_steady_steps(lbm_ens *e, int *steps_out, int *converged_out) {
@@ -550,7 +487,7 @@ int lbm_steady_steps(lbm_ens *e, int *steps_out, int *converged_out) {
 
 void lbm_ens_destroy(lbm_ens *e) {
   if (!e) return;
-  (void)hipSetDevice(e->dev);
+  (void)hipSetDevice(e->q.dev);
   free_ens(e);
 }
 

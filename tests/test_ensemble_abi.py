@@ -112,6 +112,25 @@ def test_sweep_params_and_binding_checks(lbm):
         lbm.Ensemble([], np.zeros((16, 16), dtype=np.int32))
 
 
+@pytest.mark.parametrize("sweep, make, ptype", [("sweep_params", "make_params", "Params"),
+                                                ("sweep_dparams", "make_dparams", "DParams")])
+def test_sweep_members_equal_members_built_field_by_field(lbm, sweep, make, ptype):
+    """a swept member holds, byte for byte, what assigning its fields one by one to a fresh structure gives"""
+    ob = np.zeros((16, 24), dtype=np.int32)
+    ob[3, 5:9] = 1
+    base = getattr(lbm, make)(24, 16, 7, reynolds_dim=3, density=0.11, accel=0.0051, omega=1.85, obstacles=ob)
+    omega, accel = [1.0, 1.7, 0.1 + 0.2, 1.99], [0.002, 1e-3 / 3, 0.01, 0.0051]
+    got = getattr(lbm, sweep)(base, omega=omega, accel=accel)
+    assert len(got) == 4
+    for i, g in enumerate(got):
+        p = getattr(lbm, ptype)()
+        p.nx, p.ny, p.max_iters, p.reynolds_dim = 24, 16, 7, 3
+        p.density, p.free_cells_inv = base.density, base.free_cells_inv
+        p.accel = accel[i]
+        p.omega = omega[i]
+        assert isinstance(g, getattr(lbm, ptype)) and bytes(g) == bytes(p), i
+
+
 def test_ensemble_has_no_cpu_fallback(lbm):
     """without a GPU a valid ensemble must fail loudly, never compute on the host"""
     n = ctypes.c_int()
