@@ -246,6 +246,8 @@ int lbm_reynolds(lbm_ctx *ctx, float *reynolds_out);
  *                  whatever else fills the device meanwhile (another process, a long kernel of the caller's) delays it.
  *   "chunk_rows"   most rows swept by one wave of the two-step kernel (0 = auto)
  *   "chunk_min"    fewest rows per wave at the tapered end of the schedule (0 = auto)
+ *   "pair_taper"   taper of a chunk-pair schedule of several rounds, in 1/32 (csrc/chunk_schedule.h): -1 = auto, 0 = size the
+ *                  chunks one by one as an unpaired schedule does
  *   "grid_blocks"  cap on workgroups per launch (0 = auto)
  *   "nt_stores"    1 = non-temporal stores for the destination grid, 0 = plain, -1 = auto
  *   "nt_loads"     source loads of the two-step kernel: 0 = plain, 1 = non-temporal, 2 = non-temporal except for the rows shared
@@ -278,7 +280,7 @@ int lbm_reynolds(lbm_ctx *ctx, float *reynolds_out);
  *                  edge wave is up (hipStreamWaitValue32: "staged" launch sets);
  *                  0 = edge launch / interior launch / push kernel (or RCCL exchange) on two streams
  * Read-only through lbm_get_option: "nslabs", "fuse_units", "halo_depth", "launch_steps" (most timesteps one launch of
- * the context's main kernel advances).
+ * the context's main kernel advances), "cus" (compute units of the first slab's device, which its schedules plan for).
  */
 int lbm_set_option(lbm_ctx *ctx, const char *key, long value);
 int lbm_get_option(const lbm_ctx *ctx, const char *key, long *value);

@@ -19,6 +19,7 @@
 #include "../../include/lbm.h"
 #include "d2q9_kernels.h"
 #include "deep_instances.h"
+#include "chunk_schedule.h"
 #include "halo_exchange.h"
 #include "lbm_error.h"
 
@@ -318,6 +319,7 @@ struct lbm_ctx {
   int resident = -1;        // d2q9_resident (all steps of a launch with the grid in registers): -1 auto, 0 off, 1 on where the grid allows
   int chunk_rows = 0;       // longest chunk (rows per work unit) of d2q9_step2 (0 = auto)
   int chunk_min = 0;        // shortest chunk at the tapered end of a band (0 = auto)
+  int pair_taper = -1;      // taper of a multi-round pair schedule in 1/32 (-1 = kPairTaper32, 0 = chunk by chunk; csrc/chunk_schedule.h)
   bool vec4 = true;
   double *av_host = nullptr;  // staging for downloads
 };
@@ -351,12 +353,6 @@ int step_blocks(const lbm_ctx *c, int work_rows) {
   return std::max(1, nb);
 }
 
-void split_rows(int ny, int P, int idx, int *y0, int *rows) {
-  const int base = ny / P, rem = ny % P;
-  *y0 = idx * base + std::min(idx, rem);
-  *rows = base + (idx < rem ? 1 : 0);
-}
-
 // two-steps-per-launch kernel: float4 rows of at least one wave, a few rows per slab
 bool windows_in_lds(const lbm_ctx *c) { return c->windows < 0 ? kStep3LdsDefault : c->windows != 0; }
 int step3_load_bufs(const lbm_ctx *c) { return c->load_bufs > 0 ? c->load_bufs : (windows_in_lds(c) ? 1 : 2); }
@@ -373,6 +369,8 @@ int step3_sched_waves(const lbm_ctx *c) {
   return (long)c->p.nx * c->rows_min <= 800L * 1024 ? 1 : 2;
 }
 int step4_sched_waves(const lbm_ctx *c) { return c->sched_waves > 0 ? c->sched_waves : 2; }
+
+int pair_taper(const lbm_ctx *c) { return c->pair_taper >= 0 ? c->pair_taper : kPairTaper32; }
 
 bool fuse_possible(const lbm_ctx *c) {
   if (!c->vec4 || c->p.nx < 256) return false;
@@ -571,83 +569,20 @@ bool compact_sets(const lbm_ctx *c) {
   return (lvl == 3 || lvl == 4) && windows_in_lds(c) && step3_load_bufs(c) == 1;
 }
 
-// Work decomposition of d2q9_step2 over stored rows [r0, r1): strips x chunks.  A unit's cost is
-// proportional to its rows + 2 and all units of a launch finish at about the same time, so equal chunks
-// leave the chip partly idle during the last round of units (17 % of the launch with 32-row chunks on
-// 8192x8192).  The schedule therefore tapers: every band (the share of one XCD) starts with chunks of
-// `cmax` rows and ends with ever shorter ones (guided self-scheduling), down to `cmin`.  (R full rounds of equal
-// chunks instead of the taper: within +-2 % on 8192x1024 ... 8192x8192, no consistent sign — not adopted.)
+// Work decomposition of d2q9_step2 over stored rows [r0, r1): strips x chunks.  The table is planned by plan_chunks
+// (csrc/chunk_schedule.h, which says why it tapers); this uploads it.
 int fuse_schedule(const Slab &s, int r0, int r1, int cmax, int cmin, bool allow_bands, FuseGeom &g, int waves_per_simd = 2,
-                  int reserve = 0, bool pairs = false, int strips_of_kernel = 0, int cmax_one = 0) {
-  if (cmax_one < cmax) cmax_one = cmax;  // longest chunk of a ONE-round schedule (d2q9_deep: longer than the tapered schedules' first chunks)
-  const int rows = r1 - r0;
+                  int reserve = 0, bool pairs = false, int strips_of_kernel = 0, int cmax_one = 0, int pair_taper32 = kPairTaper32) {
   const int strips = strips_of_kernel > 0 ? strips_of_kernel : s.strips;
-  g.nbands = (allow_bands && rows >= 8 * 4 * cmin) ? 8 : 1;
   // CUs x SIMDs x waves per SIMD the kernel's registers / LDS allow, minus the wave slots a concurrent launch needs
   // (slab mode: the edge launch, which must find its slots at once — see slab_geometry)
   const int waves_resident = std::max(s.cus, s.cus * 4 * waves_per_simd - reserve);
-  // The chunk-pair kernels (d2q9_step3p / d2q9_step4p) hold the LDS of BOTH chunks of a pair until the longer one is
-  // done, so a one-round schedule needs an EVEN number of chunks per band that still fits the wave slots: 7.3 slots
-  // per band means 6 chunks with 8 bands (82 % of the slots) but 14 with 4 bands (96 %) — take the band count that
-  // keeps most waves busy, preferring more bands (neighbouring strips then share an XCD's L2).
-  g.single_round = false;
-  // (the same choice for d2q9_deep, unpaired: 4096x4096 has 6.9 slots per band and strip with 8 bands — 6 chunks, 87 % of
-  // the slots, 85 rows + 14 start-up iterations each — but 55 per strip with one band: 75 rows + 14)
-  const bool flex_bands = strips_of_kernel > 0;
-  if ((pairs || flex_bands) && g.nbands == 8) {
-    int best_nb = 8;
-    double best = -1.0;
-    for (int nb = 8; nb >= 1; nb /= 2) {
-      const int fl = pairs ? std::max(2, (int)std::floor((double)waves_resident / nb / strips) & ~1)
-                           : std::max(1, (int)std::floor((double)waves_resident / nb / strips));
-      const int nrows = div_up(rows, nb);
-      if ((int)std::ceil((double)nrows / fl) > cmax_one) continue;  // not a one-round schedule with this band count
-      const double busy = (double)std::min(fl, nrows) * nb * (1.0 + 0.01 * nb);
-      if (busy > best) { best = busy; best_nb = nb; }
-    }
-    g.nbands = best_nb;
-  }
-  double slots = std::max(1.0, (double)waves_resident / g.nbands / strips);  // concurrent chunks per band
-  if (pairs) slots = std::max(2.0, (double)((int)std::floor(slots) & ~1));
-  std::vector<int> starts;
-  int chunks_per_band = 0;
-  for (int b = 0; b < g.nbands; b++) {
-    int y0, n;
-    split_rows(rows, g.nbands, b, &y0, &n);
-    std::vector<int> sizes;
-    int rem = n;
-    // a grid small enough to be done in ONE round of units (all of them resident at once) gets equal chunks
-    // that just fill the wave slots: every extra unit costs two redundant rows, and a second, partly filled
-    // round costs more than it balances (1024x1024: 3-row chunks = 1720 units: 10.2 us/step; 2-row chunks =
-    // 2560 units: 12.1; 4-row chunks = 1280 units: 11.6 — tools/ab.py)
-    const int one_round = (int)std::ceil(n / std::max(1.0, std::floor(slots)));
-    // (one round only if the units really are resident at once: a pair schedule needs two slots per band and strip —
-    // with fewer, "one round" of 64-row chunks was 2192 units on 1500 free slots and the last workgroups started when the
-    // first had finished: compact 8192x1024 slab 212 instead of 220 GLUPS)
-    const bool fits = (double)waves_resident / g.nbands / strips >= (pairs ? 2.0 : 1.0);
-    const bool single_round = one_round <= cmax_one && fits;
-    if (b == 0) g.single_round = single_round;
-    while (rem > 0) {
-      int sz = single_round ? std::max(2, one_round) : (int)std::ceil(rem / (2.0 * slots));
-      if (!single_round) sz = std::max(cmin, std::min(cmax, sz));
-      sz = std::min(sz, rem);
-      sizes.push_back(sz);
-      rem -= sz;
-    }
-    // all bands need the same number of chunks (unit arithmetic in the kernel): band 0 is never
-    // shorter than the others (split_rows); pad with empty chunks / merge surplus into the last one
-    // (an even count for the chunk-pair kernels, which pair chunks 2p and 2p+1)
-    if (b == 0) chunks_per_band = pairs ? ((int)sizes.size() + 1) / 2 * 2 : (int)sizes.size();
-    while ((int)sizes.size() < chunks_per_band) sizes.push_back(0);
-    int extra = 0;
-    while ((int)sizes.size() > chunks_per_band) { extra += sizes.back(); sizes.pop_back(); }
-    if (extra) sizes.back() += extra;
-    int y = r0 + y0;
-    for (int sz : sizes) { starts.push_back(y); y += sz; }
-  }
-  starts.push_back(r1);
-  g.nchunks = chunks_per_band * g.nbands;
-  g.units_per_band = chunks_per_band * strips;
+  const ChunkPlan plan = plan_chunks(r1 - r0, allow_bands, strips, waves_resident, cmax, cmin, cmax_one, pairs, strips_of_kernel > 0, r0, pair_taper32);
+  const std::vector<int> &starts = plan.starts;
+  g.nbands = plan.nbands;
+  g.single_round = plan.single_round;
+  g.nchunks = plan.chunks_per_band * g.nbands;
+  g.units_per_band = plan.chunks_per_band * strips;
   g.units = g.units_per_band * g.nbands;
   g.starts = starts;
   if (set_dev(s)) return LBM_ERR_HIP;
@@ -668,7 +603,7 @@ int fuse_schedule_pairs(const lbm_ctx *c, const Slab &s, int r0, int r1, int cma
   // (not with row slabs: next to the edge launch's 20-KB workgroups and the RCCL kernel the 40-KB pairs of the interior
   // launch no longer all fit at once — 8192x1024 ring of one: 168 GLUPS paired, 232 unpaired, tools/ab.py)
   if (kernel_can_pair && c->pair != 0 && !(c->halo_mode && c->pair < 0 && !compact_sets(c))) {
-    if (int rc = fuse_schedule(s, r0, r1, cmax, cmin, true, g, waves_per_simd, 2 * reserve, true)) return rc;
+    if (int rc = fuse_schedule(s, r0, r1, cmax, cmin, true, g, waves_per_simd, 2 * reserve, true, 0, 0, pair_taper(c))) return rc;
     if (g.single_round || c->pair > 0) {
       g.paired = true;
       return LBM_OK;
@@ -796,11 +731,11 @@ int deep_geometry(const lbm_ctx *c, Slab &s) {
   const int nh = c->balance != 0 ? (int)s.heavy.size() : 0;  // strips that get a second (virtual) strip in one-round schedules
   // a one-round schedule planned for strips2 + nh strips, balanced; any other schedule as it is
   auto one_slab_schedule = [&](FuseGeom &g, bool pairs) -> int {
-    if (int rc = fuse_schedule(s, 0, s.rows, c6max, c6min, true, g, 2, 0, pairs, s.strips2, c6one)) return rc;
+    if (int rc = fuse_schedule(s, 0, s.rows, c6max, c6min, true, g, 2, 0, pairs, s.strips2, c6one, pair_taper(c))) return rc;
     if (nh == 0 || !g.single_round) return LBM_OK;
-    if (int rc = fuse_schedule(s, 0, s.rows, c6max, c6min, true, g, 2, 0, pairs, s.strips2 + nh, c6one)) return rc;
+    if (int rc = fuse_schedule(s, 0, s.rows, c6max, c6min, true, g, 2, 0, pairs, s.strips2 + nh, c6one, pair_taper(c))) return rc;
     if (g.single_round) return balance_heavy_strips(s, g, pairs, s.strips2, nh);
-    return fuse_schedule(s, 0, s.rows, c6max, c6min, true, g, 2, 0, pairs, s.strips2, c6one);
+    return fuse_schedule(s, 0, s.rows, c6max, c6min, true, g, 2, 0, pairs, s.strips2, c6one, pair_taper(c));
   };
   if (!c->halo_mode) {
     if (int rc = one_slab_schedule(s.f6_main, false)) return rc;
@@ -822,7 +757,7 @@ int deep_geometry(const lbm_ctx *c, Slab &s) {
         s.lanes_tw = s.lanes2;
       }
       if (tw_cap <= kDeepTwinDefault) {
-        if (int rc = fuse_schedule(s, 0, s.rows, c6max, c6min, true, s.f6_twin, 2, 0, true, s.strips_tw)) return rc;
+        if (int rc = fuse_schedule(s, 0, s.rows, c6max, c6min, true, s.f6_twin, 2, 0, true, s.strips_tw, 0, pair_taper(c))) return rc;
       } else if (int rc = one_slab_schedule(s.f6_twin, true)) {  // (the eight-step twins run d2q9_deep's strips)
         return rc;
       }
@@ -936,7 +871,7 @@ int deep_geometry(const lbm_ctx *c, Slab &s) {
       // more rows than one round of units takes (the slabs of a 2-GPU run, of the weak-scaling leg): the tapered multi-round
       // schedule, as chunk pairs where the launch set is compact (measured on one slab without halo rows: 8192x4096 383 -> 405)
       const bool pairs = c->pair != 0 && compact_sets(c) && rows > (long)c6max * n_full;
-      if (int rc = fuse_schedule(s, i0, i1, c6max, c6min, true, s.f6_main, 2, 2 * edge_work, pairs, s.strips2)) return rc;
+      if (int rc = fuse_schedule(s, i0, i1, c6max, c6min, true, s.f6_main, 2, 2 * edge_work, pairs, s.strips2, 0, pair_taper(c))) return rc;
       s.f6_main.paired = pairs;
     }
   }
@@ -971,7 +906,7 @@ int twin5_slab_geometry(const lbm_ctx *c, Slab &s) {
   if (tab[3] > tab[2]) {
     const int c6max = std::max(8, std::min(c->chunk_rows > 0 ? c->chunk_rows : 96, s.rows));
     const int c6min = std::max(4, std::min(c->chunk_min > 0 ? c->chunk_min : 24, c6max));
-    if (int rc = fuse_schedule(s, tab[2], tab[3], c6max, c6min, true, g, 2, e.units, true, s.strips_tw)) return rc;
+    if (int rc = fuse_schedule(s, tab[2], tab[3], c6max, c6min, true, g, 2, e.units, true, s.strips_tw, 0, pair_taper(c))) return rc;
   }
   s.nb_total = std::max(s.nb_total, g.units + e.units);
   return LBM_OK;
@@ -3047,6 +2982,12 @@ int lbm_set_option(lbm_ctx *c, const char *key, long value) {
     (key[6] == 'r' ? c->chunk_rows : c->chunk_min) = (int)value;
     return rebuild_geometry(c);
   }
+  if (!strcmp(key, "pair_taper")) {
+    if (value < -1 || value > 1024) return fail(LBM_ERR_ARG, "pair_taper must be -1 (auto), 0 (chunk by chunk) or 1..1024 (in 1/32)");
+    if (int rc = sync_all(c)) return rc;
+    c->pair_taper = (int)value;
+    return rebuild_geometry(c);
+  }
   return fail(LBM_ERR_ARG, "unknown option '%s'", key);
 }
 
@@ -3062,6 +3003,7 @@ int lbm_get_option(const lbm_ctx *c, const char *key, long *value) {
   else if (!strcmp(key, "multistep")) *value = p.kind == KIND_MULTI ? p.cap : 0;
   else if (!strcmp(key, "resident")) *value = p.kind == KIND_RESIDENT ? s0->res_bh : 0;  // rows per band, 0 = not in use
   else if (!strcmp(key, "chunk_rows")) *value = c->chunk_rows;
+  else if (!strcmp(key, "pair_taper")) *value = pair_taper(c);
   else if (!strcmp(key, "windows")) *value = windows_in_lds(c);
   else if (!strcmp(key, "pair")) *value = p.pairs;
   else if (!strcmp(key, "load_bufs")) *value = step3_load_bufs(c);
@@ -3084,6 +3026,7 @@ int lbm_get_option(const lbm_ctx *c, const char *key, long *value) {
   else if (!strcmp(key, "compact")) *value = p.compact();
   else if (!strcmp(key, "halo_depth")) *value = c->halo_mode ? c->halo_depth : 0;
   else if (!strcmp(key, "nslabs")) *value = c->nslabs_global;
+  else if (!strcmp(key, "cus")) *value = s0 ? s0->cus : 0;  // compute units the schedules of the first slab plan for
   else return fail(LBM_ERR_ARG, "unknown option '%s'", key);
   return LBM_OK;
 }
