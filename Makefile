@@ -19,7 +19,7 @@ all: $(LIB) $(EXE) $(EXE).exe oracle
 # lbm_version() carries a digest of the device + host sources the library was built from: a committed profile
 # (profiles/traffic.json) names the build it measured, and bench.py refuses its counters for any other build
 CSRC   = $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/deep_instances.h $(PKG)/csrc/halo_exchange.h $(PKG)/csrc/chunk_schedule.h $(PKG)/csrc/lbm_hip.cpp $(PKG)/csrc/lbm_deep.cpp \
-         $(PKG)/csrc/ensemble_kernels.h $(PKG)/csrc/steady_kernels.h $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h
+         $(PKG)/csrc/ensemble_kernels.h $(PKG)/csrc/steady_kernels.h $(PKG)/csrc/steady_words.h $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h
 SRC_ID = $(shell cat $(CSRC) | sha256sum | cut -c1-12)
 
 # Three translation units: the deep window kernels get the compiler's max-ILP scheduling strategy (csrc/deep_instances.h says
@@ -30,7 +30,7 @@ $(PKG)/csrc/lbm_hip.o: $(CSRC) include/lbm.h
 $(PKG)/csrc/lbm_deep.o: $(PKG)/csrc/lbm_deep.cpp $(PKG)/csrc/deep_instances.h $(PKG)/csrc/d2q9_kernels.h
 	$(HIPCC) $(HIPFLAGS) -mllvm -amdgpu-sched-strategy=max-ilp -c $(PKG)/csrc/lbm_deep.cpp -o $@
 
-$(PKG)/csrc/lbm_ensemble.o: $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/ensemble_kernels.h $(PKG)/csrc/steady_kernels.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h include/lbm.h
+$(PKG)/csrc/lbm_ensemble.o: $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/ensemble_kernels.h $(PKG)/csrc/steady_kernels.h $(PKG)/csrc/steady_words.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h include/lbm.h
 	$(HIPCC) $(HIPFLAGS) -c $(PKG)/csrc/lbm_ensemble.cpp -o $@
 
 # The double-precision entry points (lbm_dp_*) and their kernels are a fourth unit.  They stay out of CSRC: the digest names
@@ -41,9 +41,10 @@ $(PKG)/csrc/lbm_dp.o: $(PKG)/csrc/lbm_dp.cpp $(PKG)/csrc/dp_kernels.h $(PKG)/csr
 	$(HIPCC) $(HIPFLAGS) $(LBM_DP_FLAGS) -c $(PKG)/csrc/lbm_dp.cpp -o $@
 
 # The double-precision ensembles (lbm_dens_*) are a fifth unit: the member axis of ensemble_kernels.h over the arithmetic of
-# dp_kernels.h, which it includes.  Out of CSRC for the same reason.  LBM_DENS_FLAGS: a measurement build that forces one
+# dp_kernels.h, which it includes, and their steady runs (lbm_dsteady_*: dp_steady_kernels.h over the words of steady_words.h,
+# which is in CSRC because the third unit includes it).  Out of CSRC for the same reason.  LBM_DENS_FLAGS: a measurement build that forces one
 # tile shape (csrc/lbm_dens.cpp, LBM_DENS_TY / LBM_DENS_TMAX / LBM_DENS_THREADS; tools/dp_ensemble_ab.py).
-$(PKG)/csrc/lbm_dens.o: $(PKG)/csrc/lbm_dens.cpp $(PKG)/csrc/dp_ensemble_kernels.h $(PKG)/csrc/dp_kernels.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h include/lbm.h
+$(PKG)/csrc/lbm_dens.o: $(PKG)/csrc/lbm_dens.cpp $(PKG)/csrc/dp_ensemble_kernels.h $(PKG)/csrc/dp_steady_kernels.h $(PKG)/csrc/steady_words.h $(PKG)/csrc/dp_kernels.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h include/lbm.h
 	$(HIPCC) $(HIPFLAGS) $(LBM_DENS_FLAGS) -c $(PKG)/csrc/lbm_dens.cpp -o $@
 
 $(LIB): $(PKG)/csrc/lbm_hip.o $(PKG)/csrc/lbm_deep.o $(PKG)/csrc/lbm_ensemble.o $(PKG)/csrc/lbm_dp.o $(PKG)/csrc/lbm_dens.o

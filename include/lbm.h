@@ -401,10 +401,10 @@ void lbm_ens_destroy(lbm_ens *e);
  * ensemble is an ordinary one again and lbm_ens_run continues it.  Otherwise lbm_ens_run, lbm_ens_run_timed and
  * lbm_steady_run answer LBM_ERR_STATE until lbm_ens_upload, which resets counts, parities and flags.
  *
- * Limits: fp32 ensembles only (lbm_dens_* has no steady run yet); the record of a step is the launch split's (a leg of 7
- * steps sums its tiles in another order than a launch of 8, so A(s) agrees with an uninterrupted lbm_ens_run up to
- * summation order and bit for bit with lbm_ens_run(e, window) repeated); the stopped members' workgroups are still
- * launched, and return at once.
+ * Limits: these two entry points take fp32 ensembles (the double-precision ensembles have their own, lbm_dsteady_run and
+ * lbm_dsteady_steps, further down); the record of a step is the launch split's (a leg of 7 steps sums its tiles in another
+ * order than a launch of 8, so A(s) agrees with an uninterrupted lbm_ens_run up to summation order and bit for bit with
+ * lbm_ens_run(e, window) repeated); the stopped members' workgroups are still launched, and return at once.
  */
 
 /*
@@ -561,6 +561,64 @@ int lbm_dens_members(const lbm_dens *e);
 
 /* Release everything (beside lbm_ens_destroy / lbm_dp_destroy: d2q9-bgk.c:729-741).  NULL is a no-op. */
 void lbm_dens_destroy(lbm_dens *e);
+
+/*
+ * ---- Steady runs of double-precision ensembles: every member to its own steady state, in fp64 ------------------------
+ *
+ * lbm_steady_run / lbm_steady_steps (above) for an lbm_dens: a Reynolds-number sweep that has to land on fp64 results is
+ * run for each member's steady state, and the members reach theirs at very different step counts.  A steady run advances
+ * the ensemble in legs of `window` steps and, after each leg, stops every member whose own av_vels record has settled.  The
+ * decision is taken on the device: a stopped member's workgroups return before they touch its cells, its state and its
+ * record beyond its count are never written again, and no host round trip separates the legs.  The reference has no
+ * counterpart (one grid, a fixed maxIters: d2q9-bgk.c:221-239).
+ *
+ * Check points.  With s0 = lbm_dens_steps_done(e) at the call, a check point is a step count s = s0 + k * window, k = 1, 2,
+ * ..., with s <= s0 + max_steps and s - window >= 1.  Between check points the members still active advance by `window`
+ * steps exactly as lbm_dens_run(e, window) advances them: the accelerate prologue, the fewest launches of equal depth (at
+ * most 3 steps each), no fused acceleration on the last launch, the segment sums reduced into the record.  If max_steps is
+ * not a multiple of window the last leg is shorter; it is run, and no check follows it.
+ *
+ * Criterion, entirely in double.  Let A(s) = av_sum[s - 1] * free_cells_inv be the double that lbm_dens_download returns
+ * for the s-th step of a member: the member's per-step sum times its own free_cells_inv (lbm_dparams), one multiplication.
+ * A member stops at check point s if
+ *     fabs(A(s) - A(s - window)) <= rel_tol * fabs(A(s)),
+ * evaluated on the device in IEEE double with exactly these operations, the difference and the product as separate
+ * statements without contraction: the host can reproduce every decision from the downloaded record.  A NaN never stops a
+ * member; that covers a member without a free cell whose free_cells_inv is inf (0 * inf is NaN): it runs to max_steps.  A
+ * member whose A is exactly 0 throughout (no free cell, a finite free_cells_inv) stops at its first check point.
+ *
+ * Bit identity.  A step's segment sums are added in one fixed order that does not depend on the depth of the launch that
+ * computed it, so, unlike an fp32 steady run, the record does not depend on how the legs cut the launches: a member that
+ * stopped at count c holds the same bits as a double-precision context (lbm_dp_*), or as a plain lbm_dens ensemble,
+ * advanced to c by one run of c steps — cells, av_vels[0..c), the four fields and the Reynolds number.
+ *
+ * The host reads one word back every few legs, the count of active members, and stops enqueuing when it is 0; what a
+ * member computes does not depend on that.  The call returns after a final synchronisation.
+ *
+ * Afterwards lbm_dens_steps_done returns the largest member count; lbm_dens_download, lbm_dens_final_state and
+ * lbm_dens_reynolds return each member's own last state (the two grid arrays are double-buffered and a leg may be an odd
+ * number of launches, so which array holds a member's state is the member's own from then on), and av_vels_out is
+ * double[n][steps_done] with exactly +0.0 at and beyond a member's own count.  If all members ended at the same count the
+ * ensemble is an ordinary one again, on the parity read back from the device, and lbm_dens_run continues it.  Otherwise
+ * lbm_dens_run, lbm_dens_run_timed and lbm_dsteady_run answer LBM_ERR_STATE until lbm_dens_upload, which resets counts,
+ * parities and flags.
+ *
+ * Limits: the stopped members' workgroups are still launched, and return at once.
+ */
+
+/*
+ * Advance every member until ITS OWN av_vels record has settled, at most max_steps steps (beside lbm_steady_run /
+ * lbm_dens_run).  Synchronises.  Refused with LBM_ERR_ARG before the ensemble or a device is touched: a NULL ensemble,
+ * max_steps < 0, window < 1, rel_tol negative or not finite (the message names the argument).  s0 + max_steps > max_iters,
+ * and an ensemble whose members are at different counts, are answered with LBM_ERR_STATE.  max_steps == 0 is a no-op.  A
+ * failure after launches began is handled as in lbm_dens_run: what was enqueued is drained, and the ensemble accepts only
+ * lbm_dens_destroy.
+ */
+int lbm_dsteady_run(lbm_dens *e, int max_steps, int window, double rel_tol);
+
+/* Per member: steps applied since the last lbm_dens_upload, and whether it met the criterion of the last lbm_dsteady_run
+ * since then (beside lbm_steady_steps).  steps_out = int[n], converged_out = int[n] (1 / 0); either may be NULL. */
+int lbm_dsteady_steps(lbm_dens *e, int *steps_out /*[n]*/, int *converged_out /*[n]*/);
 
 const char *lbm_last_error(void);
 const char *lbm_version(void);

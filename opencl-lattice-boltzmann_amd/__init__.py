@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "lbm_dp_get_option", "lbm_dp_destroy",
     "lbm_dens_create", "lbm_dens_upload", "lbm_dens_run", "lbm_dens_run_timed", "lbm_dens_sync", "lbm_dens_download",
     "lbm_dens_final_state", "lbm_dens_reynolds", "lbm_dens_steps_done", "lbm_dens_members", "lbm_dens_destroy",
+    "lbm_dsteady_run", "lbm_dsteady_steps",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -144,6 +145,8 @@ def load_library():
     L.lbm_dens_members.argtypes = [vp]
     L.lbm_dens_destroy.argtypes = [vp]
     L.lbm_dens_destroy.restype = None
+    L.lbm_dsteady_run.argtypes = [vp, ci, ci, ctypes.c_double]
+    L.lbm_dsteady_steps.argtypes = [vp, vp, vp]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -568,10 +571,12 @@ def sweep_dparams(base, omega=None, accel=None):
 
 class _EnsembleOf(_Handle):
     """The body of Ensemble and EnsembleDouble.  A class names its family in `_prefix`, the numpy type of its arrays in
-    `_dtype` and the ctypes type of its members' parameters in `_ptype`."""
+    `_dtype`, the ctypes type of its members' parameters in `_ptype` and the prefix of its steady-run entry points in
+    `_steady`."""
     _handle = "ens"
     _dtype = None
     _ptype = None
+    _steady = None
 
     def __init__(self, params, obstacles):
         self.lib = load_library()
@@ -622,19 +627,14 @@ class _EnsembleOf(_Handle):
         self._call("reynolds", r.ctypes.data)
         return r
 
-
-class Ensemble(_EnsembleOf):
-    """N independent simulations of one grid size, advanced together (lbm_ens): one launch per (up to) eight timesteps for
-    all members.  Mirrors LBM with the member index as the first axis of every array.  `params`: a list of Params that share
-    nx, ny and max_iters; `obstacles`: int32[n, ny, nx], or one [ny, nx] map for all members."""
-    _prefix, _dtype, _ptype = "lbm_ens", np.float32, Params
-
     def run_until(self, max_steps, window=64, rel_tol=1e-4):
-        """Every member to its own steady state (lbm_steady_run): legs of `window` steps, a member stops at the first check
-        point s where |A(s) - A(s - window)| <= rel_tol |A(s)| on its own av_vels record, at most max_steps steps.  Returns
-        (steps int32[n], converged bool[n]).  Members that stopped at different counts leave the ensemble ragged: download(),
-        final_state() and reynolds() return every member's own last state, run() is refused until the next upload()."""
-        _check(self.lib.lbm_steady_run(self.ens, max_steps, window, rel_tol), "lbm_steady_run")
+        """Every member to its own steady state (lbm_steady_run; an EnsembleDouble: lbm_dsteady_run): legs of `window` steps,
+        a member stops at the first check point s where |A(s) - A(s - window)| <= rel_tol |A(s)| on its own av_vels record, at
+        most max_steps steps.  Returns (steps int32[n], converged bool[n]).  Members that stopped at different counts leave
+        the ensemble ragged: download(), final_state() and reynolds() return every member's own last state, run() is refused
+        until the next upload()."""
+        symbol = self._steady + "_run"
+        _check(getattr(self.lib, symbol)(self.ens, max_steps, window, rel_tol), symbol)
         return self.member_steps()
 
     def member_steps(self):
@@ -642,16 +642,25 @@ class Ensemble(_EnsembleOf):
         criterion of the last run_until since then"""
         steps = np.zeros(self.n, dtype=np.int32)
         conv = np.zeros(self.n, dtype=np.int32)
-        _check(self.lib.lbm_steady_steps(self.ens, steps.ctypes.data, conv.ctypes.data), "lbm_steady_steps")
+        symbol = self._steady + "_steps"
+        _check(getattr(self.lib, symbol)(self.ens, steps.ctypes.data, conv.ctypes.data), symbol)
         return steps, conv.astype(bool)
+
+
+class Ensemble(_EnsembleOf):
+    """N independent simulations of one grid size, advanced together (lbm_ens): one launch per (up to) eight timesteps for
+    all members.  Mirrors LBM with the member index as the first axis of every array.  `params`: a list of Params that share
+    nx, ny and max_iters; `obstacles`: int32[n, ny, nx], or one [ny, nx] map for all members."""
+    _prefix, _dtype, _ptype, _steady = "lbm_ens", np.float32, Params, "lbm_steady"
 
 
 class EnsembleDouble(_EnsembleOf):
     """N independent double-precision simulations of one grid size, advanced together (lbm_dens): one launch per several
     timesteps for all members, every member bit-identical to an LBMDouble on the same inputs.  Mirrors Ensemble with double
     in place of float.  `params`: a list of DParams that share nx, ny and max_iters (sweep_dparams); `obstacles`:
-    int32[n, ny, nx], or one [ny, nx] map for all members."""
-    _prefix, _dtype, _ptype = "lbm_dens", np.float64, DParams
+    int32[n, ny, nx], or one [ny, nx] map for all members.  run_until() stops a member where an LBMDouble run to the same
+    count would be, bit for bit, av_vels included."""
+    _prefix, _dtype, _ptype, _steady = "lbm_dens", np.float64, DParams, "lbm_dsteady"
 
     def __init__(self, params, obstacles):
         params = list(params)

@@ -55,8 +55,10 @@ struct DensArgs {
 // recomputes 1.28 x the tile per step against 2.15 x at T = 8); 16x16 at T <= 2 / 1: 25.85 / 51.75 on the first case.  One form
 // serves both sizes.  Ensembles whose tiles all get a CU of their own (<= 256 tiles) run 19-30 % faster at T <= 8 (1 x 128x128
 // 1.95 against 2.40); that form is not instantiated.  0 scratch, 0 spills in all.
-template <int TX, int TY, int TMAX, int NT = kMultiThreads>
-__global__ __launch_bounds__(NT) void d2q9_dp_ensemble(const DensArgs a) {
+// The tile body is a function of its own so that the gated kernel of a steady run (dp_steady_kernels.h) advances a member
+// with the very same instructions.
+template <int TX, int TY, int TMAX, int NT>
+__device__ __forceinline__ void dens_tile(const DensArgs a) {
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
   static_assert(TY * (TX / kDpSeg) <= NT, "one lane per segment of the tile");
   constexpr int kRX = TX + 2 * TMAX, kRY = TY + 2 * TMAX;
@@ -158,15 +160,23 @@ __global__ __launch_bounds__(NT) void d2q9_dp_ensemble(const DensArgs a) {
   }
 }
 
+template <int TX, int TY, int TMAX, int NT = kMultiThreads>
+__global__ __launch_bounds__(NT) void d2q9_dp_ensemble(const DensArgs a) {
+  dens_tile<TX, TY, TMAX, NT>(a);
+}
+
 // ---- second reduction stage with a member axis: dp_reduce's partition and order, fixed, no atomics -------------------
 // grid = (blocks, steps, members): block b of step r of member m adds in[r * in_stride + m * in_member + i] for i in its
 // contiguous chunk (lane-strided, then the wave butterfly, then the four waves in order) into
 // out[m * out_member + r * out_stride + b].  With the block count lbm_dp takes for a grid of the member's ny * nseg this
 // adds a step's segments in the order dp_reduce adds them there: once into av_sum, or twice (partials per block, then one
-// block per step and member).
+// block per step and member).  active: NULL, or one word per member; a member whose word is 0 has stopped
+// (dp_steady_kernels.h), its tiles wrote no segment sums and its record is left alone.
 static __global__ __launch_bounds__(kBlock) void dens_reduce(const double *in, unsigned long long in_stride,
                                                              unsigned long long in_member, long n, double *out,
-                                                             unsigned long long out_stride, unsigned long long out_member) {
+                                                             unsigned long long out_stride, unsigned long long out_member,
+                                                             const int *active) {
+  if (active && active[blockIdx.z] == 0) return;  // uniform over the workgroup, before the barrier
   const long chunk = (n + gridDim.x - 1) / gridDim.x;
   const long i0 = (long)blockIdx.x * chunk, i1 = i0 + chunk < n ? i0 + chunk : n;
   const double *p = in + (size_t)blockIdx.y * in_stride + (size_t)blockIdx.z * in_member;
@@ -185,11 +195,11 @@ static __global__ __launch_bounds__(kBlock) void dens_reduce(const double *in, u
 
 // ---- the helper kernels of dp_kernels.h with a member axis (blockIdx.y), same per-cell arithmetic --------------------
 
-// accelerate_flow of row ny-2 of every member (kernels.cl:9-53): prologue of a run
+// accelerate_flow of row ny-2 of every member (kernels.cl:9-53): prologue of a run.  active: as dens_reduce
 static __global__ void dens_accelerate_row(double *cells, unsigned long long plane_stride, unsigned long long member_stride,
-                                           const uint8_t *mask, const DensMember *members, int nx, int ny) {
+                                           const uint8_t *mask, const DensMember *members, int nx, int ny, const int *active) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
-  if (x >= nx) return;
+  if (x >= nx || (active && active[blockIdx.y] == 0)) return;
   const DensMember mc = members[blockIdx.y];
   const int row = ny - 2;
   double f[9];
@@ -218,10 +228,13 @@ static __global__ void dens_init_cells(double *cells, unsigned long long plane_s
 }
 
 // device layout <-> the caller's double[members][9][ny][nx] (staged in the grid array that is not current, one transfer
-// for the whole ensemble).  TO_DEVICE: flat -> cells, else cells -> flat.
+// for the whole ensemble).  TO_DEVICE: flat -> cells, else cells -> flat.  par: NULL, or one word per member that says which
+// of the two grid arrays holds that member's current state (0: cells, 1: cells_alt) once members have stopped on different
+// launch parities (dp_steady_kernels.h).
 template <bool TO_DEVICE>
-static __global__ void dens_pack_planes(double *cells, unsigned long long plane_stride, unsigned long long member_stride, int nx,
-                                        size_t n, double *flat) {
+static __global__ void dens_pack_planes(double *cells, double *cells_alt, const int *par, unsigned long long plane_stride,
+                                        unsigned long long member_stride, int nx, size_t n, double *flat) {
+  if (par && par[blockIdx.y]) cells = cells_alt;
   cells += (size_t)blockIdx.y * member_stride;
   flat += (size_t)blockIdx.y * 9 * n;
   for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
@@ -237,14 +250,16 @@ static __global__ void dens_pack_planes(double *cells, unsigned long long plane_
 
 // output stage per member (dp_final_fields: d2q9-bgk.c:787-832, 396-442, in double, the oracle's statements): outputs are
 // double[members][ny][nx], partials double[members][gridDim.x] — with dp_final_fields' block count the per-block sums of u
-// are those of an lbm_dp context of the member's size, bit for bit
-static __global__ __launch_bounds__(kBlock) void dens_final_fields(const double *cells, unsigned long long plane_stride,
+// are those of an lbm_dp context of the member's size, bit for bit.  cells_alt, par: as dens_pack_planes
+static __global__ __launch_bounds__(kBlock) void dens_final_fields(const double *cells, const double *cells_alt, const int *par,
+                                                                   unsigned long long plane_stride,
                                                                    unsigned long long member_stride, int nx, const uint8_t *mask,
                                                                    size_t n, const DensMember *members, double *u_x, double *u_y,
                                                                    double *u, double *pressure, double *partials) {
 #pragma clang fp contract(off)
   const double c_sq = 1.0 / 3.0;
   const double density = members[blockIdx.y].density;
+  if (par && par[blockIdx.y]) cells = cells_alt;
   cells += (size_t)blockIdx.y * member_stride;
   mask += (size_t)blockIdx.y * n;
   const size_t off = (size_t)blockIdx.y * n;

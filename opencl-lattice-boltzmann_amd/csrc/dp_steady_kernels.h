@@ -1,0 +1,49 @@
+// Device side of a STEADY RUN of a double-precision ensemble (include/lbm.h: lbm_dsteady_*): steady_kernels.h for the fp64
+// members of dp_ensemble_kernels.h.  The per-member words and the kernel that starts a run are steady_words.h's, one copy for
+// both families.  d2q9_dp_ensemble_gated is d2q9_dp_ensemble behind a test of `active`: one copy of the arithmetic
+// (dens_tile), so the forcing guard and every bit-identity property of the plain kernel carry over; the workgroups of a
+// stopped member return before they touch its cells or its segment sums.  dens_reduce and dens_accelerate_row skip the
+// same members, so a stopped member's cells, and its record beyond its count, are never written again.
+//
+// A step's segment sums are added in one fixed order whatever the depth of the launch that computed it (store_segments,
+// dens_reduce), so the record of a steady run does not depend on how its legs cut the launches: a member stopped at count c
+// holds the bits of an lbm_dens_run(e, c) in one piece, av_vels included.
+#pragma once
+#include "dp_ensemble_kernels.h"
+#include "steady_words.h"
+
+namespace lbm {
+
+template <int TX, int TY, int TMAX, int NT = kMultiThreads>
+__global__ __launch_bounds__(NT) void d2q9_dp_ensemble_gated(const DensArgs a, const int *active) {
+  if (active[blockIdx.y] == 0) return;  // uniform over the workgroup, before the first barrier or LDS access
+  dens_tile<TX, TY, TMAX, NT>(a);
+}
+
+// After a leg that ended at step count s on parity cur: the members that were active during it are now at s.  With
+// `check`, a member stops if |A(s) - A(s - window)| <= rel_tol |A(s)|, where A(t) is the double lbm_dens_download returns
+// for step t, av_sum[t - 1] * free_cells_inv: one multiplication by the member's own free_cells_inv.  Entirely in double,
+// difference and bound as separate statements with contraction off, so that the host reproduces every decision from the
+// downloaded record.  A NaN on either side compares false: such a member runs on (0 * inf of a member without a free cell).
+static __global__ void dens_steady_check(SteadyWords w, int n, const double *av_sum, unsigned long long record,
+                                         const double *free_cells_inv, int s, int window, double rel_tol, int check, int cur) {
+#pragma clang fp contract(off)
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= n || w.active[m] == 0) return;
+  w.steps[m] = s;
+  w.par[m] = cur;
+  if (!check) return;
+  const double *av = av_sum + (size_t)m * record;
+  const double inv = free_cells_inv[m];
+  const double a_now = av[s - 1] * inv;
+  const double a_then = av[s - window - 1] * inv;
+  const double diff = fabs(a_now - a_then);
+  const double bound = rel_tol * fabs(a_now);
+  if (diff <= bound) {
+    w.active[m] = 0;
+    w.conv[m] = 1;
+    atomicSub(w.count, 1);
+  }
+}
+
+}  // namespace lbm

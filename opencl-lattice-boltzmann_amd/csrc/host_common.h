@@ -1,5 +1,6 @@
 // What the host sides of the ensembles, the double-precision contexts and the double-precision ensembles share
 // (lbm_ensemble.cpp, lbm_dp.cpp, lbm_dens.cpp): plain inline helpers over the fields they need, no knowledge of who calls.
+// The steady-run helpers are shared by the two ensemble units.
 // Whatever differs between those units in more than a scalar type - sizes, argument structs, launches, reductions - is theirs.
 #pragma once
 #include "../../include/lbm.h"
@@ -7,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -112,6 +114,44 @@ inline int latch_failure(int rc, bool launched, hipStream_t st, bool *failed) {
     fail_again(rc, keep);
   }
   return rc;
+}
+
+// ---- steady runs (lbm_steady_run, lbm_dsteady_run) ----
+constexpr int kSteadyPollChecks = 4;  // a steady run reads the count of active members back after every so many checks
+
+// what a steady run refuses before it dereferences its ensemble
+inline int check_steady_args(int max_steps, int window, double rel_tol) {
+  if (max_steps < 0) return lbm_fail(LBM_ERR_ARG, "max_steps must be >= 0 (got %d)", max_steps);
+  if (window < 1) return lbm_fail(LBM_ERR_ARG, "window must be >= 1 (got %d)", window);
+  if (!std::isfinite(rel_tol) || rel_tol < 0.0) return lbm_fail(LBM_ERR_ARG, "rel_tol must be finite and >= 0 (got %g)", rel_tol);
+  return LBM_OK;
+}
+
+// End of a steady run: the members' words par[n], steps[n], conv[n] (one after the other on the device, from `par`) say on
+// which parity each member is, at which count, and whether it met the criterion.  The ensemble is at the largest count and
+// ragged if the counts differ; if they do not, all members stopped after the same launch and the ensemble is an ordinary
+// one on that parity.
+inline int steady_read_back(const Queue &q, const int *par, int n, std::vector<int> &m_steps, std::vector<int> &m_conv,
+                            int *steps_done, bool *ragged, int *cur) {
+  std::vector<int> words(3 * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(words.data(), par, words.size() * sizeof(int), hipMemcpyDeviceToHost, q.st));
+  HIP_TRY(hipStreamSynchronize(q.st));
+  m_steps.assign(words.begin() + n, words.begin() + 2 * (size_t)n);
+  m_conv.assign(words.begin() + 2 * (size_t)n, words.end());
+  *steps_done = *std::max_element(m_steps.begin(), m_steps.end());
+  *ragged = *std::min_element(m_steps.begin(), m_steps.end()) != *steps_done;
+  if (!*ragged) *cur = words[0];
+  return LBM_OK;
+}
+
+// lbm_steady_steps / lbm_dsteady_steps: the members of an ensemble that is not ragged are all at its count, whatever ran
+// since the last steady run
+inline void steady_steps_out(int n, bool ragged, int steps_done, const std::vector<int> &m_steps, const std::vector<int> &m_conv,
+                             int *steps_out, int *converged_out) {
+  for (int m = 0; m < n; m++) {
+    if (steps_out) steps_out[m] = ragged ? m_steps[m] : steps_done;
+    if (converged_out) converged_out[m] = m_conv.empty() ? 0 : m_conv[m];
+  }
 }
 
 // ---- creation ----

@@ -8,8 +8,13 @@
 // reduction stage, blocks of the output stage - is computed from the member's nx and ny exactly as lbm_dp.cpp computes it
 // from a grid's, so a member's cells, av_vels, fields and Reynolds number are those of an lbm_dp context, bit for bit.
 // The reference has no counterpart: one grid, one in-order queue (d2q9-bgk.c:221-239).
+//
+// A steady run (lbm_dsteady_*) is the same loop cut into legs of `window` steps behind a per-member `active` word that a
+// criterion kernel clears on the device (dp_steady_kernels.h), as lbm_ensemble.cpp's.  Members may then stop on different
+// launch parities, so from the end of such a run until the next upload the array that holds a member's state is the
+// member's own (`par`).
 #include "../../include/lbm.h"
-#include "dp_ensemble_kernels.h"
+#include "dp_steady_kernels.h"
 #include "host_common.h"
 
 #include <algorithm>
@@ -62,6 +67,13 @@ struct lbm_dens {
   int ring = 8, ring_fill = 0;
   int cur = 0, steps_done = 0;
   bool failed = false;
+  // steady runs (allocated by the first lbm_dsteady_run)
+  int *steady_words = nullptr;       // device: active[n], par[n], steps[n], conv[n], count
+  double *steady_inv = nullptr;      // device: free_cells_inv[n]
+  int *steady_count_host = nullptr;  // page-locked: where the count of active members is read back to
+  double *stage = nullptr;           // device, double[n][9][ny][nx]: staging of downloads while the ensemble is ragged
+  std::vector<int> m_steps, m_conv;  // host copies of the words after the last steady run (empty: none since the upload)
+  bool ragged = false;               // members stopped at different step counts: download and output only, until an upload
 };
 
 namespace {
@@ -76,6 +88,10 @@ void free_dens(lbm_dens *e) {
   if (e->red) (void)hipFree(e->red);
   if (e->av_sum) (void)hipFree(e->av_sum);
   if (e->fin_partials) (void)hipFree(e->fin_partials);
+  if (e->steady_words) (void)hipFree(e->steady_words);
+  if (e->steady_inv) (void)hipFree(e->steady_inv);
+  if (e->steady_count_host) (void)hipHostFree(e->steady_count_host);
+  if (e->stage) (void)hipFree(e->stage);
   queue_destroy(e->q);
   delete e;
 }
@@ -127,22 +143,24 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
   return LBM_OK;
 }
 
-int run_dens_impl(lbm_dens *e, int nsteps, bool timed, double *ms, bool *launched) {
-  if (int rc = check_runnable(nsteps, e->failed, "ensemble")) return rc;
-  if (int rc = check_record(e->max_iters, e->steps_done, nsteps, "")) return rc;
-  if (timed && ms) *ms = 0.0;
-  if (nsteps == 0) return LBM_OK;
-  HIP_TRY(hipSetDevice(e->q.dev));
-  *launched = true;
+// active: NULL for an ordinary run, the members' words for a leg of a steady run
+void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
+  const dim3 grid(e->tiles, e->n), block(kDensThreads);
+  if (!active) hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads>), grid, block, 0, e->q.st, a);
+  else hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads>), grid, block, 0, e->q.st, a, active);
+}
+
+// nsteps steps from step count `first` on, enqueued: the prologue, the launches, the reductions into the record.  Flips
+// e->cur per launch; the caller counts the steps.  active: as launch_dens.
+int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   const size_t per_step = (size_t)e->ny * e->nseg, all_step = (size_t)e->n * per_step;
-  if (int rc = timed_begin(e->q, timed)) return rc;
   // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
   // into the previous launch's write of row ny-2
   hipLaunchKernelGGL(dens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
-                     e->member_stride, (const uint8_t *)e->mask, (const DensMember *)e->members, e->nx, e->ny);
+                     e->member_stride, (const uint8_t *)e->mask, (const DensMember *)e->members, e->nx, e->ny, active);
   HIP_TRY(hipGetLastError());
 
-  int batch_first = e->steps_done;
+  int batch_first = first;
   // second reduction stage over the buffered steps (kernels.cl:234-290 counterpart), all members in one launch per stage
   auto flush = [&]() -> int {
     if (e->ring_fill == 0) return LBM_OK;
@@ -150,15 +168,15 @@ int run_dens_impl(lbm_dens *e, int nsteps, bool timed, double *ms, bool *launche
     if (e->red_blocks > 1) {
       hipLaunchKernelGGL(dens_reduce, dim3(e->red_blocks, e->ring_fill, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->seg,
                          (unsigned long long)all_step, (unsigned long long)per_step, (long)per_step, e->red,
-                         (unsigned long long)e->n * e->red_blocks, (unsigned long long)e->red_blocks);
+                         (unsigned long long)e->n * e->red_blocks, (unsigned long long)e->red_blocks, active);
       HIP_TRY(hipGetLastError());
       hipLaunchKernelGGL(dens_reduce, dim3(1, e->ring_fill, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->red,
                          (unsigned long long)e->n * e->red_blocks, (unsigned long long)e->red_blocks, (long)e->red_blocks,
-                         e->av_sum + batch_first, 1ull, record);
+                         e->av_sum + batch_first, 1ull, record, active);
     } else {
       hipLaunchKernelGGL(dens_reduce, dim3(1, e->ring_fill, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->seg,
                          (unsigned long long)all_step, (unsigned long long)per_step, (long)per_step, e->av_sum + batch_first, 1ull,
-                         record);
+                         record, active);
     }
     HIP_TRY(hipGetLastError());
     batch_first += e->ring_fill;
@@ -187,14 +205,30 @@ int run_dens_impl(lbm_dens *e, int nsteps, bool timed, double *ms, bool *launche
     a.tiles_x = e->tiles_x;
     a.T = adv;
     a.accel_next = (i + adv < nsteps) ? 1 : 0;
-    hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads>), dim3(e->tiles, e->n), dim3(kDensThreads), 0,
-                       e->q.st, a);
+    launch_dens(e, a, active);
     HIP_TRY(hipGetLastError());
     e->cur ^= 1;
     e->ring_fill += adv;
     i += adv;
   }
-  if (int rc = flush()) return rc;
+  return flush();
+}
+
+int refuse_ragged(const lbm_dens *e) {
+  return lbm_fail(LBM_ERR_STATE, "the members of this ensemble stopped at different step counts (lbm_dsteady_run; %d is the "
+                  "largest): download them, then lbm_dens_upload before the next run", e->steps_done);
+}
+
+int run_dens_impl(lbm_dens *e, int nsteps, bool timed, double *ms, bool *launched) {
+  if (int rc = check_runnable(nsteps, e->failed, "ensemble")) return rc;
+  if (e->ragged) return refuse_ragged(e);
+  if (int rc = check_record(e->max_iters, e->steps_done, nsteps, "")) return rc;
+  if (timed && ms) *ms = 0.0;
+  if (nsteps == 0) return LBM_OK;
+  HIP_TRY(hipSetDevice(e->q.dev));
+  *launched = true;
+  if (int rc = timed_begin(e->q, timed)) return rc;
+  if (int rc = enqueue_steps(e, nsteps, e->steps_done, nullptr)) return rc;
   e->steps_done += nsteps;
   return timed_end(e->q, timed, ms);
 }
@@ -205,11 +239,77 @@ int run_dens(lbm_dens *e, int nsteps, bool timed, double *ms) {
   return latch_failure(rc, launched, e->q.st, &e->failed);
 }
 
-// the output stage of all members into `d[0..3]` (any may be NULL) and the per-block sums of u
+SteadyWords steady_words(const lbm_dens *e) { return steady_words_at(e->steady_words, (size_t)e->n); }
+
+// which array holds member m, for the kernels that read a state: the members' own words while the ensemble is ragged
+const int *member_parity(const lbm_dens *e) { return e->ragged ? steady_words(e).par : nullptr; }
+
+// what a steady run needs beyond an ordinary one, allocated by the first
+int steady_alloc(lbm_dens *e) {
+  if (e->steady_words) return LBM_OK;
+  const size_t n = (size_t)e->n;
+  if (!e->steady_count_host)
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->steady_count_host), sizeof(int), hipHostMallocDefault));
+  if (!e->steady_inv) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->steady_inv), n * sizeof(double)));
+  std::vector<double> inv(n);
+  for (size_t m = 0; m < n; m++) inv[m] = e->p[m].free_cells_inv;
+  HIP_TRY(hipMemcpy(e->steady_inv, inv.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->steady_words), (kSteadyWordCount * n + 1) * sizeof(int)));
+  return LBM_OK;
+}
+
+int steady_impl(lbm_dens *e, int max_steps, int window, double rel_tol, bool *launched) {
+  if (int rc = check_runnable(max_steps, e->failed, "ensemble")) return rc;  // max_steps >= 0 here (lbm_dsteady_run)
+  if (e->ragged) return refuse_ragged(e);
+  if (int rc = check_record(e->max_iters, e->steps_done, max_steps, "up to ")) return rc;
+  if (max_steps == 0) return LBM_OK;
+  HIP_TRY(hipSetDevice(e->q.dev));
+  if (int rc = steady_alloc(e)) return rc;
+  const int n = e->n, s0 = e->steps_done;
+  const SteadyWords w = steady_words(e);
+  const dim3 mgrid((unsigned)div_up(n, 256)), mblock(256);
+  *launched = true;
+  hipLaunchKernelGGL(ens_steady_begin, mgrid, mblock, 0, e->q.st, w, n, e->cur, s0);
+  HIP_TRY(hipGetLastError());
+  int done = 0, checks = 0;
+  while (done < max_steps) {
+    const int leg = std::min(window, max_steps - done);
+    if (int rc = enqueue_steps(e, leg, s0 + done, w.active)) return rc;
+    done += leg;
+    const int s = s0 + done;
+    // a check point: a whole leg, with a record entry one window back (step counts start at 1)
+    const int check = (leg == window && s - window >= 1) ? 1 : 0;
+    hipLaunchKernelGGL(dens_steady_check, mgrid, mblock, 0, e->q.st, w, n, (const double *)e->av_sum,
+                       (unsigned long long)e->max_iters, (const double *)e->steady_inv, s, window, rel_tol, check, e->cur);
+    HIP_TRY(hipGetLastError());
+    // Every few checks: is anyone left?  Only how much is enqueued depends on the answer; what a member computes does not,
+    // the workgroups of a stopped member return at once.
+    if (check && ++checks % kSteadyPollChecks == 0 && done < max_steps) {
+      HIP_TRY(hipMemcpyAsync(e->steady_count_host, w.count, sizeof(int), hipMemcpyDeviceToHost, e->q.st));
+      HIP_TRY(hipStreamSynchronize(e->q.st));
+      if (*e->steady_count_host == 0) break;
+    }
+  }
+  return steady_read_back(e->q, w.par, n, e->m_steps, e->m_conv, &e->steps_done, &e->ragged, &e->cur);
+}
+
+// Where downloads and the output stage put their results on the device: the grid array that is not current is scratch
+// between runs; a ragged ensemble has no scratch array (both hold members' states) and gets a staging array of its own
+int stage_of(lbm_dens *e, double **stage) {
+  *stage = e->cells[e->cur ^ 1];
+  if (!e->ragged) return LBM_OK;
+  if (!e->stage) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->stage), (size_t)e->n * 9 * e->nx * e->ny * sizeof(double)));
+  *stage = e->stage;
+  return LBM_OK;
+}
+
+// the output stage of all members, each from the array that holds it, into `d[0..3]` (any may be NULL) and the per-block
+// sums of u
 int final_fields_dens(lbm_dens *e, double *const (&d)[4]) {
-  hipLaunchKernelGGL(dens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->cells[e->cur],
-                     e->plane_stride, e->member_stride, e->nx, (const uint8_t *)e->mask, (size_t)e->nx * e->ny,
-                     (const DensMember *)e->members, d[0], d[1], d[2], d[3], e->fin_partials);
+  hipLaunchKernelGGL(dens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->q.st,
+                     (const double *)e->cells[e->ragged ? 0 : e->cur], (const double *)e->cells[1], member_parity(e), e->plane_stride,
+                     e->member_stride, e->nx, (const uint8_t *)e->mask, (size_t)e->nx * e->ny, (const DensMember *)e->members, d[0],
+                     d[1], d[2], d[3], e->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
 }
@@ -268,8 +368,8 @@ int lbm_dens_upload(lbm_dens *e, const double *cells) {
     // one transfer of the caller's double[n][9][ny][nx] into the second grid array (9 nx ny <= member_stride), then one
     // launch that scatters every member's planes into the first (d2q9-bgk.c:200-203 for all members)
     HIP_TRY(hipMemcpyAsync(e->cells[1], cells, (size_t)e->n * 9 * per * sizeof(double), hipMemcpyHostToDevice, e->q.st));
-    hipLaunchKernelGGL(dens_pack_planes<true>, grid, dim3(256), 0, e->q.st, e->cells[0], e->plane_stride, e->member_stride, e->nx, per,
-                       e->cells[1]);
+    hipLaunchKernelGGL(dens_pack_planes<true>, grid, dim3(256), 0, e->q.st, e->cells[0], (double *)nullptr, (const int *)nullptr,
+                       e->plane_stride, e->member_stride, e->nx, per, e->cells[1]);
   } else {
     hipLaunchKernelGGL(dens_init_cells, grid, dim3(256), 0, e->q.st, e->cells[0], e->plane_stride, e->member_stride,
                        (const DensMember *)e->members, e->nx, per);
@@ -279,6 +379,9 @@ int lbm_dens_upload(lbm_dens *e, const double *cells) {
   e->cur = 0;
   e->steps_done = 0;
   e->ring_fill = 0;
+  e->ragged = false;
+  e->m_steps.clear();
+  e->m_conv.clear();
   return LBM_OK;
 }
 
@@ -305,11 +408,13 @@ int lbm_dens_download(lbm_dens *e, double *cells_out, double *av_vels_out) {
   if (int rc = queue_sync(e->q)) return rc;
   const size_t per = (size_t)e->nx * e->ny;
   if (cells_out) {
-    // the grid array that is not current is scratch between runs: repack every member into the caller's layout there,
-    // then one contiguous transfer
-    double *stage = e->cells[e->cur ^ 1];
+    // repack every member, from the array that holds it, into the caller's layout in the staging array, then one
+    // contiguous transfer
+    double *stage = nullptr;
+    if (int rc = stage_of(e, &stage)) return rc;
     hipLaunchKernelGGL(dens_pack_planes<false>, dim3((unsigned)std::min(div_up((long)per, 256), 1024L), e->n), dim3(256), 0, e->q.st,
-                       e->cells[e->cur], e->plane_stride, e->member_stride, e->nx, per, stage);
+                       e->cells[e->ragged ? 0 : e->cur], e->cells[1], member_parity(e), e->plane_stride, e->member_stride, e->nx,
+                       per, stage);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(cells_out, stage, (size_t)e->n * 9 * per * sizeof(double), hipMemcpyDeviceToHost, e->q.st));
     HIP_TRY(hipStreamSynchronize(e->q.st));
@@ -322,6 +427,10 @@ int lbm_dens_download(lbm_dens *e, double *cells_out, double *av_vels_out) {
     // kernels.cl:202: sum * FREE_CELLS_INV, the member's own, in double
     for (int m = 0; m < e->n; m++)
       for (int t = 0; t < T; t++) av_vels_out[(size_t)m * T + t] = sums[(size_t)m * T + t] * e->p[m].free_cells_inv;
+    // a member that stopped earlier has no record from its own count on
+    if (e->ragged)
+      for (int m = 0; m < e->n; m++)
+        for (int t = e->m_steps[m]; t < T; t++) av_vels_out[(size_t)m * T + t] = 0.0;
   }
   return LBM_OK;
 }
@@ -331,10 +440,12 @@ int lbm_dens_final_state(lbm_dens *e, double *u_x, double *u_y, double *u, doubl
   if (int rc = queue_sync(e->q)) return rc;
   const size_t all = (size_t)e->nx * e->ny * e->n;
   double *outs[4] = {u_x, u_y, u, pressure};
-  // the four columns of all members go to the grid array that is not current (4 n nx ny doubles of its 9 n nx ny)
+  // the four columns of all members go to the staging array (4 n nx ny doubles of its 9 n nx ny)
   double *d[4] = {nullptr, nullptr, nullptr, nullptr};
+  double *stage = nullptr;
+  if (int rc = stage_of(e, &stage)) return rc;
   for (int i = 0; i < 4; i++)
-    if (outs[i]) d[i] = e->cells[e->cur ^ 1] + (size_t)i * all;
+    if (outs[i]) d[i] = stage + (size_t)i * all;
   if (int rc = final_fields_dens(e, d)) return rc;
   for (int i = 0; i < 4; i++)
     if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], d[i], all * sizeof(double), hipMemcpyDeviceToHost, e->q.st));
@@ -358,6 +469,21 @@ int lbm_dens_reynolds(lbm_dens *e, double *reynolds_out) {
     const double viscosity = 1.0 / 6.0 * (2.0 / p.omega - 1.0);
     reynolds_out[m] = tot * p.free_cells_inv * (double)p.reynolds_dim / viscosity;
   }
+  return LBM_OK;
+}
+
+int lbm_dsteady_run(lbm_dens *e, int max_steps, int window, double rel_tol) {
+  // every argument error is reported before the ensemble or a device is touched
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
+  bool launched = false;
+  const int rc = steady_impl(e, max_steps, window, rel_tol, &launched);
+  return latch_failure(rc, launched, e->q.st, &e->failed);
+}
+
+int lbm_dsteady_steps(lbm_dens *e, int *steps_out, int *converged_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  steady_steps_out(e->n, e->ragged, e->steps_done, e->m_steps, e->m_conv, steps_out, converged_out);
   return LBM_OK;
 }
 

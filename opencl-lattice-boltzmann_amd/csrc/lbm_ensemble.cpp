@@ -28,7 +28,6 @@ namespace {
 constexpr int kEnsRingMax = 256;           // most steps of per-tile partial sums buffered between reductions
 constexpr long kEnsMaxCells = 300L * 1024; // the library's bound for "launch-bound" (multistep_effective, lbm_hip.cpp)
 constexpr int kEnsMaxMembers = 65535;      // member index = blockIdx.y
-constexpr int kSteadyPollChecks = 4;       // a steady run reads the count of active members back after every so many checks
 
 }  // namespace
 
@@ -222,11 +221,7 @@ int run_ens(lbm_ens *e, int nsteps, bool timed, double *ms) {
   return latch_failure(rc, launched, e->q.st, &e->failed);
 }
 
-SteadyWords steady_words(const lbm_ens *e) {
-  int *w = e->steady_words;
-  const size_t n = (size_t)e->n;
-  return SteadyWords{w, w + n, w + 2 * n, w + 3 * n, w + 4 * n};
-}
+SteadyWords steady_words(const lbm_ens *e) { return steady_words_at(e->steady_words, (size_t)e->n); }
 
 // which array holds member m, for the kernels that read a state: the members' own words while the ensemble is ragged
 const int *member_parity(const lbm_ens *e) { return e->ragged ? steady_words(e).par : nullptr; }
@@ -241,7 +236,7 @@ int steady_alloc(lbm_ens *e) {
   std::vector<float> inv(n);
   for (size_t m = 0; m < n; m++) inv[m] = e->p[m].free_cells_inv;
   HIP_TRY(hipMemcpy(e->steady_inv, inv.data(), n * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->steady_words), (4 * n + 1) * sizeof(int)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->steady_words), (kSteadyWordCount * n + 1) * sizeof(int)));
   return LBM_OK;
 }
 
@@ -277,17 +272,7 @@ int steady_impl(lbm_ens *e, int max_steps, int window, double rel_tol, bool *lau
       if (*e->steady_count_host == 0) break;
     }
   }
-  // the members' words: on which parity each one is, at which count, and whether it met the criterion
-  std::vector<int> words(3 * (size_t)n);
-  HIP_TRY(hipMemcpyAsync(words.data(), w.par, words.size() * sizeof(int), hipMemcpyDeviceToHost, e->q.st));
-  HIP_TRY(hipStreamSynchronize(e->q.st));
-  e->m_steps.assign(words.begin() + n, words.begin() + 2 * (size_t)n);
-  e->m_conv.assign(words.begin() + 2 * (size_t)n, words.end());
-  e->steps_done = *std::max_element(e->m_steps.begin(), e->m_steps.end());
-  e->ragged = *std::min_element(e->m_steps.begin(), e->m_steps.end()) != e->steps_done;
-  // all at one count: they stopped after the same launch, and the ensemble is an ordinary one on that parity
-  if (!e->ragged) e->cur = words[0];
-  return LBM_OK;
+  return steady_read_back(e->q, w.par, n, e->m_steps, e->m_conv, &e->steps_done, &e->ragged, &e->cur);
 }
 
 // the staging array of downloads while both grid arrays hold members' states
@@ -467,9 +452,7 @@ int lbm_ens_reynolds(lbm_ens *e, float *reynolds_out) {
 int lbm_steady_run(lbm_ens *e, int max_steps, int window, double rel_tol) {
   // every argument error is reported before the ensemble or a device is touched
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  if (max_steps < 0) return lbm_fail(LBM_ERR_ARG, "max_steps must be >= 0 (got %d)", max_steps);
-  if (window < 1) return lbm_fail(LBM_ERR_ARG, "window must be >= 1 (got %d)", window);
-  if (!std::isfinite(rel_tol) || rel_tol < 0.0) return lbm_fail(LBM_ERR_ARG, "rel_tol must be finite and >= 0 (got %g)", rel_tol);
+  if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
   bool launched = false;
   const int rc = steady_impl(e, max_steps, window, rel_tol, &launched);
   return latch_failure(rc, launched, e->q.st, &e->failed);
@@ -477,11 +460,7 @@ int lbm_steady_run(lbm_ens *e, int max_steps, int window, double rel_tol) {
 
 int lbm_steady_steps(lbm_ens *e, int *steps_out, int *converged_out) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  for (int m = 0; m < e->n; m++) {
-    // the members of an ensemble that is not ragged are all at its count, whatever ran since the last steady run
-    if (steps_out) steps_out[m] = e->ragged ? e->m_steps[m] : e->steps_done;
-    if (converged_out) converged_out[m] = e->m_conv.empty() ? 0 : e->m_conv[m];
-  }
+  steady_steps_out(e->n, e->ragged, e->steps_done, e->m_steps, e->m_conv, steps_out, converged_out);
   return LBM_OK;
 }
 

@@ -1,38 +1,21 @@
 // Device side of a STEADY RUN of an ensemble (include/lbm.h: lbm_steady_*): every member advances until its own av_vels
 // record has settled, and the decision is taken on the device, so a run is enqueued without a host round trip per leg.
 //
-// Per member there are four words in device memory (SteadyWords): `active` (1 while the member still advances), `par`
-// (which of the two grid arrays holds its state), `steps` (steps applied) and `conv` (it met the criterion), and one
-// counter of active members for the host to poll.  d2q9_ensemble_gated is d2q9_ensemble behind a test of `active`: the
-// workgroups of a stopped member return before they touch its cells or its partial sums.  After the reduction of every leg
-// ens_steady_check compares two entries of each active member's record and clears the word of those that have settled.
-// The members that are still active have all been advanced by the same launches, so they share one parity, the host's; a
-// stopped member keeps the parity it had when it stopped.
+// The per-member words (`active`, `par`, `steps`, `conv`, the counter of active members) and the kernel that starts a run
+// are steady_words.h's, shared with the double-precision ensembles.  d2q9_ensemble_gated is d2q9_ensemble behind a test of
+// `active`: the workgroups of a stopped member return before they touch its cells or its partial sums.  After the reduction
+// of every leg ens_steady_check compares two entries of each active member's record and clears the word of those that have
+// settled.
 #pragma once
 #include "ensemble_kernels.h"
+#include "steady_words.h"
 
 namespace lbm {
-
-struct SteadyWords {
-  int *active, *par, *steps, *conv;  // [members] each
-  int *count;                        // members with active != 0
-};
 
 template <int TX, int TY>
 __global__ __launch_bounds__(kMultiThreads) void d2q9_ensemble_gated(const EnsArgs a, const int *active) {
   if (active[blockIdx.y] == 0) return;  // uniform over the workgroup, before the first barrier
   ens_tile<TX, TY>(a);
-}
-
-// start of a steady run: every member active, on the ensemble's parity, at the ensemble's step count
-static __global__ void ens_steady_begin(SteadyWords w, int n, int cur, int s0) {
-  const int m = blockIdx.x * blockDim.x + threadIdx.x;
-  if (m == 0) *w.count = n;
-  if (m >= n) return;
-  w.active[m] = 1;
-  w.par[m] = cur;
-  w.steps[m] = s0;
-  w.conv[m] = 0;
 }
 
 // After a leg that ended at step count s on parity cur: the members that were active during it are now at s.  With
