@@ -488,10 +488,14 @@ int lbm_dp_reynolds(lbm_dp *d, double *reynolds_out);
 int lbm_dp_steps_done(const lbm_dp *d);
 
 /*
- * One option (beside lbm_set_option / lbm_get_option):
+ * Two options (beside lbm_set_option / lbm_get_option):
  *   "multistep"   -1 = auto (the LDS-tile form up to 300K cells, else one step per launch), 0 = one step per launch
  *                 (d2q9_dp_step), 1..8 = that many steps per launch on LDS-resident tiles (d2q9_dp_multi); a run is cut
  *                 into the fewest launches of equal depth.  Both forms give the same cells, av_vels and fields bit for bit.
+ *   "force"       0 (default) | 1 = record the force on the blocked cells per step ("Drag and lift", further down:
+ *                 lbm_dforce_record).  Accepted only while lbm_dp_steps_done is 0, on a fresh context or right after
+ *                 lbm_dp_upload; otherwise LBM_ERR_STATE.  Turning it on allocates double[2][max_iters] on the device.
+ *                 Cells, av_vels, fields and Reynolds number are the same bits with it on or off.
  * lbm_dp_get_option("multistep") reads back the steps per launch in force (0 = one step per launch).
  */
 int lbm_dp_set_option(lbm_dp *d, const char *key, long value);
@@ -507,8 +511,8 @@ void lbm_dp_destroy(lbm_dp *d);
  * the golden files — a Reynolds-number sweep that has to land on fp64 results.  An ensemble holds N members on the current
  * device, each with its own run constants (lbm_dparams), obstacle map and state, and advances all of them with one launch
  * per several timesteps.  The members never interact, and every member computes, bit for bit, what a double-precision
- * context (lbm_dp_create) computes for the same inputs: cells, av_vels, fields and Reynolds number.  No options, row slabs
- * or ranks.  The reference has no counterpart: one grid, one in-order queue (d2q9-bgk.c:221-239); each entry point below
+ * context (lbm_dp_create) computes for the same inputs: cells, av_vels, fields and Reynolds number.  One option ("force":
+ * lbm_dforce_ens_set_option, further down), no row slabs or ranks.  The reference has no counterpart: one grid, one in-order queue (d2q9-bgk.c:221-239); each entry point below
  * stands beside the lbm_ens_ / lbm_dp_ one of the same name and says which call sites that one replaces.  Conventions as at
  * the top of this file; one host thread drives an ensemble; arrays carry the member index first: cells =
  * double[n][9][ny][nx], obstacles = int32[n][ny][nx], fields = double[n][ny][nx].
@@ -619,6 +623,68 @@ int lbm_dsteady_run(lbm_dens *e, int max_steps, int window, double rel_tol);
 /* Per member: steps applied since the last lbm_dens_upload, and whether it met the criterion of the last lbm_dsteady_run
  * since then (beside lbm_steady_steps).  steps_out = int[n], converged_out = int[n] (1 / 0); either may be NULL. */
 int lbm_dsteady_steps(lbm_dens *e, int *steps_out /*[n]*/, int *converged_out /*[n]*/);
+
+/*
+ * ---- Drag and lift: the momentum-exchange force on the blocked cells, in the double-precision families -----------------
+ *
+ * What a sweep over omega / accel or over obstacle maps is run for is the force the flow exerts on the solid cells: drag and
+ * lift, drag against Reynolds number at steady state, the lift signal of an unsteady wake.  The reference's timestep is a
+ * gather followed by full-way bounce-back (kernels.cl:69, 104-112, 187-197): a blocked cell keeps what streamed into it and
+ * hands it back reversed in the next step, so the momentum the solid cells take from the fluid in one step is a closed sum
+ * over the solid-fluid links of values the step kernels already hold.  The reference has no counterpart (it writes av_vels
+ * and the final state only, d2q9-bgk.c:241-263).
+ *
+ * Definition.  Speeds and their vectors c_k as at the top of this file (1 E, 2 N, 3 W, 4 S, 5 NE, 6 NW, 7 SW, 8 SE), opp(k)
+ * the opposite speed.  Let f be the state that a step streams: the state AFTER accelerate_flow for that step.  For every
+ * blocked cell o and every k = 1..8 whose neighbour x = o - c_k (periodic wrap in x and y) is fluid, the link term is
+ *     s = f_k(x) + f_opp(k)(o)        one addition, contraction off
+ *     F += c_k * s                    i.e. +-s into F_x and / or F_y, k in ascending order within a cell
+ * f_k(x) is what o gathers in that step, f_opp(k)(o) is o's own stored value, which x gathers in the same step.  Links
+ * between two blocked cells do not count.  A grid without blocked cells, or without fluid cells, gives exactly +0.0.
+ * F[t], t 0-based like av_vels, is this sum for step t, in lattice units per step, not divided by anything.
+ *
+ * Order of summation, fixed as for av_vels: a cell's eight terms in order of k; the cells of a 16-cell row segment in the
+ * segment tree; the segments of a step by the second reduction stage in its order.  Hence the record is bit-identical between
+ * the kernel forms ("multistep"), between launch splits, between runs, and between a double-precision context and a member
+ * of a double-precision ensemble on the same inputs; and the output stage (lbm_dforce, lbm_dforce_ens) returns, bit for bit,
+ * the record entry the next step writes.
+ *
+ * Names: lbm_dforce_* beside lbm_dsteady_*, on both double-precision handles.  The record is switched on by the option
+ * "force" (lbm_dp_set_option; lbm_dforce_ens_set_option for an ensemble) before the first step; the output stage needs no
+ * option.
+ *
+ * Out of scope: fp32 contexts and fp32 ensembles (ten kernel families, row slabs, ranks) have no force, and a steady run
+ * still stops a member on its av_vels record, not on its force.
+ */
+
+/* The force record of a double-precision context: fx_out, fy_out = double[lbm_dp_steps_done], either may be NULL (not both:
+ * LBM_ERR_ARG).  LBM_ERR_STATE if the option "force" is off.  Synchronises. */
+int lbm_dforce_record(lbm_dp *d, double *fx_out, double *fy_out);
+
+/* Output stage (beside lbm_dp_reynolds): F of the CURRENT state as the next step would stream it — accelerate_flow of row
+ * ny-2 is applied on the fly, the state is not modified.  Works whether or not "force" is on.  Either pointer may be NULL
+ * (not both: LBM_ERR_ARG).  Synchronises. */
+int lbm_dforce(lbm_dp *d, double *fx, double *fy);
+
+/*
+ * The options of a double-precision ensemble (beside lbm_dp_set_option / lbm_dp_get_option); one key:
+ *   "force"       0 (default) | 1 = record every member's force per step.  Accepted only while lbm_dens_steps_done is 0, on
+ *                 a fresh ensemble or right after lbm_dens_upload; otherwise LBM_ERR_STATE.  Turning it on allocates
+ *                 double[2][n][max_iters] on the device.  Cells, av_vels, fields and Reynolds numbers are the same bits with
+ *                 it on or off; a steady run (lbm_dsteady_run) records the force of every member while it is active.
+ * Unknown keys, NULL arguments: LBM_ERR_ARG.
+ */
+int lbm_dforce_ens_set_option(lbm_dens *e, const char *key, long value);
+int lbm_dforce_ens_get_option(const lbm_dens *e, const char *key, long *value);
+
+/* The force records of all members: fx_out, fy_out = double[n][lbm_dens_steps_done], either may be NULL (not both:
+ * LBM_ERR_ARG).  After a steady run exactly +0.0 at and beyond a member's own count, as av_vels.  LBM_ERR_STATE if the option
+ * "force" is off.  Synchronises. */
+int lbm_dforce_ens_record(lbm_dens *e, double *fx_out /*[n][steps]*/, double *fy_out /*[n][steps]*/);
+
+/* Output stage per member (beside lbm_dens_reynolds): lbm_dforce for every member, fx, fy = double[n], either may be NULL
+ * (not both).  After a steady run each member's own last state is read, from the grid array that holds it.  Synchronises. */
+int lbm_dforce_ens(lbm_dens *e, double *fx /*[n]*/, double *fy /*[n]*/);
 
 const char *lbm_last_error(void);
 const char *lbm_version(void);

@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "lbm_dens_create", "lbm_dens_upload", "lbm_dens_run", "lbm_dens_run_timed", "lbm_dens_sync", "lbm_dens_download",
     "lbm_dens_final_state", "lbm_dens_reynolds", "lbm_dens_steps_done", "lbm_dens_members", "lbm_dens_destroy",
     "lbm_dsteady_run", "lbm_dsteady_steps",
+    "lbm_dforce_record", "lbm_dforce", "lbm_dforce_ens_set_option", "lbm_dforce_ens_get_option", "lbm_dforce_ens_record",
+    "lbm_dforce_ens",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -147,6 +149,12 @@ def load_library():
     L.lbm_dens_destroy.restype = None
     L.lbm_dsteady_run.argtypes = [vp, ci, ci, ctypes.c_double]
     L.lbm_dsteady_steps.argtypes = [vp, vp, vp]
+    L.lbm_dforce_record.argtypes = [vp, vp, vp]
+    L.lbm_dforce.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    L.lbm_dforce_ens_set_option.argtypes = [vp, cp, ctypes.c_long]
+    L.lbm_dforce_ens_get_option.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_long)]
+    L.lbm_dforce_ens_record.argtypes = [vp, vp, vp]
+    L.lbm_dforce_ens.argtypes = [vp, vp, vp]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -537,6 +545,21 @@ class LBMDouble(_Handle):
         _check(self.lib.lbm_dp_get_option(self.ctx, key.encode(), ctypes.byref(v)), "lbm_dp_get_option(%s)" % key)
         return v.value
 
+    def force(self):
+        """(F_x, F_y): the momentum-exchange force on the blocked cells of the current state as the next step would stream
+        it (lbm_dforce), in lattice units per step.  The state is not modified."""
+        fx, fy = ctypes.c_double(), ctypes.c_double()
+        _check(self.lib.lbm_dforce(self.ctx, ctypes.byref(fx), ctypes.byref(fy)), "lbm_dforce")
+        return fx.value, fy.value
+
+    def force_record(self):
+        """(F_x float64[steps_done], F_y float64[steps_done]): the force of every step since the upload; needs
+        set_option("force", 1) before the first step."""
+        steps = self.steps_done
+        fx, fy = np.zeros(max(steps, 1), dtype=np.float64), np.zeros(max(steps, 1), dtype=np.float64)
+        _check(self.lib.lbm_dforce_record(self.ctx, fx.ctypes.data, fy.ctypes.data), "lbm_dforce_record")
+        return fx[:steps], fy[:steps]
+
     def write_values(self, final_state_path="final_state.dat", av_vels_path="av_vels.dat"):
         """The two output files in the reference's %.12E formats (d2q9-bgk.c:835,848-851), as check/check.py reads them."""
         fields = self.final_state()
@@ -667,3 +690,28 @@ class EnsembleDouble(_EnsembleOf):
         if not all(isinstance(p, DParams) for p in params):
             raise LBMError("EnsembleDouble takes DParams (make_dparams / read_inputs_double / sweep_dparams)")
         super().__init__(params, obstacles)
+
+    def set_option(self, key, value):
+        """one key, "force": 1 = record every member's force per step (before the first step)"""
+        _check(self.lib.lbm_dforce_ens_set_option(self.ens, key.encode(), int(value)), "lbm_dforce_ens_set_option(%s)" % key)
+
+    def get_option(self, key):
+        v = ctypes.c_long()
+        _check(self.lib.lbm_dforce_ens_get_option(self.ens, key.encode(), ctypes.byref(v)), "lbm_dforce_ens_get_option(%s)" % key)
+        return v.value
+
+    def force(self):
+        """(F_x float64[n], F_y float64[n]): every member's momentum-exchange force of its current state as the next step
+        would stream it (lbm_dforce_ens).  The states are not modified."""
+        fx, fy = np.zeros(self.n, dtype=np.float64), np.zeros(self.n, dtype=np.float64)
+        _check(self.lib.lbm_dforce_ens(self.ens, fx.ctypes.data, fy.ctypes.data), "lbm_dforce_ens")
+        return fx, fy
+
+    def force_record(self):
+        """(F_x float64[n, steps_done], F_y float64[n, steps_done]): every member's force of every step since the upload,
+        +0.0 at and beyond the count of a member that run_until() stopped earlier; needs set_option("force", 1) before the
+        first step."""
+        steps = self.steps_done
+        fx, fy = (np.zeros((self.n, max(steps, 1)), dtype=np.float64) for _ in range(2))
+        _check(self.lib.lbm_dforce_ens_record(self.ens, fx.ctypes.data, fy.ctypes.data), "lbm_dforce_ens_record")
+        return fx[:, :steps].copy(), fy[:, :steps].copy()

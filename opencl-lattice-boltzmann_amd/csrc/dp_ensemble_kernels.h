@@ -26,9 +26,10 @@ struct DensArgs {
   double *dst;
   const uint8_t *mask;       // member m: mask + m * nx * ny
   const DensMember *members;
-  double *seg;               // [T][members][ny][nseg]: the segment sums of each of the T steps
+  double *seg;               // [T][members][ny][nseg]: the segment sums of each of the T steps; FORCE:
+                             // [T][3][members][ny][nseg], |u|, F_x, F_y
   unsigned long long plane_stride, member_stride;   // row_stride = 9 * plane_stride
-  unsigned long long seg_step;                      // = members * ny * nseg
+  unsigned long long seg_step;                      // = members * ny * nseg; FORCE: three times that
   int nx, ny, nseg;
   int tiles_x;
   int T;                     // steps in this launch
@@ -57,7 +58,13 @@ struct DensArgs {
 // 1.95 against 2.40); that form is not instantiated.  0 scratch, 0 spills in all.
 // The tile body is a function of its own so that the gated kernel of a steady run (dp_steady_kernels.h) advances a member
 // with the very same instructions.
-template <int TX, int TY, int TMAX, int NT>
+//
+// FORCE (the option "force": the momentum-exchange force on the blocked cells, include/lbm.h): d2q9_dp_multi's pass, before
+// each step's collision loop.  Two more double-buffered LDS tiles beside tval would bring 16 x 16 at T <= 3 to 74 276 + 8 192 =
+// 82 468 B, one workgroup per CU (the 28.8 against 20.3 us of the table above), and single-buffered ones put a barrier and the
+// segment lanes' sums on every step's critical path (measured: 28.7 us, as bad).  The pass needs neither: F_x and F_y never
+// touch LDS, a segment's sixteen lanes add them in registers in the tree's order.  74 280 B in both instances.
+template <int TX, int TY, int TMAX, int NT, bool FORCE>
 __device__ __forceinline__ void dens_tile(const DensArgs a) {
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
   static_assert(TY * (TX / kDpSeg) <= NT, "one lane per segment of the tile");
@@ -85,8 +92,10 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
   // segment sums of step s (1-based) from tval[s & 1]
   auto store_segments = [&](int s) {
     constexpr int kSegs = TY * (TX / kDpSeg);
-    if (tid < kSegs) {
-      const int oy = tid / (TX / kDpSeg), sx = tid - oy * (TX / kDpSeg);
+    int lane = tid;
+    if constexpr (FORCE) asm volatile("" : "+v"(lane));  // as in the force pass below: nothing of this is kept across the collision loop
+    if (lane < kSegs) {
+      const int oy = lane / (TX / kDpSeg), sx = lane - oy * (TX / kDpSeg);
       const int gy = tile_y * TY + oy;
       const double *v = &tval[s & 1][oy][sx * kDpSeg];
       double p[8];
@@ -114,6 +123,48 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
 
   for (int s = 1; s <= T; s++) {
     if (s > 1) store_segments(s - 1);
+    if constexpr (FORCE) {
+      // The force of step s, from the state it streams (lds[in]): one lane per cell of the tile (every one, and its eight
+      // neighbours, is inside the region of every step; cells past the grid's edge and fluid cells count +0.0), sixteen
+      // neighbouring lanes = one row segment.  The segment tree of store_segments over those lanes in registers
+      // (dp_segment_tree16: every lane ends with the tree's bits), and the segment's first lane stores F_x
+      // and F_y one and two components (members * ny * nseg each) behind |u|.  No LDS, no barrier: the pass reads what the last barrier
+      // published and writes only global memory.  A pass of its own, from an opaque copy of the lane index, so that the
+      // collision loop below is the FORCE = false one and keeps nothing of this in registers.
+      static_assert(kDpSeg == 16 && (TX * TY) % 64 == 0 && NT % 64 == 0, "whole waves of whole segments take the butterfly");
+      int first = tid;
+      asm volatile("" : "+v"(first));
+      static_assert(TX * TY <= NT, "one lane per cell of the tile");
+      if (const int i = first; i < TX * TY) {
+        const int oy = i / TX, ox = i - oy * TX;
+        const int c = (oy + T) * kRX + ox + T;
+        const int gy = tile_y * TY + oy;
+        double fx = 0.0, fy = 0.0;
+        const bool counts = lmask[c] != 0 && tile_x * TX + ox < a.nx && gy < a.ny;
+        if (counts) {
+          const double(*f)[kRY * kRX] = lds[(s - 1) & 1];
+          const double g[9] = {0.0, f[1][c - 1], f[2][c - kRX], f[3][c + 1], f[4][c + kRX], f[5][c - kRX - 1],
+                               f[6][c - kRX + 1], f[7][c + kRX + 1], f[8][c + kRX - 1]};
+          double own[9];
+#pragma unroll
+          for (int k = 0; k < 9; k++) own[k] = f[k][c];
+          const uint8_t nb[9] = {0, lmask[c - 1], lmask[c - kRX], lmask[c + 1], lmask[c + kRX], lmask[c - kRX - 1],
+                                 lmask[c - kRX + 1], lmask[c + kRX + 1], lmask[c + kRX - 1]};
+          dp_force_cell(g, own, nb, fx, fy);
+        }
+        if (__ballot(counts) != 0ull) {   // a wave without a counting cell adds +0.0 to +0.0
+          fx = dp_segment_tree16(fx);
+          fy = dp_segment_tree16(fy);
+        }
+        const int seg = tile_x * (TX / kDpSeg) + ox / kDpSeg;
+        if ((ox & (kDpSeg - 1)) == 0 && gy < a.ny && seg < a.nseg) {
+          double *at = seg_out + (size_t)(s - 1) * a.seg_step + (size_t)gy * a.nseg + seg;
+          const unsigned comp = gridDim.y * (unsigned)(a.ny * a.nseg);   // members * ny * nseg < 2^31 (lbm_dens_create's bounds)
+          at[comp] = fx;
+          at[2 * (size_t)comp] = fy;
+        }
+      }
+    }
     const int in = (s - 1) & 1, out = s & 1;
     const int w = RX - 2 * s, h = RY - 2 * s;
     const bool accel_step = (s < T) || a.accel_next;
@@ -160,9 +211,10 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
   }
 }
 
-template <int TX, int TY, int TMAX, int NT = kMultiThreads>
-__global__ __launch_bounds__(NT) void d2q9_dp_ensemble(const DensArgs a) {
-  dens_tile<TX, TY, TMAX, NT>(a);
+// The FORCE instance states its two workgroups per CU (NT / 128 waves per SIMD) to the compiler: 60 VGPRs, 78 SGPRs, 0 scratch.
+template <int TX, int TY, int TMAX, int NT, bool FORCE>
+__global__ __launch_bounds__(NT, FORCE ? NT / 128 : 1) void d2q9_dp_ensemble(const DensArgs a) {
+  dens_tile<TX, TY, TMAX, NT, FORCE>(a);
 }
 
 // ---- second reduction stage with a member axis: dp_reduce's partition and order, fixed, no atomics -------------------

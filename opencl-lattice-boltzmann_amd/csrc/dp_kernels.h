@@ -14,6 +14,11 @@
 // (x = 16s .. 16s+15 of row y) in one fixed tree, ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)) with p_i the sum of cells 2i, 2i+1,
 // and dp_reduce adds the segments of a step in a fixed order.  So av_vels, too, are bit-identical between the forms and
 // between runs.
+//
+// With the option "force" the kernels also record the momentum-exchange force on the blocked cells (include/lbm.h, "Drag and
+// lift"): dp_force_cell per blocked cell, its two components summed per segment in the same tree and per step by the same
+// dp_reduce, so that record, too, is bit-identical between the forms.  Every step kernel has a `bool FORCE` template
+// parameter; the false instances are the kernels without it, instruction for instruction.
 #pragma once
 #include "d2q9_kernels.h"
 
@@ -73,11 +78,51 @@ __device__ __forceinline__ void dp_accelerate_cell(double (&f)[9], bool obstacle
   }
 }
 
+// Momentum-exchange force on one blocked cell o in the step that streams the state f (include/lbm.h): for k = 1..8 in
+// ascending order, if the neighbour x = o - c_k is fluid, s = f_k(x) + f_opp(k)(o) goes into F with the signs of c_k.
+//   g[k]   = f_k(o - c_k), what o gathers in that step        own[k] = o's own stored f_k
+//   nb[k]  = mask byte of o - c_k (non-zero: blocked, the link does not count)
+// One addition per link term, contraction off; a cell without a counted link gives +0.0, +0.0.
+__device__ __forceinline__ void dp_force_cell(const double (&g)[9], const double (&own)[9], const uint8_t (&nb)[9], double &fx,
+                                              double &fy) {
+#pragma clang fp contract(off)
+  fx = 0.0;
+  fy = 0.0;
+  if (nb[1] == 0) { const double s = g[1] + own[3]; fx += s; }            // E
+  if (nb[2] == 0) { const double s = g[2] + own[4]; fy += s; }            // N
+  if (nb[3] == 0) { const double s = g[3] + own[1]; fx -= s; }            // W
+  if (nb[4] == 0) { const double s = g[4] + own[2]; fy -= s; }            // S
+  if (nb[5] == 0) { const double s = g[5] + own[7]; fx += s; fy += s; }   // NE
+  if (nb[6] == 0) { const double s = g[6] + own[8]; fx -= s; fy += s; }   // NW
+  if (nb[7] == 0) { const double s = g[7] + own[5]; fx -= s; fy -= s; }   // SW
+  if (nb[8] == 0) { const double s = g[8] + own[6]; fx += s; fy -= s; }   // SE
+}
+
+// The segment tree over sixteen neighbouring lanes, one cell each (lane l of the segment holds cell l): pairs, then quads,
+// then the two halves of each half, then the two halves - ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)) with p_i the sum of cells 2i,
+// 2i+1 in every lane, because IEEE addition commutes.  DPP moves inside a row of sixteen lanes (quad_perm [1,0,3,2] and
+// [2,3,0,1], row_half_mirror, row_mirror: after each stage the lanes that trade hold their group's one value, so a mirror
+// serves as the exchange); all lanes of the wave active.
+template <int CTRL>
+__device__ __forceinline__ double dp_dpp_move(double v) {
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double dp_segment_tree16(double v) {
+#pragma clang fp contract(off)
+  v += dp_dpp_move<0xB1>(v);
+  v += dp_dpp_move<0x4E>(v);
+  v += dp_dpp_move<0x141>(v);
+  v += dp_dpp_move<0x140>(v);
+  return v;
+}
+
 struct DpStepArgs {
   const double *src;
   double *dst;
   const uint8_t *mask;       // [ny][nx]
-  double *seg;               // [ny][nseg] segment sums of this step
+  double *seg;               // [ny][nseg] segment sums of this step; FORCE: [3][ny][nseg], |u|, F_x, F_y
   unsigned long long plane_stride;
   int nx, ny;
   int lanes_per_row;         // ceil(nx / 2) rounded up to a multiple of 8: eight lanes = one 16-cell segment
@@ -87,13 +132,17 @@ struct DpStepArgs {
 
 // One timestep, lane = cells x0, x0+1 of one row.  x-1 / x+1 neighbours: aligned 16-B loads plus one scalar load per
 // streamed plane at the wrap column (an L1 hit).  A lane past the row's end (x0 >= nx) only joins the segment sum with 0.
+// FORCE: a lane with a blocked cell also loads that cell's own streamed planes and its eight neighbours' mask bytes, under a
+// branch, for dp_force_cell; fluid cells and lanes past the row's end count +0.0.
 // static, like the helper kernels below: two translation units include this header (lbm_dp.cpp, lbm_dens.cpp).
+template <bool FORCE>
 static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a) {
   const unsigned t = blockIdx.x * kBlock + threadIdx.x;
   const unsigned lpr = (unsigned)a.lanes_per_row;
   const int y = (int)(t / lpr);
   const int x0 = 2 * (int)(t - (unsigned)y * lpr);
   double tot = 0.0;
+  double tfx = 0.0, tfy = 0.0;
   const bool live = y < a.ny && x0 < a.nx;
   if (live) {
     const bool has_b = x0 + 1 < a.nx;
@@ -117,6 +166,24 @@ static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a
     const bool ob_a = m[0] != 0, ob_b = has_b && m[1] != 0;
     double ga[9] = {c0.x, w1, c2.x, has_b ? c3.y : e3, c4.x, w5, has_b ? c6.y : e6, has_b ? c7.y : e7, w8};
     double gb[9] = {c0.y, c1.x, c2.y, e3, c4.y, c5.x, e6, e7, c8.x};
+    if constexpr (FORCE) {
+      double fxa = 0.0, fya = 0.0, fxb = 0.0, fyb = 0.0;
+      // cell x of this row: its own planes 1..8 and the masks of (x -+ 1, y -+ 1), periodic (kernels.cl:91-102)
+      auto cell_force = [&](int x, const double (&g)[9], double &fx, double &fy) {
+        const int xl = (x == 0) ? a.nx - 1 : x - 1, xr = (x + 1 == a.nx) ? 0 : x + 1;
+        const uint8_t *mc = a.mask + (size_t)y * a.nx, *ms = a.mask + (size_t)ys * a.nx, *mn = a.mask + (size_t)yn * a.nx;
+        double own[9];
+        own[0] = 0.0;
+#pragma unroll
+        for (int k = 1; k < 9; k++) own[k] = rc[k * ps + x];
+        const uint8_t nb[9] = {0, mc[xl], ms[x], mc[xr], mn[x], ms[xl], ms[xr], mn[xr], mn[xl]};
+        dp_force_cell(g, own, nb, fx, fy);
+      };
+      if (ob_a) cell_force(x0, ga, fxa, fya);
+      if (ob_b) cell_force(x0 + 1, gb, fxb, fyb);
+      tfx = has_b ? fxa + fxb : fxa + 0.0;
+      tfy = has_b ? fya + fyb : fya + 0.0;
+    }
     double oa[9], ob[9];
     const double ta = dp_collide_cell(ga, ob_a, a.omega, oa);
     const double tb = dp_collide_cell(gb, ob_b, a.omega, ob);
@@ -144,14 +211,28 @@ static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a
   tot += __shfl_xor(tot, 2, 64);
   tot += __shfl_xor(tot, 4, 64);
   if (y < a.ny && ((t - (unsigned)y * lpr) & 7u) == 0) a.seg[(size_t)y * (lpr >> 3) + ((t - (unsigned)y * lpr) >> 3)] = tot;
+  if constexpr (FORCE) {
+    tfx += __shfl_xor(tfx, 1, 64);
+    tfx += __shfl_xor(tfx, 2, 64);
+    tfx += __shfl_xor(tfx, 4, 64);
+    tfy += __shfl_xor(tfy, 1, 64);
+    tfy += __shfl_xor(tfy, 2, 64);
+    tfy += __shfl_xor(tfy, 4, 64);
+    if (y < a.ny && ((t - (unsigned)y * lpr) & 7u) == 0) {
+      const size_t comp = (size_t)a.ny * (lpr >> 3);
+      const size_t at = (size_t)y * (lpr >> 3) + ((t - (unsigned)y * lpr) >> 3);
+      a.seg[comp + at] = tfx;
+      a.seg[2 * comp + at] = tfy;
+    }
+  }
 }
 
 struct DpMultiArgs {
   const double *src;
   double *dst;
   const uint8_t *mask;
-  double *seg;              // [T][ny][nseg]: the segment sums of each of the T steps
-  unsigned long long plane_stride, seg_step;   // seg_step = ny * nseg
+  double *seg;              // [T][ny][nseg]: the segment sums of each of the T steps; FORCE: [T][3][ny][nseg], |u|, F_x, F_y
+  unsigned long long plane_stride, seg_step;   // seg_step = ny * nseg; FORCE: 3 ny nseg
   int nx, ny, nseg;
   int tiles_x;
   int T;                    // steps in this launch
@@ -169,7 +250,10 @@ struct DpMultiArgs {
 //   16x8,  T <= 8 (113 KB)                               1.71 / 3.60 / 12.09  (wins only where every tile has a CU of its own)
 //   16x16, T <= 4 (85 KB)                                2.13 / 2.99 / 8.43
 // and one step per launch (d2q9_dp_step) 3.78 / 4.45 / 9.53, at 1024^2 23.8 against this kernel's 28.2: auto up to 300K cells.
-template <int TX, int TY, int TMAX>
+// FORCE: a blocked cell of the tile has both values of every link in lds[in] and the neighbours' bytes in lmask; a pass of one
+// lane per tile cell before each step's collision loop evaluates dp_force_cell there and adds F_x and F_y per segment in
+// registers, in the tree's order.  No LDS beyond the FORCE = false instance's.
+template <int TX, int TY, int TMAX, bool FORCE>
 __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs a) {
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
   constexpr int kRX = TX + 2 * TMAX, kRY = TY + 2 * TMAX;
@@ -218,6 +302,48 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
 
   for (int s = 1; s <= T; s++) {
     if (s > 1) store_segments(s - 1);
+    if constexpr (FORCE) {
+      // The force of step s, from the state it streams (lds[in]): one lane per cell of the tile (every one, and its eight
+      // neighbours, is inside the region of every step; cells past the grid's edge and fluid cells count +0.0), sixteen
+      // neighbouring lanes = one row segment.  The segment tree of store_segments over those lanes in registers
+      // (dp_segment_tree16: every lane ends with the tree's bits), and the segment's first lane stores F_x
+      // and F_y one and two components (ny * nseg each) behind |u|.  No LDS, no barrier: the pass reads what the last barrier
+      // published and writes only global memory.  A pass of its own, from an opaque copy of the lane index, so that the
+      // collision loop below is the FORCE = false one and keeps nothing of this in registers.
+      static_assert(kDpSeg == 16 && (TX * TY) % 64 == 0 && kMultiThreads % 64 == 0, "whole waves of whole segments take the butterfly");
+      int first = tid;
+      asm volatile("" : "+v"(first));
+      static_assert(TX * TY <= kMultiThreads, "one lane per cell of the tile");
+      if (const int i = first; i < TX * TY) {
+        const int oy = i / TX, ox = i - oy * TX;
+        const int c = (oy + T) * kRX + ox + T;
+        const int gy = tile_y * TY + oy;
+        double fx = 0.0, fy = 0.0;
+        const bool counts = lmask[c] != 0 && tile_x * TX + ox < a.nx && gy < a.ny;
+        if (counts) {
+          const double(*f)[kRY * kRX] = lds[(s - 1) & 1];
+          const double g[9] = {0.0, f[1][c - 1], f[2][c - kRX], f[3][c + 1], f[4][c + kRX], f[5][c - kRX - 1],
+                               f[6][c - kRX + 1], f[7][c + kRX + 1], f[8][c + kRX - 1]};
+          double own[9];
+#pragma unroll
+          for (int k = 0; k < 9; k++) own[k] = f[k][c];
+          const uint8_t nb[9] = {0, lmask[c - 1], lmask[c - kRX], lmask[c + 1], lmask[c + kRX], lmask[c - kRX - 1],
+                                 lmask[c - kRX + 1], lmask[c + kRX + 1], lmask[c + kRX - 1]};
+          dp_force_cell(g, own, nb, fx, fy);
+        }
+        if (__ballot(counts) != 0ull) {   // a wave without a counting cell adds +0.0 to +0.0
+          fx = dp_segment_tree16(fx);
+          fy = dp_segment_tree16(fy);
+        }
+        const int seg = tile_x * (TX / kDpSeg) + ox / kDpSeg;
+        if ((ox & (kDpSeg - 1)) == 0 && gy < a.ny && seg < a.nseg) {
+          double *at = a.seg + (size_t)(s - 1) * a.seg_step + (size_t)gy * a.nseg + seg;
+          const size_t comp = (size_t)a.ny * a.nseg;
+          at[comp] = fx;
+          at[2 * comp] = fy;
+        }
+      }
+    }
     const int in = (s - 1) & 1, out = s & 1;
     const int w = RX - 2 * s, h = RY - 2 * s;
     const bool accel_step = (s < T) || a.accel_next;
@@ -367,6 +493,89 @@ static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *c
     double t = wsum[0];
     for (int i = 1; i < kBlock / 64; i++) t += wsum[i];
     partials[blockIdx.x] = t;
+  }
+}
+
+// output stage: the force of the CURRENT state as the next step would stream it (include/lbm.h: lbm_dforce,
+// lbm_dforce_ens).  grid = (blocks of d2q9_dp_step's lanes, members): member m's state lies m * member_stride into cells (or
+// cells_alt where par[m] is set: dens_pack_planes), its mask m * nx * ny into mask, its segment sums m * ny * nseg into
+// seg_x and seg_y.  A blocked cell gathers from each fluid neighbour that neighbour's value after accelerate_flow: on row
+// ny - 2 the neighbour's nine values go through dp_accelerate_cell in registers, the state is not written.  The per-cell
+// function, the segment tree and, behind it, the reduction are the step kernels', so the value equals the record entry
+// the next step writes, bit for bit.  aw: NULL (aw1, aw2 are the arguments), or member m's aw1, aw2 at aw[m * aw_stride],
+// aw[m * aw_stride + 1].
+struct DpForceArgs {
+  const double *cells, *cells_alt;
+  const int *par;
+  const uint8_t *mask;
+  double *seg_x, *seg_y;     // [members][ny][nseg]
+  const double *aw;
+  unsigned long long plane_stride, member_stride, aw_stride;
+  int nx, ny;
+  int lanes_per_row;         // as DpStepArgs
+  double aw1, aw2;
+};
+
+static __global__ __launch_bounds__(kBlock) void dp_force_state(const DpForceArgs a) {
+  const unsigned t = blockIdx.x * kBlock + threadIdx.x;
+  const unsigned lpr = (unsigned)a.lanes_per_row;
+  const int member = blockIdx.y;
+  const int y = (int)(t / lpr);
+  const int x0 = 2 * (int)(t - (unsigned)y * lpr);
+  double tfx = 0.0, tfy = 0.0;
+  if (y < a.ny && x0 < a.nx) {
+    const bool has_b = x0 + 1 < a.nx;
+    const size_t ps = a.plane_stride, rs = 9 * ps;
+    const double *cells = ((a.par && a.par[member]) ? a.cells_alt : a.cells) + (size_t)member * a.member_stride;
+    const uint8_t *mask = a.mask + (size_t)member * ((size_t)a.nx * a.ny);
+    const double aw1 = a.aw ? a.aw[(size_t)member * a.aw_stride] : a.aw1;
+    const double aw2 = a.aw ? a.aw[(size_t)member * a.aw_stride + 1] : a.aw2;
+    const int ys = (y == 0) ? a.ny - 1 : y - 1, yn = (y + 1 == a.ny) ? 0 : y + 1;  // kernels.cl:91-93
+    auto cell_force = [&](int x, double &fx, double &fy) {
+      const int xl = (x == 0) ? a.nx - 1 : x - 1, xr = (x + 1 == a.nx) ? 0 : x + 1;   // kernels.cl:99-102
+      // the neighbour o - c_k of speed k (the cell o gathers f_k from)
+      const int qx[9] = {x, xl, x, xr, x, xl, xr, xr, xl};
+      const int qy[9] = {y, y, ys, y, yn, ys, ys, yn, yn};
+      double g[9], own[9];
+      uint8_t nb[9];
+      const double *o = cells + (size_t)y * rs + x;
+#pragma unroll
+      for (int k = 0; k < 9; k++) own[k] = o[k * ps];
+      g[0] = 0.0;
+      nb[0] = 0;
+#pragma unroll
+      for (int k = 1; k < 9; k++) {
+        nb[k] = mask[(size_t)qy[k] * a.nx + qx[k]];
+        g[k] = 0.0;
+        if (nb[k] == 0) {
+          double f[9];
+          const double *q = cells + (size_t)qy[k] * rs + qx[k];
+#pragma unroll
+          for (int j = 0; j < 9; j++) f[j] = q[j * ps];
+          if (qy[k] == a.ny - 2) dp_accelerate_cell(f, false, aw1, aw2);
+          g[k] = f[k];
+        }
+      }
+      dp_force_cell(g, own, nb, fx, fy);
+    };
+    double fxa = 0.0, fya = 0.0, fxb = 0.0, fyb = 0.0;
+    const uint8_t *m = mask + (size_t)y * a.nx + x0;
+    if (m[0] != 0) cell_force(x0, fxa, fya);
+    if (has_b && m[1] != 0) cell_force(x0 + 1, fxb, fyb);
+    tfx = has_b ? fxa + fxb : fxa + 0.0;
+    tfy = has_b ? fya + fyb : fya + 0.0;
+  }
+  // d2q9_dp_step's tree
+  tfx += __shfl_xor(tfx, 1, 64);
+  tfx += __shfl_xor(tfx, 2, 64);
+  tfx += __shfl_xor(tfx, 4, 64);
+  tfy += __shfl_xor(tfy, 1, 64);
+  tfy += __shfl_xor(tfy, 2, 64);
+  tfy += __shfl_xor(tfy, 4, 64);
+  if (y < a.ny && ((t - (unsigned)y * lpr) & 7u) == 0) {
+    const size_t at = (size_t)member * ((size_t)a.ny * (lpr >> 3)) + (size_t)y * (lpr >> 3) + ((t - (unsigned)y * lpr) >> 3);
+    a.seg_x[at] = tfx;
+    a.seg_y[at] = tfy;
   }
 }
 

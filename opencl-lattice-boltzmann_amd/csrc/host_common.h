@@ -31,6 +31,18 @@ inline bool positive_finite(double v) { return std::isfinite(v) && v > 0.0; }
 // `rem` steps in as few launches of at most T steps as possible, of equal depth: the depth of the next one (20 at T = 8: 7 + 7 + 6)
 inline int equal_depth(int rem, int T) { return (int)div_up(rem, div_up(rem, T)); }
 
+// Steps a ring of per-step segment sums holds: as many as fit `ring_bytes` at `step_bytes` a step, at least `least` (the
+// most steps one launch advances), at most `most`
+inline int ring_steps(size_t step_bytes, int least, int most, size_t ring_bytes) {
+  return (int)std::max<size_t>((size_t)least, std::min<size_t>((size_t)most, ring_bytes / step_bytes));
+}
+
+// hipMalloc for callers that undo something on failure instead of returning at once
+inline int hip_alloc(void **ptr, size_t bytes) {
+  HIP_TRY(hipMalloc(ptr, bytes));
+  return LBM_OK;
+}
+
 // ---- the device, its stream and the two events of a timed run ----
 struct Queue {
   int dev = 0;

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -62,6 +63,9 @@ struct lbm_dens {
   double *red = nullptr;           // [ring][n][red_blocks]: first reduction stage
   double *av_sum = nullptr;        // [n][max_iters]
   double *fin_partials = nullptr;  // [n][fin_blocks]
+  double *force_rec = nullptr;     // option "force": [2][n][max_iters], F_x then F_y per member and step
+  double *force_now = nullptr;     // [2][n]: lbm_dforce_ens's F_x, F_y (allocated by the first call)
+  bool force = false;              // option "force": the kernels' FORCE instances, three values per segment
   int nseg = 1, red_blocks = 1, fin_blocks = 1;
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
@@ -88,12 +92,31 @@ void free_dens(lbm_dens *e) {
   if (e->red) (void)hipFree(e->red);
   if (e->av_sum) (void)hipFree(e->av_sum);
   if (e->fin_partials) (void)hipFree(e->fin_partials);
+  if (e->force_rec) (void)hipFree(e->force_rec);
+  if (e->force_now) (void)hipFree(e->force_now);
   if (e->steady_words) (void)hipFree(e->steady_words);
   if (e->steady_inv) (void)hipFree(e->steady_inv);
   if (e->steady_count_host) (void)hipHostFree(e->steady_count_host);
   if (e->stage) (void)hipFree(e->stage);
   queue_destroy(e->q);
   delete e;
+}
+
+// values per segment and step: |u|, and F_x, F_y with the option "force"
+int seg_values(const lbm_dens *e) { return e->force ? 3 : 1; }
+
+// The ring of per-step segment sums of all members and the first reduction stage's partials, (re)allocated for the values
+// a segment carries (alloc_ring of lbm_dp.cpp).  How many steps lie between two reductions decides no sum.
+int alloc_ring(lbm_dens *e) {
+  const size_t all_step = (size_t)e->n * e->ny * e->nseg * seg_values(e);
+  e->ring = ring_steps(all_step * sizeof(double), kDensTMax, kDensRingMax, kDensRingBytes);
+  if (e->seg) HIP_TRY(hipFree(e->seg));
+  e->seg = nullptr;
+  if (e->red) HIP_TRY(hipFree(e->red));
+  e->red = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->seg), (size_t)e->ring * all_step * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->red), (size_t)e->ring * e->n * e->red_blocks * sizeof(double)));
+  return LBM_OK;
 }
 
 int build_dens(lbm_dens *e, const int32_t *obstacles) {
@@ -110,7 +133,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
   e->red_blocks = (int)std::min(512L, div_up((long)per_step, kDensSegsPerBlock));
   e->fin_blocks = (int)std::max(1L, std::min(div_up((long)cells_per, kBlock), 2048L));
   const size_t all_step = (size_t)n * per_step;
-  e->ring = (int)std::max<size_t>(kDensTMax, std::min<size_t>(kDensRingMax, kDensRingBytes / (all_step * sizeof(double))));
+  e->ring = ring_steps(all_step * sizeof(double), kDensTMax, kDensRingMax, kDensRingBytes);
 
   // what the ensemble needs against what the device has free: refuse here rather than fail half-way through
   const size_t cells_bytes = ((size_t)n * e->member_stride + 32) * sizeof(double);
@@ -130,8 +153,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
   }
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->mask), (size_t)n * cells_per + 64));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), (size_t)n * sizeof(DensMember)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->seg), (size_t)e->ring * all_step * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->red), (size_t)e->ring * n * e->red_blocks * sizeof(double)));
+  if (int rc = alloc_ring(e)) return rc;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->av_sum), (size_t)n * e->max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->fin_partials), (size_t)n * e->fin_blocks * sizeof(double)));
   // the members' byte masks from the caller's int32[n][ny][nx]
@@ -144,16 +166,46 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
 }
 
 // active: NULL for an ordinary run, the members' words for a leg of a steady run
-void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
+template <bool FORCE>
+void launch_dens_form(const lbm_dens *e, const DensArgs &a, const int *active) {
   const dim3 grid(e->tiles, e->n), block(kDensThreads);
-  if (!active) hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads>), grid, block, 0, e->q.st, a);
-  else hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads>), grid, block, 0, e->q.st, a, active);
+  if (!active) hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE>), grid, block, 0, e->q.st, a);
+  else hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE>), grid, block, 0, e->q.st, a, active);
+}
+
+void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
+  if (e->force) launch_dens_form<true>(e, a, active);
+  else launch_dens_form<false>(e, a, active);
+}
+
+// Second reduction stage, all members in one launch per stage: the per_step segment sums of each member (per_step apart) and
+// each of `steps` steps (`in_stride` apart from `in`) into out[m * out_member + r], in one stage or, where a step has many
+// segments, in two.  active: as launch_dens.
+int reduce_steps(lbm_dens *e, const double *in, size_t in_stride, int steps, double *out, unsigned long long out_member,
+                 const int *active) {
+  const size_t per_step = (size_t)e->ny * e->nseg;
+  if (e->red_blocks > 1) {
+    hipLaunchKernelGGL(dens_reduce, dim3(e->red_blocks, steps, e->n), dim3(kBlock), 0, e->q.st, in, (unsigned long long)in_stride,
+                       (unsigned long long)per_step, (long)per_step, e->red, (unsigned long long)e->n * e->red_blocks,
+                       (unsigned long long)e->red_blocks, active);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(dens_reduce, dim3(1, steps, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->red,
+                       (unsigned long long)e->n * e->red_blocks, (unsigned long long)e->red_blocks, (long)e->red_blocks, out, 1ull,
+                       out_member, active);
+  } else {
+    hipLaunchKernelGGL(dens_reduce, dim3(1, steps, e->n), dim3(kBlock), 0, e->q.st, in, (unsigned long long)in_stride,
+                       (unsigned long long)per_step, (long)per_step, out, 1ull, out_member, active);
+  }
+  HIP_TRY(hipGetLastError());
+  return LBM_OK;
 }
 
 // nsteps steps from step count `first` on, enqueued: the prologue, the launches, the reductions into the record.  Flips
 // e->cur per launch; the caller counts the steps.  active: as launch_dens.
 int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   const size_t per_step = (size_t)e->ny * e->nseg, all_step = (size_t)e->n * per_step;
+  const int nval = seg_values(e);
+  const size_t slot = all_step * nval;   // one step in the ring: [nval][n][ny][nseg]
   // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
   // into the previous launch's write of row ny-2
   hipLaunchKernelGGL(dens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
@@ -161,24 +213,15 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   HIP_TRY(hipGetLastError());
 
   int batch_first = first;
-  // second reduction stage over the buffered steps (kernels.cl:234-290 counterpart), all members in one launch per stage
+  // second reduction stage over the buffered steps: |u| into av_sum and, with "force", F_x and F_y into their records,
+  // the same launches on each value's segments
   auto flush = [&]() -> int {
     if (e->ring_fill == 0) return LBM_OK;
     const unsigned long long record = (unsigned long long)e->max_iters;
-    if (e->red_blocks > 1) {
-      hipLaunchKernelGGL(dens_reduce, dim3(e->red_blocks, e->ring_fill, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->seg,
-                         (unsigned long long)all_step, (unsigned long long)per_step, (long)per_step, e->red,
-                         (unsigned long long)e->n * e->red_blocks, (unsigned long long)e->red_blocks, active);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(dens_reduce, dim3(1, e->ring_fill, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->red,
-                         (unsigned long long)e->n * e->red_blocks, (unsigned long long)e->red_blocks, (long)e->red_blocks,
-                         e->av_sum + batch_first, 1ull, record, active);
-    } else {
-      hipLaunchKernelGGL(dens_reduce, dim3(1, e->ring_fill, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->seg,
-                         (unsigned long long)all_step, (unsigned long long)per_step, (long)per_step, e->av_sum + batch_first, 1ull,
-                         record, active);
+    for (int v = 0; v < nval; v++) {
+      double *out = (v == 0 ? e->av_sum : e->force_rec + (size_t)(v - 1) * e->n * e->max_iters) + batch_first;
+      if (int rc = reduce_steps(e, e->seg + (size_t)v * all_step, slot, e->ring_fill, out, record, active)) return rc;
     }
-    HIP_TRY(hipGetLastError());
     batch_first += e->ring_fill;
     e->ring_fill = 0;
     return LBM_OK;
@@ -195,10 +238,10 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
     a.dst = e->cells[e->cur ^ 1];
     a.mask = e->mask;
     a.members = e->members;
-    a.seg = e->seg + (size_t)e->ring_fill * all_step;
+    a.seg = e->seg + (size_t)e->ring_fill * slot;
     a.plane_stride = e->plane_stride;
     a.member_stride = e->member_stride;
-    a.seg_step = all_step;
+    a.seg_step = slot;
     a.nx = e->nx;
     a.ny = e->ny;
     a.nseg = e->nseg;
@@ -484,6 +527,98 @@ int lbm_dsteady_run(lbm_dens *e, int max_steps, int window, double rel_tol) {
 int lbm_dsteady_steps(lbm_dens *e, int *steps_out, int *converged_out) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   steady_steps_out(e->n, e->ragged, e->steps_done, e->m_steps, e->m_conv, steps_out, converged_out);
+  return LBM_OK;
+}
+
+int lbm_dforce_ens_set_option(lbm_dens *e, const char *key, long value) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!key) return lbm_fail(LBM_ERR_ARG, "key is NULL");
+  if (strcmp(key, "force")) return lbm_fail(LBM_ERR_ARG, "unknown option '%s' (a double-precision ensemble has \"force\")", key);
+  if (value != 0 && value != 1) return lbm_fail(LBM_ERR_ARG, "force must be 0 or 1 (got %ld)", value);
+  if (e->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "\"force\" is set before the first step (%d done): the record holds every step since "
+                    "lbm_dens_upload", e->steps_done);
+  if ((value != 0) == e->force) return LBM_OK;
+  if (int rc = queue_sync(e->q)) return rc;
+  const bool before = e->force;
+  e->force = value != 0;
+  int rc = alloc_ring(e);
+  if (rc == LBM_OK && e->force && !e->force_rec)
+    rc = hip_alloc(reinterpret_cast<void **>(&e->force_rec), 2 * (size_t)e->n * e->max_iters * sizeof(double));
+  if (rc != LBM_OK) {
+    // back to a ring that fits the option as it was
+    const std::string keep = lbm_last_error();
+    e->force = before;
+    if (alloc_ring(e) != LBM_OK) e->failed = true;
+    return fail_again(rc, keep);
+  }
+  return LBM_OK;
+}
+
+int lbm_dforce_ens_get_option(const lbm_dens *e, const char *key, long *value) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!key) return lbm_fail(LBM_ERR_ARG, "key is NULL");
+  if (!value) return lbm_fail(LBM_ERR_ARG, "value is NULL");
+  if (strcmp(key, "force")) return lbm_fail(LBM_ERR_ARG, "unknown option '%s' (a double-precision ensemble has \"force\")", key);
+  *value = e->force ? 1 : 0;
+  return LBM_OK;
+}
+
+int lbm_dforce_ens_record(lbm_dens *e, double *fx_out, double *fy_out) {
+  // argument errors before a device is touched
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!fx_out && !fy_out) return lbm_fail(LBM_ERR_ARG, "fx_out and fy_out are both NULL");
+  if (!e->force)
+    return lbm_fail(LBM_ERR_STATE, "no force record: option \"force\" is off (lbm_dforce_ens_set_option before the first step)");
+  if (int rc = queue_sync(e->q)) return rc;
+  const int T = e->steps_done;
+  double *outs[2] = {fx_out, fy_out};
+  for (int c = 0; c < 2; c++) {
+    if (!outs[c] || T == 0) continue;
+    HIP_TRY(hipMemcpy2D(outs[c], (size_t)T * sizeof(double), e->force_rec + (size_t)c * e->n * e->max_iters,
+                        (size_t)e->max_iters * sizeof(double), (size_t)T * sizeof(double), e->n, hipMemcpyDeviceToHost));
+    // a member that stopped earlier has no record from its own count on (lbm_dens_download's av_vels)
+    if (e->ragged)
+      for (int m = 0; m < e->n; m++)
+        for (int t = e->m_steps[m]; t < T; t++) outs[c][(size_t)m * T + t] = 0.0;
+  }
+  return LBM_OK;
+}
+
+int lbm_dforce_ens(lbm_dens *e, double *fx, double *fy) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!fx && !fy) return lbm_fail(LBM_ERR_ARG, "fx and fy are both NULL");
+  if (int rc = queue_sync(e->q)) return rc;
+  const size_t n = (size_t)e->n;
+  if (!e->force_now) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->force_now), 2 * n * sizeof(double)));
+  // between runs the ring is empty (every run ends with its reduction): its first two blocks of n * ny * nseg take the
+  // segment sums of F_x and F_y, which then go the way a step's go.  Each member from the array that holds it.
+  const size_t all_step = n * e->ny * e->nseg;
+  DpForceArgs a{};
+  a.cells = e->cells[e->ragged ? 0 : e->cur];
+  a.cells_alt = e->cells[1];
+  a.par = member_parity(e);
+  a.mask = e->mask;
+  a.seg_x = e->seg;
+  a.seg_y = e->seg + all_step;
+  a.aw = &e->members[0].aw1;                 // a device address: aw1, aw2 lie side by side in a DensMember
+  a.aw_stride = sizeof(DensMember) / sizeof(double);
+  a.plane_stride = e->plane_stride;
+  a.member_stride = e->member_stride;
+  a.nx = e->nx;
+  a.ny = e->ny;
+  a.lanes_per_row = e->nseg * 8;
+  hipLaunchKernelGGL(dp_force_state, dim3((unsigned)div_up((long)a.lanes_per_row * e->ny, kBlock), e->n), dim3(kBlock), 0, e->q.st, a);
+  HIP_TRY(hipGetLastError());
+  for (int c = 0; c < 2; c++)
+    if (int rc = reduce_steps(e, e->seg + (size_t)c * all_step, all_step, 1, e->force_now + (size_t)c * n, 1ull, nullptr)) return rc;
+  std::vector<double> f(2 * n);
+  HIP_TRY(hipMemcpyAsync(f.data(), e->force_now, f.size() * sizeof(double), hipMemcpyDeviceToHost, e->q.st));
+  HIP_TRY(hipStreamSynchronize(e->q.st));
+  for (size_t m = 0; m < n; m++) {
+    if (fx) fx[m] = f[m];
+    if (fy) fy[m] = f[n + m];
+  }
   return LBM_OK;
 }
 

@@ -48,10 +48,13 @@ struct lbm_dp {
   double *red = nullptr;          // [ring][red_blocks]: first reduction stage
   double *av_sum = nullptr;       // [max_iters]
   double *fin_partials = nullptr; // [fin_blocks]
+  double *force_rec = nullptr;    // option "force": [2][max_iters], F_x then F_y per step
+  double *force_now = nullptr;    // [2]: lbm_dforce's F_x, F_y (allocated by the first call)
   int lanes_per_row = 8, nseg = 1, red_blocks = 1, fin_blocks = 1;
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
   int multistep = -1;             // option "multistep": -1 auto, 0 one step per launch, 1..8
+  bool force = false;             // option "force": the kernels' FORCE instances, three values per segment
   int cur = 0, steps_done = 0;
   bool failed = false;
 };
@@ -73,8 +76,27 @@ void free_dp(lbm_dp *d) {
   if (d->red) (void)hipFree(d->red);
   if (d->av_sum) (void)hipFree(d->av_sum);
   if (d->fin_partials) (void)hipFree(d->fin_partials);
+  if (d->force_rec) (void)hipFree(d->force_rec);
+  if (d->force_now) (void)hipFree(d->force_now);
   queue_destroy(d->q);
   delete d;
+}
+
+// values per segment and step: |u|, and F_x, F_y with the option "force"
+int seg_values(const lbm_dp *d) { return d->force ? 3 : 1; }
+
+// The ring of per-step segment sums and the first reduction stage's partials, (re)allocated for the values a segment
+// carries: the ring holds as many steps as fit kDpRingBytes.  How many steps lie between two reductions decides no sum.
+int alloc_ring(lbm_dp *d) {
+  const size_t per_step = (size_t)d->p.ny * d->nseg * seg_values(d);
+  d->ring = ring_steps(per_step * sizeof(double), kMultiMaxT, kDpRingMax, kDpRingBytes);
+  if (d->seg) HIP_TRY(hipFree(d->seg));
+  d->seg = nullptr;
+  if (d->red) HIP_TRY(hipFree(d->red));
+  d->red = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->seg), (size_t)d->ring * per_step * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->red), (size_t)d->ring * d->red_blocks * sizeof(double)));
+  return LBM_OK;
 }
 
 int build_dp(lbm_dp *d, const int32_t *obstacles) {
@@ -88,7 +110,7 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
   d->tiles = d->tiles_x * (int)div_up(ny, kDpTY);
   const size_t per_step = (size_t)ny * d->nseg;
   d->red_blocks = (int)std::min(512L, div_up((long)per_step, kDpSegsPerBlock));
-  d->ring = (int)std::max<size_t>(kMultiMaxT, std::min<size_t>(kDpRingMax, kDpRingBytes / (per_step * sizeof(double))));
+  d->ring = ring_steps(per_step * sizeof(double), kMultiMaxT, kDpRingMax, kDpRingBytes);
   d->fin_blocks = (int)std::max(1L, std::min(div_up((long)cells, kBlock), 2048L));
   if ((long)d->lanes_per_row * ny > 0x7fffffffL)
     return lbm_fail(LBM_ERR_ARG, "a grid of %dx%d cells is beyond the 2^31 lanes of one launch", nx, ny);
@@ -109,11 +131,28 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
     HIP_TRY(hipMemset(d->cells[i], 0, grid_bytes));
   }
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->mask), cells + 64));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->seg), (size_t)d->ring * per_step * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->red), (size_t)d->ring * d->red_blocks * sizeof(double)));
+  if (int rc = alloc_ring(d)) return rc;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->av_sum), (size_t)d->p.max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->fin_partials), (size_t)d->fin_blocks * sizeof(double)));
   return upload_mask(d->mask, obstacles, cells);
+}
+
+// Second reduction stage (kernels.cl:234-290 counterpart): the per_step segment sums of each of `steps` steps, `in_stride`
+// apart from `in`, into out[r * out_stride], in one stage or, where a step has many segments, in two
+int reduce_steps(lbm_dp *d, const double *in, size_t in_stride, int steps, double *out, unsigned long long out_stride) {
+  const size_t per_step = (size_t)d->p.ny * d->nseg;
+  if (d->red_blocks > 1) {
+    hipLaunchKernelGGL(dp_reduce, dim3(d->red_blocks, steps), dim3(kBlock), 0, d->q.st, in, (unsigned long long)in_stride,
+                       (long)per_step, d->red, (unsigned long long)d->red_blocks);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(dp_reduce, dim3(1, steps), dim3(kBlock), 0, d->q.st, (const double *)d->red,
+                       (unsigned long long)d->red_blocks, (long)d->red_blocks, out, out_stride);
+  } else {
+    hipLaunchKernelGGL(dp_reduce, dim3(1, steps), dim3(kBlock), 0, d->q.st, in, (unsigned long long)in_stride, (long)per_step, out,
+                       out_stride);
+  }
+  HIP_TRY(hipGetLastError());
+  return LBM_OK;
 }
 
 int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
@@ -127,6 +166,8 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   const double aw1 = d->p.density * d->p.accel / 9.0;   // kernels.cl:14-15
   const double aw2 = d->p.density * d->p.accel / 36.0;
   const size_t per_step = (size_t)ny * d->nseg;
+  const int nval = seg_values(d);
+  const size_t slot = per_step * nval;   // one step in the ring: [nval][ny][nseg]
   const int T = multistep_effective(d);
   if (int rc = timed_begin(d->q, timed)) return rc;
   // prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53); later steps get theirs fused into
@@ -136,20 +177,14 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   HIP_TRY(hipGetLastError());
 
   int batch_first = d->steps_done;
-  // second reduction stage over the buffered steps (kernels.cl:234-290 counterpart)
+  // second reduction stage over the buffered steps
   auto flush = [&]() -> int {
     if (d->ring_fill == 0) return LBM_OK;
-    if (d->red_blocks > 1) {
-      hipLaunchKernelGGL(dp_reduce, dim3(d->red_blocks, d->ring_fill), dim3(kBlock), 0, d->q.st, (const double *)d->seg,
-                         (unsigned long long)per_step, (long)per_step, d->red, (unsigned long long)d->red_blocks);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(dp_reduce, dim3(1, d->ring_fill), dim3(kBlock), 0, d->q.st, (const double *)d->red,
-                         (unsigned long long)d->red_blocks, (long)d->red_blocks, d->av_sum + batch_first, 1ull);
-    } else {
-      hipLaunchKernelGGL(dp_reduce, dim3(1, d->ring_fill), dim3(kBlock), 0, d->q.st, (const double *)d->seg,
-                         (unsigned long long)per_step, (long)per_step, d->av_sum + batch_first, 1ull);
+    // |u| into av_sum and, with "force", F_x and F_y into their records: the same launches on each value's segments
+    for (int v = 0; v < nval; v++) {
+      double *record = (v == 0 ? d->av_sum : d->force_rec + (size_t)(v - 1) * d->p.max_iters) + batch_first;
+      if (int rc = reduce_steps(d, d->seg + (size_t)v * per_step, slot, d->ring_fill, record, 1ull)) return rc;
     }
-    HIP_TRY(hipGetLastError());
     batch_first += d->ring_fill;
     d->ring_fill = 0;
     return LBM_OK;
@@ -162,7 +197,7 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
     if (d->ring_fill + adv > d->ring)
       if (int rc = flush()) return rc;
     const bool accel_next = i + adv < nsteps;
-    double *seg = d->seg + (size_t)d->ring_fill * per_step;
+    double *seg = d->seg + (size_t)d->ring_fill * slot;
     if (T > 0) {
       DpMultiArgs a{};
       a.src = d->cells[d->cur];
@@ -170,7 +205,7 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.mask = d->mask;
       a.seg = seg;
       a.plane_stride = d->plane_stride;
-      a.seg_step = per_step;
+      a.seg_step = slot;
       a.nx = nx;
       a.ny = ny;
       a.nseg = d->nseg;
@@ -180,7 +215,8 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.omega = d->p.omega;
       a.aw1 = aw1;
       a.aw2 = aw2;
-      hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
+      if (d->force) hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, true>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
+      else hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, false>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
     } else {
       DpStepArgs a{};
       a.src = d->cells[d->cur];
@@ -195,7 +231,9 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.omega = d->p.omega;
       a.aw1 = aw1;
       a.aw2 = aw2;
-      hipLaunchKernelGGL(d2q9_dp_step, dim3((unsigned)div_up((long)d->lanes_per_row * ny, kBlock)), dim3(kBlock), 0, d->q.st, a);
+      const dim3 grid((unsigned)div_up((long)d->lanes_per_row * ny, kBlock));
+      if (d->force) hipLaunchKernelGGL(d2q9_dp_step<true>, grid, dim3(kBlock), 0, d->q.st, a);
+      else hipLaunchKernelGGL(d2q9_dp_step<false>, grid, dim3(kBlock), 0, d->q.st, a);
     }
     HIP_TRY(hipGetLastError());
     d->cur ^= 1;
@@ -360,7 +398,28 @@ int lbm_dp_set_option(lbm_dp *d, const char *key, long value) {
     d->multistep = (int)value;
     return LBM_OK;
   }
-  return lbm_fail(LBM_ERR_ARG, "unknown option '%s' (a double-precision context has \"multistep\")", key);
+  if (!strcmp(key, "force")) {
+    if (value != 0 && value != 1) return lbm_fail(LBM_ERR_ARG, "force must be 0 or 1 (got %ld)", value);
+    if (d->steps_done != 0)
+      return lbm_fail(LBM_ERR_STATE, "\"force\" is set before the first step (%d done): the record holds every step since "
+                      "lbm_dp_upload", d->steps_done);
+    if ((value != 0) == d->force) return LBM_OK;
+    if (int rc = queue_sync(d->q)) return rc;
+    const bool before = d->force;
+    d->force = value != 0;
+    int rc = alloc_ring(d);
+    if (rc == LBM_OK && d->force && !d->force_rec)
+      rc = hip_alloc(reinterpret_cast<void **>(&d->force_rec), 2 * (size_t)d->p.max_iters * sizeof(double));
+    if (rc != LBM_OK) {
+      // back to a ring that fits the option as it was
+      const std::string keep = lbm_last_error();
+      d->force = before;
+      if (alloc_ring(d) != LBM_OK) d->failed = true;
+      return fail_again(rc, keep);
+    }
+    return LBM_OK;
+  }
+  return lbm_fail(LBM_ERR_ARG, "unknown option '%s' (a double-precision context has \"multistep\" and \"force\")", key);
 }
 
 int lbm_dp_get_option(const lbm_dp *d, const char *key, long *value) {
@@ -369,7 +428,56 @@ int lbm_dp_get_option(const lbm_dp *d, const char *key, long *value) {
     *value = multistep_effective(d);
     return LBM_OK;
   }
-  return lbm_fail(LBM_ERR_ARG, "unknown option '%s' (a double-precision context has \"multistep\")", key);
+  if (!strcmp(key, "force")) {
+    *value = d->force ? 1 : 0;
+    return LBM_OK;
+  }
+  return lbm_fail(LBM_ERR_ARG, "unknown option '%s' (a double-precision context has \"multistep\" and \"force\")", key);
+}
+
+int lbm_dforce_record(lbm_dp *d, double *fx_out, double *fy_out) {
+  // argument errors before a device is touched
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!fx_out && !fy_out) return lbm_fail(LBM_ERR_ARG, "fx_out and fy_out are both NULL");
+  if (!d->force) return lbm_fail(LBM_ERR_STATE, "no force record: option \"force\" is off (lbm_dp_set_option before the first step)");
+  if (int rc = queue_sync(d->q)) return rc;
+  double *outs[2] = {fx_out, fy_out};
+  for (int c = 0; c < 2; c++)
+    if (outs[c] && d->steps_done > 0)
+      HIP_TRY(hipMemcpy(outs[c], d->force_rec + (size_t)c * d->p.max_iters, (size_t)d->steps_done * sizeof(double),
+                        hipMemcpyDeviceToHost));
+  return LBM_OK;
+}
+
+int lbm_dforce(lbm_dp *d, double *fx, double *fy) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!fx && !fy) return lbm_fail(LBM_ERR_ARG, "fx and fy are both NULL");
+  if (int rc = queue_sync(d->q)) return rc;
+  if (!d->force_now) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->force_now), 2 * sizeof(double)));
+  // between runs the ring is empty (every run ends with its reduction): its first two blocks of ny * nseg take the
+  // segment sums of F_x and F_y, which then go the way a step's go
+  const size_t per_step = (size_t)d->p.ny * d->nseg;
+  DpForceArgs a{};
+  a.cells = d->cells[d->cur];
+  a.mask = d->mask;
+  a.seg_x = d->seg;
+  a.seg_y = d->seg + per_step;
+  a.plane_stride = d->plane_stride;
+  a.nx = d->p.nx;
+  a.ny = d->p.ny;
+  a.lanes_per_row = d->lanes_per_row;
+  a.aw1 = d->p.density * d->p.accel / 9.0;   // kernels.cl:14-15, run_dp_impl's statements
+  a.aw2 = d->p.density * d->p.accel / 36.0;
+  hipLaunchKernelGGL(dp_force_state, dim3((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock), 1), dim3(kBlock), 0, d->q.st, a);
+  HIP_TRY(hipGetLastError());
+  for (int c = 0; c < 2; c++)
+    if (int rc = reduce_steps(d, d->seg + (size_t)c * per_step, per_step, 1, d->force_now + c, 1ull)) return rc;
+  double f[2] = {0.0, 0.0};
+  HIP_TRY(hipMemcpyAsync(f, d->force_now, sizeof(f), hipMemcpyDeviceToHost, d->q.st));
+  HIP_TRY(hipStreamSynchronize(d->q.st));
+  if (fx) *fx = f[0];
+  if (fy) *fy = f[1];
+  return LBM_OK;
 }
 
 void lbm_dp_destroy(lbm_dp *d) {
