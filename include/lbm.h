@@ -459,7 +459,8 @@ int lbm_dp_create(lbm_dp **out, const lbm_dparams *params, const int32_t *obstac
 int lbm_dp_upload(lbm_dp *d, const double *cells);
 
 /* Host -> device copy of the obstacle map, int32[ny][nx] (beside lbm_upload_obstacles: d2q9-bgk.c:205-209); same nx, ny;
- * free_cells_inv stays the caller's to keep consistent.  Synchronises. */
+ * free_cells_inv stays the caller's to keep consistent.  Resets the body map (lbm_dbody_set, "Drag of a body" further down)
+ * to "every blocked cell": a body is made of the blocked cells of the map it was set on.  Synchronises. */
 int lbm_dp_upload_obstacles(lbm_dp *d, const int32_t *obstacles);
 
 /* Advance nsteps timesteps (accelerate_flow on row ny-2 + timestep + av_vels reduction each); asynchronous, repeatable
@@ -653,8 +654,7 @@ int lbm_dsteady_steps(lbm_dens *e, int *steps_out /*[n]*/, int *converged_out /*
  * "force" (lbm_dp_set_option; lbm_dforce_ens_set_option for an ensemble) before the first step; the output stage needs no
  * option.
  *
- * Out of scope: fp32 contexts and fp32 ensembles (ten kernel families, row slabs, ranks) have no force, and a steady run
- * still stops a member on its av_vels record, not on its force.
+ * Out of scope: fp32 contexts and fp32 ensembles (ten kernel families, row slabs, ranks) have no force.
  */
 
 /* The force record of a double-precision context: fx_out, fy_out = double[lbm_dp_steps_done], either may be NULL (not both:
@@ -685,6 +685,66 @@ int lbm_dforce_ens_record(lbm_dens *e, double *fx_out /*[n][steps]*/, double *fy
 /* Output stage per member (beside lbm_dens_reynolds): lbm_dforce for every member, fx, fy = double[n], either may be NULL
  * (not both).  After a steady run each member's own last state is read, from the grid array that holds it.  Synchronises. */
 int lbm_dforce_ens(lbm_dens *e, double *fx /*[n]*/, double *fy /*[n]*/);
+
+/*
+ * ---- Drag of a body: the force on chosen blocked cells, and steady runs that stop on it ----------------------------------
+ *
+ * The inputs drag sweeps run on are walled channels with a body in them, and the force above counts the walls with the body.
+ * A body map says which blocked cells count: int32[ny][nx] (int32[n][ny][nx] for an ensemble), non-zero = "this blocked
+ * cell's links count".
+ *
+ * Semantics.  With a body map the definition of "Drag and lift" is unchanged except that the outer sum runs over the blocked
+ * cells of the body only.  A link still counts only if the neighbour o - c_k is fluid: a blocked neighbour, in the body or
+ * not, gives no link.  No body map is the default: every blocked cell counts.  A body map with no cell set gives exactly +0.0
+ * in both components.  A body map that selects every blocked cell gives the bits that no body map gives.  A non-zero entry
+ * on a fluid cell is refused with LBM_ERR_ARG, the message names the first such cell (member, y, x), and nothing on the device
+ * changes.
+ *
+ * Nothing else moves.  Cells, av_vels, the four fields and Reynolds numbers are the same bits with any body map as with none:
+ * a blocked cell outside the body is a blocked cell to collision, acceleration and the output stages.  The record with a
+ * body keeps every bit identity stated under "Drag and lift" (kernel forms, launch splits, runs, context and ensemble
+ * member, steady-run member and plain run), and the output stage equals the record entry the next step writes.  The caller
+ * never sees how the device tells the two kinds of blocked cell apart: lbm_dbody_get returns 0 and 1 only.
+ *
+ * When a map is accepted.  With the option "force" off: at any time; the output stage (lbm_dforce, lbm_dforce_ens) reads the
+ * body in force at the call, so the forces of several bodies on one state are several set + force calls.  With "force" on:
+ * only while steps_done is 0, the rule of the option itself; otherwise LBM_ERR_STATE, so one record never mixes two bodies
+ * (that includes an ensemble left ragged by a steady run: its counts are not 0).  lbm_dp_upload_obstacles resets the body
+ * to "every blocked cell"; lbm_dp_upload and lbm_dens_upload keep it.  Setting a map rewrites the device mask from the host's
+ * copy of the obstacle map and synchronises.
+ *
+ * Drag criterion.  lbm_dbody_steady_run is lbm_dsteady_run in everything but the criterion: the legs, check points, polling,
+ * gating, lbm_dsteady_steps for the per-member counts, raggedness, what downloads return afterwards, argument refusals and
+ * the failure latch are that entry point's.  Let F(s) be the F_x record entry of the member's s-th step, fx_out[m][s - 1] as
+ * lbm_dforce_ens_record returns it; nothing is multiplied into it.  A member stops at check point s if
+ *     fabs(F(s) - F(s - window)) <= rel_tol * fabs(F(s)),
+ * evaluated on the device in IEEE double, the difference and the product as separate statements without contraction: the
+ * host reproduces every decision from the downloaded record.  A NaN never stops a member.  A member whose F_x is exactly 0
+ * throughout (an empty body, or no blocked cell) stops at its first check point.
+ *
+ * Out of scope here: more than one body per record (the output stage with the record off covers several bodies on one
+ * state), drag and lift coefficients (the reference velocity and length are the caller's), a combined av_vels-and-drag
+ * criterion.
+ */
+
+/* Set the body map of a double-precision context, int32[ny][nx], borrowed for the call; NULL: every blocked cell counts
+ * again.  LBM_ERR_ARG: a NULL context, a non-zero entry on a fluid cell.  LBM_ERR_STATE: "force" on and steps done.
+ * Synchronises. */
+int lbm_dbody_set(lbm_dp *d, const int32_t *body);
+
+/* body_out = int32[ny][nx]: 1 where a blocked cell counts, else 0.  A NULL context or a NULL body_out: LBM_ERR_ARG. */
+int lbm_dbody_get(lbm_dp *d, int32_t *body_out);
+
+/* The same for all members of a double-precision ensemble, int32[n][ny][nx]. */
+int lbm_dbody_ens_set(lbm_dens *e, const int32_t *body);
+int lbm_dbody_ens_get(lbm_dens *e, int32_t *body_out);
+
+/*
+ * Advance every member until ITS OWN drag has settled, at most max_steps steps (beside lbm_dsteady_run, whose refusals it
+ * shares).  The option "force" must be on: otherwise LBM_ERR_STATE, and the message says to switch it on before the first
+ * step.  Synchronises.
+ */
+int lbm_dbody_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol);
 
 const char *lbm_last_error(void);
 const char *lbm_version(void);

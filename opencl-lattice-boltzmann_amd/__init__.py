@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "lbm_dsteady_run", "lbm_dsteady_steps",
     "lbm_dforce_record", "lbm_dforce", "lbm_dforce_ens_set_option", "lbm_dforce_ens_get_option", "lbm_dforce_ens_record",
     "lbm_dforce_ens",
+    "lbm_dbody_set", "lbm_dbody_get", "lbm_dbody_ens_set", "lbm_dbody_ens_get", "lbm_dbody_steady_run",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -155,6 +156,11 @@ def load_library():
     L.lbm_dforce_ens_get_option.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_long)]
     L.lbm_dforce_ens_record.argtypes = [vp, vp, vp]
     L.lbm_dforce_ens.argtypes = [vp, vp, vp]
+    L.lbm_dbody_set.argtypes = [vp, vp]
+    L.lbm_dbody_get.argtypes = [vp, vp]
+    L.lbm_dbody_ens_set.argtypes = [vp, vp]
+    L.lbm_dbody_ens_get.argtypes = [vp, vp]
+    L.lbm_dbody_steady_run.argtypes = [vp, ci, ci, ctypes.c_double]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -552,6 +558,22 @@ class LBMDouble(_Handle):
         _check(self.lib.lbm_dforce(self.ctx, ctypes.byref(fx), ctypes.byref(fy)), "lbm_dforce")
         return fx.value, fy.value
 
+    def set_body(self, body):
+        """The blocked cells whose links count in the force (lbm_dbody_set): int32[ny, nx], non-zero = counts; None = every
+        blocked cell again.  With "force" on only before the first step."""
+        if body is None:
+            _check(self.lib.lbm_dbody_set(self.ctx, None), "lbm_dbody_set")
+        else:
+            b = np.ascontiguousarray(body, dtype=np.int32)
+            assert b.shape == (self.ny, self.nx)
+            _check(self.lib.lbm_dbody_set(self.ctx, b.ctypes.data), "lbm_dbody_set")
+
+    def body(self):
+        """int32[ny, nx]: 1 where a blocked cell counts in the force, else 0 (lbm_dbody_get)"""
+        b = np.zeros((self.ny, self.nx), dtype=np.int32)
+        _check(self.lib.lbm_dbody_get(self.ctx, b.ctypes.data), "lbm_dbody_get")
+        return b
+
     def force_record(self):
         """(F_x float64[steps_done], F_y float64[steps_done]): the force of every step since the upload; needs
         set_option("force", 1) before the first step."""
@@ -699,6 +721,37 @@ class EnsembleDouble(_EnsembleOf):
         v = ctypes.c_long()
         _check(self.lib.lbm_dforce_ens_get_option(self.ens, key.encode(), ctypes.byref(v)), "lbm_dforce_ens_get_option(%s)" % key)
         return v.value
+
+    def set_body(self, body):
+        """Per member the blocked cells whose links count in the force (lbm_dbody_ens_set): int32[n, ny, nx], or one [ny, nx]
+        map for all members; non-zero = counts; None = every blocked cell again.  With "force" on only before the first
+        step."""
+        if body is None:
+            _check(self.lib.lbm_dbody_ens_set(self.ens, None), "lbm_dbody_ens_set")
+            return
+        b = np.asarray(body, dtype=np.int32)
+        if b.ndim == 2:
+            b = np.broadcast_to(b, (self.n,) + b.shape)
+        b = np.ascontiguousarray(b)
+        assert b.shape == (self.n, self.ny, self.nx)
+        _check(self.lib.lbm_dbody_ens_set(self.ens, b.ctypes.data), "lbm_dbody_ens_set")
+
+    def body(self):
+        """int32[n, ny, nx]: 1 where a blocked cell counts in the force, else 0 (lbm_dbody_ens_get)"""
+        b = np.zeros((self.n, self.ny, self.nx), dtype=np.int32)
+        _check(self.lib.lbm_dbody_ens_get(self.ens, b.ctypes.data), "lbm_dbody_ens_get")
+        return b
+
+    def run_until(self, max_steps, window=64, rel_tol=1e-4, on="av_vels"):
+        """_EnsembleOf.run_until with a choice of criterion: on="av_vels" (lbm_dsteady_run), or on="drag"
+        (lbm_dbody_steady_run): |F(s) - F(s - window)| <= rel_tol |F(s)| on the member's own F_x record, the force on its body
+        (set_body); needs set_option("force", 1) before the first step."""
+        if on == "av_vels":
+            return super().run_until(max_steps, window=window, rel_tol=rel_tol)
+        if on != "drag":
+            raise ValueError("run_until(on=%r): the criteria are \"av_vels\" and \"drag\"" % (on,))
+        _check(self.lib.lbm_dbody_steady_run(self.ens, max_steps, window, rel_tol), "lbm_dbody_steady_run")
+        return self.member_steps()
 
     def force(self):
         """(F_x float64[n], F_y float64[n]): every member's momentum-exchange force of its current state as the next step

@@ -140,7 +140,7 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
         const int c = (oy + T) * kRX + ox + T;
         const int gy = tile_y * TY + oy;
         double fx = 0.0, fy = 0.0;
-        const bool counts = lmask[c] != 0 && tile_x * TX + ox < a.nx && gy < a.ny;
+        const bool counts = lmask[c] == 1 && tile_x * TX + ox < a.nx && gy < a.ny;   // 2: blocked, outside the body
         if (counts) {
           const double(*f)[kRY * kRX] = lds[(s - 1) & 1];
           const double g[9] = {0.0, f[1][c - 1], f[2][c - kRX], f[3][c + 1], f[4][c + kRX], f[5][c - kRX - 1],

@@ -81,7 +81,7 @@ __device__ __forceinline__ void dp_accelerate_cell(double (&f)[9], bool obstacle
 // Momentum-exchange force on one blocked cell o in the step that streams the state f (include/lbm.h): for k = 1..8 in
 // ascending order, if the neighbour x = o - c_k is fluid, s = f_k(x) + f_opp(k)(o) goes into F with the signs of c_k.
 //   g[k]   = f_k(o - c_k), what o gathers in that step        own[k] = o's own stored f_k
-//   nb[k]  = mask byte of o - c_k (non-zero: blocked, the link does not count)
+//   nb[k]  = mask byte of o - c_k (non-zero: blocked, in the body or not; the link does not count)
 // One addition per link term, contraction off; a cell without a counted link gives +0.0, +0.0.
 __device__ __forceinline__ void dp_force_cell(const double (&g)[9], const double (&own)[9], const uint8_t (&nb)[9], double &fx,
                                               double &fy) {
@@ -179,8 +179,9 @@ static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a
         const uint8_t nb[9] = {0, mc[xl], ms[x], mc[xr], mn[x], ms[xl], ms[xr], mn[xr], mn[xl]};
         dp_force_cell(g, own, nb, fx, fy);
       };
-      if (ob_a) cell_force(x0, ga, fxa, fya);
-      if (ob_b) cell_force(x0 + 1, gb, fxb, fyb);
+      // byte 1: blocked and counted; 2: blocked, outside the body (include/lbm.h, "Drag of a body")
+      if (m[0] == 1) cell_force(x0, ga, fxa, fya);
+      if (has_b && m[1] == 1) cell_force(x0 + 1, gb, fxb, fyb);
       tfx = has_b ? fxa + fxb : fxa + 0.0;
       tfy = has_b ? fya + fyb : fya + 0.0;
     }
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
         const int c = (oy + T) * kRX + ox + T;
         const int gy = tile_y * TY + oy;
         double fx = 0.0, fy = 0.0;
-        const bool counts = lmask[c] != 0 && tile_x * TX + ox < a.nx && gy < a.ny;
+        const bool counts = lmask[c] == 1 && tile_x * TX + ox < a.nx && gy < a.ny;   // 2: blocked, outside the body
         if (counts) {
           const double(*f)[kRY * kRX] = lds[(s - 1) & 1];
           const double g[9] = {0.0, f[1][c - 1], f[2][c - kRX], f[3][c + 1], f[4][c + kRX], f[5][c - kRX - 1],
@@ -560,8 +561,8 @@ static __global__ __launch_bounds__(kBlock) void dp_force_state(const DpForceArg
     };
     double fxa = 0.0, fya = 0.0, fxb = 0.0, fyb = 0.0;
     const uint8_t *m = mask + (size_t)y * a.nx + x0;
-    if (m[0] != 0) cell_force(x0, fxa, fya);
-    if (has_b && m[1] != 0) cell_force(x0 + 1, fxb, fyb);
+    if (m[0] == 1) cell_force(x0, fxa, fya);                  // 2: blocked, outside the body
+    if (has_b && m[1] == 1) cell_force(x0 + 1, fxb, fyb);
     tfx = has_b ? fxa + fxb : fxa + 0.0;
     tfy = has_b ? fya + fyb : fya + 0.0;
   }

@@ -46,4 +46,29 @@ static __global__ void dens_steady_check(SteadyWords w, int n, const double *av_
   }
 }
 
+// dens_steady_check on the member's drag (include/lbm.h: lbm_dbody_steady_run): the same words, the same bookkeeping, and
+// the criterion fabs(F(s) - F(s - window)) <= rel_tol * fabs(F(s)) on F(t) = fx_rec[m][t - 1], the F_x record entry of the
+// member's t-th step as lbm_dforce_ens_record returns it, nothing multiplied into it.  The reductions that write the leg's
+// entries precede this launch on the stream (enqueue_steps' flush).  A record of exact zeros (an empty body) gives 0 <= 0:
+// such a member stops at its first check point; a NaN compares false.
+static __global__ void dens_drag_check(SteadyWords w, int n, const double *fx_rec, unsigned long long record, int s, int window,
+                                       double rel_tol, int check, int cur) {
+#pragma clang fp contract(off)
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= n || w.active[m] == 0) return;
+  w.steps[m] = s;
+  w.par[m] = cur;
+  if (!check) return;
+  const double *fx = fx_rec + (size_t)m * record;
+  const double f_now = fx[s - 1];
+  const double f_then = fx[s - window - 1];
+  const double diff = fabs(f_now - f_then);
+  const double bound = rel_tol * fabs(f_now);
+  if (diff <= bound) {
+    w.active[m] = 0;
+    w.conv[m] = 1;
+    atomicSub(w.count, 1);
+  }
+}
+
 }  // namespace lbm

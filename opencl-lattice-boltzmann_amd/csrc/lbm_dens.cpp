@@ -14,6 +14,7 @@
 // launch parities, so from the end of such a run until the next upload the array that holds a member's state is the
 // member's own (`par`).
 #include "../../include/lbm.h"
+#include "body_map.h"
 #include "dp_steady_kernels.h"
 #include "host_common.h"
 
@@ -57,7 +58,8 @@ struct lbm_dens {
   Queue q;
   size_t plane_stride = 0, member_stride = 0;  // doubles
   double *cells[2] = {nullptr, nullptr};
-  uint8_t *mask = nullptr;         // [n][ny][nx]
+  uint8_t *mask = nullptr;         // [n][ny][nx]: 0 fluid, 1 blocked and counted in the force, 2 blocked outside the body
+  BodyMap body;                    // the host's copy of what the mask was made of (body_map.h)
   DensMember *members = nullptr;   // [n]
   double *seg = nullptr;           // [ring][n][ny][nseg]
   double *red = nullptr;           // [ring][n][red_blocks]: first reduction stage
@@ -158,6 +160,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->fin_partials), (size_t)n * e->fin_blocks * sizeof(double)));
   // the members' byte masks from the caller's int32[n][ny][nx]
   if (int rc = upload_mask(e->mask, obstacles, (size_t)n * cells_per)) return rc;
+  body_reset(e->body, obstacles, (size_t)n * cells_per);
   // in double these are lbm_dp.cpp's own statements (run_dp_impl, lbm_dp_upload): a member's constants are a context's
   std::vector<DensMember> t(n);
   for (int i = 0; i < n; i++) t[i] = member_constants<DensMember>(e->p[i]);
@@ -301,7 +304,9 @@ int steady_alloc(lbm_dens *e) {
   return LBM_OK;
 }
 
-int steady_impl(lbm_dens *e, int max_steps, int window, double rel_tol, bool *launched) {
+// drag_rec: NULL for the av_vels criterion (dens_steady_check), the members' F_x records for the drag criterion
+// (dens_drag_check); everything else is one loop
+int steady_impl(lbm_dens *e, int max_steps, int window, double rel_tol, const double *drag_rec, bool *launched) {
   if (int rc = check_runnable(max_steps, e->failed, "ensemble")) return rc;  // max_steps >= 0 here (lbm_dsteady_run)
   if (e->ragged) return refuse_ragged(e);
   if (int rc = check_record(e->max_iters, e->steps_done, max_steps, "up to ")) return rc;
@@ -322,8 +327,13 @@ int steady_impl(lbm_dens *e, int max_steps, int window, double rel_tol, bool *la
     const int s = s0 + done;
     // a check point: a whole leg, with a record entry one window back (step counts start at 1)
     const int check = (leg == window && s - window >= 1) ? 1 : 0;
-    hipLaunchKernelGGL(dens_steady_check, mgrid, mblock, 0, e->q.st, w, n, (const double *)e->av_sum,
-                       (unsigned long long)e->max_iters, (const double *)e->steady_inv, s, window, rel_tol, check, e->cur);
+    // enqueue_steps ended with its flush: the leg's reductions into av_sum and the force records are on the stream already
+    if (!drag_rec)
+      hipLaunchKernelGGL(dens_steady_check, mgrid, mblock, 0, e->q.st, w, n, (const double *)e->av_sum,
+                         (unsigned long long)e->max_iters, (const double *)e->steady_inv, s, window, rel_tol, check, e->cur);
+    else
+      hipLaunchKernelGGL(dens_drag_check, mgrid, mblock, 0, e->q.st, w, n, drag_rec, (unsigned long long)e->max_iters, s, window,
+                         rel_tol, check, e->cur);
     HIP_TRY(hipGetLastError());
     // Every few checks: is anyone left?  Only how much is enqueued depends on the answer; what a member computes does not,
     // the workgroups of a stopped member return at once.
@@ -520,7 +530,7 @@ int lbm_dsteady_run(lbm_dens *e, int max_steps, int window, double rel_tol) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
   bool launched = false;
-  const int rc = steady_impl(e, max_steps, window, rel_tol, &launched);
+  const int rc = steady_impl(e, max_steps, window, rel_tol, nullptr, &launched);
   return latch_failure(rc, launched, e->q.st, &e->failed);
 }
 
@@ -620,6 +630,35 @@ int lbm_dforce_ens(lbm_dens *e, double *fx, double *fy) {
     if (fy) fy[m] = f[n + m];
   }
   return LBM_OK;
+}
+
+int lbm_dbody_ens_set(lbm_dens *e, const int32_t *body) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (e->force && e->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "with \"force\" on, a body map is set before the first step (%d done): one record holds one body",
+                    e->steps_done);
+  if (int rc = queue_sync(e->q)) return rc;
+  return body_apply(e->body, e->mask, body, e->n, e->ny, e->nx, true);
+}
+
+int lbm_dbody_ens_get(lbm_dens *e, int32_t *body_out) {
+  // argument errors before anything of the ensemble is read
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!body_out) return lbm_fail(LBM_ERR_ARG, "body_out is NULL");
+  body_read(e->body, body_out);
+  return LBM_OK;
+}
+
+int lbm_dbody_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol) {
+  // every argument error is reported before the ensemble or a device is touched
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
+  if (!e->force)
+    return lbm_fail(LBM_ERR_STATE, "the drag criterion reads the force record: option \"force\" is off (lbm_dforce_ens_set_option "
+                    "switches it on before the first step)");
+  bool launched = false;
+  const int rc = steady_impl(e, max_steps, window, rel_tol, e->force_rec, &launched);
+  return latch_failure(rc, launched, e->q.st, &e->failed);
 }
 
 void lbm_dens_destroy(lbm_dens *e) {

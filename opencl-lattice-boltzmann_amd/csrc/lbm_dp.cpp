@@ -7,6 +7,7 @@
 // of row ny-2, and the second reduction stage over the buffered steps.  The reference's counterpart is its one grid and
 // in-order queue (d2q9-bgk.c:221-239), in the precision of its fp64 ancestor.
 #include "../../include/lbm.h"
+#include "body_map.h"
 #include "dp_kernels.h"
 #include "host_common.h"
 
@@ -43,7 +44,8 @@ struct lbm_dp {
   Queue q;
   size_t plane_stride = 0;        // doubles
   double *cells[2] = {nullptr, nullptr};
-  uint8_t *mask = nullptr;        // [ny][nx]
+  uint8_t *mask = nullptr;        // [ny][nx]: 0 fluid, 1 blocked and counted in the force, 2 blocked outside the body
+  BodyMap body;                   // the host's copy of what the mask was made of (body_map.h)
   double *seg = nullptr;          // [ring][ny][nseg]
   double *red = nullptr;          // [ring][red_blocks]: first reduction stage
   double *av_sum = nullptr;       // [max_iters]
@@ -134,6 +136,7 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
   if (int rc = alloc_ring(d)) return rc;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->av_sum), (size_t)d->p.max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->fin_partials), (size_t)d->fin_blocks * sizeof(double)));
+  body_reset(d->body, obstacles, cells);
   return upload_mask(d->mask, obstacles, cells);
 }
 
@@ -317,7 +320,10 @@ int lbm_dp_upload(lbm_dp *d, const double *cells) {
 int lbm_dp_upload_obstacles(lbm_dp *d, const int32_t *obstacles) {
   if (!d || !obstacles) return lbm_fail(LBM_ERR_ARG, "NULL argument");
   if (int rc = queue_sync(d->q)) return rc;
-  return upload_mask(d->mask, obstacles, (size_t)d->p.nx * d->p.ny);
+  // the body map, if one was set, described the old map's blocked cells: every blocked cell counts again
+  if (int rc = upload_mask(d->mask, obstacles, (size_t)d->p.nx * d->p.ny)) return rc;
+  body_reset(d->body, obstacles, (size_t)d->p.nx * d->p.ny);
+  return LBM_OK;
 }
 
 int lbm_dp_run(lbm_dp *d, int nsteps) {
@@ -477,6 +483,23 @@ int lbm_dforce(lbm_dp *d, double *fx, double *fy) {
   HIP_TRY(hipStreamSynchronize(d->q.st));
   if (fx) *fx = f[0];
   if (fy) *fy = f[1];
+  return LBM_OK;
+}
+
+int lbm_dbody_set(lbm_dp *d, const int32_t *body) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (d->force && d->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "with \"force\" on, a body map is set before the first step (%d done): one record holds one body",
+                    d->steps_done);
+  if (int rc = queue_sync(d->q)) return rc;
+  return body_apply(d->body, d->mask, body, 1, d->p.ny, d->p.nx, false);
+}
+
+int lbm_dbody_get(lbm_dp *d, int32_t *body_out) {
+  // argument errors before anything of the context is read
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!body_out) return lbm_fail(LBM_ERR_ARG, "body_out is NULL");
+  body_read(d->body, body_out);
   return LBM_OK;
 }
 
