@@ -18,7 +18,7 @@ all: $(LIB) $(EXE) $(EXE).exe oracle
 
 # lbm_version() carries a digest of the device + host sources the library was built from: a committed profile
 # (profiles/traffic.json) names the build it measured, and bench.py refuses its counters for any other build
-CSRC   = $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/deep_instances.h $(PKG)/csrc/halo_exchange.h $(PKG)/csrc/chunk_schedule.h $(PKG)/csrc/lbm_hip.cpp $(PKG)/csrc/lbm_deep.cpp \
+CSRC   = $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/core_interval.h $(PKG)/csrc/deep_instances.h $(PKG)/csrc/halo_exchange.h $(PKG)/csrc/chunk_schedule.h $(PKG)/csrc/lbm_hip.cpp $(PKG)/csrc/lbm_deep.cpp \
          $(PKG)/csrc/ensemble_kernels.h $(PKG)/csrc/steady_kernels.h $(PKG)/csrc/steady_words.h $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h
 SRC_ID = $(shell cat $(CSRC) | sha256sum | cut -c1-12)
 
@@ -27,7 +27,7 @@ SRC_ID = $(shell cat $(CSRC) | sha256sum | cut -c1-12)
 $(PKG)/csrc/lbm_hip.o: $(CSRC) include/lbm.h
 	$(HIPCC) $(HIPFLAGS) -DLBM_SRC_ID=\"$(SRC_ID)\" -c $(PKG)/csrc/lbm_hip.cpp -o $@
 
-$(PKG)/csrc/lbm_deep.o: $(PKG)/csrc/lbm_deep.cpp $(PKG)/csrc/deep_instances.h $(PKG)/csrc/d2q9_kernels.h
+$(PKG)/csrc/lbm_deep.o: $(PKG)/csrc/lbm_deep.cpp $(PKG)/csrc/deep_instances.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/core_interval.h
 	$(HIPCC) $(HIPFLAGS) -mllvm -amdgpu-sched-strategy=max-ilp -c $(PKG)/csrc/lbm_deep.cpp -o $@
 
 $(PKG)/csrc/lbm_ensemble.o: $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/ensemble_kernels.h $(PKG)/csrc/steady_kernels.h $(PKG)/csrc/steady_words.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h include/lbm.h

@@ -222,6 +222,10 @@ int lbm_reynolds(lbm_ctx *ctx, float *reynolds_out);
  *   "free_sweeps"  deep window kernel at 6, 7, 8 timesteps per launch: 1 (and -1, auto) = a wave whose chunk of rows holds no
  *                  blocked cell inside its strip (looked up in a map built from the obstacle map) sweeps it without any
  *                  obstacle handling, 0 = every wave looks level by level ("obst_paths").  Same results bit for bit.
+ *   "core_loop"    deep window kernel, free sweeps: 1 (and -1, auto) = the rows of a chunk's interior — every level on one of
+ *                  the chunk's own rows, none on the accelerated row, no row wrap — run a form of the row loop without the
+ *                  per-level tests and with carried row pointers, 0 = the steady form throughout.  Reads back as 0 or 1.
+ *                  Same results bit for bit.
  *   "windows", "load_bufs"   kept for callers that set them: the three-step kernel exists in ONE form since round 4 — its two
  *                  windows in LDS (two waves per SIMD), one row-set of source loads in flight; "windows" accepts -1 / 1,
  *                  "load_bufs" 0 / 1 (the register-window form and the two-row-set form, 253-256 registers at one wave per

@@ -38,6 +38,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "core_interval.h"
+
 namespace lbm {
 
 constexpr int kBlock = 256;  // 4 wave64 per workgroup
@@ -597,6 +599,7 @@ struct Step2Args {
   const int *vmap;
   const int *vtab;
   int strips_edge;             // real strips per row: what the EDGE units of a compact launch set are numbered by
+  int core_loop;               // d2q9_deep / d2q9_deep_twin, free sweeps: run the chunk's interior rows in the CORE form of the row loop (deep_sweep)
 };
 
 // Which work unit a workgroup has (compact launch sets: edge schedule first).  All wave-uniform.
@@ -1754,6 +1757,25 @@ __device__ __forceinline__ v2f lds_pair_shifted(const float *p) {  // 4-byte ali
 }
 __device__ __forceinline__ void lds_pair_put(float *p, v2f v) { *reinterpret_cast<v2f *>(p) = v; }
 
+// The nine planes of issue_pair_loads from a row pointer the caller carries (Rc: a row of the source grid whose south and
+// north neighbours are the rows next to it in memory — no wrap), for a sweep without obstacle handling and without edge
+// elements: neither mask nor halo loads.  Every plane's row pointer is made opaque in scalar registers and the address is
+// typed as global memory, as in deep_sweep's stores: a pointer that comes out of a loop-carried scalar otherwise turns into
+// nine 64-bit vector additions (or flat loads).
+__device__ __forceinline__ void issue_pair_loads_at(const float *Rc, size_t ps, size_t rs, int xcol, PairLoads &in) {
+  unsigned xb = (unsigned)xcol * 4u;
+  asm volatile("" : "+v"(xb));
+  auto ld = [&](const float *p) {
+    unsigned long long pk = (unsigned long long)p;
+    asm volatile("" : "+s"(pk));
+    return *(const global_v2f *)(pk + xb);
+  };
+  const float *const Rs = Rc - rs, *const Rn = Rc + rs;
+  in.c[0] = ld(Rc); in.c[1] = ld(Rc + ps); in.c[3] = ld(Rc + 3 * ps);
+  in.c[2] = ld(Rs + 2 * ps); in.c[5] = ld(Rs + 5 * ps); in.c[6] = ld(Rs + 6 * ps);
+  in.c[4] = ld(Rn + 4 * ps); in.c[7] = ld(Rn + 7 * ps); in.c[8] = ld(Rn + 8 * ps);
+}
+
 constexpr int deep_halo_lanes(int D) { return D / 2; }           // ceil((D-1)/2) lanes of two cells at either end of a strip
 // Does level 0 need the element beyond the strip's first / last cell (an extra load by lanes 0 and 63)?  Level l's output
 // is valid from cell l + (0 with that element, 1 without) inwards; the owned cells start at cell 2*HL: with an even depth
@@ -1882,10 +1904,9 @@ __device__ __forceinline__ void deep_sweep(const Step2Args &a, const int L_arg, 
   v2f out[9];  // the last level's row of the previous iteration
 #pragma unroll
   for (int kk = 0; kk < 9; kk++) out[kk] = splat2(0.f);
-  auto store_row = [&](int kprev) __attribute__((always_inline)) {
+  auto store_row_at = [&](float *const row) __attribute__((always_inline)) {
     if (owner) {
       // SGPR-base form again: uniform pointer to the row's plane + the lane's byte offset
-      float *const row = a.dst + (size_t)(r0 + (kprev - (L - 1)) * d) * a.row_stride;
       unsigned xb = (unsigned)xcol * 4u;
       asm volatile("" : "+v"(xb));
 #pragma unroll
@@ -1900,23 +1921,40 @@ __device__ __forceinline__ void deep_sweep(const Step2Args &a, const int L_arg, 
       }
     }
   };
+  auto store_row = [&](int kprev) __attribute__((always_inline)) { store_row_at(a.dst + (size_t)(r0 + (kprev - (L - 1)) * d) * a.row_stride); };
+  // The CORE form (below) carries its row pointers from iteration to iteration: core_src = the row of a.src that the next
+  // iteration's level 0 works on, core_dst = the row of a.dst the last level's row of the previous iteration belongs to;
+  // either moves by one row, in the sweep's direction, per iteration.
+  constexpr bool HAS_CORE = LT > 0 && FREE && !deep_edge_loads(D);
+  const float *core_src = a.src;
+  float *core_dst = a.dst;
+  const long long core_step = UP ? (long long)a.row_stride : -(long long)a.row_stride;
   // One row iteration.  lt_tag 0: the general form — the depth L is a run-time value, a level runs once its first row has
   // arrived (`active`), the level chain ends with a `break`.  lt_tag > 0: the STEADY form for launches of exactly that many
   // timesteps, valid once every level is active (k > sf*(L-1)): depth, activity and "is this the last level" are
   // compile-time facts, so the chain of levels is straight-line code — `nxt` of one level IS `top` of the next (a
   // renaming, where the general form's control flow made the compiler copy nine register pairs per level, ~20 % of its
   // VALU instructions), the last level's row lands in `out` where it is produced, and the start-up branches, the twins'
-  // hand-overs and their barriers are gone.  Both forms do the same arithmetic in the same order on every cell.
-  auto iteration = [&](const int k, auto lt_tag) __attribute__((always_inline)) {
+  // hand-overs and their barriers are gone.  core_tag: the CORE form of the steady form, for the iterations of
+  // lbm::core_interval (core_interval.h) — every level works on one of the chunk's own rows, none on the accelerated row,
+  // and no row that is loaded or stored wraps: the shift registers are neither updated nor tested (the driver sets them on
+  // leaving), the accelerate step is compiled out, the sums are added under `owner` alone, and the rows are addressed
+  // through the carried pointers — no row * row_stride products, no wrap().  All forms do the same arithmetic in the same
+  // order on every cell.
+  auto iteration = [&](const int k, auto lt_tag, auto core_tag) __attribute__((always_inline)) {
     constexpr int LS = decltype(lt_tag)::value;
     constexpr bool STEADY = LS > 0;
+    constexpr bool CORE = decltype(core_tag)::value;
+    static_assert(!CORE || (STEADY && HAS_CORE), "the CORE form is a steady form of the free sweeps");
     const int LL = STEADY ? LS : L;
     const int par = k & 1;
     v2f top[9], pre[2][6];  // pre[l & 1]: the window planes of level l, read one level ahead
     uint32_t m_top;
-    const int row0 = wrap(r0 + k * d);
-    accbits = ((accbits << 1) | ((row0 == a.accel_row || row0 == a.accel_row_b) ? 1u : 0u)) & accmask;
-    ownbits = (ownbits << 1) | ((k >= lead && k <= n + lead - 1) ? 1u : 0u);
+    if (!CORE) {
+      const int row0 = wrap(r0 + k * d);
+      accbits = ((accbits << 1) | ((row0 == a.accel_row || row0 == a.accel_row_b) ? 1u : 0u)) & accmask;
+      ownbits = (ownbits << 1) | ((k >= lead && k <= n + lead - 1) ? 1u : 0u);
+    }
     if (STEADY || k >= sf) window_read(1, par, STEADY ? -1 : k, pre[1]);  // issued before level 0's arithmetic: the LDS latency hides behind it
     {  // level 0: step t+1 of row0 from the loaded source rows
       v2f g[9];
@@ -1930,17 +1968,24 @@ __device__ __forceinline__ void deep_sweep(const Step2Args &a, const int L_arg, 
       }
       m_top = FREE ? 0u : in.m >> mask_shift;  // (bits 16.. may hold the neighbouring pair's bytes: every test masks)
       v2f t;
-      if (FREE || (OBST_PATHS && __builtin_amdgcn_ballot_w64((m_top & 0xffffu) != 0) == 0ull)) t = collide2<false>(g, m_top, a.omega, (accbits & 1u) != 0, a.aw1, a.aw2, top);
+      if (FREE || (OBST_PATHS && __builtin_amdgcn_ballot_w64((m_top & 0xffffu) != 0) == 0ull)) t = collide2<false>(g, m_top, a.omega, !CORE && (accbits & 1u) != 0, a.aw1, a.aw2, top);
       else t = collide2<true>(g, m_top, a.omega, (accbits & 1u) != 0, a.aw1, a.aw2, top);
-      if ((ownbits & 1u) && owner) sum[0] += t.x + t.y;
+      if ((CORE || (ownbits & 1u)) && owner) sum[0] += t.x + t.y;
       // The row the last level finished in the PREVIOUS iteration is stored here, right before this iteration's loads:
       // the wave waits for its loads at the top of the next iteration with the memory counter at zero, stores
       // included — with the stores at the end of an iteration that wait exposed the round trip of stores just issued;
       // now everything it covers was issued a whole iteration of arithmetic earlier.
       // (stores and loads issued BEFORE level 0's arithmetic, right after its gather: 1 % slower everywhere, tools/ab.py --libs)
-      if (STEADY || k - 1 >= sf * (LL - 1)) store_row(k - 1);
-      // (unconditional: the last iteration loads its own row once more rather than branching around the loads)
-      issue_pair_loads<false, deep_edge_loads(D)>(a, wrap(r0 + (k < last ? k + 1 : k) * d), xcol, xhalo_w, xhalo_e, lane, in);
+      if (CORE) {
+        store_row_at(core_dst);
+        issue_pair_loads_at(core_src, ps, a.row_stride, xcol, in);
+        core_dst += core_step;
+        core_src += core_step;
+      } else {
+        if (STEADY || k - 1 >= sf * (LL - 1)) store_row(k - 1);
+        // (unconditional: the last iteration loads its own row once more rather than branching around the loads)
+        issue_pair_loads<false, deep_edge_loads(D)>(a, wrap(r0 + (k < last ? k + 1 : k) * d), xcol, xhalo_w, xhalo_e, lane, in);
+      }
     }
 #pragma unroll
     for (int l = 1; l < D; l++) {
@@ -1968,12 +2013,12 @@ __device__ __forceinline__ void deep_sweep(const Step2Args &a, const int L_arg, 
           g[2] = top[2]; g[5] = pair_from_west(top[5]); g[6] = pair_from_east(top[6]);
         }
         m_nxt = FREE ? 0u : m_mid[l - 1];
-        const bool acc = ((accbits >> l) & 1u) != 0;
+        const bool acc = !CORE && ((accbits >> l) & 1u) != 0;
         v2f t;
         if (FREE || (OBST_PATHS && __builtin_amdgcn_ballot_w64((m_nxt & 0xffffu) != 0) == 0ull)) t = collide2<false>(g, m_nxt, a.omega, acc, a.aw1, a.aw2, nxt);
         else t = collide2<true>(g, m_nxt, a.omega, acc, a.aw1, a.aw2, nxt);
         if (!final) {
-          if (((ownbits >> l) & 1u) && owner) sum[l] += t.x + t.y;
+          if ((CORE || ((ownbits >> l) & 1u)) && owner) sum[l] += t.x + t.y;
         } else {  // the last level: every row it works on is one of the chunk's own; stored in the NEXT iteration
           if (owner) sum[l] += t.x + t.y;
 #pragma unroll
@@ -2016,13 +2061,34 @@ __device__ __forceinline__ void deep_sweep(const Step2Args &a, const int L_arg, 
   // that constant); LT = 0 is the kernel for any depth, general form throughout.  (Tried and dropped: all depths in one
   // kernel — one loop per form: what the later loops hoist is live through the earlier ones, 600 spilled registers;
   // one loop that picks its body per iteration: 44-206.)
+  // Within the steady stretch, the iterations of the chunk's interior run in the CORE form (free sweeps of the depths with
+  // a kernel of their own; a.core_loop: option "core_loop"): steady up to the interval, CORE, steady to the end — one loop
+  // around ONE instance of either form.
   const int k_steady = sf * (L - 1) + 1;
   int k = 0;
   if (LT > 0) {
-    for (; k < k_steady && k <= last; k++) iteration(k, std::integral_constant<int, 0>{});
-    for (; k <= last; k++) iteration(k, std::integral_constant<int, LT>{});
+    for (; k < k_steady && k <= last; k++) iteration(k, std::integral_constant<int, 0>{}, std::false_type{});
+    if constexpr (HAS_CORE) {
+      CoreInterval ci = {0, 0};
+      if (a.core_loop) ci = core_interval(ys, ye, L, a.ny, UP, twinned, a.accel_row, a.accel_row_b, a.accel_next != 0);
+      const int kc0 = __builtin_amdgcn_readfirstlane(ci.kc0), kc1 = __builtin_amdgcn_readfirstlane(ci.kc1);
+      bool core_ahead = kc1 > kc0;
+      for (;;) {
+        const int stop = core_ahead ? kc0 : last + 1;
+        for (; k < stop; k++) iteration(k, std::integral_constant<int, LT>{}, std::false_type{});
+        if (!core_ahead) break;
+        core_ahead = false;
+        core_src = a.src + (long long)(r0 + (kc0 + 1) * d) * (long long)a.row_stride;
+        core_dst = a.dst + (long long)(r0 + (kc0 - L) * d) * (long long)a.row_stride;
+        for (; k < kc1; k++) iteration(k, std::integral_constant<int, LT>{}, std::true_type{});
+        ownbits = (1u << L) - 1u;  // what the shifts of these iterations would have left: every level on an own row,
+        accbits = 0;               // none on the accelerated row
+      }
+    } else {
+      for (; k <= last; k++) iteration(k, std::integral_constant<int, LT>{}, std::false_type{});
+    }
   } else {
-    for (; k <= last; k++) iteration(k, std::integral_constant<int, 0>{});
+    for (; k <= last; k++) iteration(k, std::integral_constant<int, 0>{}, std::false_type{});
   }
   store_row(last);
 #pragma unroll

@@ -315,6 +315,7 @@ struct lbm_ctx {
                             // (balance_heavy_strips), 0 = every strip the same chunks
   int free_sweeps = -1;     // d2q9_deep at the depths with a kernel of their own: 1 (and -1, auto) = a wave whose rows hold no blocked cell in its
                             // strip runs the sweep without obstacle handling (the map of Slab::clean_bits), 0 = every wave looks level by level
+  int core_loop = -1;       // free sweeps: 1 (and -1, auto) = a chunk's interior rows run the CORE form of the row loop (deep_sweep), 0 = steady form throughout
   int multistep = -1;       // T timesteps per launch on LDS tiles (d2q9_multi, small grids): -1 auto, 0 off, 1..8 = T
   int resident = -1;        // d2q9_resident (all steps of a launch with the grid in registers): -1 auto, 0 off, 1 on where the grid allows
   int chunk_rows = 0;       // longest chunk (rows per work unit) of d2q9_step2 (0 = auto)
@@ -1209,6 +1210,7 @@ Step2Args base_args2(const lbm_ctx *c, const Slab &s, int src, bool accel_next, 
   a.accel_row = s.accel_ext;
   a.accel_row_b = s.accel_ext_b;
   a.accel_next = accel_next ? 1 : 0;
+  a.core_loop = c->core_loop != 0 ? 1 : 0;
   a.omega = c->p.omega;
   a.aw1 = c->p.density * c->p.accel / 9.0f;
   a.aw2 = c->p.density * c->p.accel / 36.0f;
@@ -2871,6 +2873,11 @@ int lbm_set_option(lbm_ctx *c, const char *key, long value) {
     c->free_sweeps = (int)value;
     return LBM_OK;
   }
+  if (!strcmp(key, "core_loop")) {  // (a launch argument: nothing to rebuild)
+    if (value < -1 || value > 1) return fail(LBM_ERR_ARG, "core_loop must be -1 (auto), 0 or 1");
+    c->core_loop = (int)value;
+    return LBM_OK;
+  }
   if (!strcmp(key, "tile_shape")) {
     if (value < -1 || value > 2) return fail(LBM_ERR_ARG, "tile_shape must be -1..2");
     if (int rc = sync_all(c)) return rc;
@@ -3019,6 +3026,7 @@ int lbm_get_option(const lbm_ctx *c, const char *key, long *value) {
   }
   else if (!strcmp(key, "free_sweeps"))  // are the launches of the context's deep window kernel given the map?
     *value = s0 && p.fuse_lvl >= kDeepMin && clean_bits_for(c, *s0, *set_geom(p, *s0, KIND_DEEP).main) != nullptr;
+  else if (!strcmp(key, "core_loop")) *value = c->core_loop != 0;
   else if (!strcmp(key, "halo_sync")) *value = c->halo_sync;
   else if (!strcmp(key, "halo_timeout_ms")) *value = (long)c->halo_timeout_ms;
   else if (!strcmp(key, "push_release")) *value = c->slabs.empty() ? 0 : push_release_effective(c, c->slabs[0]);
