@@ -750,6 +750,66 @@ int lbm_dbody_ens_get(lbm_dens *e, int32_t *body_out);
  */
 int lbm_dbody_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol);
 
+/*
+ * ---- Two relaxation times: a second collision operator for the double-precision families -------------------------------
+ *
+ * A drag-against-Reynolds-number sweep is a sweep over omega, and with BGK and bounce-back the plane where a wall
+ * effectively sits moves with the relaxation rate: every member of the sweep sees a slightly different body in a slightly
+ * different channel, an error in the drag curve that no step count removes.  The two-relaxation-time (TRT) operator relaxes
+ * the symmetric part of each pair of opposite populations with omega, which sets the viscosity, and the antisymmetric part
+ * with a second rate omega_m, tied to omega by the magic parameter
+ *     Lambda = (1/omega - 1/2) (1/omega_m - 1/2).
+ * At fixed Lambda the wall location does not depend on the viscosity: Lambda = 3/16 puts a straight wall exactly half-way
+ * between the blocked cell and its fluid neighbour, Lambda = 1/4 is the most stable choice.  Off by default: BGK, the
+ * reference's operator (kernels.cl:119-198), keeps every bit.  The reference has no counterpart.
+ *
+ * Definition.  The host computes omega_m in double, three separate statements without contraction:
+ *     tp = 1.0 / omega - 0.5;
+ *     tm = magic / tp + 0.5;
+ *     omega_m = 1.0 / tm;
+ * A fluid cell's density, momentum, u_sq and equilibrium eq[0..8] from its gathered values g[0..8] are the BGK statements,
+ * unchanged, and so are the |u| it adds to av_vels and the bounce-back of a blocked cell.  Only the relaxation lines differ,
+ * contraction off:
+ *     out[0] = g[0] + omega * (eq[0] - g[0]);
+ *     for (k, q) in (1,3), (2,4), (5,7), (6,8):
+ *         a  = eq[k] - g[k];      b  = eq[q] - g[q];
+ *         sp = 0.5 * (a + b);     sm = 0.5 * (a - b);
+ *         rp = omega * sp;        rm = omega_m * sm;
+ *         out[k] = g[k] + (rp + rm);
+ *         out[q] = g[q] + (rp - rm);
+ * Lambda = 1/4 at omega = 1 gives omega_m = 1 exactly; that TRT step rounds five more times per value than the BGK step and is
+ * not promised its bits, only to stay within those roundings of it.
+ *
+ * Nothing else moves: accelerate_flow, bounce-back, the momentum-exchange force and its body maps, the order of every sum,
+ * the four fields, and the Reynolds number, whose viscosity still comes from omega.  Every bit identity stated for BGK holds
+ * for TRT: between the kernel forms ("multistep"), launch splits and runs; between a double-precision context and a member
+ * of a double-precision ensemble with the same magic parameter; between a member stopped by lbm_dsteady_run or
+ * lbm_dbody_steady_run at count c and a plain run of c steps.  Both steady runs work with TRT unchanged.
+ *
+ * When it is accepted.  Only while steps_done is 0, on a fresh handle or right after an upload, the rule of the option
+ * "force": otherwise LBM_ERR_STATE.  lbm_dp_upload, lbm_dens_upload and lbm_dp_upload_obstacles keep the setting.  An ensemble
+ * runs either all members TRT, each with its own magic parameter, or all BGK.
+ *
+ * Names: lbm_dtrt_*, on both double-precision handles (the option entry points take a long, which cannot carry 3/16).
+ * Out of scope: fp32 contexts and fp32 ensembles, whose checker contract is the reference's BGK.
+ */
+
+/* Set the collision operator of a double-precision context: magic == 0.0 is BGK (the default), magic > 0 and finite is TRT
+ * with that magic parameter.  LBM_ERR_ARG, before the context is read: a NULL context, magic negative, NaN or infinite.
+ * LBM_ERR_ARG: magic > 0 on a context whose 1/omega - 1/2 <= 0, that is omega >= 2 (the message names omega).
+ * LBM_ERR_STATE: steps done. */
+int lbm_dtrt_set(lbm_dp *d, double magic);
+
+/* The magic parameter in force (0.0: BGK) and the second relaxation rate, which is omega itself under BGK.  Either output may
+ * be NULL; both NULL (magic_out and omega_minus_out), or a NULL context: LBM_ERR_ARG. */
+int lbm_dtrt_get(const lbm_dp *d, double *magic_out, double *omega_minus_out);
+
+/* The same for a double-precision ensemble: magic = double[n], every entry > 0 and finite, members may differ; NULL: all
+ * members BGK.  LBM_ERR_ARG, the message names the member: an entry that is 0, negative, NaN or infinite, a member whose
+ * omega >= 2; nothing on the device changes after a refusal.  LBM_ERR_STATE: steps done.  Synchronises. */
+int lbm_dtrt_ens_set(lbm_dens *e, const double *magic /*[n]*/);
+int lbm_dtrt_ens_get(const lbm_dens *e, double *magic_out /*[n]*/, double *omega_minus_out /*[n]*/);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "lbm_dforce_record", "lbm_dforce", "lbm_dforce_ens_set_option", "lbm_dforce_ens_get_option", "lbm_dforce_ens_record",
     "lbm_dforce_ens",
     "lbm_dbody_set", "lbm_dbody_get", "lbm_dbody_ens_set", "lbm_dbody_ens_get", "lbm_dbody_steady_run",
+    "lbm_dtrt_set", "lbm_dtrt_get", "lbm_dtrt_ens_set", "lbm_dtrt_ens_get",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -161,6 +162,10 @@ def load_library():
     L.lbm_dbody_ens_set.argtypes = [vp, vp]
     L.lbm_dbody_ens_get.argtypes = [vp, vp]
     L.lbm_dbody_steady_run.argtypes = [vp, ci, ci, ctypes.c_double]
+    L.lbm_dtrt_set.argtypes = [vp, ctypes.c_double]
+    L.lbm_dtrt_get.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    L.lbm_dtrt_ens_set.argtypes = [vp, vp]
+    L.lbm_dtrt_ens_get.argtypes = [vp, vp, vp]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -574,6 +579,18 @@ class LBMDouble(_Handle):
         _check(self.lib.lbm_dbody_get(self.ctx, b.ctypes.data), "lbm_dbody_get")
         return b
 
+    def set_trt(self, magic):
+        """The collision operator (lbm_dtrt_set): magic > 0 = two relaxation times with that magic parameter (3/16: a straight
+        bounce-back wall exactly half-way, 1/4: the most stable), 0.0 = BGK, the default.  Only before the first step."""
+        _check(self.lib.lbm_dtrt_set(self.ctx, float(magic)), "lbm_dtrt_set")
+
+    def trt(self):
+        """(magic, omega_minus): the magic parameter in force (0.0: BGK) and the second relaxation rate, omega itself under
+        BGK (lbm_dtrt_get)"""
+        magic, om = ctypes.c_double(), ctypes.c_double()
+        _check(self.lib.lbm_dtrt_get(self.ctx, ctypes.byref(magic), ctypes.byref(om)), "lbm_dtrt_get")
+        return magic.value, om.value
+
     def force_record(self):
         """(F_x float64[steps_done], F_y float64[steps_done]): the force of every step since the upload; needs
         set_option("force", 1) before the first step."""
@@ -741,6 +758,26 @@ class EnsembleDouble(_EnsembleOf):
         b = np.zeros((self.n, self.ny, self.nx), dtype=np.int32)
         _check(self.lib.lbm_dbody_ens_get(self.ens, b.ctypes.data), "lbm_dbody_ens_get")
         return b
+
+    def set_trt(self, magic):
+        """The collision operator of all members (lbm_dtrt_ens_set): one magic parameter for all, or an array-like of n, every
+        entry > 0 = two relaxation times; None = BGK, the default.  Only before the first step."""
+        if magic is None:
+            _check(self.lib.lbm_dtrt_ens_set(self.ens, None), "lbm_dtrt_ens_set")
+            return
+        m = np.asarray(magic, dtype=np.float64)
+        if m.ndim == 0:
+            m = np.full(self.n, float(m), dtype=np.float64)
+        m = np.ascontiguousarray(m)
+        assert m.shape == (self.n,)
+        _check(self.lib.lbm_dtrt_ens_set(self.ens, m.ctypes.data), "lbm_dtrt_ens_set")
+
+    def trt(self):
+        """(magic float64[n], omega_minus float64[n]): per member the magic parameter in force (0.0: BGK) and the second
+        relaxation rate, the member's omega under BGK (lbm_dtrt_ens_get)"""
+        magic, om = np.zeros(self.n, dtype=np.float64), np.zeros(self.n, dtype=np.float64)
+        _check(self.lib.lbm_dtrt_ens_get(self.ens, magic.ctypes.data, om.ctypes.data), "lbm_dtrt_ens_get")
+        return magic, om
 
     def run_until(self, max_steps, window=64, rel_tol=1e-4, on="av_vels"):
         """_EnsembleOf.run_until with a choice of criterion: on="av_vels" (lbm_dsteady_run), or on="drag"

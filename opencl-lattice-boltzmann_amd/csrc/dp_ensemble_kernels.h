@@ -18,8 +18,12 @@ struct DensMember {
   double omega, aw1, aw2;  // aw1 = density*accel/9, aw2 = density*accel/36 (kernels.cl:14-15), in double
   double density;
   double w0, w1, w2;       // rest state (d2q9-bgk.c:529-531)
-  double pad;
+  union {
+    double omega_m;        // the second relaxation rate of the TRT instances (dp_trt_omega_minus); omega where the member is BGK
+    double pad;            // the name under which member_constants (host_common.h) zeroes the table's last slot
+  };
 };
+static_assert(sizeof(DensMember) == 64, "a member's constants are one 64-B line");
 
 struct DensArgs {
   const double *src;         // member m: src + m * member_stride
@@ -64,7 +68,10 @@ struct DensArgs {
 // 82 468 B, one workgroup per CU (the 28.8 against 20.3 us of the table above), and single-buffered ones put a barrier and the
 // segment lanes' sums on every step's critical path (measured: 28.7 us, as bad).  The pass needs neither: F_x and F_y never
 // touch LDS, a segment's sixteen lanes add them in registers in the tree's order.  74 280 B in both instances.
-template <int TX, int TY, int TMAX, int NT, bool FORCE>
+//
+// TRT (lbm_dtrt_*: the two-relaxation-time collision): dp_collide_cell<true> with the member's omega_m in the collision
+// loop, nothing else.  An ensemble is all TRT or all BGK, so no instance branches per member.
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT>
 __device__ __forceinline__ void dens_tile(const DensArgs a) {
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
   static_assert(TY * (TX / kDpSeg) <= NT, "one lane per segment of the tile");
@@ -184,7 +191,7 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
       g[7] = lds[in][7][c + kRX + 1];
       g[8] = lds[in][8][c + kRX - 1];
       const bool obst = lmask[c] != 0;
-      const double t = dp_collide_cell(g, obst, mc.omega, o);
+      const double t = dp_collide_cell<TRT>(g, obst, mc.omega, mc.omega_m, o);
       if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, mc.aw1, mc.aw2);
 #pragma unroll
       for (int k = 0; k < 9; k++) lds[out][k][c] = o[k];
@@ -212,9 +219,10 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
 }
 
 // The FORCE instance states its two workgroups per CU (NT / 128 waves per SIMD) to the compiler: 60 VGPRs, 78 SGPRs, 0 scratch.
-template <int TX, int TY, int TMAX, int NT, bool FORCE>
-__global__ __launch_bounds__(NT, FORCE ? NT / 128 : 1) void d2q9_dp_ensemble(const DensArgs a) {
-  dens_tile<TX, TY, TMAX, NT, FORCE>(a);
+// So do the TRT instances (DESIGN.md section 3.7 holds their table).
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT>
+__global__ __launch_bounds__(NT, (FORCE || TRT) ? NT / 128 : 1) void d2q9_dp_ensemble(const DensArgs a) {
+  dens_tile<TX, TY, TMAX, NT, FORCE, TRT>(a);
 }
 
 // ---- second reduction stage with a member axis: dp_reduce's partition and order, fixed, no atomics -------------------

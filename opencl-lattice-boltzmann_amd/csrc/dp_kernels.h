@@ -28,10 +28,26 @@ constexpr int kDpSeg = 16;  // cells per row segment of the velocity sum
 
 typedef double v2d __attribute__((ext_vector_type(2)));
 
-// BGK collision of one cell in fp64 (kernels.cl:119-198).  The statements of the fp64 oracle (oracle/d2q9_oracle.c,
-// timestep_row) with pairwise momenta, contraction off: every kernel that inlines this rounds identically, and the cell
-// equals the oracle's pairwise no-FMA build bit for bit.  Returns |u| = sqrt(j^2)/rho of a fluid cell, 0 for an obstacle.
-__device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obstacle, double omega, double (&out)[9]) {
+// The second relaxation rate of the two-relaxation-time operator from omega and the magic parameter
+// Lambda = (1/omega - 1/2)(1/omega_m - 1/2), on the host, in double: the three statements of include/lbm.h ("Two relaxation
+// times"), contraction off.  The callers have refused magic <= 0 and omega >= 2.
+inline double dp_trt_omega_minus(double omega, double magic) {
+#pragma clang fp contract(off)
+  const double tp = 1.0 / omega - 0.5;
+  const double tm = magic / tp + 0.5;
+  const double omega_m = 1.0 / tm;
+  return omega_m;
+}
+
+// Collision of one cell in fp64.  TRT = false: BGK (kernels.cl:119-198), the statements of the fp64 oracle
+// (oracle/d2q9_oracle.c, timestep_row) with pairwise momenta, contraction off: every kernel that inlines this rounds
+// identically, and the cell equals the oracle's pairwise no-FMA build bit for bit; omega_m is not read.  TRT = true: the
+// two-relaxation-time operator of include/lbm.h ("Two relaxation times") - moments, equilibrium and the obstacle branch are
+// the same statements, only the relaxation lines differ: of each pair of opposite speeds the symmetric part of eq - g relaxes
+// with omega, the antisymmetric part with omega_m.  Returns |u| = sqrt(j^2)/rho of a fluid cell, 0 for an obstacle.
+template <bool TRT>
+__device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obstacle, double omega, double omega_m,
+                                                  double (&out)[9]) {
 #pragma clang fp contract(off)
   if (obstacle) {
     // bounce-back: the un-relaxed value leaves through the opposite speed (kernels.cl:69, 187-197)
@@ -64,8 +80,22 @@ __device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obs
     const double tsq = t * uvec[k];
     eq[k] = ((k < 5) ? w1 : w2) * (dens + t + half_densinv_icsq * (tsq - u_sq));
   }
+  if constexpr (TRT) {
+    constexpr int pairs[4][2] = {{1, 3}, {2, 4}, {5, 7}, {6, 8}};
+    out[0] = g[0] + omega * (eq[0] - g[0]);
 #pragma unroll
-  for (int k = 0; k < 9; k++) out[k] = g[k] + omega * (eq[k] - g[k]);
+    for (int i = 0; i < 4; i++) {
+      const int k = pairs[i][0], q = pairs[i][1];
+      const double a = eq[k] - g[k], b = eq[q] - g[q];
+      const double sp = 0.5 * (a + b), sm = 0.5 * (a - b);
+      const double rp = omega * sp, rm = omega_m * sm;
+      out[k] = g[k] + (rp + rm);
+      out[q] = g[q] + (rp - rm);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; k++) out[k] = g[k] + omega * (eq[k] - g[k]);
+  }
   return __builtin_sqrt(u_sq) * densinv;
 }
 
@@ -128,14 +158,16 @@ struct DpStepArgs {
   int lanes_per_row;         // ceil(nx / 2) rounded up to a multiple of 8: eight lanes = one 16-cell segment
   int accel_row;             // row that gets the NEXT step's accelerate_flow, or -1
   double omega, aw1, aw2;
+  double omega_m;            // TRT: the second relaxation rate (dp_trt_omega_minus)
 };
 
 // One timestep, lane = cells x0, x0+1 of one row.  x-1 / x+1 neighbours: aligned 16-B loads plus one scalar load per
 // streamed plane at the wrap column (an L1 hit).  A lane past the row's end (x0 >= nx) only joins the segment sum with 0.
 // FORCE: a lane with a blocked cell also loads that cell's own streamed planes and its eight neighbours' mask bytes, under a
 // branch, for dp_force_cell; fluid cells and lanes past the row's end count +0.0.
+// TRT: dp_collide_cell<true>, nothing else; the false instances are the kernels without it, as with FORCE.
 // static, like the helper kernels below: two translation units include this header (lbm_dp.cpp, lbm_dens.cpp).
-template <bool FORCE>
+template <bool FORCE, bool TRT>
 static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a) {
   const unsigned t = blockIdx.x * kBlock + threadIdx.x;
   const unsigned lpr = (unsigned)a.lanes_per_row;
@@ -186,8 +218,8 @@ static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a
       tfy = has_b ? fya + fyb : fya + 0.0;
     }
     double oa[9], ob[9];
-    const double ta = dp_collide_cell(ga, ob_a, a.omega, oa);
-    const double tb = dp_collide_cell(gb, ob_b, a.omega, ob);
+    const double ta = dp_collide_cell<TRT>(ga, ob_a, a.omega, a.omega_m, oa);
+    const double tb = dp_collide_cell<TRT>(gb, ob_b, a.omega, a.omega_m, ob);
     if (y == a.accel_row) {
       dp_accelerate_cell(oa, ob_a, a.aw1, a.aw2);
       dp_accelerate_cell(ob, ob_b, a.aw1, a.aw2);
@@ -239,6 +271,7 @@ struct DpMultiArgs {
   int T;                    // steps in this launch
   int accel_next;           // apply the following step's accelerate_flow to the final state
   double omega, aw1, aw2;
+  double omega_m;           // TRT: the second relaxation rate (dp_trt_omega_minus)
 };
 
 // T <= TMAX timesteps per launch: a (TX + 2T) x (TY + 2T) region around the TX x TY output tile is loaded into LDS,
@@ -253,8 +286,8 @@ struct DpMultiArgs {
 // and one step per launch (d2q9_dp_step) 3.78 / 4.45 / 9.53, at 1024^2 23.8 against this kernel's 28.2: auto up to 300K cells.
 // FORCE: a blocked cell of the tile has both values of every link in lds[in] and the neighbours' bytes in lmask; a pass of one
 // lane per tile cell before each step's collision loop evaluates dp_force_cell there and adds F_x and F_y per segment in
-// registers, in the tree's order.  No LDS beyond the FORCE = false instance's.
-template <int TX, int TY, int TMAX, bool FORCE>
+// registers, in the tree's order.  No LDS beyond the FORCE = false instance's.  TRT: dp_collide_cell<true> in the collision loop.
+template <int TX, int TY, int TMAX, bool FORCE, bool TRT>
 __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs a) {
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
   constexpr int kRX = TX + 2 * TMAX, kRY = TY + 2 * TMAX;
@@ -364,7 +397,7 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
       g[7] = lds[in][7][c + kRX + 1];
       g[8] = lds[in][8][c + kRX - 1];
       const bool obst = lmask[c] != 0;
-      const double t = dp_collide_cell(g, obst, a.omega, o);
+      const double t = dp_collide_cell<TRT>(g, obst, a.omega, a.omega_m, o);
       if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, a.aw1, a.aw2);
 #pragma unroll
       for (int k = 0; k < 9; k++) lds[out][k][c] = o[k];

@@ -68,6 +68,9 @@ struct lbm_dens {
   double *force_rec = nullptr;     // option "force": [2][n][max_iters], F_x then F_y per member and step
   double *force_now = nullptr;     // [2][n]: lbm_dforce_ens's F_x, F_y (allocated by the first call)
   bool force = false;              // option "force": the kernels' FORCE instances, three values per segment
+  bool trt = false;                // lbm_dtrt_ens_set: the kernels' TRT instances, for all members
+  std::vector<double> magic;       // [n]: every member's magic parameter, 0 while the ensemble is BGK
+  std::vector<double> omega_m;     // [n]: the host's copy of DensMember::omega_m (BGK: the member's omega)
   int nseg = 1, red_blocks = 1, fin_blocks = 1;
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
@@ -121,6 +124,17 @@ int alloc_ring(lbm_dens *e) {
   return LBM_OK;
 }
 
+// The table of per-member constants with these second relaxation rates, to the device
+int upload_members(lbm_dens *e, const std::vector<double> &omega_m) {
+  std::vector<DensMember> t(e->n);
+  for (int i = 0; i < e->n; i++) {
+    t[i] = member_constants<DensMember>(e->p[i]);
+    t[i].omega_m = omega_m[i];
+  }
+  HIP_TRY(hipMemcpy(e->members, t.data(), t.size() * sizeof(DensMember), hipMemcpyHostToDevice));
+  return LBM_OK;
+}
+
 int build_dens(lbm_dens *e, const int32_t *obstacles) {
   const int n = e->n, nx = e->nx, ny = e->ny;
   const size_t cells_per = (size_t)nx * ny;
@@ -162,23 +176,24 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
   if (int rc = upload_mask(e->mask, obstacles, (size_t)n * cells_per)) return rc;
   body_reset(e->body, obstacles, (size_t)n * cells_per);
   // in double these are lbm_dp.cpp's own statements (run_dp_impl, lbm_dp_upload): a member's constants are a context's
-  std::vector<DensMember> t(n);
-  for (int i = 0; i < n; i++) t[i] = member_constants<DensMember>(e->p[i]);
-  HIP_TRY(hipMemcpy(e->members, t.data(), t.size() * sizeof(DensMember), hipMemcpyHostToDevice));
-  return LBM_OK;
+  e->magic.assign(n, 0.0);
+  e->omega_m.resize(n);
+  for (int i = 0; i < n; i++) e->omega_m[i] = e->p[i].omega;
+  return upload_members(e, e->omega_m);
 }
 
 // active: NULL for an ordinary run, the members' words for a leg of a steady run
-template <bool FORCE>
+template <bool FORCE, bool TRT>
 void launch_dens_form(const lbm_dens *e, const DensArgs &a, const int *active) {
   const dim3 grid(e->tiles, e->n), block(kDensThreads);
-  if (!active) hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE>), grid, block, 0, e->q.st, a);
-  else hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE>), grid, block, 0, e->q.st, a, active);
+  if (!active) hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT>), grid, block, 0, e->q.st, a);
+  else hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT>), grid, block, 0, e->q.st, a, active);
 }
 
+// FORCE from the option "force", TRT from lbm_dtrt_ens_set: with both off these are the launches of a library without either
 void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
-  if (e->force) launch_dens_form<true>(e, a, active);
-  else launch_dens_form<false>(e, a, active);
+  if (e->force) e->trt ? launch_dens_form<true, true>(e, a, active) : launch_dens_form<true, false>(e, a, active);
+  else e->trt ? launch_dens_form<false, true>(e, a, active) : launch_dens_form<false, false>(e, a, active);
 }
 
 // Second reduction stage, all members in one launch per stage: the per_step segment sums of each member (per_step apart) and
@@ -659,6 +674,41 @@ int lbm_dbody_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol)
   bool launched = false;
   const int rc = steady_impl(e, max_steps, window, rel_tol, e->force_rec, &launched);
   return latch_failure(rc, launched, e->q.st, &e->failed);
+}
+
+int lbm_dtrt_ens_set(lbm_dens *e, const double *magic) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  // every member is checked before anything changes, on the host or on the device
+  std::vector<double> omega_m(e->n);
+  for (int m = 0; m < e->n; m++) {
+    const double omega = e->p[m].omega;
+    omega_m[m] = omega;
+    if (!magic) continue;
+    if (!(magic[m] > 0.0) || !std::isfinite(magic[m]))
+      return lbm_fail(LBM_ERR_ARG, "member %d: magic must be finite and positive (got %g); an ensemble is all TRT or, with a NULL "
+                      "array, all BGK", m, magic[m]);
+    if (!(1.0 / omega - 0.5 > 0.0))
+      return lbm_fail(LBM_ERR_ARG, "member %d: the two-relaxation-time operator needs 1/omega - 1/2 > 0: omega is %g", m, omega);
+    omega_m[m] = dp_trt_omega_minus(omega, magic[m]);
+  }
+  if (e->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "the collision operator is set before the first step (%d done): one record holds one operator",
+                    e->steps_done);
+  if (int rc = queue_sync(e->q)) return rc;
+  if (int rc = upload_members(e, omega_m)) return rc;
+  e->trt = magic != nullptr;
+  if (magic) e->magic.assign(magic, magic + e->n);
+  else e->magic.assign(e->n, 0.0);
+  e->omega_m = omega_m;
+  return LBM_OK;
+}
+
+int lbm_dtrt_ens_get(const lbm_dens *e, double *magic_out, double *omega_minus_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!magic_out && !omega_minus_out) return lbm_fail(LBM_ERR_ARG, "magic_out and omega_minus_out are both NULL");
+  if (magic_out) std::copy(e->magic.begin(), e->magic.end(), magic_out);
+  if (omega_minus_out) std::copy(e->omega_m.begin(), e->omega_m.end(), omega_minus_out);
+  return LBM_OK;
 }
 
 void lbm_dens_destroy(lbm_dens *e) {

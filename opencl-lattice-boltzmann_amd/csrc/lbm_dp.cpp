@@ -57,6 +57,8 @@ struct lbm_dp {
   int ring = 8, ring_fill = 0;
   int multistep = -1;             // option "multistep": -1 auto, 0 one step per launch, 1..8
   bool force = false;             // option "force": the kernels' FORCE instances, three values per segment
+  double magic = 0.0;             // lbm_dtrt_set: 0 = BGK, > 0 = the TRT instances with this magic parameter
+  double omega_m = 0.0;           // the second relaxation rate of `magic` and p.omega (dp_trt_omega_minus); BGK: p.omega
   int cur = 0, steps_done = 0;
   bool failed = false;
 };
@@ -158,6 +160,31 @@ int reduce_steps(lbm_dp *d, const double *in, size_t in_stride, int steps, doubl
   return LBM_OK;
 }
 
+// The instance the options choose: FORCE from "force", TRT from lbm_dtrt_set.  With both off these are the launches of a
+// library without either.
+template <bool FORCE, bool TRT>
+void launch_multi_form(const lbm_dp *d, const DpMultiArgs &a) {
+  hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
+}
+
+void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
+  const bool trt = d->magic > 0.0;
+  if (d->force) trt ? launch_multi_form<true, true>(d, a) : launch_multi_form<true, false>(d, a);
+  else trt ? launch_multi_form<false, true>(d, a) : launch_multi_form<false, false>(d, a);
+}
+
+template <bool FORCE, bool TRT>
+void launch_step_form(const lbm_dp *d, const DpStepArgs &a) {
+  const dim3 grid((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock));
+  hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT>), grid, dim3(kBlock), 0, d->q.st, a);
+}
+
+void launch_step(const lbm_dp *d, const DpStepArgs &a) {
+  const bool trt = d->magic > 0.0;
+  if (d->force) trt ? launch_step_form<true, true>(d, a) : launch_step_form<true, false>(d, a);
+  else trt ? launch_step_form<false, true>(d, a) : launch_step_form<false, false>(d, a);
+}
+
 int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   if (int rc = check_runnable(nsteps, d->failed, "context")) return rc;
   if (int rc = check_record(d->p.max_iters, d->steps_done, nsteps, "")) return rc;
@@ -218,8 +245,8 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.omega = d->p.omega;
       a.aw1 = aw1;
       a.aw2 = aw2;
-      if (d->force) hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, true>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
-      else hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, false>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
+      a.omega_m = d->omega_m;
+      launch_multi(d, a);
     } else {
       DpStepArgs a{};
       a.src = d->cells[d->cur];
@@ -234,9 +261,8 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.omega = d->p.omega;
       a.aw1 = aw1;
       a.aw2 = aw2;
-      const dim3 grid((unsigned)div_up((long)d->lanes_per_row * ny, kBlock));
-      if (d->force) hipLaunchKernelGGL(d2q9_dp_step<true>, grid, dim3(kBlock), 0, d->q.st, a);
-      else hipLaunchKernelGGL(d2q9_dp_step<false>, grid, dim3(kBlock), 0, d->q.st, a);
+      a.omega_m = d->omega_m;
+      launch_step(d, a);
     }
     HIP_TRY(hipGetLastError());
     d->cur ^= 1;
@@ -285,6 +311,7 @@ int lbm_dp_create(lbm_dp **out, const lbm_dparams *p, const int32_t *obstacles) 
 
   lbm_dp *d = new lbm_dp();
   d->p = *p;
+  d->omega_m = p->omega;
   if (int rc = build_dp(d, obstacles)) {
     const std::string keep = lbm_last_error();
     free_dp(d);
@@ -500,6 +527,29 @@ int lbm_dbody_get(lbm_dp *d, int32_t *body_out) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
   if (!body_out) return lbm_fail(LBM_ERR_ARG, "body_out is NULL");
   body_read(d->body, body_out);
+  return LBM_OK;
+}
+
+int lbm_dtrt_set(lbm_dp *d, double magic) {
+  // argument errors before anything of the context is read
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!(magic >= 0.0) || !std::isfinite(magic))
+    return lbm_fail(LBM_ERR_ARG, "magic must be 0 (BGK) or finite and positive (got %g)", magic);
+  if (magic > 0.0 && !(1.0 / d->p.omega - 0.5 > 0.0))
+    return lbm_fail(LBM_ERR_ARG, "the two-relaxation-time operator needs 1/omega - 1/2 > 0: omega is %g", d->p.omega);
+  if (d->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "the collision operator is set before the first step (%d done): one record holds one operator",
+                    d->steps_done);
+  d->magic = magic;
+  d->omega_m = magic > 0.0 ? dp_trt_omega_minus(d->p.omega, magic) : d->p.omega;
+  return LBM_OK;
+}
+
+int lbm_dtrt_get(const lbm_dp *d, double *magic_out, double *omega_minus_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!magic_out && !omega_minus_out) return lbm_fail(LBM_ERR_ARG, "magic_out and omega_minus_out are both NULL");
+  if (magic_out) *magic_out = d->magic;
+  if (omega_minus_out) *omega_minus_out = d->omega_m;
   return LBM_OK;
 }
 
