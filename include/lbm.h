@@ -810,6 +810,76 @@ int lbm_dtrt_get(const lbm_dp *d, double *magic_out, double *omega_minus_out);
 int lbm_dtrt_ens_set(lbm_dens *e, const double *magic /*[n]*/);
 int lbm_dtrt_ens_get(const lbm_dens *e, double *magic_out /*[n]*/, double *omega_minus_out /*[n]*/);
 
+/*
+ * ---- Open boundaries: velocity inlet and pressure outlet for the double-precision families ------------------------------
+ *
+ * Every double-precision grid is periodic in x and y, and the flow is driven by accelerate_flow on the row ny - 2: a body in
+ * such a channel stands in its own wake, which re-enters from the left, and nothing defines a free-stream velocity or a drag
+ * coefficient.  With open boundaries the fluid cells of column 0 carry a prescribed velocity profile (u_in[y], 0) and the
+ * fluid cells of column nx - 1 a prescribed density rho_out, both by the Zou-He construction: the populations that entered
+ * across the x wrap are replaced by the non-equilibrium bounce-back of their opposites plus what the prescribed moment asks
+ * for.  Off by default: the periodic, accelerated flow of the reference (kernels.cl:9-53, 56-231) keeps every bit.  The
+ * reference has no counterpart.
+ *
+ * Definition.  With open boundaries on, a step is gather, boundary fix, collision.
+ *   Gather.  Unchanged: g[k](x) = f_k(x - c_k), periodic wrap in x and y.
+ *   No accelerate_flow.  It is not applied anywhere: not as the prologue of a run, not fused into a step, not in the output
+ *   stage of the force (lbm_dforce, lbm_dforce_ens).  `accel` in the params is ignored while the setting is on.
+ *   Boundary fix.  It replaces three gathered values of every FLUID cell of column 0 and of column nx - 1, before the collision
+ *   (BGK or TRT, as set).  Blocked cells are untouched and bounce back what they gathered.  All in double, contraction off,
+ *   one IEEE operation per written operator, in this order; 2.0 / 3.0 and 1.0 / 6.0 are double constants.
+ * Inlet, x == 0, fluid, u = u_in[y]:
+ *     s0 = (g[0] + g[2]) + g[4];      s1 = (g[3] + g[6]) + g[7];
+ *     rho = (s0 + 2.0 * s1) / (1.0 - u);
+ *     ru = rho * u;                   d = 0.5 * (g[2] - g[4]);
+ *     g[1] = g[3] + (2.0 / 3.0) * ru;
+ *     g[5] = (g[7] - d) + (1.0 / 6.0) * ru;
+ *     g[8] = (g[6] + d) + (1.0 / 6.0) * ru;
+ * Outlet, x == nx - 1, fluid, rho_out:
+ *     s0 = (g[0] + g[2]) + g[4];      s1 = (g[1] + g[5]) + g[8];
+ *     ru = (s0 + 2.0 * s1) - rho_out; d = 0.5 * (g[2] - g[4]);
+ *     g[3] = g[1] - (2.0 / 3.0) * ru;
+ *     g[7] = (g[5] + d) - (1.0 / 6.0) * ru;
+ *     g[6] = (g[8] - d) - (1.0 / 6.0) * ru;
+ * nx >= 3 holds for every grid, so the two columns are distinct.  Every population that crosses the x wrap into a fluid cell is
+ * one of the six replaced: the fluid is decoupled across the wrap.  The y wrap stays; the channels have walls there.
+ *
+ * Force.  The per-cell definition of "Drag and lift" and the order of every sum are unchanged.  One rule is added: while open
+ * boundaries are on, the blocked cells of columns 0 and nx - 1 count as outside every body (with or without a body map), so
+ * that no link across the x wrap enters a force.  lbm_dbody_get still returns the caller's body.
+ *
+ * Nothing else moves: av_vels, the four fields and the Reynolds number keep their definitions, and every bit identity stated
+ * for the periodic flow holds with open boundaries: between the kernel forms ("multistep"), launch splits and runs; between a
+ * double-precision context and a member of a double-precision ensemble with the same profile and rho_out; between a member
+ * stopped by lbm_dsteady_run or lbm_dbody_steady_run at count c and a plain run of c steps.  It composes with "force", body
+ * maps and TRT.
+ *
+ * When it is accepted.  Only while steps_done is 0, the rule of the option "force" and of lbm_dtrt_set: otherwise
+ * LBM_ERR_STATE.  lbm_dp_upload, lbm_dens_upload and lbm_dp_upload_obstacles keep the setting; the obstacle upload rewrites
+ * the device mask under the column rule above.  An ensemble is all open or all periodic; members differ in profile and
+ * rho_out.  After a refusal nothing has changed, on the host or on the device.
+ *
+ * Names: lbm_dopen_*, on both double-precision handles.  Out of scope: fp32 contexts and fp32 ensembles, whose checker
+ * contract is the reference's periodic flow.
+ */
+
+/* Open boundaries of a double-precision context: u_in = double[ny], borrowed for the call, the inlet velocity of every row
+ * (entries on rows whose column-0 cell is blocked are not read by any kernel but are checked like the others); rho_out the
+ * outlet density.  u_in == NULL: off (the default), rho_out is not read.  LBM_ERR_ARG: a NULL context; rho_out not finite and
+ * positive; a u_in entry that is not finite or is >= 1 (the message names the row).  LBM_ERR_STATE: steps done.  Synchronises. */
+int lbm_dopen_set(lbm_dp *d, const double *u_in /*[ny]*/, double rho_out);
+
+/* on_out: 1 while open boundaries are on, else 0; while they are on, u_in_out = double[ny] and rho_out_out get the setting,
+ * while they are off neither is written.  Any output may be NULL; all three NULL (on_out, u_in_out and rho_out_out), or a NULL
+ * context: LBM_ERR_ARG. */
+int lbm_dopen_get(const lbm_dp *d, int *on_out, double *u_in_out /*[ny]*/, double *rho_out_out);
+
+/* The same for all members of a double-precision ensemble: u_in = double[n][ny], rho_out = double[n]; u_in == NULL: off.
+ * Everything is checked before anything changes, then copied once; the message names the member and the row.  A NULL rho_out
+ * beside a non-NULL u_in: LBM_ERR_ARG. */
+int lbm_dopen_ens_set(lbm_dens *e, const double *u_in /*[n][ny]*/, const double *rho_out /*[n]*/);
+int lbm_dopen_ens_get(const lbm_dens *e, int *on_out, double *u_in_out /*[n][ny]*/, double *rho_out_out /*[n]*/);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

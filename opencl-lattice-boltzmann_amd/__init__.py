@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "lbm_dforce_ens",
     "lbm_dbody_set", "lbm_dbody_get", "lbm_dbody_ens_set", "lbm_dbody_ens_get", "lbm_dbody_steady_run",
     "lbm_dtrt_set", "lbm_dtrt_get", "lbm_dtrt_ens_set", "lbm_dtrt_ens_get",
+    "lbm_dopen_set", "lbm_dopen_get", "lbm_dopen_ens_set", "lbm_dopen_ens_get",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -166,6 +167,10 @@ def load_library():
     L.lbm_dtrt_get.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     L.lbm_dtrt_ens_set.argtypes = [vp, vp]
     L.lbm_dtrt_ens_get.argtypes = [vp, vp, vp]
+    L.lbm_dopen_set.argtypes = [vp, vp, ctypes.c_double]
+    L.lbm_dopen_get.argtypes = [vp, ctypes.POINTER(ci), vp, ctypes.POINTER(ctypes.c_double)]
+    L.lbm_dopen_ens_set.argtypes = [vp, vp, vp]
+    L.lbm_dopen_ens_get.argtypes = [vp, ctypes.POINTER(ci), vp, vp]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -591,6 +596,23 @@ class LBMDouble(_Handle):
         _check(self.lib.lbm_dtrt_get(self.ctx, ctypes.byref(magic), ctypes.byref(om)), "lbm_dtrt_get")
         return magic.value, om.value
 
+    def set_open(self, u_in, rho_out=None):
+        """Open boundaries (lbm_dopen_set): u_in float64[ny], the inlet velocity of every row on column 0, and rho_out, the
+        outlet density on column nx - 1; set_open(None) = periodic and accelerated, the default.  Only before the first step."""
+        if u_in is None:
+            _check(self.lib.lbm_dopen_set(self.ctx, None, 0.0), "lbm_dopen_set")
+            return
+        u = np.ascontiguousarray(u_in, dtype=np.float64)
+        assert u.shape == (self.ny,)
+        _check(self.lib.lbm_dopen_set(self.ctx, u.ctypes.data, float(rho_out)), "lbm_dopen_set")
+
+    def open(self):
+        """(u_in float64[ny], rho_out) while open boundaries are on, None while they are off (lbm_dopen_get)"""
+        on, rho = ctypes.c_int(), ctypes.c_double()
+        u = np.zeros(self.ny, dtype=np.float64)
+        _check(self.lib.lbm_dopen_get(self.ctx, ctypes.byref(on), u.ctypes.data, ctypes.byref(rho)), "lbm_dopen_get")
+        return (u, rho.value) if on.value else None
+
     def force_record(self):
         """(F_x float64[steps_done], F_y float64[steps_done]): the force of every step since the upload; needs
         set_option("force", 1) before the first step."""
@@ -778,6 +800,32 @@ class EnsembleDouble(_EnsembleOf):
         magic, om = np.zeros(self.n, dtype=np.float64), np.zeros(self.n, dtype=np.float64)
         _check(self.lib.lbm_dtrt_ens_get(self.ens, magic.ctypes.data, om.ctypes.data), "lbm_dtrt_ens_get")
         return magic, om
+
+    def set_open(self, u_in, rho_out=None):
+        """Open boundaries of all members (lbm_dopen_ens_set): u_in float64[n, ny] (or one [ny] profile for all), rho_out
+        float64[n] (or one value for all); set_open(None) = periodic and accelerated, the default.  Only before the first
+        step."""
+        if u_in is None:
+            _check(self.lib.lbm_dopen_ens_set(self.ens, None, None), "lbm_dopen_ens_set")
+            return
+        u = np.asarray(u_in, dtype=np.float64)
+        if u.ndim == 1:
+            u = np.broadcast_to(u, (self.n,) + u.shape)
+        u = np.ascontiguousarray(u)
+        r = np.asarray(rho_out, dtype=np.float64)
+        if r.ndim == 0:
+            r = np.full(self.n, float(r), dtype=np.float64)
+        r = np.ascontiguousarray(r)
+        assert u.shape == (self.n, self.ny) and r.shape == (self.n,)
+        _check(self.lib.lbm_dopen_ens_set(self.ens, u.ctypes.data, r.ctypes.data), "lbm_dopen_ens_set")
+
+    def open(self):
+        """(u_in float64[n, ny], rho_out float64[n]) while open boundaries are on, None while they are off
+        (lbm_dopen_ens_get)"""
+        on = ctypes.c_int()
+        u, r = np.zeros((self.n, self.ny), dtype=np.float64), np.zeros(self.n, dtype=np.float64)
+        _check(self.lib.lbm_dopen_ens_get(self.ens, ctypes.byref(on), u.ctypes.data, r.ctypes.data), "lbm_dopen_ens_get")
+        return (u, r) if on.value else None
 
     def run_until(self, max_steps, window=64, rel_tol=1e-4, on="av_vels"):
         """_EnsembleOf.run_until with a choice of criterion: on="av_vels" (lbm_dsteady_run), or on="drag"

@@ -7,6 +7,10 @@
 // same cell to collision, acceleration, fields and av_vels.  The host keeps the 0 / 1 map it made of the caller's obstacle
 // map (`blocked`) and the map of counted cells (`counted`, empty: every blocked cell); the device mask is rewritten from the
 // two, never read back.
+//
+// Open boundaries (include/lbm.h, "Open boundaries"): while they are on, the blocked cells of columns 0 and nx - 1 are outside
+// every body, byte 2, so that no link across the x wrap enters a force.  The host's two maps do not change with the setting:
+// lbm_dbody_get returns the caller's body.
 #pragma once
 #include "host_common.h"
 
@@ -27,14 +31,33 @@ inline void body_reset(BodyMap &b, const int32_t *obstacles, size_t count) {
   b.counted.clear();
 }
 
+// The device bytes of the two maps; `open`: the column rule of open boundaries
+inline std::vector<uint8_t> body_bytes(const std::vector<uint8_t> &blocked, const std::vector<uint8_t> &counted, int nx, bool open) {
+  std::vector<uint8_t> bytes(blocked.size());
+  for (size_t i = 0; i < bytes.size(); i++) {
+    const int x = (int)(i % (size_t)nx);
+    const bool counts = (counted.empty() || counted[i]) && !(open && (x == 0 || x == nx - 1));
+    bytes[i] = blocked[i] ? (counts ? 1 : 2) : 0;
+  }
+  return bytes;
+}
+
+// The device mask once more from the host's maps: open boundaries went on or off, or an obstacle map arrived while they are on
+inline int body_rewrite(const BodyMap &b, uint8_t *mask, int nx, bool open) {
+  const std::vector<uint8_t> bytes = body_bytes(b.blocked, b.counted, nx, open);
+  HIP_TRY(hipMemcpy(mask, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+  return LBM_OK;
+}
+
 // lbm_dbody_set / lbm_dbody_ens_set after their own checks: body == NULL is "every blocked cell".  A non-zero entry on a
 // fluid cell is refused before anything changes, on the host or on the device.  `members` grids of ny x nx; the message
 // names the first such cell, with its member for an ensemble.
-inline int body_apply(BodyMap &b, uint8_t *mask, const int32_t *body, int members, int ny, int nx, bool ensemble) {
+inline int body_apply(BodyMap &b, uint8_t *mask, const int32_t *body, int members, int ny, int nx, bool ensemble, bool open) {
   const size_t per = (size_t)nx * ny, count = per * members;
   if (!body) {
+    const std::vector<uint8_t> bytes = body_bytes(b.blocked, std::vector<uint8_t>(), nx, open);
+    HIP_TRY(hipMemcpy(mask, bytes.data(), count, hipMemcpyHostToDevice));
     b.counted.clear();
-    HIP_TRY(hipMemcpy(mask, b.blocked.data(), count, hipMemcpyHostToDevice));
     return LBM_OK;
   }
   for (size_t i = 0; i < count; i++)
@@ -45,11 +68,9 @@ inline int body_apply(BodyMap &b, uint8_t *mask, const int32_t *body, int member
                         y, x);
       return lbm_fail(LBM_ERR_ARG, "body is non-zero on a fluid cell: y %d, x %d (a body is made of blocked cells)", y, x);
     }
-  std::vector<uint8_t> counted(count), bytes(count);
-  for (size_t i = 0; i < count; i++) {
-    counted[i] = b.blocked[i] && body[i] != 0;
-    bytes[i] = b.blocked[i] ? (counted[i] ? 1 : 2) : 0;
-  }
+  std::vector<uint8_t> counted(count);
+  for (size_t i = 0; i < count; i++) counted[i] = b.blocked[i] && body[i] != 0;
+  const std::vector<uint8_t> bytes = body_bytes(b.blocked, counted, nx, open);
   HIP_TRY(hipMemcpy(mask, bytes.data(), count, hipMemcpyHostToDevice));
   b.counted.swap(counted);
   return LBM_OK;

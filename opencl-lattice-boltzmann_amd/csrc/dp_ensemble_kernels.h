@@ -29,7 +29,7 @@ struct DensArgs {
   const double *src;         // member m: src + m * member_stride
   double *dst;
   const uint8_t *mask;       // member m: mask + m * nx * ny
-  const DensMember *members;
+  const DensMember *members; // [members], and behind them the open-boundary table (OPEN: dens_open_table)
   double *seg;               // [T][members][ny][nseg]: the segment sums of each of the T steps; FORCE:
                              // [T][3][members][ny][nseg], |u|, F_x, F_y
   unsigned long long plane_stride, member_stride;   // row_stride = 9 * plane_stride
@@ -39,6 +39,12 @@ struct DensArgs {
   int T;                     // steps in this launch
   int accel_next;            // apply the following step's accelerate_flow to the final state
 };
+
+// Open boundaries: member m's inlet profile u_in[ny] and, behind it, its rho_out lie m * (ny + 1) doubles into a second table,
+// which starts where the table of DensMember ends: one allocation, and DensArgs is the struct of a library without it.
+__host__ __device__ inline const double *dens_open_table(const DensMember *members, int n) {
+  return reinterpret_cast<const double *>(members + n);
+}
 
 // grid = (tiles per member, members), NT threads.  TX x TY output tile, T <= TMAX steps LDS -> LDS on a region that shrinks
 // by one cell per step (d2q9_dp_multi's scheme; halo cells are computed redundantly by the member's neighbouring tiles).
@@ -71,7 +77,13 @@ struct DensArgs {
 //
 // TRT (lbm_dtrt_*: the two-relaxation-time collision): dp_collide_cell<true> with the member's omega_m in the collision
 // loop, nothing else.  An ensemble is all TRT or all BGK, so no instance branches per member.
-template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT>
+//
+// OPEN (lbm_dopen_*: velocity inlet on column 0, pressure outlet on column nx - 1): d2q9_dp_multi's scheme.  The region load
+// marks the fluid cells of the two columns in spare bits of their lmask byte, the collision loop applies dp_open_inlet /
+// dp_open_outlet to a marked cell before dp_collide_cell and has no accelerate_flow.  The member's u_in on the region's rows
+// and its rho_out are staged in LDS with the region (184 B; reading them from global memory under the branch put a load's
+// latency on every step of an end tile: 23.2 against 19.6 us/step on 64 x 128x128).  An ensemble is all open or all periodic.
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN>
 __device__ __forceinline__ void dens_tile(const DensArgs a) {
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
   static_assert(TY * (TX / kDpSeg) <= NT, "one lane per segment of the tile");
@@ -91,6 +103,14 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
   const uint8_t *const mask = a.mask + (size_t)member * ((size_t)a.nx * a.ny);
   double *const seg_out = a.seg + (size_t)member * ((size_t)a.ny * a.nseg);
   const DensMember mc = a.members[member];
+  // OPEN: the member's profile on the region's rows and, behind them, its rho_out, staged in LDS with the region: a marked
+  // cell reads them under its branch without a global load on a step's critical path, and no register holds an address
+  // across the loops.  184 B.
+  [[maybe_unused]] double *lopen = nullptr;
+  if constexpr (OPEN) {
+    __shared__ double open_rows[kRY + 1];
+    lopen = open_rows;
+  }
   // grid row of region row ry: periodic wrap inside the member (kernels.cl:91-93)
   auto grid_row = [&](int ry) {
     int r = (gy0 + ry) % a.ny;
@@ -124,7 +144,18 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
     const double *p = src + (size_t)gy * rs + gx;
 #pragma unroll
     for (int k = 0; k < 9; k++) lds[0][k][ry * kRX + rx] = p[k * ps];
-    lmask[ry * kRX + rx] = mask[(size_t)gy * a.nx + gx];
+    uint8_t mb = mask[(size_t)gy * a.nx + gx];
+    if constexpr (OPEN) {
+      if (mb == 0 && gx == 0) mb = kOpenInlet;
+      if (mb == 0 && gx == a.nx - 1) mb = kOpenOutlet;
+    }
+    lmask[ry * kRX + rx] = mb;
+  }
+  if constexpr (OPEN) {
+    static_assert(kRY + 1 <= NT, "one lane per region row");
+    const double *u_in = dens_open_table(a.members, (int)gridDim.y) + (size_t)member * (a.ny + 1);
+    if (tid < RY) lopen[tid] = u_in[grid_row(tid)];
+    if (tid == RY) lopen[kRY] = u_in[a.ny];
   }
   __syncthreads();
 
@@ -155,8 +186,10 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
           double own[9];
 #pragma unroll
           for (int k = 0; k < 9; k++) own[k] = f[k][c];
-          const uint8_t nb[9] = {0, lmask[c - 1], lmask[c - kRX], lmask[c + 1], lmask[c + kRX], lmask[c - kRX - 1],
-                                 lmask[c - kRX + 1], lmask[c + kRX + 1], lmask[c + kRX - 1]};
+          // OPEN: a marked fluid neighbour reads as fluid
+          auto nbyte = [&](int at) -> uint8_t { return OPEN ? (uint8_t)(lmask[at] & kOpenBlocked) : lmask[at]; };
+          const uint8_t nb[9] = {0, nbyte(c - 1), nbyte(c - kRX), nbyte(c + 1), nbyte(c + kRX), nbyte(c - kRX - 1),
+                                 nbyte(c - kRX + 1), nbyte(c + kRX + 1), nbyte(c + kRX - 1)};
           dp_force_cell(g, own, nb, fx, fy);
         }
         if (__ballot(counts) != 0ull) {   // a wave without a counting cell adds +0.0 to +0.0
@@ -174,7 +207,7 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
     }
     const int in = (s - 1) & 1, out = s & 1;
     const int w = RX - 2 * s, h = RY - 2 * s;
-    const bool accel_step = (s < T) || a.accel_next;
+    [[maybe_unused]] const bool accel_step = (s < T) || a.accel_next;
     const float inv = 1.0f / (float)w;
     for (int i = tid; i < w * h; i += NT) {
       const int q = (int)(((float)i + 0.5f) * inv);
@@ -190,9 +223,15 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
       g[6] = lds[in][6][c - kRX + 1];
       g[7] = lds[in][7][c + kRX + 1];
       g[8] = lds[in][8][c + kRX - 1];
-      const bool obst = lmask[c] != 0;
+      const uint8_t mb = lmask[c];
+      const bool obst = OPEN ? (mb & kOpenBlocked) != 0 : mb != 0;
+      if constexpr (OPEN) {
+        if (mb & kOpenInlet) dp_open_inlet(g, lopen[ry]);
+        else if (mb & kOpenOutlet) dp_open_outlet(g, lopen[kRY]);
+      }
       const double t = dp_collide_cell<TRT>(g, obst, mc.omega, mc.omega_m, o);
-      if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, mc.aw1, mc.aw2);
+      if constexpr (!OPEN)
+        if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, mc.aw1, mc.aw2);
 #pragma unroll
       for (int k = 0; k < 9; k++) lds[out][k][c] = o[k];
       // the tile's own cells: every one is inside the region of every step; cells past the grid's edge count 0
@@ -219,10 +258,10 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
 }
 
 // The FORCE instance states its two workgroups per CU (NT / 128 waves per SIMD) to the compiler: 60 VGPRs, 78 SGPRs, 0 scratch.
-// So do the TRT instances (DESIGN.md section 3.7 holds their table).
-template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT>
-__global__ __launch_bounds__(NT, (FORCE || TRT) ? NT / 128 : 1) void d2q9_dp_ensemble(const DensArgs a) {
-  dens_tile<TX, TY, TMAX, NT, FORCE, TRT>(a);
+// So do the TRT and the OPEN instances (DESIGN.md section 3.7 holds their tables).
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN>
+__global__ __launch_bounds__(NT, (FORCE || TRT || OPEN) ? NT / 128 : 1) void d2q9_dp_ensemble(const DensArgs a) {
+  dens_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN>(a);
 }
 
 // ---- second reduction stage with a member axis: dp_reduce's partition and order, fixed, no atomics -------------------

@@ -108,6 +108,36 @@ __device__ __forceinline__ void dp_accelerate_cell(double (&f)[9], bool obstacle
   }
 }
 
+// Open boundaries (include/lbm.h, "Open boundaries"): the Zou-He fix of a FLUID cell's gathered values, between gather and
+// dp_collide_cell.  The inlet (column 0) replaces the three values that crossed the x wrap from column nx - 1 so that the
+// cell carries the velocity (u, 0); the outlet (column nx - 1) replaces the three that came from column 0 so that it carries
+// the density rho_out.  The header's statements, one IEEE operation per operator, contraction off.
+__device__ __forceinline__ void dp_open_inlet(double (&g)[9], double u) {
+#pragma clang fp contract(off)
+  const double s0 = (g[0] + g[2]) + g[4];
+  const double s1 = (g[3] + g[6]) + g[7];
+  const double rho = (s0 + 2.0 * s1) / (1.0 - u);
+  const double ru = rho * u;
+  const double d = 0.5 * (g[2] - g[4]);
+  g[1] = g[3] + (2.0 / 3.0) * ru;
+  g[5] = (g[7] - d) + (1.0 / 6.0) * ru;
+  g[8] = (g[6] + d) + (1.0 / 6.0) * ru;
+}
+__device__ __forceinline__ void dp_open_outlet(double (&g)[9], double rho_out) {
+#pragma clang fp contract(off)
+  const double s0 = (g[0] + g[2]) + g[4];
+  const double s1 = (g[1] + g[5]) + g[8];
+  const double ru = (s0 + 2.0 * s1) - rho_out;
+  const double d = 0.5 * (g[2] - g[4]);
+  g[3] = g[1] - (2.0 / 3.0) * ru;
+  g[7] = (g[5] + d) - (1.0 / 6.0) * ru;
+  g[6] = (g[8] - d) - (1.0 / 6.0) * ru;
+}
+
+// The LDS-tile kernels' mark of a fluid cell of column 0 / column nx - 1 in its lmask byte (OPEN instances only): the region
+// load knows the grid column, the collision loop does not.  Blocked-ness is the low two bits there (body_map.h: 0, 1, 2).
+constexpr uint8_t kOpenInlet = 4, kOpenOutlet = 8, kOpenBlocked = 3;
+
 // Momentum-exchange force on one blocked cell o in the step that streams the state f (include/lbm.h): for k = 1..8 in
 // ascending order, if the neighbour x = o - c_k is fluid, s = f_k(x) + f_opp(k)(o) goes into F with the signs of c_k.
 //   g[k]   = f_k(o - c_k), what o gathers in that step        own[k] = o's own stored f_k
@@ -159,6 +189,8 @@ struct DpStepArgs {
   int accel_row;             // row that gets the NEXT step's accelerate_flow, or -1
   double omega, aw1, aw2;
   double omega_m;            // TRT: the second relaxation rate (dp_trt_omega_minus)
+  const double *u_in;        // OPEN: the inlet profile, [ny]
+  double rho_out;            // OPEN: the outlet density
 };
 
 // One timestep, lane = cells x0, x0+1 of one row.  x-1 / x+1 neighbours: aligned 16-B loads plus one scalar load per
@@ -166,8 +198,11 @@ struct DpStepArgs {
 // FORCE: a lane with a blocked cell also loads that cell's own streamed planes and its eight neighbours' mask bytes, under a
 // branch, for dp_force_cell; fluid cells and lanes past the row's end count +0.0.
 // TRT: dp_collide_cell<true>, nothing else; the false instances are the kernels without it, as with FORCE.
+// OPEN: the fluid cell of column 0 (cell a of the lane x0 == 0) and of column nx - 1 (cell b where nx is even, cell a of the
+// row's last lane where it is odd) go through dp_open_inlet / dp_open_outlet before the collision; the host passes accel_row
+// -1.  The false instances are the kernels without it.
 // static, like the helper kernels below: two translation units include this header (lbm_dp.cpp, lbm_dens.cpp).
-template <bool FORCE, bool TRT>
+template <bool FORCE, bool TRT, bool OPEN>
 static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a) {
   const unsigned t = blockIdx.x * kBlock + threadIdx.x;
   const unsigned lpr = (unsigned)a.lanes_per_row;
@@ -216,6 +251,14 @@ static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a
       if (has_b && m[1] == 1) cell_force(x0 + 1, gb, fxb, fyb);
       tfx = has_b ? fxa + fxb : fxa + 0.0;
       tfy = has_b ? fya + fyb : fya + 0.0;
+    }
+    if constexpr (OPEN) {
+      if (x0 == 0 && !ob_a) dp_open_inlet(ga, a.u_in[y]);
+      if (has_b) {
+        if (x0 + 2 == a.nx && !ob_b) dp_open_outlet(gb, a.rho_out);
+      } else if (!ob_a) {
+        dp_open_outlet(ga, a.rho_out);   // nx odd: the row's last lane holds column nx - 1 alone
+      }
     }
     double oa[9], ob[9];
     const double ta = dp_collide_cell<TRT>(ga, ob_a, a.omega, a.omega_m, oa);
@@ -272,6 +315,8 @@ struct DpMultiArgs {
   int accel_next;           // apply the following step's accelerate_flow to the final state
   double omega, aw1, aw2;
   double omega_m;           // TRT: the second relaxation rate (dp_trt_omega_minus)
+  const double *u_in;       // OPEN: the inlet profile, [ny]
+  double rho_out;           // OPEN: the outlet density
 };
 
 // T <= TMAX timesteps per launch: a (TX + 2T) x (TY + 2T) region around the TX x TY output tile is loaded into LDS,
@@ -287,7 +332,12 @@ struct DpMultiArgs {
 // FORCE: a blocked cell of the tile has both values of every link in lds[in] and the neighbours' bytes in lmask; a pass of one
 // lane per tile cell before each step's collision loop evaluates dp_force_cell there and adds F_x and F_y per segment in
 // registers, in the tree's order.  No LDS beyond the FORCE = false instance's.  TRT: dp_collide_cell<true> in the collision loop.
-template <int TX, int TY, int TMAX, bool FORCE, bool TRT>
+// OPEN: the fix keys on the GRID column of every region cell (a tile at one end of the grid recomputes cells of the other end
+// in its halo, and a region wider than nx holds column 0 more than once).  The region load, which has the grid column, marks
+// the fluid cells of columns 0 and nx - 1 in two spare bits of their lmask byte; the collision loop branches on the byte it
+// reads anyway, and blocked-ness is the low two bits, the neighbour bytes of the force pass included.  The profile on the
+// region's rows is staged in LDS with the region (256 B).  No accelerate_flow.
+template <int TX, int TY, int TMAX, bool FORCE, bool TRT, bool OPEN>
 __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs a) {
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
   constexpr int kRX = TX + 2 * TMAX, kRY = TY + 2 * TMAX;
@@ -295,6 +345,12 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
   __shared__ uint8_t lmask[kRY * kRX];
   __shared__ double tval[2][TY][TX];
   const int tid = threadIdx.x;
+  // OPEN: the profile on the region's rows, staged with the region (dp_ensemble_kernels.h says why)
+  [[maybe_unused]] double *lopen = nullptr;
+  if constexpr (OPEN) {
+    __shared__ double open_rows[kRY];
+    lopen = open_rows;
+  }
   const int T = a.T;
   const int RX = TX + 2 * T, RY = TY + 2 * T;
   const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
@@ -330,7 +386,16 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
     const double *p = a.src + (size_t)gy * rs + gx;
 #pragma unroll
     for (int k = 0; k < 9; k++) lds[0][k][ry * kRX + rx] = p[k * ps];
-    lmask[ry * kRX + rx] = a.mask[(size_t)gy * a.nx + gx];
+    uint8_t mb = a.mask[(size_t)gy * a.nx + gx];
+    if constexpr (OPEN) {
+      if (mb == 0 && gx == 0) mb = kOpenInlet;
+      if (mb == 0 && gx == a.nx - 1) mb = kOpenOutlet;
+    }
+    lmask[ry * kRX + rx] = mb;
+  }
+  if constexpr (OPEN) {
+    static_assert(kRY <= kMultiThreads, "one lane per region row");
+    if (tid < RY) lopen[tid] = a.u_in[grid_row(tid)];
   }
   __syncthreads();
 
@@ -361,8 +426,10 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
           double own[9];
 #pragma unroll
           for (int k = 0; k < 9; k++) own[k] = f[k][c];
-          const uint8_t nb[9] = {0, lmask[c - 1], lmask[c - kRX], lmask[c + 1], lmask[c + kRX], lmask[c - kRX - 1],
-                                 lmask[c - kRX + 1], lmask[c + kRX + 1], lmask[c + kRX - 1]};
+          // OPEN: a marked fluid neighbour reads as fluid
+          auto nbyte = [&](int at) -> uint8_t { return OPEN ? (uint8_t)(lmask[at] & kOpenBlocked) : lmask[at]; };
+          const uint8_t nb[9] = {0, nbyte(c - 1), nbyte(c - kRX), nbyte(c + 1), nbyte(c + kRX), nbyte(c - kRX - 1),
+                                 nbyte(c - kRX + 1), nbyte(c + kRX + 1), nbyte(c + kRX - 1)};
           dp_force_cell(g, own, nb, fx, fy);
         }
         if (__ballot(counts) != 0ull) {   // a wave without a counting cell adds +0.0 to +0.0
@@ -380,7 +447,7 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
     }
     const int in = (s - 1) & 1, out = s & 1;
     const int w = RX - 2 * s, h = RY - 2 * s;
-    const bool accel_step = (s < T) || a.accel_next;
+    [[maybe_unused]] const bool accel_step = (s < T) || a.accel_next;
     const float inv = 1.0f / (float)w;
     for (int i = tid; i < w * h; i += kMultiThreads) {
       const int q = (int)(((float)i + 0.5f) * inv);
@@ -396,9 +463,15 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
       g[6] = lds[in][6][c - kRX + 1];
       g[7] = lds[in][7][c + kRX + 1];
       g[8] = lds[in][8][c + kRX - 1];
-      const bool obst = lmask[c] != 0;
+      const uint8_t mb = lmask[c];
+      const bool obst = OPEN ? (mb & kOpenBlocked) != 0 : mb != 0;
+      if constexpr (OPEN) {
+        if (mb & kOpenInlet) dp_open_inlet(g, lopen[ry]);
+        else if (mb & kOpenOutlet) dp_open_outlet(g, a.rho_out);
+      }
       const double t = dp_collide_cell<TRT>(g, obst, a.omega, a.omega_m, o);
-      if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, a.aw1, a.aw2);
+      if constexpr (!OPEN)
+        if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, a.aw1, a.aw2);
 #pragma unroll
       for (int k = 0; k < 9; k++) lds[out][k][c] = o[k];
       // the tile's own cells: every one is inside the region of every step; cells past the grid's edge count 0
@@ -548,6 +621,7 @@ struct DpForceArgs {
   int nx, ny;
   int lanes_per_row;         // as DpStepArgs
   double aw1, aw2;
+  int no_accel;              // open boundaries: the next step has no accelerate_flow, the neighbours' values go as stored
 };
 
 static __global__ __launch_bounds__(kBlock) void dp_force_state(const DpForceArgs a) {
@@ -586,7 +660,7 @@ static __global__ __launch_bounds__(kBlock) void dp_force_state(const DpForceArg
           const double *q = cells + (size_t)qy[k] * rs + qx[k];
 #pragma unroll
           for (int j = 0; j < 9; j++) f[j] = q[j * ps];
-          if (qy[k] == a.ny - 2) dp_accelerate_cell(f, false, aw1, aw2);
+          if (!a.no_accel && qy[k] == a.ny - 2) dp_accelerate_cell(f, false, aw1, aw2);
           g[k] = f[k];
         }
       }

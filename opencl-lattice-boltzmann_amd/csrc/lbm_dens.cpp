@@ -60,7 +60,7 @@ struct lbm_dens {
   double *cells[2] = {nullptr, nullptr};
   uint8_t *mask = nullptr;         // [n][ny][nx]: 0 fluid, 1 blocked and counted in the force, 2 blocked outside the body
   BodyMap body;                    // the host's copy of what the mask was made of (body_map.h)
-  DensMember *members = nullptr;   // [n]
+  DensMember *members = nullptr;   // [n], then the open-boundary table double[n][ny + 1] (dens_open_table)
   double *seg = nullptr;           // [ring][n][ny][nseg]
   double *red = nullptr;           // [ring][n][red_blocks]: first reduction stage
   double *av_sum = nullptr;        // [n][max_iters]
@@ -71,6 +71,8 @@ struct lbm_dens {
   bool trt = false;                // lbm_dtrt_ens_set: the kernels' TRT instances, for all members
   std::vector<double> magic;       // [n]: every member's magic parameter, 0 while the ensemble is BGK
   std::vector<double> omega_m;     // [n]: the host's copy of DensMember::omega_m (BGK: the member's omega)
+  bool open = false;               // lbm_dopen_ens_set: the kernels' OPEN instances for all members, no accelerate_flow
+  std::vector<double> open_host;   // [n][ny + 1]: per member u_in[ny], then rho_out (empty while off); on the device behind `members`
   int nseg = 1, red_blocks = 1, fin_blocks = 1;
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
@@ -153,7 +155,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
 
   // what the ensemble needs against what the device has free: refuse here rather than fail half-way through
   const size_t cells_bytes = ((size_t)n * e->member_stride + 32) * sizeof(double);
-  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + (size_t)n * sizeof(DensMember) +
+  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + (size_t)n * (sizeof(DensMember) + (size_t)(ny + 1) * sizeof(double)) +
                       (size_t)e->ring * all_step * sizeof(double) + (size_t)e->ring * n * e->red_blocks * sizeof(double) +
                       (size_t)n * e->max_iters * sizeof(double) + (size_t)n * e->fin_blocks * sizeof(double);
   size_t free_b = 0, total_b = 0;
@@ -168,7 +170,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
     HIP_TRY(hipMemset(e->cells[i], 0, cells_bytes));
   }
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->mask), (size_t)n * cells_per + 64));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), (size_t)n * sizeof(DensMember)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), (size_t)n * (sizeof(DensMember) + (size_t)(ny + 1) * sizeof(double))));
   if (int rc = alloc_ring(e)) return rc;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->av_sum), (size_t)n * e->max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->fin_partials), (size_t)n * e->fin_blocks * sizeof(double)));
@@ -183,17 +185,23 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
 }
 
 // active: NULL for an ordinary run, the members' words for a leg of a steady run
-template <bool FORCE, bool TRT>
+template <bool FORCE, bool TRT, bool OPEN>
 void launch_dens_form(const lbm_dens *e, const DensArgs &a, const int *active) {
   const dim3 grid(e->tiles, e->n), block(kDensThreads);
-  if (!active) hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT>), grid, block, 0, e->q.st, a);
-  else hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT>), grid, block, 0, e->q.st, a, active);
+  if (!active) hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN>), grid, block, 0, e->q.st, a);
+  else hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN>), grid, block, 0, e->q.st, a, active);
 }
 
-// FORCE from the option "force", TRT from lbm_dtrt_ens_set: with both off these are the launches of a library without either
+template <bool FORCE, bool TRT>
+void launch_dens_open(const lbm_dens *e, const DensArgs &a, const int *active) {
+  e->open ? launch_dens_form<FORCE, TRT, true>(e, a, active) : launch_dens_form<FORCE, TRT, false>(e, a, active);
+}
+
+// FORCE from the option "force", TRT from lbm_dtrt_ens_set, OPEN from lbm_dopen_ens_set: with all off these are the launches
+// of a library without any of them
 void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
-  if (e->force) e->trt ? launch_dens_form<true, true>(e, a, active) : launch_dens_form<true, false>(e, a, active);
-  else e->trt ? launch_dens_form<false, true>(e, a, active) : launch_dens_form<false, false>(e, a, active);
+  if (e->force) e->trt ? launch_dens_open<true, true>(e, a, active) : launch_dens_open<true, false>(e, a, active);
+  else e->trt ? launch_dens_open<false, true>(e, a, active) : launch_dens_open<false, false>(e, a, active);
 }
 
 // Second reduction stage, all members in one launch per stage: the per_step segment sums of each member (per_step apart) and
@@ -225,10 +233,12 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   const int nval = seg_values(e);
   const size_t slot = all_step * nval;   // one step in the ring: [nval][n][ny][nseg]
   // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
-  // into the previous launch's write of row ny-2
-  hipLaunchKernelGGL(dens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
-                     e->member_stride, (const uint8_t *)e->mask, (const DensMember *)e->members, e->nx, e->ny, active);
-  HIP_TRY(hipGetLastError());
+  // into the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
+  if (!e->open) {
+    hipLaunchKernelGGL(dens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
+                       e->member_stride, (const uint8_t *)e->mask, (const DensMember *)e->members, e->nx, e->ny, active);
+    HIP_TRY(hipGetLastError());
+  }
 
   int batch_first = first;
   // second reduction stage over the buffered steps: |u| into av_sum and, with "force", F_x and F_y into their records,
@@ -265,7 +275,7 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
     a.nseg = e->nseg;
     a.tiles_x = e->tiles_x;
     a.T = adv;
-    a.accel_next = (i + adv < nsteps) ? 1 : 0;
+    a.accel_next = (!e->open && i + adv < nsteps) ? 1 : 0;
     launch_dens(e, a, active);
     HIP_TRY(hipGetLastError());
     e->cur ^= 1;
@@ -633,6 +643,7 @@ int lbm_dforce_ens(lbm_dens *e, double *fx, double *fy) {
   a.nx = e->nx;
   a.ny = e->ny;
   a.lanes_per_row = e->nseg * 8;
+  a.no_accel = e->open ? 1 : 0;
   hipLaunchKernelGGL(dp_force_state, dim3((unsigned)div_up((long)a.lanes_per_row * e->ny, kBlock), e->n), dim3(kBlock), 0, e->q.st, a);
   HIP_TRY(hipGetLastError());
   for (int c = 0; c < 2; c++)
@@ -653,7 +664,7 @@ int lbm_dbody_ens_set(lbm_dens *e, const int32_t *body) {
     return lbm_fail(LBM_ERR_STATE, "with \"force\" on, a body map is set before the first step (%d done): one record holds one body",
                     e->steps_done);
   if (int rc = queue_sync(e->q)) return rc;
-  return body_apply(e->body, e->mask, body, e->n, e->ny, e->nx, true);
+  return body_apply(e->body, e->mask, body, e->n, e->ny, e->nx, true, e->open);
 }
 
 int lbm_dbody_ens_get(lbm_dens *e, int32_t *body_out) {
@@ -708,6 +719,56 @@ int lbm_dtrt_ens_get(const lbm_dens *e, double *magic_out, double *omega_minus_o
   if (!magic_out && !omega_minus_out) return lbm_fail(LBM_ERR_ARG, "magic_out and omega_minus_out are both NULL");
   if (magic_out) std::copy(e->magic.begin(), e->magic.end(), magic_out);
   if (omega_minus_out) std::copy(e->omega_m.begin(), e->omega_m.end(), omega_minus_out);
+  return LBM_OK;
+}
+
+int lbm_dopen_ens_set(lbm_dens *e, const double *u_in, const double *rho_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (u_in && !rho_out) return lbm_fail(LBM_ERR_ARG, "rho_out is NULL (u_in is not: every member needs its outlet density)");
+  // every member is checked before anything changes, on the host or on the device
+  const size_t ny = (size_t)e->ny;
+  std::vector<double> table;
+  if (u_in) {
+    table.resize((size_t)e->n * (ny + 1));
+    for (int m = 0; m < e->n; m++) {
+      if (!positive_finite(rho_out[m]))
+        return lbm_fail(LBM_ERR_ARG, "member %d: rho_out must be finite and positive (got %g)", m, rho_out[m]);
+      for (size_t y = 0; y < ny; y++) {
+        const double u = u_in[(size_t)m * ny + y];
+        if (!std::isfinite(u) || !(u < 1.0))
+          return lbm_fail(LBM_ERR_ARG, "member %d: u_in of row %d must be finite and below 1 (got %g)", m, (int)y, u);
+        table[(size_t)m * (ny + 1) + y] = u;
+      }
+      table[(size_t)m * (ny + 1) + ny] = rho_out[m];
+    }
+  }
+  if (e->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "open boundaries are set before the first step (%d done): one record holds one flow",
+                    e->steps_done);
+  if (!u_in && !e->open) return LBM_OK;
+  if (int rc = queue_sync(e->q)) return rc;
+  HIP_TRY(hipSetDevice(e->q.dev));
+  if (u_in)
+    HIP_TRY(hipMemcpy(const_cast<double *>(dens_open_table(e->members, e->n)), table.data(), table.size() * sizeof(double),
+                      hipMemcpyHostToDevice));
+  // the device mask under the column rule, or without it again
+  if (int rc = body_rewrite(e->body, e->mask, e->nx, u_in != nullptr)) return rc;
+  e->open = u_in != nullptr;
+  e->open_host.swap(table);
+  return LBM_OK;
+}
+
+int lbm_dopen_ens_get(const lbm_dens *e, int *on_out, double *u_in_out, double *rho_out_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!on_out && !u_in_out && !rho_out_out) return lbm_fail(LBM_ERR_ARG, "on_out, u_in_out and rho_out_out are all NULL");
+  if (on_out) *on_out = e->open ? 1 : 0;
+  if (!e->open) return LBM_OK;
+  const size_t ny = (size_t)e->ny;
+  for (int m = 0; m < e->n; m++) {
+    const double *row = e->open_host.data() + (size_t)m * (ny + 1);
+    if (u_in_out) std::copy(row, row + ny, u_in_out + (size_t)m * ny);
+    if (rho_out_out) rho_out_out[m] = row[ny];
+  }
   return LBM_OK;
 }
 

@@ -59,6 +59,10 @@ struct lbm_dp {
   bool force = false;             // option "force": the kernels' FORCE instances, three values per segment
   double magic = 0.0;             // lbm_dtrt_set: 0 = BGK, > 0 = the TRT instances with this magic parameter
   double omega_m = 0.0;           // the second relaxation rate of `magic` and p.omega (dp_trt_omega_minus); BGK: p.omega
+  bool open = false;              // lbm_dopen_set: the kernels' OPEN instances, no accelerate_flow
+  std::vector<double> u_in;       // [ny]: the host's copy of the inlet profile (empty while off)
+  double rho_out = 0.0;           // the outlet density
+  double *u_in_dev = nullptr;     // [ny] (allocated by the first lbm_dopen_set that switches on)
   int cur = 0, steps_done = 0;
   bool failed = false;
 };
@@ -82,6 +86,7 @@ void free_dp(lbm_dp *d) {
   if (d->fin_partials) (void)hipFree(d->fin_partials);
   if (d->force_rec) (void)hipFree(d->force_rec);
   if (d->force_now) (void)hipFree(d->force_now);
+  if (d->u_in_dev) (void)hipFree(d->u_in_dev);
   queue_destroy(d->q);
   delete d;
 }
@@ -160,29 +165,39 @@ int reduce_steps(lbm_dp *d, const double *in, size_t in_stride, int steps, doubl
   return LBM_OK;
 }
 
-// The instance the options choose: FORCE from "force", TRT from lbm_dtrt_set.  With both off these are the launches of a
-// library without either.
-template <bool FORCE, bool TRT>
+// The instance the options choose: FORCE from "force", TRT from lbm_dtrt_set, OPEN from lbm_dopen_set.  With all off these
+// are the launches of a library without any of them.
+template <bool FORCE, bool TRT, bool OPEN>
 void launch_multi_form(const lbm_dp *d, const DpMultiArgs &a) {
-  hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
+  hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT, OPEN>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
+}
+
+template <bool FORCE, bool TRT>
+void launch_multi_open(const lbm_dp *d, const DpMultiArgs &a) {
+  d->open ? launch_multi_form<FORCE, TRT, true>(d, a) : launch_multi_form<FORCE, TRT, false>(d, a);
 }
 
 void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
   const bool trt = d->magic > 0.0;
-  if (d->force) trt ? launch_multi_form<true, true>(d, a) : launch_multi_form<true, false>(d, a);
-  else trt ? launch_multi_form<false, true>(d, a) : launch_multi_form<false, false>(d, a);
+  if (d->force) trt ? launch_multi_open<true, true>(d, a) : launch_multi_open<true, false>(d, a);
+  else trt ? launch_multi_open<false, true>(d, a) : launch_multi_open<false, false>(d, a);
+}
+
+template <bool FORCE, bool TRT, bool OPEN>
+void launch_step_form(const lbm_dp *d, const DpStepArgs &a) {
+  const dim3 grid((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock));
+  hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT, OPEN>), grid, dim3(kBlock), 0, d->q.st, a);
 }
 
 template <bool FORCE, bool TRT>
-void launch_step_form(const lbm_dp *d, const DpStepArgs &a) {
-  const dim3 grid((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock));
-  hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT>), grid, dim3(kBlock), 0, d->q.st, a);
+void launch_step_open(const lbm_dp *d, const DpStepArgs &a) {
+  d->open ? launch_step_form<FORCE, TRT, true>(d, a) : launch_step_form<FORCE, TRT, false>(d, a);
 }
 
 void launch_step(const lbm_dp *d, const DpStepArgs &a) {
   const bool trt = d->magic > 0.0;
-  if (d->force) trt ? launch_step_form<true, true>(d, a) : launch_step_form<true, false>(d, a);
-  else trt ? launch_step_form<false, true>(d, a) : launch_step_form<false, false>(d, a);
+  if (d->force) trt ? launch_step_open<true, true>(d, a) : launch_step_open<true, false>(d, a);
+  else trt ? launch_step_open<false, true>(d, a) : launch_step_open<false, false>(d, a);
 }
 
 int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
@@ -201,10 +216,12 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   const int T = multistep_effective(d);
   if (int rc = timed_begin(d->q, timed)) return rc;
   // prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53); later steps get theirs fused into
-  // the previous launch's write of row ny-2
-  hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(nx, 128)), dim3(128), 0, d->q.st, d->cells[d->cur], d->plane_stride, d->mask,
-                     nx, ny - 2, aw1, aw2);
-  HIP_TRY(hipGetLastError());
+  // the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
+  if (!d->open) {
+    hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(nx, 128)), dim3(128), 0, d->q.st, d->cells[d->cur], d->plane_stride, d->mask,
+                       nx, ny - 2, aw1, aw2);
+    HIP_TRY(hipGetLastError());
+  }
 
   int batch_first = d->steps_done;
   // second reduction stage over the buffered steps
@@ -226,7 +243,7 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
     const int adv = T > 0 ? equal_depth(rem, T) : 1;
     if (d->ring_fill + adv > d->ring)
       if (int rc = flush()) return rc;
-    const bool accel_next = i + adv < nsteps;
+    const bool accel_next = !d->open && i + adv < nsteps;
     double *seg = d->seg + (size_t)d->ring_fill * slot;
     if (T > 0) {
       DpMultiArgs a{};
@@ -246,6 +263,8 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.aw1 = aw1;
       a.aw2 = aw2;
       a.omega_m = d->omega_m;
+      a.u_in = d->u_in_dev;
+      a.rho_out = d->rho_out;
       launch_multi(d, a);
     } else {
       DpStepArgs a{};
@@ -262,6 +281,8 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.aw1 = aw1;
       a.aw2 = aw2;
       a.omega_m = d->omega_m;
+      a.u_in = d->u_in_dev;
+      a.rho_out = d->rho_out;
       launch_step(d, a);
     }
     HIP_TRY(hipGetLastError());
@@ -350,6 +371,8 @@ int lbm_dp_upload_obstacles(lbm_dp *d, const int32_t *obstacles) {
   // the body map, if one was set, described the old map's blocked cells: every blocked cell counts again
   if (int rc = upload_mask(d->mask, obstacles, (size_t)d->p.nx * d->p.ny)) return rc;
   body_reset(d->body, obstacles, (size_t)d->p.nx * d->p.ny);
+  // open boundaries stay on: the blocked cells of columns 0 and nx - 1 are outside every body
+  if (d->open) return body_rewrite(d->body, d->mask, d->p.nx, true);
   return LBM_OK;
 }
 
@@ -501,6 +524,7 @@ int lbm_dforce(lbm_dp *d, double *fx, double *fy) {
   a.lanes_per_row = d->lanes_per_row;
   a.aw1 = d->p.density * d->p.accel / 9.0;   // kernels.cl:14-15, run_dp_impl's statements
   a.aw2 = d->p.density * d->p.accel / 36.0;
+  a.no_accel = d->open ? 1 : 0;
   hipLaunchKernelGGL(dp_force_state, dim3((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock), 1), dim3(kBlock), 0, d->q.st, a);
   HIP_TRY(hipGetLastError());
   for (int c = 0; c < 2; c++)
@@ -519,7 +543,7 @@ int lbm_dbody_set(lbm_dp *d, const int32_t *body) {
     return lbm_fail(LBM_ERR_STATE, "with \"force\" on, a body map is set before the first step (%d done): one record holds one body",
                     d->steps_done);
   if (int rc = queue_sync(d->q)) return rc;
-  return body_apply(d->body, d->mask, body, 1, d->p.ny, d->p.nx, false);
+  return body_apply(d->body, d->mask, body, 1, d->p.ny, d->p.nx, false, d->open);
 }
 
 int lbm_dbody_get(lbm_dp *d, int32_t *body_out) {
@@ -550,6 +574,42 @@ int lbm_dtrt_get(const lbm_dp *d, double *magic_out, double *omega_minus_out) {
   if (!magic_out && !omega_minus_out) return lbm_fail(LBM_ERR_ARG, "magic_out and omega_minus_out are both NULL");
   if (magic_out) *magic_out = d->magic;
   if (omega_minus_out) *omega_minus_out = d->omega_m;
+  return LBM_OK;
+}
+
+int lbm_dopen_set(lbm_dp *d, const double *u_in, double rho_out) {
+  // argument errors before anything of the context is read, or before a device is touched
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (u_in && !positive_finite(rho_out)) return lbm_fail(LBM_ERR_ARG, "rho_out must be finite and positive (got %g)", rho_out);
+  if (u_in)
+    for (int y = 0; y < d->p.ny; y++)
+      if (!std::isfinite(u_in[y]) || !(u_in[y] < 1.0))
+        return lbm_fail(LBM_ERR_ARG, "u_in of row %d must be finite and below 1 (got %g)", y, u_in[y]);
+  if (d->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "open boundaries are set before the first step (%d done): one record holds one flow",
+                    d->steps_done);
+  if (!u_in && !d->open) return LBM_OK;
+  if (int rc = queue_sync(d->q)) return rc;
+  HIP_TRY(hipSetDevice(d->q.dev));
+  if (u_in) {
+    if (!d->u_in_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->u_in_dev), (size_t)d->p.ny * sizeof(double)));
+    HIP_TRY(hipMemcpy(d->u_in_dev, u_in, (size_t)d->p.ny * sizeof(double), hipMemcpyHostToDevice));
+  }
+  // the device mask under the column rule, or without it again
+  if (int rc = body_rewrite(d->body, d->mask, d->p.nx, u_in != nullptr)) return rc;
+  d->open = u_in != nullptr;
+  if (u_in) d->u_in.assign(u_in, u_in + d->p.ny);
+  else d->u_in.clear();
+  d->rho_out = u_in ? rho_out : 0.0;
+  return LBM_OK;
+}
+
+int lbm_dopen_get(const lbm_dp *d, int *on_out, double *u_in_out, double *rho_out_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!on_out && !u_in_out && !rho_out_out) return lbm_fail(LBM_ERR_ARG, "on_out, u_in_out and rho_out_out are all NULL");
+  if (on_out) *on_out = d->open ? 1 : 0;
+  if (d->open && u_in_out) std::copy(d->u_in.begin(), d->u_in.end(), u_in_out);
+  if (d->open && rho_out_out) *rho_out_out = d->rho_out;
   return LBM_OK;
 }
 
