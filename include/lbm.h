@@ -880,6 +880,70 @@ int lbm_dopen_get(const lbm_dp *d, int *on_out, double *u_in_out /*[ny]*/, doubl
 int lbm_dopen_ens_set(lbm_dens *e, const double *u_in /*[n][ny]*/, const double *rho_out /*[n]*/);
 int lbm_dopen_ens_get(const lbm_dens *e, int *on_out, double *u_in_out /*[n][ny]*/, double *rho_out_out /*[n]*/);
 
+/*
+ * ---- Moving walls: velocity bounce-back for the double-precision families ------------------------------------------------
+ *
+ * Every blocked cell of a double-precision grid stands still: a channel is driven by accelerate_flow or by an inlet, never by
+ * a wall, so neither Couette flow nor a lid-driven cavity can be run, and the disc of "Drag of a body" cannot spin.  With
+ * moving walls a blocked cell may carry a wall velocity (u_x, u_y); a context carries one wall density rho_wall, each member
+ * of an ensemble its own.  What such a cell bounces back gains the momentum the wall gives the fluid, 6 w_k rho_wall c_k . u_wall
+ * on speed k.  Off by default: walls at rest, the reference's bounce-back (kernels.cl:69, 187-197), keep every bit.  The
+ * reference has no counterpart.
+ *
+ * Definition.  A blocked cell whose two components both compare equal to 0.0 is a resting wall: the existing bounce-back,
+ * no arithmetic, so signed zeros survive and a map of zeros (of either sign) is the flow without the setting, bit for bit.
+ * Any other blocked cell writes, from its gathered values g[0..8], the following instead of the plain swap.  All in double,
+ * contraction off, one IEEE operation per written operator, in this order; 2.0 / 3.0 and 1.0 / 6.0 are double constants.
+ * Moving wall, blocked, (u_x, u_y) != (0, 0):
+ *     rx = rho_wall * u_x;            ry = rho_wall * u_y;
+ *     a  = (2.0 / 3.0) * rx;          b  = (2.0 / 3.0) * ry;
+ *     p  = (1.0 / 6.0) * (rx + ry);   q  = (1.0 / 6.0) * (ry - rx);
+ *     out[0] = g[0];
+ *     out[1] = g[3] + a;   out[3] = g[1] - a;
+ *     out[2] = g[4] + b;   out[4] = g[2] - b;
+ *     out[5] = g[7] + p;   out[7] = g[5] - p;
+ *     out[6] = g[8] + q;   out[8] = g[6] - q;
+ * The cell still returns |u| = 0.  Fluid cells are untouched: accelerate_flow, the open columns and TRT act on them alone.
+ *
+ * Nothing else moves: av_vels, the four fields (a moving cell reads 0, 0, 0, density / 3 like every blocked cell), the Reynolds
+ * number, the force definition and the order of its sums, the body rules including the open-column rule, accelerate_flow, and
+ * both steady criteria are unchanged.  The force needs no new term: the stored value own[opp] of a link already carries what
+ * the wall added, so the momentum-exchange sum of "Drag and lift" is Ladd's sum for a moving wall.
+ *
+ * Mass.  A wall velocity along the wall conserves mass.  One with a component normal to the fluid adds or removes mass every
+ * step; that is the caller's business, nothing checks it.
+ *
+ * Every bit identity stated for the existing flow holds with walls moving: between the kernel forms ("multistep"), launch
+ * splits and runs; between a double-precision context and a member of a double-precision ensemble with the same velocities
+ * and rho_wall; between a member stopped by lbm_dsteady_run or lbm_dbody_steady_run at count c and a plain run of c steps.
+ * It composes with "force", body maps, TRT and open boundaries.
+ *
+ * When it is accepted.  Only while steps_done is 0, the rule of lbm_dopen_set: otherwise LBM_ERR_STATE.  lbm_dp_upload,
+ * lbm_dens_upload and lbm_dp_upload_obstacles keep the setting; a velocity is read only while its cell is blocked.  An ensemble
+ * has the setting on or off for all members; members differ in velocities and rho_wall.  Everything is checked before anything
+ * changes: after a refusal nothing has changed, on the host or on the device.
+ *
+ * Names: lbm_dwall_*, on both double-precision handles.  Out of scope: fp32 contexts and fp32 ensembles, whose checker
+ * contract is the reference's resting walls.
+ */
+
+/* Wall velocities of a double-precision context: u_x, u_y = double[ny][nx], borrowed for the call; rho_wall the wall density.
+ * u_x == NULL and u_y == NULL: off (the default), rho_wall is not read.  LBM_ERR_ARG: a NULL context; exactly one of u_x and
+ * u_y NULL; rho_wall not finite and positive; an entry that is not finite; a non-zero entry on a fluid cell, as lbm_dbody_set
+ * refuses a body there (the message names the cell).  LBM_ERR_STATE: steps done.  Synchronises. */
+int lbm_dwall_set(lbm_dp *d, const double *u_x /*[ny][nx]*/, const double *u_y /*[ny][nx]*/, double rho_wall);
+
+/* on_out: 1 while wall velocities are on, else 0; while they are on, u_x_out, u_y_out = double[ny][nx] and rho_wall_out get
+ * the setting, while they are off none is written.  Any output may be NULL; all four NULL (on_out, u_x_out, u_y_out and
+ * rho_wall_out), or a NULL context: LBM_ERR_ARG. */
+int lbm_dwall_get(const lbm_dp *d, int *on_out, double *u_x_out, double *u_y_out, double *rho_wall_out);
+
+/* The same for all members of a double-precision ensemble: u_x, u_y = double[n][ny][nx], rho_wall = double[n]; u_x == NULL and
+ * u_y == NULL: off.  Everything is checked before anything changes, then copied once; the message names the member and the
+ * cell.  A NULL rho_wall beside non-NULL velocities: LBM_ERR_ARG. */
+int lbm_dwall_ens_set(lbm_dens *e, const double *u_x /*[n][ny][nx]*/, const double *u_y, const double *rho_wall /*[n]*/);
+int lbm_dwall_ens_get(const lbm_dens *e, int *on_out, double *u_x_out, double *u_y_out, double *rho_wall_out /*[n]*/);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

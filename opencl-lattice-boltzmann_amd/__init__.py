@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "lbm_dbody_set", "lbm_dbody_get", "lbm_dbody_ens_set", "lbm_dbody_ens_get", "lbm_dbody_steady_run",
     "lbm_dtrt_set", "lbm_dtrt_get", "lbm_dtrt_ens_set", "lbm_dtrt_ens_get",
     "lbm_dopen_set", "lbm_dopen_get", "lbm_dopen_ens_set", "lbm_dopen_ens_get",
+    "lbm_dwall_set", "lbm_dwall_get", "lbm_dwall_ens_set", "lbm_dwall_ens_get",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -171,6 +172,10 @@ def load_library():
     L.lbm_dopen_get.argtypes = [vp, ctypes.POINTER(ci), vp, ctypes.POINTER(ctypes.c_double)]
     L.lbm_dopen_ens_set.argtypes = [vp, vp, vp]
     L.lbm_dopen_ens_get.argtypes = [vp, ctypes.POINTER(ci), vp, vp]
+    L.lbm_dwall_set.argtypes = [vp, vp, vp, ctypes.c_double]
+    L.lbm_dwall_get.argtypes = [vp, ctypes.POINTER(ci), vp, vp, ctypes.POINTER(ctypes.c_double)]
+    L.lbm_dwall_ens_set.argtypes = [vp, vp, vp, vp]
+    L.lbm_dwall_ens_get.argtypes = [vp, ctypes.POINTER(ci), vp, vp, vp]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -613,6 +618,28 @@ class LBMDouble(_Handle):
         _check(self.lib.lbm_dopen_get(self.ctx, ctypes.byref(on), u.ctypes.data, ctypes.byref(rho)), "lbm_dopen_get")
         return (u, rho.value) if on.value else None
 
+    def set_wall(self, u_x, u_y, rho_wall=None):
+        """Moving walls (lbm_dwall_set): u_x, u_y float64[ny, nx], the wall velocity of every blocked cell (zero on fluid cells),
+        and rho_wall, the wall density (None: params.density); set_wall(None, None) = every wall at rest, the default.  Only
+        before the first step."""
+        if u_x is None and u_y is None:
+            _check(self.lib.lbm_dwall_set(self.ctx, None, None, 0.0), "lbm_dwall_set")
+            return
+        ux = None if u_x is None else np.ascontiguousarray(u_x, dtype=np.float64)
+        uy = None if u_y is None else np.ascontiguousarray(u_y, dtype=np.float64)
+        assert all(u is None or u.shape == (self.ny, self.nx) for u in (ux, uy))
+        rho = self.params.density if rho_wall is None else float(rho_wall)
+        _check(self.lib.lbm_dwall_set(self.ctx, None if ux is None else ux.ctypes.data, None if uy is None else uy.ctypes.data, rho),
+               "lbm_dwall_set")
+
+    def wall(self):
+        """(u_x float64[ny, nx], u_y float64[ny, nx], rho_wall) while wall velocities are on, None while they are off
+        (lbm_dwall_get)"""
+        on, rho = ctypes.c_int(), ctypes.c_double()
+        ux, uy = (np.zeros((self.ny, self.nx), dtype=np.float64) for _ in range(2))
+        _check(self.lib.lbm_dwall_get(self.ctx, ctypes.byref(on), ux.ctypes.data, uy.ctypes.data, ctypes.byref(rho)), "lbm_dwall_get")
+        return (ux, uy, rho.value) if on.value else None
+
     def force_record(self):
         """(F_x float64[steps_done], F_y float64[steps_done]): the force of every step since the upload; needs
         set_option("force", 1) before the first step."""
@@ -826,6 +853,40 @@ class EnsembleDouble(_EnsembleOf):
         u, r = np.zeros((self.n, self.ny), dtype=np.float64), np.zeros(self.n, dtype=np.float64)
         _check(self.lib.lbm_dopen_ens_get(self.ens, ctypes.byref(on), u.ctypes.data, r.ctypes.data), "lbm_dopen_ens_get")
         return (u, r) if on.value else None
+
+    def set_wall(self, u_x, u_y, rho_wall=None):
+        """Moving walls of all members (lbm_dwall_ens_set): u_x, u_y float64[n, ny, nx] (or one [ny, nx] map for all), the wall
+        velocity of every blocked cell (zero on fluid cells); rho_wall float64[n], one value for all, or None: each member's
+        density from its params.  set_wall(None, None) = every wall at rest, the default.  Only before the first step."""
+        if u_x is None and u_y is None:
+            _check(self.lib.lbm_dwall_ens_set(self.ens, None, None, None), "lbm_dwall_ens_set")
+            return
+        maps = []
+        for u in (u_x, u_y):
+            if u is not None:
+                u = np.asarray(u, dtype=np.float64)
+                if u.ndim == 2:
+                    u = np.broadcast_to(u, (self.n,) + u.shape)
+                u = np.ascontiguousarray(u)
+                assert u.shape == (self.n, self.ny, self.nx)
+            maps.append(u)
+        r = np.array([p.density for p in self.params] if rho_wall is None else rho_wall, dtype=np.float64)
+        if r.ndim == 0:
+            r = np.full(self.n, float(r), dtype=np.float64)
+        r = np.ascontiguousarray(r)
+        assert r.shape == (self.n,)
+        _check(self.lib.lbm_dwall_ens_set(self.ens, *[None if u is None else u.ctypes.data for u in maps], r.ctypes.data),
+               "lbm_dwall_ens_set")
+
+    def wall(self):
+        """(u_x float64[n, ny, nx], u_y float64[n, ny, nx], rho_wall float64[n]) while wall velocities are on, None while they
+        are off (lbm_dwall_ens_get)"""
+        on = ctypes.c_int()
+        ux, uy = (np.zeros((self.n, self.ny, self.nx), dtype=np.float64) for _ in range(2))
+        r = np.zeros(self.n, dtype=np.float64)
+        _check(self.lib.lbm_dwall_ens_get(self.ens, ctypes.byref(on), ux.ctypes.data, uy.ctypes.data, r.ctypes.data),
+               "lbm_dwall_ens_get")
+        return (ux, uy, r) if on.value else None
 
     def run_until(self, max_steps, window=64, rel_tol=1e-4, on="av_vels"):
         """_EnsembleOf.run_until with a choice of criterion: on="av_vels" (lbm_dsteady_run), or on="drag"

@@ -14,6 +14,7 @@
 #pragma once
 #include "host_common.h"
 
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -73,6 +74,24 @@ inline int body_apply(BodyMap &b, uint8_t *mask, const int32_t *body, int member
   const std::vector<uint8_t> bytes = body_bytes(b.blocked, counted, nx, open);
   HIP_TRY(hipMemcpy(mask, bytes.data(), count, hipMemcpyHostToDevice));
   b.counted.swap(counted);
+  return LBM_OK;
+}
+
+// lbm_dwall_set / lbm_dwall_ens_set after their own checks (include/lbm.h, "Moving walls"): every entry of the two velocity
+// maps is finite, and zero (of either sign) on a fluid cell, as a body is refused there.  Nothing is changed; the message names
+// the first such cell, with its member for an ensemble.
+inline int wall_check(const BodyMap &b, const double *u_x, const double *u_y, int members, int ny, int nx, bool ensemble) {
+  const size_t per = (size_t)nx * ny, count = per * members;
+  for (size_t i = 0; i < count; i++) {
+    const bool finite = std::isfinite(u_x[i]) && std::isfinite(u_y[i]);
+    if (finite && (b.blocked[i] || (u_x[i] == 0.0 && u_y[i] == 0.0))) continue;
+    const int m = (int)(i / per), y = (int)((i % per) / nx), x = (int)(i % nx);
+    const char *what = finite ? "is non-zero on a fluid cell" : "is not finite";
+    const char *why = finite ? " (a wall is made of blocked cells)" : "";
+    if (ensemble)
+      return lbm_fail(LBM_ERR_ARG, "the wall velocity %s: member %d, y %d, x %d, (%g, %g)%s", what, m, y, x, u_x[i], u_y[i], why);
+    return lbm_fail(LBM_ERR_ARG, "the wall velocity %s: y %d, x %d, (%g, %g)%s", what, y, x, u_x[i], u_y[i], why);
+  }
   return LBM_OK;
 }
 

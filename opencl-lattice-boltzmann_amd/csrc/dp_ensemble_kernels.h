@@ -39,11 +39,23 @@ struct DensArgs {
   int T;                     // steps in this launch
   int accel_next;            // apply the following step's accelerate_flow to the final state
 };
+// What a WALL instance takes beyond that: the members' wall velocities, [2][members][ny][nx], u_x then u_y (lbm_dwall_ens_set;
+// one address: the kernel is short of SGPRs).  The WALL = false instances keep the argument struct of a library without moving
+// walls.
+struct DensWallArgs : DensArgs {
+  const double *wall_u;
+};
+template <bool WALL>
+using DensArgsOf = std::conditional_t<WALL, DensWallArgs, DensArgs>;
 
 // Open boundaries: member m's inlet profile u_in[ny] and, behind it, its rho_out lie m * (ny + 1) doubles into a second table,
 // which starts where the table of DensMember ends: one allocation, and DensArgs is the struct of a library without it.
 __host__ __device__ inline const double *dens_open_table(const DensMember *members, int n) {
   return reinterpret_cast<const double *>(members + n);
+}
+// Moving walls: member m's rho_wall is entry m of a third table, behind the open-boundary table
+__host__ __device__ inline const double *dens_wall_table(const DensMember *members, int n, int ny) {
+  return dens_open_table(members, n) + (size_t)n * (ny + 1);
 }
 
 // grid = (tiles per member, members), NT threads.  TX x TY output tile, T <= TMAX steps LDS -> LDS on a region that shrinks
@@ -83,8 +95,19 @@ __host__ __device__ inline const double *dens_open_table(const DensMember *membe
 // dp_open_outlet to a marked cell before dp_collide_cell and has no accelerate_flow.  The member's u_in on the region's rows
 // and its rho_out are staged in LDS with the region (184 B; reading them from global memory under the branch put a load's
 // latency on every step of an end tile: 23.2 against 19.6 us/step on 64 x 128x128).  An ensemble is all open or all periodic.
-template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN>
-__device__ __forceinline__ void dens_tile(const DensArgs a) {
+//
+// WALL (lbm_dwall_*: a wall velocity per blocked cell): d2q9_dp_multi's scheme.  The 74 472 B of LDS must stay at or below 81 920
+// for two workgroups per CU, and two doubles per region cell would be 7 744 B; a moving cell is rare.  A pass behind the region
+// load reads the two velocities of every blocked cell by its grid cell and marks one that moves in a third spare bit of its
+// lmask byte; a pass behind the collision loop finds the grid cell of a marked byte (the region's rows and columns in the grid
+// are staged in LDS, 176 B), reads the member's two values and its rho_wall from global memory under that branch and adds
+// dp_wall_cell's terms to the bounce-back in LDS.  With the branch inside the collision loop the compiler, at the 64 VGPRs of
+// two workgroups per CU, issued the nine plane loads of the region load one after the other: 29.5 against 19.5 us/step on
+// 64 x 128x128 with a spinning disc, 25.8 now (tools/wall_ab.py).  74 464 B of LDS without and 74 656 B with OPEN.  An ensemble
+// has wall velocities on or off for all members; a member without a moving cell takes the branch nowhere.
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL = false>
+__device__ __forceinline__ void dens_tile(const DensArgsOf<WALL> a) {
+  constexpr bool MARKED = OPEN || WALL;   // lmask bytes carry marks above the low two bits
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
   static_assert(TY * (TX / kDpSeg) <= NT, "one lane per segment of the tile");
   constexpr int kRX = TX + 2 * TMAX, kRY = TY + 2 * TMAX;
@@ -111,6 +134,13 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
     __shared__ double open_rows[kRY + 1];
     lopen = open_rows;
   }
+  // WALL: where the region's rows and columns lie in the member's grid, gy * nx per row and then gx per column, staged with the
+  // region (176 B): a moving cell finds its two velocities without a division in the step loop
+  [[maybe_unused]] int *lwall = nullptr;
+  if constexpr (WALL) {
+    __shared__ int wall_cells[kRY + kRX];
+    lwall = wall_cells;
+  }
   // grid row of region row ry: periodic wrap inside the member (kernels.cl:91-93)
   auto grid_row = [&](int ry) {
     int r = (gy0 + ry) % a.ny;
@@ -120,7 +150,8 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
   auto store_segments = [&](int s) {
     constexpr int kSegs = TY * (TX / kDpSeg);
     int lane = tid;
-    if constexpr (FORCE) asm volatile("" : "+v"(lane));  // as in the force pass below: nothing of this is kept across the collision loop
+    // as in the force pass below: nothing of this is kept across the collision loop (WALL: its branch needs the registers)
+    if constexpr (FORCE || WALL) asm volatile("" : "+v"(lane));
     if (lane < kSegs) {
       const int oy = lane / (TX / kDpSeg), sx = lane - oy * (TX / kDpSeg);
       const int gy = tile_y * TY + oy;
@@ -142,8 +173,20 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
     if (gx < 0) gx += a.nx;
     const int gy = grid_row(ry);
     const double *p = src + (size_t)gy * rs + gx;
+    if constexpr (WALL) {
+      // At the 64 VGPRs of two workgroups per CU the compiler issues the nine loads of a WALL instance one after the other,
+      // each waited for before the next (29.5 against 19.5 us/step on 64 x 128x128).  One statement that takes all nine values
+      // keeps them in flight together, as the WALL = false instances have them.
+      double v[9];
 #pragma unroll
-    for (int k = 0; k < 9; k++) lds[0][k][ry * kRX + rx] = p[k * ps];
+      for (int k = 0; k < 9; k++) v[k] = p[k * ps];
+      asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]));
+#pragma unroll
+      for (int k = 0; k < 9; k++) lds[0][k][ry * kRX + rx] = v[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 9; k++) lds[0][k][ry * kRX + rx] = p[k * ps];
+    }
     uint8_t mb = mask[(size_t)gy * a.nx + gx];
     if constexpr (OPEN) {
       if (mb == 0 && gx == 0) mb = kOpenInlet;
@@ -156,6 +199,31 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
     const double *u_in = dens_open_table(a.members, (int)gridDim.y) + (size_t)member * (a.ny + 1);
     if (tid < RY) lopen[tid] = u_in[grid_row(tid)];
     if (tid == RY) lopen[kRY] = u_in[a.ny];
+  }
+  if constexpr (WALL) {
+    // The marks, in a pass of its own: every lane revisits the bytes it wrote itself (no barrier) and reads the two velocities
+    // of a blocked cell.  From an opaque copy of the lane index, as the force pass: nothing of this is kept in registers across
+    // the region load, whose nine plane loads the compiler otherwise issues one after the other.
+    int mine = tid;
+    asm volatile("" : "+v"(mine));
+    for (int i = mine; i < RX * RY; i += NT) {
+      const int ry = (int)(((float)i + 0.5f) * rinv), rx = i - ry * RX;
+      const uint8_t mb = lmask[ry * kRX + rx];
+      if ((mb & kOpenBlocked) != 0) {
+        int gx = (gx0 + rx) % a.nx;
+        if (gx < 0) gx += a.nx;
+        const size_t at = (size_t)member * ((size_t)a.nx * a.ny) + (size_t)grid_row(ry) * a.nx + gx;
+        const double *u_y = a.wall_u + (size_t)gridDim.y * ((size_t)a.nx * a.ny);
+        if (dp_wall_moves(a.wall_u[at], u_y[at])) lmask[ry * kRX + rx] = mb | kWallMoving;
+      }
+    }
+    static_assert(kRY + kRX <= NT, "one lane per region row and column");
+    if (mine < RY) {
+      lwall[mine] = grid_row(mine) * a.nx;
+    } else if (mine < RY + RX) {
+      int gx = (gx0 + mine - RY) % a.nx;
+      lwall[kRY + mine - RY] = gx < 0 ? gx + a.nx : gx;
+    }
   }
   __syncthreads();
 
@@ -178,7 +246,8 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
         const int c = (oy + T) * kRX + ox + T;
         const int gy = tile_y * TY + oy;
         double fx = 0.0, fy = 0.0;
-        const bool counts = lmask[c] == 1 && tile_x * TX + ox < a.nx && gy < a.ny;   // 2: blocked, outside the body
+        // 2: blocked, outside the body; WALL: a moving cell's byte carries its mark
+        const bool counts = (WALL ? lmask[c] & kOpenBlocked : lmask[c]) == 1 && tile_x * TX + ox < a.nx && gy < a.ny;
         if (counts) {
           const double(*f)[kRY * kRX] = lds[(s - 1) & 1];
           const double g[9] = {0.0, f[1][c - 1], f[2][c - kRX], f[3][c + 1], f[4][c + kRX], f[5][c - kRX - 1],
@@ -186,8 +255,8 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
           double own[9];
 #pragma unroll
           for (int k = 0; k < 9; k++) own[k] = f[k][c];
-          // OPEN: a marked fluid neighbour reads as fluid
-          auto nbyte = [&](int at) -> uint8_t { return OPEN ? (uint8_t)(lmask[at] & kOpenBlocked) : lmask[at]; };
+          // OPEN: a marked fluid neighbour reads as fluid; WALL: a marked moving one as blocked
+          auto nbyte = [&](int at) -> uint8_t { return MARKED ? (uint8_t)(lmask[at] & kOpenBlocked) : lmask[at]; };
           const uint8_t nb[9] = {0, nbyte(c - 1), nbyte(c - kRX), nbyte(c + 1), nbyte(c + kRX), nbyte(c - kRX - 1),
                                  nbyte(c - kRX + 1), nbyte(c + kRX + 1), nbyte(c + kRX - 1)};
           dp_force_cell(g, own, nb, fx, fy);
@@ -224,7 +293,7 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
       g[7] = lds[in][7][c + kRX + 1];
       g[8] = lds[in][8][c + kRX - 1];
       const uint8_t mb = lmask[c];
-      const bool obst = OPEN ? (mb & kOpenBlocked) != 0 : mb != 0;
+      const bool obst = MARKED ? (mb & kOpenBlocked) != 0 : mb != 0;
       if constexpr (OPEN) {
         if (mb & kOpenInlet) dp_open_inlet(g, lopen[ry]);
         else if (mb & kOpenOutlet) dp_open_outlet(g, lopen[kRY]);
@@ -238,6 +307,28 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
       const int ox = rx - T, oy = ry - T;
       if (ox >= 0 && ox < TX && oy >= 0 && oy < TY)
         tval[s & 1][oy][ox] = (tile_x * TX + ox < a.nx && tile_y * TY + oy < a.ny) ? t : 0.0;
+    }
+    if constexpr (WALL) {
+      // The moving cells, in a pass of its own behind the collision loop, which stays the WALL = false one: every lane
+      // revisits the cells it wrote itself (no barrier), and one whose byte is marked adds the wall's terms to the bounce-back
+      // it stored.  From an opaque copy of the lane index, as the force pass.
+      int first = tid;
+      asm volatile("" : "+v"(first));
+      for (int i = first; i < w * h; i += NT) {
+        const int q = (int)(((float)i + 0.5f) * inv);
+        const int rx = s + (i - q * w), ry = s + q;
+        const int c = ry * kRX + rx;
+        if (lmask[c] & kWallMoving) {
+          const size_t at = (size_t)member * ((size_t)a.nx * a.ny) + (size_t)(lwall[ry] + lwall[kRY + rx]);
+          double o[9];
+#pragma unroll
+          for (int k = 1; k < 9; k++) o[k] = lds[out][k][c];
+          const double *u_y = a.wall_u + (size_t)gridDim.y * ((size_t)a.nx * a.ny);
+          dp_wall_cell(o, a.wall_u[at], u_y[at], dens_wall_table(a.members, (int)gridDim.y, a.ny)[member]);
+#pragma unroll
+          for (int k = 1; k < 9; k++) lds[out][k][c] = o[k];
+        }
+      }
     }
     __syncthreads();
   }
@@ -259,9 +350,9 @@ __device__ __forceinline__ void dens_tile(const DensArgs a) {
 
 // The FORCE instance states its two workgroups per CU (NT / 128 waves per SIMD) to the compiler: 60 VGPRs, 78 SGPRs, 0 scratch.
 // So do the TRT and the OPEN instances (DESIGN.md section 3.7 holds their tables).
-template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN>
-__global__ __launch_bounds__(NT, (FORCE || TRT || OPEN) ? NT / 128 : 1) void d2q9_dp_ensemble(const DensArgs a) {
-  dens_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN>(a);
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL = false>
+__global__ __launch_bounds__(NT, (FORCE || TRT || OPEN || WALL) ? NT / 128 : 1) void d2q9_dp_ensemble(const DensArgsOf<WALL> a) {
+  dens_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN, WALL>(a);
 }
 
 // ---- second reduction stage with a member axis: dp_reduce's partition and order, fixed, no atomics -------------------

@@ -22,6 +22,8 @@
 #pragma once
 #include "d2q9_kernels.h"
 
+#include <type_traits>
+
 namespace lbm {
 
 constexpr int kDpSeg = 16;  // cells per row segment of the velocity sum
@@ -138,6 +140,35 @@ __device__ __forceinline__ void dp_open_outlet(double (&g)[9], double rho_out) {
 // load knows the grid column, the collision loop does not.  Blocked-ness is the low two bits there (body_map.h: 0, 1, 2).
 constexpr uint8_t kOpenInlet = 4, kOpenOutlet = 8, kOpenBlocked = 3;
 
+// Moving walls (include/lbm.h, "Moving walls"): a blocked cell with a wall velocity adds 6 w_k rho_wall c_k . u_wall to what it
+// bounces back.  `out` holds the plain bounce-back of dp_collide_cell's obstacle branch (out[1] = g[3], ...), so each line is
+// the header's statement: one IEEE operation per operator, contraction off.  A cell whose two components compare equal to 0.0
+// is at rest and never comes here: no arithmetic touches it, signed zeros survive.
+__device__ __forceinline__ bool dp_wall_moves(double u_x, double u_y) { return !(u_x == 0.0 && u_y == 0.0); }
+__device__ __forceinline__ void dp_wall_cell(double (&out)[9], double u_x, double u_y, double rho_wall) {
+#pragma clang fp contract(off)
+  const double rx = rho_wall * u_x, ry = rho_wall * u_y;
+  const double a = (2.0 / 3.0) * rx, b = (2.0 / 3.0) * ry;
+  const double p = (1.0 / 6.0) * (rx + ry), q = (1.0 / 6.0) * (ry - rx);
+  out[1] = out[1] + a; out[3] = out[3] - a;
+  out[2] = out[2] + b; out[4] = out[4] - b;
+  out[5] = out[5] + p; out[7] = out[7] - p;
+  out[6] = out[6] + q; out[8] = out[8] - q;
+}
+
+// The LDS-tile kernels' mark of a blocked cell that moves, in a third spare bit of its lmask byte (WALL instances only): a pass
+// behind the region load reads the cell's two velocities by its grid cell and marks it, a pass behind the collision loop
+// finds the grid cell of a marked byte and reads them again under that branch - a moving cell is rare, and no LDS holds a
+// velocity.
+constexpr uint8_t kWallMoving = 16;
+
+// The wall velocities of a context, [ny][nx] each, and its wall density: what a WALL instance takes beyond the arguments of
+// the kernel without it.  The WALL = false instances keep the argument struct of a library without moving walls.
+struct DpWall {
+  const double *u_x, *u_y;
+  double rho_wall;
+};
+
 // Momentum-exchange force on one blocked cell o in the step that streams the state f (include/lbm.h): for k = 1..8 in
 // ascending order, if the neighbour x = o - c_k is fluid, s = f_k(x) + f_opp(k)(o) goes into F with the signs of c_k.
 //   g[k]   = f_k(o - c_k), what o gathers in that step        own[k] = o's own stored f_k
@@ -192,6 +223,11 @@ struct DpStepArgs {
   const double *u_in;        // OPEN: the inlet profile, [ny]
   double rho_out;            // OPEN: the outlet density
 };
+struct DpStepWallArgs : DpStepArgs {
+  DpWall wall;
+};
+template <bool WALL>
+using DpStepArgsOf = std::conditional_t<WALL, DpStepWallArgs, DpStepArgs>;
 
 // One timestep, lane = cells x0, x0+1 of one row.  x-1 / x+1 neighbours: aligned 16-B loads plus one scalar load per
 // streamed plane at the wrap column (an L1 hit).  A lane past the row's end (x0 >= nx) only joins the segment sum with 0.
@@ -201,9 +237,11 @@ struct DpStepArgs {
 // OPEN: the fluid cell of column 0 (cell a of the lane x0 == 0) and of column nx - 1 (cell b where nx is even, cell a of the
 // row's last lane where it is odd) go through dp_open_inlet / dp_open_outlet before the collision; the host passes accel_row
 // -1.  The false instances are the kernels without it.
+// WALL: a lane with a blocked cell loads that cell's two wall velocities under the branch it takes for the obstacle, and a
+// cell that moves goes through dp_wall_cell after its bounce-back.  The false instances are the kernels without it.
 // static, like the helper kernels below: two translation units include this header (lbm_dp.cpp, lbm_dens.cpp).
-template <bool FORCE, bool TRT, bool OPEN>
-static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a) {
+template <bool FORCE, bool TRT, bool OPEN, bool WALL = false>
+static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgsOf<WALL> a) {
   const unsigned t = blockIdx.x * kBlock + threadIdx.x;
   const unsigned lpr = (unsigned)a.lanes_per_row;
   const int y = (int)(t / lpr);
@@ -263,6 +301,17 @@ static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgs a
     double oa[9], ob[9];
     const double ta = dp_collide_cell<TRT>(ga, ob_a, a.omega, a.omega_m, oa);
     const double tb = dp_collide_cell<TRT>(gb, ob_b, a.omega, a.omega_m, ob);
+    if constexpr (WALL) {
+      const size_t at = (size_t)y * a.nx + x0;   // ob_b implies has_b: at + 1 is a cell of this row
+      if (ob_a) {
+        const double u_x = a.wall.u_x[at], u_y = a.wall.u_y[at];
+        if (dp_wall_moves(u_x, u_y)) dp_wall_cell(oa, u_x, u_y, a.wall.rho_wall);
+      }
+      if (ob_b) {
+        const double u_x = a.wall.u_x[at + 1], u_y = a.wall.u_y[at + 1];
+        if (dp_wall_moves(u_x, u_y)) dp_wall_cell(ob, u_x, u_y, a.wall.rho_wall);
+      }
+    }
     if (y == a.accel_row) {
       dp_accelerate_cell(oa, ob_a, a.aw1, a.aw2);
       dp_accelerate_cell(ob, ob_b, a.aw1, a.aw2);
@@ -318,6 +367,11 @@ struct DpMultiArgs {
   const double *u_in;       // OPEN: the inlet profile, [ny]
   double rho_out;           // OPEN: the outlet density
 };
+struct DpMultiWallArgs : DpMultiArgs {
+  DpWall wall;
+};
+template <bool WALL>
+using DpMultiArgsOf = std::conditional_t<WALL, DpMultiWallArgs, DpMultiArgs>;
 
 // T <= TMAX timesteps per launch: a (TX + 2T) x (TY + 2T) region around the TX x TY output tile is loaded into LDS,
 // advanced T times LDS -> LDS on a region that shrinks by one cell per step (halo cells computed redundantly by the
@@ -337,8 +391,16 @@ struct DpMultiArgs {
 // the fluid cells of columns 0 and nx - 1 in two spare bits of their lmask byte; the collision loop branches on the byte it
 // reads anyway, and blocked-ness is the low two bits, the neighbour bytes of the force pass included.  The profile on the
 // region's rows is staged in LDS with the region (256 B).  No accelerate_flow.
-template <int TX, int TY, int TMAX, bool FORCE, bool TRT, bool OPEN>
-__global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs a) {
+// WALL: the tile holds about 152 of the 160 KB of LDS, two doubles per region cell would be 16 KB more.  A pass behind the region
+// load reads the two velocities of every blocked cell by its grid cell and marks one that moves in a third spare bit of its byte
+// (kWallMoving); a pass behind the collision loop finds the grid cell of a marked byte from its region cell (the region's rows
+// and columns in the grid are staged in LDS as gy * nx and gx, 256 B; nx * ny is below 2^31 for every grid whose two arrays a
+// device holds), reads the two values from global memory under that branch and adds dp_wall_cell's terms to the bounce-back in
+// LDS.  Every copy of a wall cell in a region wider than the grid gets the velocity of its own grid cell.  Blocked-ness stays
+// the low two bits, for the force pass's own byte and its neighbours'.
+template <int TX, int TY, int TMAX, bool FORCE, bool TRT, bool OPEN, bool WALL = false>
+__global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgsOf<WALL> a) {
+  constexpr bool MARKED = OPEN || WALL;   // lmask bytes carry marks above the low two bits
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
   constexpr int kRX = TX + 2 * TMAX, kRY = TY + 2 * TMAX;
   __shared__ double lds[2][9][kRY * kRX];
@@ -350,6 +412,13 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
   if constexpr (OPEN) {
     __shared__ double open_rows[kRY];
     lopen = open_rows;
+  }
+  // WALL: where the region's rows and columns lie in the grid, gy * nx per row and then gx per column, staged with the region
+  // (256 B): a moving cell finds its two velocities without a division in the step loop
+  [[maybe_unused]] int *lwall = nullptr;
+  if constexpr (WALL) {
+    __shared__ int wall_cells[kRY + kRX];
+    lwall = wall_cells;
   }
   const int T = a.T;
   const int RX = TX + 2 * T, RY = TY + 2 * T;
@@ -397,6 +466,30 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
     static_assert(kRY <= kMultiThreads, "one lane per region row");
     if (tid < RY) lopen[tid] = a.u_in[grid_row(tid)];
   }
+  if constexpr (WALL) {
+    // The marks, in a pass of its own: every lane revisits the bytes it wrote itself (no barrier) and reads the two velocities
+    // of a blocked cell.  From an opaque copy of the lane index, as the force pass: nothing of this is kept in registers across
+    // the region load, whose nine plane loads the compiler otherwise issues one after the other.
+    int mine = tid;
+    asm volatile("" : "+v"(mine));
+    for (int i = mine; i < RX * RY; i += kMultiThreads) {
+      const int ry = (int)(((float)i + 0.5f) * rinv), rx = i - ry * RX;
+      const uint8_t mb = lmask[ry * kRX + rx];
+      if ((mb & kOpenBlocked) != 0) {
+        int gx = (gx0 + rx) % a.nx;
+        if (gx < 0) gx += a.nx;
+        const size_t at = (size_t)grid_row(ry) * a.nx + gx;
+        if (dp_wall_moves(a.wall.u_x[at], a.wall.u_y[at])) lmask[ry * kRX + rx] = mb | kWallMoving;
+      }
+    }
+    static_assert(kRY + kRX <= kMultiThreads, "one lane per region row and column");
+    if (mine < RY) {
+      lwall[mine] = grid_row(mine) * a.nx;
+    } else if (mine < RY + RX) {
+      int gx = (gx0 + mine - RY) % a.nx;
+      lwall[kRY + mine - RY] = gx < 0 ? gx + a.nx : gx;
+    }
+  }
   __syncthreads();
 
   for (int s = 1; s <= T; s++) {
@@ -418,7 +511,8 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
         const int c = (oy + T) * kRX + ox + T;
         const int gy = tile_y * TY + oy;
         double fx = 0.0, fy = 0.0;
-        const bool counts = lmask[c] == 1 && tile_x * TX + ox < a.nx && gy < a.ny;   // 2: blocked, outside the body
+        // 2: blocked, outside the body; WALL: a moving cell's byte carries its mark
+        const bool counts = (WALL ? lmask[c] & kOpenBlocked : lmask[c]) == 1 && tile_x * TX + ox < a.nx && gy < a.ny;
         if (counts) {
           const double(*f)[kRY * kRX] = lds[(s - 1) & 1];
           const double g[9] = {0.0, f[1][c - 1], f[2][c - kRX], f[3][c + 1], f[4][c + kRX], f[5][c - kRX - 1],
@@ -426,8 +520,8 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
           double own[9];
 #pragma unroll
           for (int k = 0; k < 9; k++) own[k] = f[k][c];
-          // OPEN: a marked fluid neighbour reads as fluid
-          auto nbyte = [&](int at) -> uint8_t { return OPEN ? (uint8_t)(lmask[at] & kOpenBlocked) : lmask[at]; };
+          // OPEN: a marked fluid neighbour reads as fluid; WALL: a marked moving one as blocked
+          auto nbyte = [&](int at) -> uint8_t { return MARKED ? (uint8_t)(lmask[at] & kOpenBlocked) : lmask[at]; };
           const uint8_t nb[9] = {0, nbyte(c - 1), nbyte(c - kRX), nbyte(c + 1), nbyte(c + kRX), nbyte(c - kRX - 1),
                                  nbyte(c - kRX + 1), nbyte(c + kRX + 1), nbyte(c + kRX - 1)};
           dp_force_cell(g, own, nb, fx, fy);
@@ -464,7 +558,7 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
       g[7] = lds[in][7][c + kRX + 1];
       g[8] = lds[in][8][c + kRX - 1];
       const uint8_t mb = lmask[c];
-      const bool obst = OPEN ? (mb & kOpenBlocked) != 0 : mb != 0;
+      const bool obst = MARKED ? (mb & kOpenBlocked) != 0 : mb != 0;
       if constexpr (OPEN) {
         if (mb & kOpenInlet) dp_open_inlet(g, lopen[ry]);
         else if (mb & kOpenOutlet) dp_open_outlet(g, a.rho_out);
@@ -478,6 +572,27 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
       const int ox = rx - T, oy = ry - T;
       if (ox >= 0 && ox < TX && oy >= 0 && oy < TY)
         tval[s & 1][oy][ox] = (tile_x * TX + ox < a.nx && tile_y * TY + oy < a.ny) ? t : 0.0;
+    }
+    if constexpr (WALL) {
+      // The moving cells, in a pass of its own behind the collision loop, which stays the WALL = false one: every lane
+      // revisits the cells it wrote itself (no barrier), and one whose byte is marked adds the wall's terms to the bounce-back
+      // it stored.  From an opaque copy of the lane index, as the force pass.
+      int first = tid;
+      asm volatile("" : "+v"(first));
+      for (int i = first; i < w * h; i += kMultiThreads) {
+        const int q = (int)(((float)i + 0.5f) * inv);
+        const int rx = s + (i - q * w), ry = s + q;
+        const int c = ry * kRX + rx;
+        if (lmask[c] & kWallMoving) {
+          const int at = lwall[ry] + lwall[kRY + rx];
+          double o[9];
+#pragma unroll
+          for (int k = 1; k < 9; k++) o[k] = lds[out][k][c];
+          dp_wall_cell(o, a.wall.u_x[at], a.wall.u_y[at], a.wall.rho_wall);
+#pragma unroll
+          for (int k = 1; k < 9; k++) lds[out][k][c] = o[k];
+        }
+      }
     }
     __syncthreads();
   }

@@ -60,7 +60,8 @@ struct lbm_dens {
   double *cells[2] = {nullptr, nullptr};
   uint8_t *mask = nullptr;         // [n][ny][nx]: 0 fluid, 1 blocked and counted in the force, 2 blocked outside the body
   BodyMap body;                    // the host's copy of what the mask was made of (body_map.h)
-  DensMember *members = nullptr;   // [n], then the open-boundary table double[n][ny + 1] (dens_open_table)
+  DensMember *members = nullptr;   // [n], then the open-boundary table double[n][ny + 1] (dens_open_table), then rho_wall[n]
+                                   // (dens_wall_table)
   double *seg = nullptr;           // [ring][n][ny][nseg]
   double *red = nullptr;           // [ring][n][red_blocks]: first reduction stage
   double *av_sum = nullptr;        // [n][max_iters]
@@ -73,6 +74,10 @@ struct lbm_dens {
   std::vector<double> omega_m;     // [n]: the host's copy of DensMember::omega_m (BGK: the member's omega)
   bool open = false;               // lbm_dopen_ens_set: the kernels' OPEN instances for all members, no accelerate_flow
   std::vector<double> open_host;   // [n][ny + 1]: per member u_in[ny], then rho_out (empty while off); on the device behind `members`
+  bool wall = false;               // lbm_dwall_ens_set: the kernels' WALL instances for all members
+  std::vector<double> wall_u;      // [2][n][ny][nx]: the host's copy of the wall velocities, u_x then u_y (empty while off)
+  std::vector<double> rho_wall;    // [n]: the members' wall densities (empty while off); on the device behind the open table
+  double *wall_dev = nullptr;      // [2][n][ny][nx] (allocated by the first lbm_dwall_ens_set that switches on)
   int nseg = 1, red_blocks = 1, fin_blocks = 1;
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
@@ -101,6 +106,7 @@ void free_dens(lbm_dens *e) {
   if (e->fin_partials) (void)hipFree(e->fin_partials);
   if (e->force_rec) (void)hipFree(e->force_rec);
   if (e->force_now) (void)hipFree(e->force_now);
+  if (e->wall_dev) (void)hipFree(e->wall_dev);
   if (e->steady_words) (void)hipFree(e->steady_words);
   if (e->steady_inv) (void)hipFree(e->steady_inv);
   if (e->steady_count_host) (void)hipHostFree(e->steady_count_host);
@@ -155,7 +161,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
 
   // what the ensemble needs against what the device has free: refuse here rather than fail half-way through
   const size_t cells_bytes = ((size_t)n * e->member_stride + 32) * sizeof(double);
-  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + (size_t)n * (sizeof(DensMember) + (size_t)(ny + 1) * sizeof(double)) +
+  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + (size_t)n * (sizeof(DensMember) + (size_t)(ny + 2) * sizeof(double)) +
                       (size_t)e->ring * all_step * sizeof(double) + (size_t)e->ring * n * e->red_blocks * sizeof(double) +
                       (size_t)n * e->max_iters * sizeof(double) + (size_t)n * e->fin_blocks * sizeof(double);
   size_t free_b = 0, total_b = 0;
@@ -170,7 +176,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
     HIP_TRY(hipMemset(e->cells[i], 0, cells_bytes));
   }
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->mask), (size_t)n * cells_per + 64));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), (size_t)n * (sizeof(DensMember) + (size_t)(ny + 1) * sizeof(double))));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), (size_t)n * (sizeof(DensMember) + (size_t)(ny + 2) * sizeof(double))));
   if (int rc = alloc_ring(e)) return rc;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->av_sum), (size_t)n * e->max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->fin_partials), (size_t)n * e->fin_blocks * sizeof(double)));
@@ -185,20 +191,32 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
 }
 
 // active: NULL for an ordinary run, the members' words for a leg of a steady run
-template <bool FORCE, bool TRT, bool OPEN>
-void launch_dens_form(const lbm_dens *e, const DensArgs &a, const int *active) {
+template <bool FORCE, bool TRT, bool OPEN, bool WALL>
+void launch_dens_form(const lbm_dens *e, const DensArgsOf<WALL> &a, const int *active) {
   const dim3 grid(e->tiles, e->n), block(kDensThreads);
-  if (!active) hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN>), grid, block, 0, e->q.st, a);
-  else hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN>), grid, block, 0, e->q.st, a, active);
+  if (!active)
+    hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL>), grid, block, 0, e->q.st, a);
+  else
+    hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL>), grid, block, 0,
+                       e->q.st, a, active);
+}
+
+template <bool FORCE, bool TRT, bool OPEN>
+void launch_dens_wall(const lbm_dens *e, const DensArgs &a, const int *active) {
+  if (!e->wall) return launch_dens_form<FORCE, TRT, OPEN, false>(e, a, active);
+  DensWallArgs w{};
+  static_cast<DensArgs &>(w) = a;
+  w.wall_u = e->wall_dev;
+  launch_dens_form<FORCE, TRT, OPEN, true>(e, w, active);
 }
 
 template <bool FORCE, bool TRT>
 void launch_dens_open(const lbm_dens *e, const DensArgs &a, const int *active) {
-  e->open ? launch_dens_form<FORCE, TRT, true>(e, a, active) : launch_dens_form<FORCE, TRT, false>(e, a, active);
+  e->open ? launch_dens_wall<FORCE, TRT, true>(e, a, active) : launch_dens_wall<FORCE, TRT, false>(e, a, active);
 }
 
-// FORCE from the option "force", TRT from lbm_dtrt_ens_set, OPEN from lbm_dopen_ens_set: with all off these are the launches
-// of a library without any of them
+// FORCE from the option "force", TRT from lbm_dtrt_ens_set, OPEN from lbm_dopen_ens_set, WALL from lbm_dwall_ens_set: with all
+// off these are the launches of a library without any of them
 void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
   if (e->force) e->trt ? launch_dens_open<true, true>(e, a, active) : launch_dens_open<true, false>(e, a, active);
   else e->trt ? launch_dens_open<false, true>(e, a, active) : launch_dens_open<false, false>(e, a, active);
@@ -769,6 +787,56 @@ int lbm_dopen_ens_get(const lbm_dens *e, int *on_out, double *u_in_out, double *
     if (u_in_out) std::copy(row, row + ny, u_in_out + (size_t)m * ny);
     if (rho_out_out) rho_out_out[m] = row[ny];
   }
+  return LBM_OK;
+}
+
+int lbm_dwall_ens_set(lbm_dens *e, const double *u_x, const double *u_y, const double *rho_wall) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if ((u_x == nullptr) != (u_y == nullptr))
+    return lbm_fail(LBM_ERR_ARG, "%s is NULL and %s is not: a wall velocity has two components (both NULL: off)", u_x ? "u_y" : "u_x",
+                    u_x ? "u_x" : "u_y");
+  if (u_x && !rho_wall) return lbm_fail(LBM_ERR_ARG, "rho_wall is NULL (u_x is not: every member needs its wall density)");
+  // every member is checked before anything changes, on the host or on the device
+  if (u_x) {
+    for (int m = 0; m < e->n; m++)
+      if (!positive_finite(rho_wall[m]))
+        return lbm_fail(LBM_ERR_ARG, "member %d: rho_wall must be finite and positive (got %g)", m, rho_wall[m]);
+    if (int rc = wall_check(e->body, u_x, u_y, e->n, e->ny, e->nx, true)) return rc;
+  }
+  if (e->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "wall velocities are set before the first step (%d done): one record holds one flow", e->steps_done);
+  if (!u_x) {
+    e->wall = false;
+    e->wall_u.clear();
+    e->rho_wall.clear();
+    return LBM_OK;
+  }
+  if (int rc = queue_sync(e->q)) return rc;
+  HIP_TRY(hipSetDevice(e->q.dev));
+  const size_t all = (size_t)e->n * e->nx * e->ny;
+  if (!e->wall_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->wall_dev), 2 * all * sizeof(double)));
+  std::vector<double> u(2 * all);
+  std::copy(u_x, u_x + all, u.begin());
+  std::copy(u_y, u_y + all, u.begin() + all);
+  HIP_TRY(hipMemcpy(e->wall_dev, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(const_cast<double *>(dens_wall_table(e->members, e->n, e->ny)), rho_wall, (size_t)e->n * sizeof(double),
+                    hipMemcpyHostToDevice));
+  e->wall = true;
+  e->wall_u.swap(u);
+  e->rho_wall.assign(rho_wall, rho_wall + e->n);
+  return LBM_OK;
+}
+
+int lbm_dwall_ens_get(const lbm_dens *e, int *on_out, double *u_x_out, double *u_y_out, double *rho_wall_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!on_out && !u_x_out && !u_y_out && !rho_wall_out)
+    return lbm_fail(LBM_ERR_ARG, "on_out, u_x_out, u_y_out and rho_wall_out are all NULL");
+  if (on_out) *on_out = e->wall ? 1 : 0;
+  if (!e->wall) return LBM_OK;
+  const size_t all = (size_t)e->n * e->nx * e->ny;
+  if (u_x_out) std::copy(e->wall_u.begin(), e->wall_u.begin() + all, u_x_out);
+  if (u_y_out) std::copy(e->wall_u.begin() + all, e->wall_u.end(), u_y_out);
+  if (rho_wall_out) std::copy(e->rho_wall.begin(), e->rho_wall.end(), rho_wall_out);
   return LBM_OK;
 }
 

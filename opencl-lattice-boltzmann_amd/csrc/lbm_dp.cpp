@@ -63,6 +63,10 @@ struct lbm_dp {
   std::vector<double> u_in;       // [ny]: the host's copy of the inlet profile (empty while off)
   double rho_out = 0.0;           // the outlet density
   double *u_in_dev = nullptr;     // [ny] (allocated by the first lbm_dopen_set that switches on)
+  bool wall = false;              // lbm_dwall_set: the kernels' WALL instances
+  std::vector<double> wall_u;     // [2][ny][nx]: the host's copy of the wall velocities, u_x then u_y (empty while off)
+  double rho_wall = 0.0;          // the wall density
+  double *wall_dev = nullptr;     // [2][ny][nx] (allocated by the first lbm_dwall_set that switches on)
   int cur = 0, steps_done = 0;
   bool failed = false;
 };
@@ -87,6 +91,7 @@ void free_dp(lbm_dp *d) {
   if (d->force_rec) (void)hipFree(d->force_rec);
   if (d->force_now) (void)hipFree(d->force_now);
   if (d->u_in_dev) (void)hipFree(d->u_in_dev);
+  if (d->wall_dev) (void)hipFree(d->wall_dev);
   queue_destroy(d->q);
   delete d;
 }
@@ -165,16 +170,31 @@ int reduce_steps(lbm_dp *d, const double *in, size_t in_stride, int steps, doubl
   return LBM_OK;
 }
 
-// The instance the options choose: FORCE from "force", TRT from lbm_dtrt_set, OPEN from lbm_dopen_set.  With all off these
-// are the launches of a library without any of them.
+// The instance the options choose: FORCE from "force", TRT from lbm_dtrt_set, OPEN from lbm_dopen_set, WALL from lbm_dwall_set.
+// With all off these are the launches of a library without any of them.
+template <bool FORCE, bool TRT, bool OPEN, bool WALL>
+void launch_multi_form(const lbm_dp *d, const DpMultiArgsOf<WALL> &a) {
+  hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT, OPEN, WALL>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
+}
+
+// what a WALL instance takes beyond the arguments of the kernel without it
+DpWall wall_args(const lbm_dp *d) {
+  const size_t n = (size_t)d->p.nx * d->p.ny;
+  return DpWall{d->wall_dev, d->wall_dev + n, d->rho_wall};
+}
+
 template <bool FORCE, bool TRT, bool OPEN>
-void launch_multi_form(const lbm_dp *d, const DpMultiArgs &a) {
-  hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT, OPEN>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
+void launch_multi_wall(const lbm_dp *d, const DpMultiArgs &a) {
+  if (!d->wall) return launch_multi_form<FORCE, TRT, OPEN, false>(d, a);
+  DpMultiWallArgs w{};
+  static_cast<DpMultiArgs &>(w) = a;
+  w.wall = wall_args(d);
+  launch_multi_form<FORCE, TRT, OPEN, true>(d, w);
 }
 
 template <bool FORCE, bool TRT>
 void launch_multi_open(const lbm_dp *d, const DpMultiArgs &a) {
-  d->open ? launch_multi_form<FORCE, TRT, true>(d, a) : launch_multi_form<FORCE, TRT, false>(d, a);
+  d->open ? launch_multi_wall<FORCE, TRT, true>(d, a) : launch_multi_wall<FORCE, TRT, false>(d, a);
 }
 
 void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
@@ -183,15 +203,24 @@ void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
   else trt ? launch_multi_open<false, true>(d, a) : launch_multi_open<false, false>(d, a);
 }
 
-template <bool FORCE, bool TRT, bool OPEN>
-void launch_step_form(const lbm_dp *d, const DpStepArgs &a) {
+template <bool FORCE, bool TRT, bool OPEN, bool WALL>
+void launch_step_form(const lbm_dp *d, const DpStepArgsOf<WALL> &a) {
   const dim3 grid((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock));
-  hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT, OPEN>), grid, dim3(kBlock), 0, d->q.st, a);
+  hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT, OPEN, WALL>), grid, dim3(kBlock), 0, d->q.st, a);
+}
+
+template <bool FORCE, bool TRT, bool OPEN>
+void launch_step_wall(const lbm_dp *d, const DpStepArgs &a) {
+  if (!d->wall) return launch_step_form<FORCE, TRT, OPEN, false>(d, a);
+  DpStepWallArgs w{};
+  static_cast<DpStepArgs &>(w) = a;
+  w.wall = wall_args(d);
+  launch_step_form<FORCE, TRT, OPEN, true>(d, w);
 }
 
 template <bool FORCE, bool TRT>
 void launch_step_open(const lbm_dp *d, const DpStepArgs &a) {
-  d->open ? launch_step_form<FORCE, TRT, true>(d, a) : launch_step_form<FORCE, TRT, false>(d, a);
+  d->open ? launch_step_wall<FORCE, TRT, true>(d, a) : launch_step_wall<FORCE, TRT, false>(d, a);
 }
 
 void launch_step(const lbm_dp *d, const DpStepArgs &a) {
@@ -371,6 +400,7 @@ int lbm_dp_upload_obstacles(lbm_dp *d, const int32_t *obstacles) {
   // the body map, if one was set, described the old map's blocked cells: every blocked cell counts again
   if (int rc = upload_mask(d->mask, obstacles, (size_t)d->p.nx * d->p.ny)) return rc;
   body_reset(d->body, obstacles, (size_t)d->p.nx * d->p.ny);
+  // wall velocities stay as set: a kernel reads one only while its cell is blocked
   // open boundaries stay on: the blocked cells of columns 0 and nx - 1 are outside every body
   if (d->open) return body_rewrite(d->body, d->mask, d->p.nx, true);
   return LBM_OK;
@@ -610,6 +640,50 @@ int lbm_dopen_get(const lbm_dp *d, int *on_out, double *u_in_out, double *rho_ou
   if (on_out) *on_out = d->open ? 1 : 0;
   if (d->open && u_in_out) std::copy(d->u_in.begin(), d->u_in.end(), u_in_out);
   if (d->open && rho_out_out) *rho_out_out = d->rho_out;
+  return LBM_OK;
+}
+
+int lbm_dwall_set(lbm_dp *d, const double *u_x, const double *u_y, double rho_wall) {
+  // argument errors before anything of the context is read, or before a device is touched
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if ((u_x == nullptr) != (u_y == nullptr))
+    return lbm_fail(LBM_ERR_ARG, "%s is NULL and %s is not: a wall velocity has two components (both NULL: off)", u_x ? "u_y" : "u_x",
+                    u_x ? "u_x" : "u_y");
+  if (u_x && !positive_finite(rho_wall)) return lbm_fail(LBM_ERR_ARG, "rho_wall must be finite and positive (got %g)", rho_wall);
+  if (u_x)
+    if (int rc = wall_check(d->body, u_x, u_y, 1, d->p.ny, d->p.nx, false)) return rc;
+  if (d->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "wall velocities are set before the first step (%d done): one record holds one flow", d->steps_done);
+  if (!u_x) {
+    d->wall = false;
+    d->wall_u.clear();
+    d->rho_wall = 0.0;
+    return LBM_OK;
+  }
+  if (int rc = queue_sync(d->q)) return rc;
+  HIP_TRY(hipSetDevice(d->q.dev));
+  const size_t n = (size_t)d->p.nx * d->p.ny;
+  if (!d->wall_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->wall_dev), 2 * n * sizeof(double)));
+  std::vector<double> u(2 * n);
+  std::copy(u_x, u_x + n, u.begin());
+  std::copy(u_y, u_y + n, u.begin() + n);
+  HIP_TRY(hipMemcpy(d->wall_dev, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice));
+  d->wall = true;
+  d->wall_u.swap(u);
+  d->rho_wall = rho_wall;
+  return LBM_OK;
+}
+
+int lbm_dwall_get(const lbm_dp *d, int *on_out, double *u_x_out, double *u_y_out, double *rho_wall_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!on_out && !u_x_out && !u_y_out && !rho_wall_out)
+    return lbm_fail(LBM_ERR_ARG, "on_out, u_x_out, u_y_out and rho_wall_out are all NULL");
+  if (on_out) *on_out = d->wall ? 1 : 0;
+  if (!d->wall) return LBM_OK;
+  const size_t n = (size_t)d->p.nx * d->p.ny;
+  if (u_x_out) std::copy(d->wall_u.begin(), d->wall_u.begin() + n, u_x_out);
+  if (u_y_out) std::copy(d->wall_u.begin() + n, d->wall_u.end(), u_y_out);
+  if (rho_wall_out) *rho_wall_out = d->rho_wall;
   return LBM_OK;
 }
 
