@@ -208,6 +208,51 @@ __device__ __forceinline__ double dp_segment_tree16(double v) {
   v += dp_dpp_move<0x140>(v);
   return v;
 }
+// The same tree over the eight neighbouring lanes of a segment that hold two cells each (d2q9_dp_step's lanes): v is the
+// lane's pair sum p_i, then xor 1, 2, 4 (IEEE addition commutes: every lane of the segment ends with the tree's bits)
+__device__ __forceinline__ double dp_segment_tree8(double v) {
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  v += __shfl_xor(v, 4, 64);
+  return v;
+}
+
+// The sum of v over a workgroup of kBlock lanes in one fixed order, returned to lane 0 (0.0 elsewhere): the wave butterfly, then
+// the four waves in order.  Every lane of the workgroup calls it (a barrier), once per kernel.
+__device__ __forceinline__ double dp_block_sum(double v) {
+  __shared__ double wsum[kBlock / 64];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0) {
+    t = wsum[0];
+    for (int i = 1; i < kBlock / 64; i++) t += wsum[i];
+  }
+  return t;
+}
+
+// Output stage, one fluid cell from its nine values: the columns of final_state.dat (d2q9-bgk.c:787-832, 396-442) in double,
+// the oracle's statements (cell_moments), contraction off
+__device__ __forceinline__ void dp_output_cell(const double (&f)[9], double &ux, double &uy, double &uu, double &pr) {
+#pragma clang fp contract(off)
+  double local_density = 0.0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) local_density += f[k];
+  ux = (f[1] + f[5] + f[8] - f[3] - f[6] - f[7]) / local_density;
+  uy = (f[2] + f[5] + f[6] - f[4] - f[7] - f[8]) / local_density;
+  uu = __builtin_sqrt(ux * ux + uy * uy);
+  pr = local_density * (1.0 / 3.0);
+}
+
+// Host side: the instance four run-time options choose.  f(force, trt, open, wall) is called once, with the std::bool_constant
+// of each option, so a launch site names its kernel's template flags as decltype(force)::value, ... and widens its argument
+// struct where wall is true.  Every launch site goes through here: the sixteen instances of a kernel are these sixteen.
+template <class F>
+inline void dp_with_flags(bool force, bool trt, bool open, bool wall, F &&f) {
+  auto pick = [](bool on, auto &&g) { on ? g(std::true_type{}) : g(std::false_type{}); };
+  pick(force, [&](auto fo) { pick(trt, [&](auto tr) { pick(open, [&](auto op) { pick(wall, [&](auto wa) { f(fo, tr, op, wa); }); }); }); });
+}
 
 struct DpStepArgs {
   const double *src;
@@ -330,19 +375,12 @@ static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgsOf
       tot = ta + 0.0;
     }
   }
-  // the segment's tree: pairs, then xor 1, 2, 4 across its eight lanes (IEEE addition commutes: every lane of the
-  // segment ends with the same bits, the d2q9_dp_multi tree's)
-  tot += __shfl_xor(tot, 1, 64);
-  tot += __shfl_xor(tot, 2, 64);
-  tot += __shfl_xor(tot, 4, 64);
+  // the segment's tree across its eight lanes: the d2q9_dp_multi tree's bits
+  tot = dp_segment_tree8(tot);
   if (y < a.ny && ((t - (unsigned)y * lpr) & 7u) == 0) a.seg[(size_t)y * (lpr >> 3) + ((t - (unsigned)y * lpr) >> 3)] = tot;
   if constexpr (FORCE) {
-    tfx += __shfl_xor(tfx, 1, 64);
-    tfx += __shfl_xor(tfx, 2, 64);
-    tfx += __shfl_xor(tfx, 4, 64);
-    tfy += __shfl_xor(tfy, 1, 64);
-    tfy += __shfl_xor(tfy, 2, 64);
-    tfy += __shfl_xor(tfy, 4, 64);
+    tfx = dp_segment_tree8(tfx);
+    tfy = dp_segment_tree8(tfy);
     if (y < a.ny && ((t - (unsigned)y * lpr) & 7u) == 0) {
       const size_t comp = (size_t)a.ny * (lpr >> 3);
       const size_t at = (size_t)y * (lpr >> 3) + ((t - (unsigned)y * lpr) >> 3);
@@ -373,243 +411,43 @@ struct DpMultiWallArgs : DpMultiArgs {
 template <bool WALL>
 using DpMultiArgsOf = std::conditional_t<WALL, DpMultiWallArgs, DpMultiArgs>;
 
-// T <= TMAX timesteps per launch: a (TX + 2T) x (TY + 2T) region around the TX x TY output tile is loaded into LDS,
-// advanced T times LDS -> LDS on a region that shrinks by one cell per step (halo cells computed redundantly by the
-// neighbouring tiles), and the central tile is stored (d2q9_multi, d2q9_kernels.h).  Each step's |u| of the tile's cells
-// goes to an LDS tile of its own; one lane per 16-cell segment adds it up in the segment tree while the next step runs.
+}  // namespace lbm
+#include "dp_tile.h"   // dp_tile, on the per-cell functions above
+namespace lbm {
+
+// The one grid of a context as dp_tile takes it (dp_tile.h): the argument struct's own fields
+template <bool WALL>
+struct DpMultiGrid {
+  static constexpr bool kStageRhoOut = false;   // rho_out is a kernel argument, in SGPRs already; in LDS it cost two VGPRs
+  const DpMultiArgsOf<WALL> &a;
+  const double *src;
+  double *dst;
+  const uint8_t *mask;
+  double *seg_out;
+  double omega, omega_m, aw1, aw2;
+  __device__ __forceinline__ explicit DpMultiGrid(const DpMultiArgsOf<WALL> &a_)
+      : a(a_), src(a_.src), dst(a_.dst), mask(a_.mask), seg_out(a_.seg), omega(a_.omega), omega_m(a_.omega_m),
+        aw1(a_.aw1), aw2(a_.aw2) {}
+  __device__ __forceinline__ unsigned comp() const { return (unsigned)(a.ny * a.nseg); }
+  __device__ __forceinline__ const double *u_in() const { return a.u_in; }
+  __device__ __forceinline__ double rho_out() const { return a.rho_out; }
+  __device__ __forceinline__ size_t wall_cell0() const { return 0; }
+  __device__ __forceinline__ const double *wall_u_x() const { return a.wall.u_x; }
+  __device__ __forceinline__ const double *wall_u_y() const { return a.wall.u_y; }
+  __device__ __forceinline__ double rho_wall() const { return a.wall.rho_wall; }
+};
+
+// T <= TMAX timesteps per launch on one grid: dp_tile (dp_tile.h) with kMultiThreads threads, tile = blockIdx.x.
 //
 // Tile shape and depth, measured (tools/dp_throughput.py, one call, us/step at 128^2 / 256^2 / 512^2; profiles/dp_throughput.txt):
 //   16x16, T <= 8 (149 KB of LDS, one workgroup per CU)  1.98 / 2.53 / 8.07   <- instantiated
 //   16x8,  T <= 8 (113 KB)                               1.71 / 3.60 / 12.09  (wins only where every tile has a CU of its own)
 //   16x16, T <= 4 (85 KB)                                2.13 / 2.99 / 8.43
 // and one step per launch (d2q9_dp_step) 3.78 / 4.45 / 9.53, at 1024^2 23.8 against this kernel's 28.2: auto up to 300K cells.
-// FORCE: a blocked cell of the tile has both values of every link in lds[in] and the neighbours' bytes in lmask; a pass of one
-// lane per tile cell before each step's collision loop evaluates dp_force_cell there and adds F_x and F_y per segment in
-// registers, in the tree's order.  No LDS beyond the FORCE = false instance's.  TRT: dp_collide_cell<true> in the collision loop.
-// OPEN: the fix keys on the GRID column of every region cell (a tile at one end of the grid recomputes cells of the other end
-// in its halo, and a region wider than nx holds column 0 more than once).  The region load, which has the grid column, marks
-// the fluid cells of columns 0 and nx - 1 in two spare bits of their lmask byte; the collision loop branches on the byte it
-// reads anyway, and blocked-ness is the low two bits, the neighbour bytes of the force pass included.  The profile on the
-// region's rows is staged in LDS with the region (256 B).  No accelerate_flow.
-// WALL: the tile holds about 152 of the 160 KB of LDS, two doubles per region cell would be 16 KB more.  A pass behind the region
-// load reads the two velocities of every blocked cell by its grid cell and marks one that moves in a third spare bit of its byte
-// (kWallMoving); a pass behind the collision loop finds the grid cell of a marked byte from its region cell (the region's rows
-// and columns in the grid are staged in LDS as gy * nx and gx, 256 B; nx * ny is below 2^31 for every grid whose two arrays a
-// device holds), reads the two values from global memory under that branch and adds dp_wall_cell's terms to the bounce-back in
-// LDS.  Every copy of a wall cell in a region wider than the grid gets the velocity of its own grid cell.  Blocked-ness stays
-// the low two bits, for the force pass's own byte and its neighbours'.
+// With every option on the tile holds about 152 of the 160 KB of LDS.
 template <int TX, int TY, int TMAX, bool FORCE, bool TRT, bool OPEN, bool WALL = false>
 __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgsOf<WALL> a) {
-  constexpr bool MARKED = OPEN || WALL;   // lmask bytes carry marks above the low two bits
-  static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
-  constexpr int kRX = TX + 2 * TMAX, kRY = TY + 2 * TMAX;
-  __shared__ double lds[2][9][kRY * kRX];
-  __shared__ uint8_t lmask[kRY * kRX];
-  __shared__ double tval[2][TY][TX];
-  const int tid = threadIdx.x;
-  // OPEN: the profile on the region's rows, staged with the region (dp_ensemble_kernels.h says why)
-  [[maybe_unused]] double *lopen = nullptr;
-  if constexpr (OPEN) {
-    __shared__ double open_rows[kRY];
-    lopen = open_rows;
-  }
-  // WALL: where the region's rows and columns lie in the grid, gy * nx per row and then gx per column, staged with the region
-  // (256 B): a moving cell finds its two velocities without a division in the step loop
-  [[maybe_unused]] int *lwall = nullptr;
-  if constexpr (WALL) {
-    __shared__ int wall_cells[kRY + kRX];
-    lwall = wall_cells;
-  }
-  const int T = a.T;
-  const int RX = TX + 2 * T, RY = TY + 2 * T;
-  const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
-  const int gx0 = tile_x * TX - T, gy0 = tile_y * TY - T;  // region cell (0,0)
-  const size_t ps = a.plane_stride, rs = 9 * ps;
-  auto grid_row = [&](int ry) {
-    int r = (gy0 + ry) % a.ny;
-    return r < 0 ? r + a.ny : r;
-  };
-  // segment sums of step s (1-based) from tval[s & 1]
-  auto store_segments = [&](int s) {
-    constexpr int kSegs = TY * (TX / kDpSeg);
-    if (tid < kSegs) {
-      const int oy = tid / (TX / kDpSeg), sx = tid - oy * (TX / kDpSeg);
-      const int gy = tile_y * TY + oy;
-      const double *v = &tval[s & 1][oy][sx * kDpSeg];
-      double p[8];
-#pragma unroll
-      for (int i = 0; i < 8; i++) p[i] = v[2 * i] + v[2 * i + 1];
-      const double tot = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-      const int seg = tile_x * (TX / kDpSeg) + sx;
-      if (gy < a.ny && seg < a.nseg) a.seg[(size_t)(s - 1) * a.seg_step + (size_t)gy * a.nseg + seg] = tot;
-    }
-  };
-
-  // region -> LDS (periodic wrap in x, kernels.cl:99-102)
-  const float rinv = 1.0f / (float)RX;
-  for (int i = tid; i < RX * RY; i += kMultiThreads) {
-    const int ry = (int)(((float)i + 0.5f) * rinv), rx = i - ry * RX;
-    int gx = (gx0 + rx) % a.nx;
-    if (gx < 0) gx += a.nx;
-    const int gy = grid_row(ry);
-    const double *p = a.src + (size_t)gy * rs + gx;
-#pragma unroll
-    for (int k = 0; k < 9; k++) lds[0][k][ry * kRX + rx] = p[k * ps];
-    uint8_t mb = a.mask[(size_t)gy * a.nx + gx];
-    if constexpr (OPEN) {
-      if (mb == 0 && gx == 0) mb = kOpenInlet;
-      if (mb == 0 && gx == a.nx - 1) mb = kOpenOutlet;
-    }
-    lmask[ry * kRX + rx] = mb;
-  }
-  if constexpr (OPEN) {
-    static_assert(kRY <= kMultiThreads, "one lane per region row");
-    if (tid < RY) lopen[tid] = a.u_in[grid_row(tid)];
-  }
-  if constexpr (WALL) {
-    // The marks, in a pass of its own: every lane revisits the bytes it wrote itself (no barrier) and reads the two velocities
-    // of a blocked cell.  From an opaque copy of the lane index, as the force pass: nothing of this is kept in registers across
-    // the region load, whose nine plane loads the compiler otherwise issues one after the other.
-    int mine = tid;
-    asm volatile("" : "+v"(mine));
-    for (int i = mine; i < RX * RY; i += kMultiThreads) {
-      const int ry = (int)(((float)i + 0.5f) * rinv), rx = i - ry * RX;
-      const uint8_t mb = lmask[ry * kRX + rx];
-      if ((mb & kOpenBlocked) != 0) {
-        int gx = (gx0 + rx) % a.nx;
-        if (gx < 0) gx += a.nx;
-        const size_t at = (size_t)grid_row(ry) * a.nx + gx;
-        if (dp_wall_moves(a.wall.u_x[at], a.wall.u_y[at])) lmask[ry * kRX + rx] = mb | kWallMoving;
-      }
-    }
-    static_assert(kRY + kRX <= kMultiThreads, "one lane per region row and column");
-    if (mine < RY) {
-      lwall[mine] = grid_row(mine) * a.nx;
-    } else if (mine < RY + RX) {
-      int gx = (gx0 + mine - RY) % a.nx;
-      lwall[kRY + mine - RY] = gx < 0 ? gx + a.nx : gx;
-    }
-  }
-  __syncthreads();
-
-  for (int s = 1; s <= T; s++) {
-    if (s > 1) store_segments(s - 1);
-    if constexpr (FORCE) {
-      // The force of step s, from the state it streams (lds[in]): one lane per cell of the tile (every one, and its eight
-      // neighbours, is inside the region of every step; cells past the grid's edge and fluid cells count +0.0), sixteen
-      // neighbouring lanes = one row segment.  The segment tree of store_segments over those lanes in registers
-      // (dp_segment_tree16: every lane ends with the tree's bits), and the segment's first lane stores F_x
-      // and F_y one and two components (ny * nseg each) behind |u|.  No LDS, no barrier: the pass reads what the last barrier
-      // published and writes only global memory.  A pass of its own, from an opaque copy of the lane index, so that the
-      // collision loop below is the FORCE = false one and keeps nothing of this in registers.
-      static_assert(kDpSeg == 16 && (TX * TY) % 64 == 0 && kMultiThreads % 64 == 0, "whole waves of whole segments take the butterfly");
-      int first = tid;
-      asm volatile("" : "+v"(first));
-      static_assert(TX * TY <= kMultiThreads, "one lane per cell of the tile");
-      if (const int i = first; i < TX * TY) {
-        const int oy = i / TX, ox = i - oy * TX;
-        const int c = (oy + T) * kRX + ox + T;
-        const int gy = tile_y * TY + oy;
-        double fx = 0.0, fy = 0.0;
-        // 2: blocked, outside the body; WALL: a moving cell's byte carries its mark
-        const bool counts = (WALL ? lmask[c] & kOpenBlocked : lmask[c]) == 1 && tile_x * TX + ox < a.nx && gy < a.ny;
-        if (counts) {
-          const double(*f)[kRY * kRX] = lds[(s - 1) & 1];
-          const double g[9] = {0.0, f[1][c - 1], f[2][c - kRX], f[3][c + 1], f[4][c + kRX], f[5][c - kRX - 1],
-                               f[6][c - kRX + 1], f[7][c + kRX + 1], f[8][c + kRX - 1]};
-          double own[9];
-#pragma unroll
-          for (int k = 0; k < 9; k++) own[k] = f[k][c];
-          // OPEN: a marked fluid neighbour reads as fluid; WALL: a marked moving one as blocked
-          auto nbyte = [&](int at) -> uint8_t { return MARKED ? (uint8_t)(lmask[at] & kOpenBlocked) : lmask[at]; };
-          const uint8_t nb[9] = {0, nbyte(c - 1), nbyte(c - kRX), nbyte(c + 1), nbyte(c + kRX), nbyte(c - kRX - 1),
-                                 nbyte(c - kRX + 1), nbyte(c + kRX + 1), nbyte(c + kRX - 1)};
-          dp_force_cell(g, own, nb, fx, fy);
-        }
-        if (__ballot(counts) != 0ull) {   // a wave without a counting cell adds +0.0 to +0.0
-          fx = dp_segment_tree16(fx);
-          fy = dp_segment_tree16(fy);
-        }
-        const int seg = tile_x * (TX / kDpSeg) + ox / kDpSeg;
-        if ((ox & (kDpSeg - 1)) == 0 && gy < a.ny && seg < a.nseg) {
-          double *at = a.seg + (size_t)(s - 1) * a.seg_step + (size_t)gy * a.nseg + seg;
-          const size_t comp = (size_t)a.ny * a.nseg;
-          at[comp] = fx;
-          at[2 * comp] = fy;
-        }
-      }
-    }
-    const int in = (s - 1) & 1, out = s & 1;
-    const int w = RX - 2 * s, h = RY - 2 * s;
-    [[maybe_unused]] const bool accel_step = (s < T) || a.accel_next;
-    const float inv = 1.0f / (float)w;
-    for (int i = tid; i < w * h; i += kMultiThreads) {
-      const int q = (int)(((float)i + 0.5f) * inv);
-      const int rx = s + (i - q * w), ry = s + q;
-      const int c = ry * kRX + rx;
-      double g[9], o[9];
-      g[0] = lds[in][0][c];
-      g[1] = lds[in][1][c - 1];
-      g[2] = lds[in][2][c - kRX];
-      g[3] = lds[in][3][c + 1];
-      g[4] = lds[in][4][c + kRX];
-      g[5] = lds[in][5][c - kRX - 1];
-      g[6] = lds[in][6][c - kRX + 1];
-      g[7] = lds[in][7][c + kRX + 1];
-      g[8] = lds[in][8][c + kRX - 1];
-      const uint8_t mb = lmask[c];
-      const bool obst = MARKED ? (mb & kOpenBlocked) != 0 : mb != 0;
-      if constexpr (OPEN) {
-        if (mb & kOpenInlet) dp_open_inlet(g, lopen[ry]);
-        else if (mb & kOpenOutlet) dp_open_outlet(g, a.rho_out);
-      }
-      const double t = dp_collide_cell<TRT>(g, obst, a.omega, a.omega_m, o);
-      if constexpr (!OPEN)
-        if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, a.aw1, a.aw2);
-#pragma unroll
-      for (int k = 0; k < 9; k++) lds[out][k][c] = o[k];
-      // the tile's own cells: every one is inside the region of every step; cells past the grid's edge count 0
-      const int ox = rx - T, oy = ry - T;
-      if (ox >= 0 && ox < TX && oy >= 0 && oy < TY)
-        tval[s & 1][oy][ox] = (tile_x * TX + ox < a.nx && tile_y * TY + oy < a.ny) ? t : 0.0;
-    }
-    if constexpr (WALL) {
-      // The moving cells, in a pass of its own behind the collision loop, which stays the WALL = false one: every lane
-      // revisits the cells it wrote itself (no barrier), and one whose byte is marked adds the wall's terms to the bounce-back
-      // it stored.  From an opaque copy of the lane index, as the force pass.
-      int first = tid;
-      asm volatile("" : "+v"(first));
-      for (int i = first; i < w * h; i += kMultiThreads) {
-        const int q = (int)(((float)i + 0.5f) * inv);
-        const int rx = s + (i - q * w), ry = s + q;
-        const int c = ry * kRX + rx;
-        if (lmask[c] & kWallMoving) {
-          const int at = lwall[ry] + lwall[kRY + rx];
-          double o[9];
-#pragma unroll
-          for (int k = 1; k < 9; k++) o[k] = lds[out][k][c];
-          dp_wall_cell(o, a.wall.u_x[at], a.wall.u_y[at], a.wall.rho_wall);
-#pragma unroll
-          for (int k = 1; k < 9; k++) lds[out][k][c] = o[k];
-        }
-      }
-    }
-    __syncthreads();
-  }
-  store_segments(T);
-
-  // central tile -> global
-  const int fin = T & 1;
-  for (int i = tid; i < TX * TY; i += kMultiThreads) {
-    const int oy = i / TX, ox = i - oy * TX;
-    const int gx = tile_x * TX + ox, gy = tile_y * TY + oy;
-    if (gx < a.nx && gy < a.ny) {
-      const int c = (oy + T) * kRX + ox + T;
-      double *d = a.dst + (size_t)gy * rs + gx;
-#pragma unroll
-      for (int k = 0; k < 9; k++) d[k * ps] = lds[fin][k][c];
-    }
-  }
+  dp_tile<TX, TY, TMAX, kMultiThreads, FORCE, TRT, OPEN, WALL, DpMultiGrid<WALL>>(a);
 }
 
 // ---- second reduction stage: fixed order, no atomics ---------------------------------------------------------------
@@ -623,15 +461,8 @@ static __global__ __launch_bounds__(kBlock) void dp_reduce(const double *in, uns
   const double *p = in + (size_t)blockIdx.y * in_stride;
   double acc = 0.0;
   for (long i = i0 + threadIdx.x; i < i1; i += kBlock) acc += p[i];
-  __shared__ double wsum[kBlock / 64];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = wsum[0];
-    for (int i = 1; i < kBlock / 64; i++) t += wsum[i];
-    out[(size_t)blockIdx.y * out_stride + blockIdx.x] = t;
-  }
+  const double t = dp_block_sum(acc);
+  if (threadIdx.x == 0) out[(size_t)blockIdx.y * out_stride + blockIdx.x] = t;
 }
 
 // accelerate_flow of row ny-2 (kernels.cl:9-53): prologue of a run
@@ -676,8 +507,8 @@ static __global__ void dp_pack_planes(double *cells, unsigned long long plane_st
   }
 }
 
-// output stage: the columns of final_state.dat and the velocity sum (d2q9-bgk.c:787-832, 396-442) in double, the oracle's
-// statements (cell_moments); obstacle cells give 0, 0, 0, density/3.  partials[gridDim.x]: per-block sums of u.
+// output stage: the columns of final_state.dat and the velocity sum (dp_output_cell); obstacle cells give 0, 0, 0, density/3.
+// partials[gridDim.x]: per-block sums of u.
 static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *cells, unsigned long long plane_stride, int nx,
                                                                  const uint8_t *mask, size_t n, double density, double *u_x,
                                                                  double *u_y, double *u, double *pressure, double *partials) {
@@ -688,18 +519,11 @@ static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *c
     double ux = 0.0, uy = 0.0, uu = 0.0, pr = density * c_sq;
     if (mask[i] == 0) {
       double f[9];
-      double local_density = 0.0;
       const size_t y = i / nx;
       const size_t cell = y * 9 * plane_stride + (i - y * nx);
 #pragma unroll
-      for (int k = 0; k < 9; k++) {
-        f[k] = cells[k * plane_stride + cell];
-        local_density += f[k];
-      }
-      ux = (f[1] + f[5] + f[8] - f[3] - f[6] - f[7]) / local_density;
-      uy = (f[2] + f[5] + f[6] - f[4] - f[7] - f[8]) / local_density;
-      uu = __builtin_sqrt(ux * ux + uy * uy);
-      pr = local_density * c_sq;
+      for (int k = 0; k < 9; k++) f[k] = cells[k * plane_stride + cell];
+      dp_output_cell(f, ux, uy, uu, pr);
       tot_u += uu;
     }
     if (u_x) u_x[i] = ux;
@@ -707,15 +531,8 @@ static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *c
     if (u) u[i] = uu;
     if (pressure) pressure[i] = pr;
   }
-  __shared__ double wsum[kBlock / 64];
-  tot_u = wave_sum(tot_u);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = tot_u;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = wsum[0];
-    for (int i = 1; i < kBlock / 64; i++) t += wsum[i];
-    partials[blockIdx.x] = t;
-  }
+  const double t = dp_block_sum(tot_u);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
 // output stage: the force of the CURRENT state as the next step would stream it (include/lbm.h: lbm_dforce,
@@ -789,12 +606,8 @@ static __global__ __launch_bounds__(kBlock) void dp_force_state(const DpForceArg
     tfy = has_b ? fya + fyb : fya + 0.0;
   }
   // d2q9_dp_step's tree
-  tfx += __shfl_xor(tfx, 1, 64);
-  tfx += __shfl_xor(tfx, 2, 64);
-  tfx += __shfl_xor(tfx, 4, 64);
-  tfy += __shfl_xor(tfy, 1, 64);
-  tfy += __shfl_xor(tfy, 2, 64);
-  tfy += __shfl_xor(tfy, 4, 64);
+  tfx = dp_segment_tree8(tfx);
+  tfy = dp_segment_tree8(tfy);
   if (y < a.ny && ((t - (unsigned)y * lpr) & 7u) == 0) {
     const size_t at = (size_t)member * ((size_t)a.ny * (lpr >> 3)) + (size_t)y * (lpr >> 3) + ((t - (unsigned)y * lpr) >> 3);
     a.seg_x[at] = tfx;

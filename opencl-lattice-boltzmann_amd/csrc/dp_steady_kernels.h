@@ -1,7 +1,7 @@
 // Device side of a STEADY RUN of a double-precision ensemble (include/lbm.h: lbm_dsteady_*): steady_kernels.h for the fp64
 // members of dp_ensemble_kernels.h.  The per-member words and the kernel that starts a run are steady_words.h's, one copy for
 // both families.  d2q9_dp_ensemble_gated is d2q9_dp_ensemble behind a test of `active`: one copy of the arithmetic
-// (dens_tile), so the forcing guard and every bit-identity property of the plain kernel carry over; the workgroups of a
+// (dp_tile, dp_tile.h), so the forcing guard and every bit-identity property of the plain kernel carry over; the workgroups of a
 // stopped member return before they touch its cells or its segment sums.  dens_reduce and dens_accelerate_row skip the
 // same members, so a stopped member's cells, and its record beyond its count, are never written again.
 //
@@ -18,7 +18,7 @@ template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, boo
 __global__ __launch_bounds__(NT, (FORCE || TRT || OPEN || WALL) ? NT / 128 : 1) void d2q9_dp_ensemble_gated(const DensArgsOf<WALL> a,
                                                                                                             const int *active) {
   if (active[blockIdx.y] == 0) return;  // uniform over the workgroup, before the first barrier or LDS access
-  dens_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN, WALL>(a);
+  dp_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN, WALL, DensGrid<WALL>>(a);
 }
 
 // After a leg that ended at step count s on parity cur: the members that were active during it are now at s.  With

@@ -190,36 +190,22 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
   return upload_members(e, e->omega_m);
 }
 
-// active: NULL for an ordinary run, the members' words for a leg of a steady run
-template <bool FORCE, bool TRT, bool OPEN, bool WALL>
-void launch_dens_form(const lbm_dens *e, const DensArgsOf<WALL> &a, const int *active) {
-  const dim3 grid(e->tiles, e->n), block(kDensThreads);
-  if (!active)
-    hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL>), grid, block, 0, e->q.st, a);
-  else
-    hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL>), grid, block, 0,
-                       e->q.st, a, active);
-}
-
-template <bool FORCE, bool TRT, bool OPEN>
-void launch_dens_wall(const lbm_dens *e, const DensArgs &a, const int *active) {
-  if (!e->wall) return launch_dens_form<FORCE, TRT, OPEN, false>(e, a, active);
-  DensWallArgs w{};
-  static_cast<DensArgs &>(w) = a;
-  w.wall_u = e->wall_dev;
-  launch_dens_form<FORCE, TRT, OPEN, true>(e, w, active);
-}
-
-template <bool FORCE, bool TRT>
-void launch_dens_open(const lbm_dens *e, const DensArgs &a, const int *active) {
-  e->open ? launch_dens_wall<FORCE, TRT, true>(e, a, active) : launch_dens_wall<FORCE, TRT, false>(e, a, active);
-}
-
 // FORCE from the option "force", TRT from lbm_dtrt_ens_set, OPEN from lbm_dopen_ens_set, WALL from lbm_dwall_ens_set: with all
-// off these are the launches of a library without any of them
+// off these are the launches of a library without any of them.  active: NULL for an ordinary run, the members' words for a
+// leg of a steady run
 void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
-  if (e->force) e->trt ? launch_dens_open<true, true>(e, a, active) : launch_dens_open<true, false>(e, a, active);
-  else e->trt ? launch_dens_open<false, true>(e, a, active) : launch_dens_open<false, false>(e, a, active);
+  const dim3 grid(e->tiles, e->n), block(kDensThreads);
+  dp_with_flags(e->force, e->trt, e->open, e->wall, [&](auto force, auto trt, auto open, auto wall) {
+    constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value;
+    DensArgsOf<WALL> w{};
+    static_cast<DensArgs &>(w) = a;
+    if constexpr (WALL) w.wall_u = e->wall_dev;
+    if (!active)
+      hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL>), grid, block, 0, e->q.st, w);
+    else
+      hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL>), grid, block, 0,
+                         e->q.st, w, active);
+  });
 }
 
 // Second reduction stage, all members in one launch per stage: the per_step segment sums of each member (per_step apart) and

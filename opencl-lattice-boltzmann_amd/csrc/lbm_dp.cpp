@@ -172,61 +172,31 @@ int reduce_steps(lbm_dp *d, const double *in, size_t in_stride, int steps, doubl
 
 // The instance the options choose: FORCE from "force", TRT from lbm_dtrt_set, OPEN from lbm_dopen_set, WALL from lbm_dwall_set.
 // With all off these are the launches of a library without any of them.
-template <bool FORCE, bool TRT, bool OPEN, bool WALL>
-void launch_multi_form(const lbm_dp *d, const DpMultiArgsOf<WALL> &a) {
-  hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT, OPEN, WALL>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, a);
-}
-
 // what a WALL instance takes beyond the arguments of the kernel without it
 DpWall wall_args(const lbm_dp *d) {
   const size_t n = (size_t)d->p.nx * d->p.ny;
   return DpWall{d->wall_dev, d->wall_dev + n, d->rho_wall};
 }
 
-template <bool FORCE, bool TRT, bool OPEN>
-void launch_multi_wall(const lbm_dp *d, const DpMultiArgs &a) {
-  if (!d->wall) return launch_multi_form<FORCE, TRT, OPEN, false>(d, a);
-  DpMultiWallArgs w{};
-  static_cast<DpMultiArgs &>(w) = a;
-  w.wall = wall_args(d);
-  launch_multi_form<FORCE, TRT, OPEN, true>(d, w);
-}
-
-template <bool FORCE, bool TRT>
-void launch_multi_open(const lbm_dp *d, const DpMultiArgs &a) {
-  d->open ? launch_multi_wall<FORCE, TRT, true>(d, a) : launch_multi_wall<FORCE, TRT, false>(d, a);
-}
-
 void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
-  const bool trt = d->magic > 0.0;
-  if (d->force) trt ? launch_multi_open<true, true>(d, a) : launch_multi_open<true, false>(d, a);
-  else trt ? launch_multi_open<false, true>(d, a) : launch_multi_open<false, false>(d, a);
-}
-
-template <bool FORCE, bool TRT, bool OPEN, bool WALL>
-void launch_step_form(const lbm_dp *d, const DpStepArgsOf<WALL> &a) {
-  const dim3 grid((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock));
-  hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT, OPEN, WALL>), grid, dim3(kBlock), 0, d->q.st, a);
-}
-
-template <bool FORCE, bool TRT, bool OPEN>
-void launch_step_wall(const lbm_dp *d, const DpStepArgs &a) {
-  if (!d->wall) return launch_step_form<FORCE, TRT, OPEN, false>(d, a);
-  DpStepWallArgs w{};
-  static_cast<DpStepArgs &>(w) = a;
-  w.wall = wall_args(d);
-  launch_step_form<FORCE, TRT, OPEN, true>(d, w);
-}
-
-template <bool FORCE, bool TRT>
-void launch_step_open(const lbm_dp *d, const DpStepArgs &a) {
-  d->open ? launch_step_wall<FORCE, TRT, true>(d, a) : launch_step_wall<FORCE, TRT, false>(d, a);
+  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, [&](auto force, auto trt, auto open, auto wall) {
+    constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value;
+    DpMultiArgsOf<WALL> w{};
+    static_cast<DpMultiArgs &>(w) = a;
+    if constexpr (WALL) w.wall = wall_args(d);
+    hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT, OPEN, WALL>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, w);
+  });
 }
 
 void launch_step(const lbm_dp *d, const DpStepArgs &a) {
-  const bool trt = d->magic > 0.0;
-  if (d->force) trt ? launch_step_open<true, true>(d, a) : launch_step_open<true, false>(d, a);
-  else trt ? launch_step_open<false, true>(d, a) : launch_step_open<false, false>(d, a);
+  const dim3 grid((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock));
+  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, [&](auto force, auto trt, auto open, auto wall) {
+    constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value;
+    DpStepArgsOf<WALL> w{};
+    static_cast<DpStepArgs &>(w) = a;
+    if constexpr (WALL) w.wall = wall_args(d);
+    hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT, OPEN, WALL>), grid, dim3(kBlock), 0, d->q.st, w);
+  });
 }
 
 int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {

@@ -8,7 +8,8 @@ device, with HIP events around the step loop (run_timed),
              instances of d2q9_dp_ensemble), and
   step       one double-precision context of 8192 x 8192 at "multistep" 0, the bandwidth-bound d2q9_dp_step, with the lid (the
              wall on row ny - 1) at rest and moving with u_x = 0.05, and at rest once more on a context created after the other
-             two (a control for where a context's arrays lie),
+             two (a control for where a context's arrays lie); --step-multistep N runs the same context on the LDS tiles of
+             d2q9_dp_multi, N steps per launch (with --step-size 1024 or less),
 
 each for --reps repeats after a warm-up of both sides, alternating rest and motion so that clock drift of the box hits both
 alike; every repeat starts from the rest state (same work).  Each measurement runs in a child process of its own under a time
@@ -99,7 +100,7 @@ def measure_ensemble(lbm_amd, size, members, steps, reps, warmup, off_only):
     return summary(lbm_amd, "ensemble", us, extra)
 
 
-def measure_step(lbm_amd, size, steps, reps, warmup, off_only):
+def measure_step(lbm_amd, size, steps, reps, warmup, off_only, multistep=0):
     ob = disc_channel(size)
     p = lbm_amd.make_dparams(size, size, max(steps, warmup), density=0.1, accel=0.005, omega=1.7, obstacles=ob)
     sides = {"off": lbm_amd.LBMDouble(p, ob)}
@@ -110,11 +111,11 @@ def measure_step(lbm_amd, size, steps, reps, warmup, off_only):
         # place of a context's arrays in memory does to this kernel, whatever its walls do.
         sides["off_again"] = lbm_amd.LBMDouble(p, ob)
     for sim in sides.values():
-        sim.set_option("multistep", 0)
+        sim.set_option("multistep", multistep)
     us = alternate(sides, steps, reps, warmup)
     # 144 B per lattice update: nine doubles read, nine written (dp_kernels.h)
-    extra = {"size": "%dx%d" % (size, size), "kernel": "d2q9_dp_step", "steps": steps, "reps": reps,
-             "off_gbps": round(144.0 * size * size / statistics.median(us["off"]) / 1e3, 1)}
+    extra = {"size": "%dx%d" % (size, size), "kernel": "d2q9_dp_multi" if multistep else "d2q9_dp_step", "multistep": multistep,
+             "steps": steps, "reps": reps, "off_gbps": round(144.0 * size * size / statistics.median(us["off"]) / 1e3, 1)}
     if not off_only:
         extra["on_gbps"] = round(144.0 * size * size / statistics.median(us["on"]) / 1e3, 1)
         extra["moving_cells"] = size
@@ -131,7 +132,7 @@ def child(args):
     if args.child == "ensemble":
         out = measure_ensemble(lbm_amd, args.size, args.members, args.steps, args.reps, args.warmup, args.off_only)
     else:
-        out = measure_step(lbm_amd, args.step_size, args.step_steps, args.reps, args.step_warmup, args.off_only)
+        out = measure_step(lbm_amd, args.step_size, args.step_steps, args.reps, args.step_warmup, args.off_only, args.step_multistep)
     out["tree"] = args.label
     print(json.dumps(out))
     return 0
@@ -142,7 +143,7 @@ def run_child(args, what, root, label, off_only):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", what, "--root", root, "--label", label,
            "--size", str(args.size), "--members", str(args.members), "--steps", str(args.steps), "--reps", str(args.reps),
            "--warmup", str(args.warmup), "--step-size", str(args.step_size), "--step-steps", str(args.step_steps),
-           "--step-warmup", str(args.step_warmup)] + (["--off-only"] if off_only else [])
+           "--step-warmup", str(args.step_warmup), "--step-multistep", str(args.step_multistep)] + (["--off-only"] if off_only else [])
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
     except subprocess.TimeoutExpired:
@@ -177,6 +178,8 @@ def main():
     ap.add_argument("--step-size", type=int, default=8192, help="the context of the step measurement is step-size squared")
     ap.add_argument("--step-steps", type=int, default=100)
     ap.add_argument("--step-warmup", type=int, default=5)
+    ap.add_argument("--step-multistep", type=int, default=0,
+                    help="the step context's \"multistep\": 0 = d2q9_dp_step, 1..8 = d2q9_dp_multi at that depth (grids up to 1024 x 1024)")
     ap.add_argument("--against", help="a built checkout of another commit: also compare the plain paths of the two trees")
     ap.add_argument("--rounds", type=int, default=2, help="with --against: processes per tree and measurement")
     ap.add_argument("--timeout", type=int, default=150, help="seconds one measuring child may take")
