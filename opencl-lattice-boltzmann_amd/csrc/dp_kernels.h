@@ -450,52 +450,88 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
   dp_tile<TX, TY, TMAX, kMultiThreads, FORCE, TRT, OPEN, WALL, DpMultiGrid<WALL>>(a);
 }
 
+// What differs from member to member, in device memory, read by member index (a wave-uniform load), as EnsMember.  An
+// ensemble holds a table of these (lbm_dens.cpp), a context a table of one (lbm_dp.cpp): the helper kernels below read a
+// grid's constants here in both families.
+struct DpMember {
+  double omega, aw1, aw2;  // aw1 = density*accel/9, aw2 = density*accel/36 (kernels.cl:14-15), in double
+  double density;
+  double w0, w1, w2;       // rest state (d2q9-bgk.c:529-531)
+  union {
+    double omega_m;        // the second relaxation rate of the TRT instances (dp_trt_omega_minus); omega where the member is BGK
+    double pad;            // the name under which member_constants (host_common.h) zeroes the table's last slot
+  };
+};
+static_assert(sizeof(DpMember) == 64, "a member's constants are one 64-B line");
+
+// ---- the helper kernels: one set for both families --------------------------------------------------------------------
+// Each has a member axis (blockIdx.y; blockIdx.z in dp_reduce): member m's grid lies m * member_stride into cells, its mask
+// m * nx * ny into mask, its constants at members[m].  An ensemble launches them over its members, a context with one member
+// (lbm_dp.cpp), so what a member and a context compute here is one kernel's work.  The block count along x fixes the order of
+// every sum and is each launch site's own.
+
 // ---- second reduction stage: fixed order, no atomics ---------------------------------------------------------------
-// grid = (blocks, steps): block b of step r adds in[r * in_stride + i] for i in its contiguous chunk (lane-strided, then the
-// wave butterfly, then the four waves in order) into out[r * out_stride + b].  Run once into av_sum, or twice (partials
-// per block, then one block per step) where a step has many segments.
-static __global__ __launch_bounds__(kBlock) void dp_reduce(const double *in, unsigned long long in_stride, long n, double *out,
-                                                           unsigned long long out_stride) {
+// grid = (blocks, steps, members): block b of step r of member m adds in[r * in_stride + m * in_member + i] for i in its
+// contiguous chunk (lane-strided, then the wave butterfly, then the four waves in order) into
+// out[m * out_member + r * out_stride + b].  Run once into av_sum, or twice (partials per block, then one block per step and
+// member) where a step has many segments (dp_host.h: reduce_steps).  active: NULL, or one word per member; a member whose word
+// is 0 has stopped (dp_steady_kernels.h), its tiles wrote no segment sums and its record is left alone.
+static __global__ __launch_bounds__(kBlock) void dp_reduce(const double *in, unsigned long long in_stride,
+                                                           unsigned long long in_member, long n, double *out,
+                                                           unsigned long long out_stride, unsigned long long out_member,
+                                                           const int *active) {
+  if (active && active[blockIdx.z] == 0) return;  // uniform over the workgroup, before the barrier
   const long chunk = (n + gridDim.x - 1) / gridDim.x;
   const long i0 = (long)blockIdx.x * chunk, i1 = i0 + chunk < n ? i0 + chunk : n;
-  const double *p = in + (size_t)blockIdx.y * in_stride;
+  const double *p = in + (size_t)blockIdx.y * in_stride + (size_t)blockIdx.z * in_member;
   double acc = 0.0;
   for (long i = i0 + threadIdx.x; i < i1; i += kBlock) acc += p[i];
   const double t = dp_block_sum(acc);
-  if (threadIdx.x == 0) out[(size_t)blockIdx.y * out_stride + blockIdx.x] = t;
+  if (threadIdx.x == 0) out[(size_t)blockIdx.z * out_member + (size_t)blockIdx.y * out_stride + blockIdx.x] = t;
 }
 
-// accelerate_flow of row ny-2 (kernels.cl:9-53): prologue of a run
-static __global__ void dp_accelerate_row(double *cells, unsigned long long plane_stride, const uint8_t *mask, int nx, int row,
-                                         double aw1, double aw2) {
+// accelerate_flow of row ny-2 of every member (kernels.cl:9-53): prologue of a run.  active: as dp_reduce
+static __global__ void dp_accelerate_row(double *cells, unsigned long long plane_stride, unsigned long long member_stride,
+                                         const uint8_t *mask, const DpMember *members, int nx, int ny, const int *active) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
-  if (x >= nx) return;
+  if (x >= nx || (active && active[blockIdx.y] == 0)) return;
+  const DpMember mc = members[blockIdx.y];
+  const int row = ny - 2;
   double f[9];
-  double *c = cells + (size_t)row * 9 * plane_stride + x;
+  double *c = cells + (size_t)blockIdx.y * member_stride + (size_t)row * 9 * plane_stride + x;
 #pragma unroll
   for (int k = 0; k < 9; k++) f[k] = c[k * plane_stride];
-  dp_accelerate_cell(f, mask[(size_t)row * nx + x] != 0, aw1, aw2);
+  dp_accelerate_cell(f, mask[(size_t)blockIdx.y * ((size_t)nx * ny) + (size_t)row * nx + x] != 0, mc.aw1, mc.aw2);
 #pragma unroll
   for (int k = 0; k < 9; k++) c[k * plane_stride] = f[k];
 }
 
-// the rest state (values of d2q9-bgk.c:529-550, computed on the host in double)
-static __global__ void dp_init_cells(double *cells, unsigned long long plane_stride, int nx, size_t n, double w0, double w1,
-                                     double w2) {
+// every member's rest state from its own density (values of d2q9-bgk.c:529-550, computed on the host in double)
+static __global__ void dp_init_cells(double *cells, unsigned long long plane_stride, unsigned long long member_stride,
+                                     const DpMember *members, int nx, size_t n) {
+  const DpMember mc = members[blockIdx.y];
+  cells += (size_t)blockIdx.y * member_stride;
   for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
     const size_t y = c / nx;
     const size_t i = y * 9 * plane_stride + (c - y * nx);
-    cells[i] = w0;
+    cells[i] = mc.w0;
 #pragma unroll
-    for (int k = 1; k <= 4; k++) cells[k * plane_stride + i] = w1;
+    for (int k = 1; k <= 4; k++) cells[k * plane_stride + i] = mc.w1;
 #pragma unroll
-    for (int k = 5; k <= 8; k++) cells[k * plane_stride + i] = w2;
+    for (int k = 5; k <= 8; k++) cells[k * plane_stride + i] = mc.w2;
   }
 }
 
-// device layout <-> the caller's double[9][ny][nx] (staged in the grid that is not current).  TO_DEVICE: flat -> cells.
+// device layout <-> the caller's double[members][9][ny][nx] (staged in the grid array that is not current, one transfer
+// for all members).  TO_DEVICE: flat -> cells, else cells -> flat.  par: NULL, or one word per member that says which
+// of the two grid arrays holds that member's current state (0: cells, 1: cells_alt) once members have stopped on different
+// launch parities (dp_steady_kernels.h).
 template <bool TO_DEVICE>
-static __global__ void dp_pack_planes(double *cells, unsigned long long plane_stride, int nx, size_t n, double *flat) {
+static __global__ void dp_pack_planes(double *cells, double *cells_alt, const int *par, unsigned long long plane_stride,
+                                      unsigned long long member_stride, int nx, size_t n, double *flat) {
+  if (par && par[blockIdx.y]) cells = cells_alt;
+  cells += (size_t)blockIdx.y * member_stride;
+  flat += (size_t)blockIdx.y * 9 * n;
   for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
     const size_t y = c / nx;
     const size_t i = y * 9 * plane_stride + (c - y * nx);
@@ -507,13 +543,21 @@ static __global__ void dp_pack_planes(double *cells, unsigned long long plane_st
   }
 }
 
-// output stage: the columns of final_state.dat and the velocity sum (dp_output_cell); obstacle cells give 0, 0, 0, density/3.
-// partials[gridDim.x]: per-block sums of u.
-static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *cells, unsigned long long plane_stride, int nx,
-                                                                 const uint8_t *mask, size_t n, double density, double *u_x,
-                                                                 double *u_y, double *u, double *pressure, double *partials) {
+// output stage per member: the columns of final_state.dat and the velocity sum (dp_output_cell: d2q9-bgk.c:787-832, 396-442, in
+// double, the oracle's statements); obstacle cells give 0, 0, 0, density/3.  Outputs are double[members][ny][nx], partials
+// double[members][gridDim.x]: the per-block sums of u.  cells_alt, par: as dp_pack_planes
+static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *cells, const double *cells_alt, const int *par,
+                                                                 unsigned long long plane_stride,
+                                                                 unsigned long long member_stride, int nx, const uint8_t *mask,
+                                                                 size_t n, const DpMember *members, double *u_x, double *u_y,
+                                                                 double *u, double *pressure, double *partials) {
 #pragma clang fp contract(off)
   const double c_sq = 1.0 / 3.0;
+  const double density = members[blockIdx.y].density;
+  if (par && par[blockIdx.y]) cells = cells_alt;
+  cells += (size_t)blockIdx.y * member_stride;
+  mask += (size_t)blockIdx.y * n;
+  const size_t off = (size_t)blockIdx.y * n;
   double tot_u = 0.0;
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     double ux = 0.0, uy = 0.0, uu = 0.0, pr = density * c_sq;
@@ -526,33 +570,31 @@ static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *c
       dp_output_cell(f, ux, uy, uu, pr);
       tot_u += uu;
     }
-    if (u_x) u_x[i] = ux;
-    if (u_y) u_y[i] = uy;
-    if (u) u[i] = uu;
-    if (pressure) pressure[i] = pr;
+    if (u_x) u_x[off + i] = ux;
+    if (u_y) u_y[off + i] = uy;
+    if (u) u[off + i] = uu;
+    if (pressure) pressure[off + i] = pr;
   }
   const double t = dp_block_sum(tot_u);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
 }
 
 // output stage: the force of the CURRENT state as the next step would stream it (include/lbm.h: lbm_dforce,
 // lbm_dforce_ens).  grid = (blocks of d2q9_dp_step's lanes, members): member m's state lies m * member_stride into cells (or
-// cells_alt where par[m] is set: dens_pack_planes), its mask m * nx * ny into mask, its segment sums m * ny * nseg into
-// seg_x and seg_y.  A blocked cell gathers from each fluid neighbour that neighbour's value after accelerate_flow: on row
+// cells_alt where par[m] is set: dp_pack_planes), its mask m * nx * ny into mask, its segment sums m * ny * nseg into
+// seg_x and seg_y, its aw1, aw2 are members[m]'s.  A blocked cell gathers from each fluid neighbour that neighbour's value after accelerate_flow: on row
 // ny - 2 the neighbour's nine values go through dp_accelerate_cell in registers, the state is not written.  The per-cell
 // function, the segment tree and, behind it, the reduction are the step kernels', so the value equals the record entry
-// the next step writes, bit for bit.  aw: NULL (aw1, aw2 are the arguments), or member m's aw1, aw2 at aw[m * aw_stride],
-// aw[m * aw_stride + 1].
+// the next step writes, bit for bit.
 struct DpForceArgs {
   const double *cells, *cells_alt;
   const int *par;
   const uint8_t *mask;
   double *seg_x, *seg_y;     // [members][ny][nseg]
-  const double *aw;
-  unsigned long long plane_stride, member_stride, aw_stride;
+  const DpMember *members;
+  unsigned long long plane_stride, member_stride;
   int nx, ny;
   int lanes_per_row;         // as DpStepArgs
-  double aw1, aw2;
   int no_accel;              // open boundaries: the next step has no accelerate_flow, the neighbours' values go as stored
 };
 
@@ -568,8 +610,7 @@ static __global__ __launch_bounds__(kBlock) void dp_force_state(const DpForceArg
     const size_t ps = a.plane_stride, rs = 9 * ps;
     const double *cells = ((a.par && a.par[member]) ? a.cells_alt : a.cells) + (size_t)member * a.member_stride;
     const uint8_t *mask = a.mask + (size_t)member * ((size_t)a.nx * a.ny);
-    const double aw1 = a.aw ? a.aw[(size_t)member * a.aw_stride] : a.aw1;
-    const double aw2 = a.aw ? a.aw[(size_t)member * a.aw_stride + 1] : a.aw2;
+    const double aw1 = a.members[member].aw1, aw2 = a.members[member].aw2;
     const int ys = (y == 0) ? a.ny - 1 : y - 1, yn = (y + 1 == a.ny) ? 0 : y + 1;  // kernels.cl:91-93
     auto cell_force = [&](int x, double &fx, double &fy) {
       const int xl = (x == 0) ? a.nx - 1 : x - 1, xr = (x + 1 == a.nx) ? 0 : x + 1;   // kernels.cl:99-102

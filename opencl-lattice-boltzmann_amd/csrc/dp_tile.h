@@ -1,7 +1,7 @@
 // The LDS-tile step of the double-precision families, written once: the body of d2q9_dp_multi (dp_kernels.h, one grid) and
 // of d2q9_dp_ensemble / d2q9_dp_ensemble_gated (dp_ensemble_kernels.h, dp_steady_kernels.h: many grids, member = blockIdx.y).
 // Each of those kernels names its Grid and calls dp_tile on its own argument struct; what a family does to find its grid
-// (member offsets, the DensMember load, the tables behind it) is in its Grid and nowhere else, so a physics option is one
+// (member offsets, the DpMember load, the tables behind it) is in its Grid and nowhere else, so a physics option is one
 // edit here.  dp_kernels.h includes this file below the per-cell functions it is built on; it is not included on its own.
 //
 // What the two argument structs name alike, dp_tile reads from them: plane_stride, seg_step, nx, ny, nseg, tiles_x, T,

@@ -15,6 +15,7 @@
 // member's own (`par`).
 #include "../../include/lbm.h"
 #include "body_map.h"
+#include "dp_host.h"
 #include "dp_steady_kernels.h"
 #include "host_common.h"
 
@@ -30,7 +31,7 @@ using namespace lbm_host;
 namespace {
 
 constexpr long kDensMaxCells = 300L * 1024;   // up to here lbm_dp itself takes the LDS-tile form (multistep_effective, lbm_dp.cpp)
-constexpr int kDensMaxMembers = 65535;        // member index = blockIdx.y (blockIdx.z in dens_reduce)
+constexpr int kDensMaxMembers = 65535;        // member index = blockIdx.y (blockIdx.z in dp_reduce)
 constexpr size_t kDensRingBytes = 32u << 20;  // per-step segment sums of all members buffered between reductions
 constexpr int kDensRingMax = 256;
 constexpr long kDensSegsPerBlock = 4096;      // segments per block of the first reduction stage: lbm_dp.cpp's kDpSegsPerBlock
@@ -60,7 +61,7 @@ struct lbm_dens {
   double *cells[2] = {nullptr, nullptr};
   uint8_t *mask = nullptr;         // [n][ny][nx]: 0 fluid, 1 blocked and counted in the force, 2 blocked outside the body
   BodyMap body;                    // the host's copy of what the mask was made of (body_map.h)
-  DensMember *members = nullptr;   // [n], then the open-boundary table double[n][ny + 1] (dens_open_table), then rho_wall[n]
+  DpMember *members = nullptr;     // [n], then the open-boundary table double[n][ny + 1] (dens_open_table), then rho_wall[n]
                                    // (dens_wall_table)
   double *seg = nullptr;           // [ring][n][ny][nseg]
   double *red = nullptr;           // [ring][n][red_blocks]: first reduction stage
@@ -71,7 +72,7 @@ struct lbm_dens {
   bool force = false;              // option "force": the kernels' FORCE instances, three values per segment
   bool trt = false;                // lbm_dtrt_ens_set: the kernels' TRT instances, for all members
   std::vector<double> magic;       // [n]: every member's magic parameter, 0 while the ensemble is BGK
-  std::vector<double> omega_m;     // [n]: the host's copy of DensMember::omega_m (BGK: the member's omega)
+  std::vector<double> omega_m;     // [n]: the host's copy of DpMember::omega_m (BGK: the member's omega)
   bool open = false;               // lbm_dopen_ens_set: the kernels' OPEN instances for all members, no accelerate_flow
   std::vector<double> open_host;   // [n][ny + 1]: per member u_in[ny], then rho_out (empty while off); on the device behind `members`
   bool wall = false;               // lbm_dwall_ens_set: the kernels' WALL instances for all members
@@ -134,12 +135,12 @@ int alloc_ring(lbm_dens *e) {
 
 // The table of per-member constants with these second relaxation rates, to the device
 int upload_members(lbm_dens *e, const std::vector<double> &omega_m) {
-  std::vector<DensMember> t(e->n);
+  std::vector<DpMember> t(e->n);
   for (int i = 0; i < e->n; i++) {
-    t[i] = member_constants<DensMember>(e->p[i]);
+    t[i] = member_constants<DpMember>(e->p[i]);
     t[i].omega_m = omega_m[i];
   }
-  HIP_TRY(hipMemcpy(e->members, t.data(), t.size() * sizeof(DensMember), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->members, t.data(), t.size() * sizeof(DpMember), hipMemcpyHostToDevice));
   return LBM_OK;
 }
 
@@ -161,7 +162,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
 
   // what the ensemble needs against what the device has free: refuse here rather than fail half-way through
   const size_t cells_bytes = ((size_t)n * e->member_stride + 32) * sizeof(double);
-  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + (size_t)n * (sizeof(DensMember) + (size_t)(ny + 2) * sizeof(double)) +
+  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + (size_t)n * (sizeof(DpMember) + (size_t)(ny + 2) * sizeof(double)) +
                       (size_t)e->ring * all_step * sizeof(double) + (size_t)e->ring * n * e->red_blocks * sizeof(double) +
                       (size_t)n * e->max_iters * sizeof(double) + (size_t)n * e->fin_blocks * sizeof(double);
   size_t free_b = 0, total_b = 0;
@@ -176,7 +177,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
     HIP_TRY(hipMemset(e->cells[i], 0, cells_bytes));
   }
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->mask), (size_t)n * cells_per + 64));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), (size_t)n * (sizeof(DensMember) + (size_t)(ny + 2) * sizeof(double))));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), (size_t)n * (sizeof(DpMember) + (size_t)(ny + 2) * sizeof(double))));
   if (int rc = alloc_ring(e)) return rc;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->av_sum), (size_t)n * e->max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->fin_partials), (size_t)n * e->fin_blocks * sizeof(double)));
@@ -208,28 +209,6 @@ void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
   });
 }
 
-// Second reduction stage, all members in one launch per stage: the per_step segment sums of each member (per_step apart) and
-// each of `steps` steps (`in_stride` apart from `in`) into out[m * out_member + r], in one stage or, where a step has many
-// segments, in two.  active: as launch_dens.
-int reduce_steps(lbm_dens *e, const double *in, size_t in_stride, int steps, double *out, unsigned long long out_member,
-                 const int *active) {
-  const size_t per_step = (size_t)e->ny * e->nseg;
-  if (e->red_blocks > 1) {
-    hipLaunchKernelGGL(dens_reduce, dim3(e->red_blocks, steps, e->n), dim3(kBlock), 0, e->q.st, in, (unsigned long long)in_stride,
-                       (unsigned long long)per_step, (long)per_step, e->red, (unsigned long long)e->n * e->red_blocks,
-                       (unsigned long long)e->red_blocks, active);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(dens_reduce, dim3(1, steps, e->n), dim3(kBlock), 0, e->q.st, (const double *)e->red,
-                       (unsigned long long)e->n * e->red_blocks, (unsigned long long)e->red_blocks, (long)e->red_blocks, out, 1ull,
-                       out_member, active);
-  } else {
-    hipLaunchKernelGGL(dens_reduce, dim3(1, steps, e->n), dim3(kBlock), 0, e->q.st, in, (unsigned long long)in_stride,
-                       (unsigned long long)per_step, (long)per_step, out, 1ull, out_member, active);
-  }
-  HIP_TRY(hipGetLastError());
-  return LBM_OK;
-}
-
 // nsteps steps from step count `first` on, enqueued: the prologue, the launches, the reductions into the record.  Flips
 // e->cur per launch; the caller counts the steps.  active: as launch_dens.
 int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
@@ -239,8 +218,8 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
   // into the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
   if (!e->open) {
-    hipLaunchKernelGGL(dens_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
-                       e->member_stride, (const uint8_t *)e->mask, (const DensMember *)e->members, e->nx, e->ny, active);
+    hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
+                       e->member_stride, (const uint8_t *)e->mask, (const DpMember *)e->members, e->nx, e->ny, active);
     HIP_TRY(hipGetLastError());
   }
 
@@ -252,7 +231,9 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
     const unsigned long long record = (unsigned long long)e->max_iters;
     for (int v = 0; v < nval; v++) {
       double *out = (v == 0 ? e->av_sum : e->force_rec + (size_t)(v - 1) * e->n * e->max_iters) + batch_first;
-      if (int rc = reduce_steps(e, e->seg + (size_t)v * all_step, slot, e->ring_fill, out, record, active)) return rc;
+      if (int rc = reduce_steps(e->q.st, e->seg + (size_t)v * all_step, slot, per_step, e->ring_fill, e->n, e->red, e->red_blocks, out,
+                                record, active))
+        return rc;
     }
     batch_first += e->ring_fill;
     e->ring_fill = 0;
@@ -333,8 +314,8 @@ int steady_alloc(lbm_dens *e) {
   return LBM_OK;
 }
 
-// drag_rec: NULL for the av_vels criterion (dens_steady_check), the members' F_x records for the drag criterion
-// (dens_drag_check); everything else is one loop
+// drag_rec: NULL for the av_vels criterion, the members' F_x records for the drag criterion (dens_steady_check without a
+// factor); everything else is one loop
 int steady_impl(lbm_dens *e, int max_steps, int window, double rel_tol, const double *drag_rec, bool *launched) {
   if (int rc = check_runnable(max_steps, e->failed, "ensemble")) return rc;  // max_steps >= 0 here (lbm_dsteady_run)
   if (e->ragged) return refuse_ragged(e);
@@ -357,12 +338,9 @@ int steady_impl(lbm_dens *e, int max_steps, int window, double rel_tol, const do
     // a check point: a whole leg, with a record entry one window back (step counts start at 1)
     const int check = (leg == window && s - window >= 1) ? 1 : 0;
     // enqueue_steps ended with its flush: the leg's reductions into av_sum and the force records are on the stream already
-    if (!drag_rec)
-      hipLaunchKernelGGL(dens_steady_check, mgrid, mblock, 0, e->q.st, w, n, (const double *)e->av_sum,
-                         (unsigned long long)e->max_iters, (const double *)e->steady_inv, s, window, rel_tol, check, e->cur);
-    else
-      hipLaunchKernelGGL(dens_drag_check, mgrid, mblock, 0, e->q.st, w, n, drag_rec, (unsigned long long)e->max_iters, s, window,
-                         rel_tol, check, e->cur);
+    hipLaunchKernelGGL(dens_steady_check, mgrid, mblock, 0, e->q.st, w, n, drag_rec ? drag_rec : (const double *)e->av_sum,
+                       (unsigned long long)e->max_iters, drag_rec ? (const double *)nullptr : (const double *)e->steady_inv, s, window,
+                       rel_tol, check, e->cur);
     HIP_TRY(hipGetLastError());
     // Every few checks: is anyone left?  Only how much is enqueued depends on the answer; what a member computes does not,
     // the workgroups of a stopped member return at once.
@@ -388,9 +366,9 @@ int stage_of(lbm_dens *e, double **stage) {
 // the output stage of all members, each from the array that holds it, into `d[0..3]` (any may be NULL) and the per-block
 // sums of u
 int final_fields_dens(lbm_dens *e, double *const (&d)[4]) {
-  hipLaunchKernelGGL(dens_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->q.st,
+  hipLaunchKernelGGL(dp_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->q.st,
                      (const double *)e->cells[e->ragged ? 0 : e->cur], (const double *)e->cells[1], member_parity(e), e->plane_stride,
-                     e->member_stride, e->nx, (const uint8_t *)e->mask, (size_t)e->nx * e->ny, (const DensMember *)e->members, d[0],
+                     e->member_stride, e->nx, (const uint8_t *)e->mask, (size_t)e->nx * e->ny, (const DpMember *)e->members, d[0],
                      d[1], d[2], d[3], e->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
@@ -450,11 +428,11 @@ int lbm_dens_upload(lbm_dens *e, const double *cells) {
     // one transfer of the caller's double[n][9][ny][nx] into the second grid array (9 nx ny <= member_stride), then one
     // launch that scatters every member's planes into the first (d2q9-bgk.c:200-203 for all members)
     HIP_TRY(hipMemcpyAsync(e->cells[1], cells, (size_t)e->n * 9 * per * sizeof(double), hipMemcpyHostToDevice, e->q.st));
-    hipLaunchKernelGGL(dens_pack_planes<true>, grid, dim3(256), 0, e->q.st, e->cells[0], (double *)nullptr, (const int *)nullptr,
+    hipLaunchKernelGGL(dp_pack_planes<true>, grid, dim3(256), 0, e->q.st, e->cells[0], (double *)nullptr, (const int *)nullptr,
                        e->plane_stride, e->member_stride, e->nx, per, e->cells[1]);
   } else {
-    hipLaunchKernelGGL(dens_init_cells, grid, dim3(256), 0, e->q.st, e->cells[0], e->plane_stride, e->member_stride,
-                       (const DensMember *)e->members, e->nx, per);
+    hipLaunchKernelGGL(dp_init_cells, grid, dim3(256), 0, e->q.st, e->cells[0], e->plane_stride, e->member_stride,
+                       (const DpMember *)e->members, e->nx, per);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->q.st));
@@ -494,7 +472,7 @@ int lbm_dens_download(lbm_dens *e, double *cells_out, double *av_vels_out) {
     // contiguous transfer
     double *stage = nullptr;
     if (int rc = stage_of(e, &stage)) return rc;
-    hipLaunchKernelGGL(dens_pack_planes<false>, dim3((unsigned)std::min(div_up((long)per, 256), 1024L), e->n), dim3(256), 0, e->q.st,
+    hipLaunchKernelGGL(dp_pack_planes<false>, dim3((unsigned)std::min(div_up((long)per, 256), 1024L), e->n), dim3(256), 0, e->q.st,
                        e->cells[e->ragged ? 0 : e->cur], e->cells[1], member_parity(e), e->plane_stride, e->member_stride, e->nx,
                        per, stage);
     HIP_TRY(hipGetLastError());
@@ -630,28 +608,19 @@ int lbm_dforce_ens(lbm_dens *e, double *fx, double *fy) {
   if (int rc = queue_sync(e->q)) return rc;
   const size_t n = (size_t)e->n;
   if (!e->force_now) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->force_now), 2 * n * sizeof(double)));
-  // between runs the ring is empty (every run ends with its reduction): its first two blocks of n * ny * nseg take the
-  // segment sums of F_x and F_y, which then go the way a step's go.  Each member from the array that holds it.
-  const size_t all_step = n * e->ny * e->nseg;
+  // each member from the array that holds it
   DpForceArgs a{};
   a.cells = e->cells[e->ragged ? 0 : e->cur];
   a.cells_alt = e->cells[1];
   a.par = member_parity(e);
   a.mask = e->mask;
-  a.seg_x = e->seg;
-  a.seg_y = e->seg + all_step;
-  a.aw = &e->members[0].aw1;                 // a device address: aw1, aw2 lie side by side in a DensMember
-  a.aw_stride = sizeof(DensMember) / sizeof(double);
+  a.members = e->members;
   a.plane_stride = e->plane_stride;
   a.member_stride = e->member_stride;
   a.nx = e->nx;
   a.ny = e->ny;
-  a.lanes_per_row = e->nseg * 8;
   a.no_accel = e->open ? 1 : 0;
-  hipLaunchKernelGGL(dp_force_state, dim3((unsigned)div_up((long)a.lanes_per_row * e->ny, kBlock), e->n), dim3(kBlock), 0, e->q.st, a);
-  HIP_TRY(hipGetLastError());
-  for (int c = 0; c < 2; c++)
-    if (int rc = reduce_steps(e, e->seg + (size_t)c * all_step, all_step, 1, e->force_now + (size_t)c * n, 1ull, nullptr)) return rc;
+  if (int rc = force_state(e->q.st, a, e->nseg, e->n, e->seg, e->red, e->red_blocks, e->force_now)) return rc;
   std::vector<double> f(2 * n);
   HIP_TRY(hipMemcpyAsync(f.data(), e->force_now, f.size() * sizeof(double), hipMemcpyDeviceToHost, e->q.st));
   HIP_TRY(hipStreamSynchronize(e->q.st));

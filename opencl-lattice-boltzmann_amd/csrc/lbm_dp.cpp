@@ -8,6 +8,7 @@
 // in-order queue (d2q9-bgk.c:221-239), in the precision of its fp64 ancestor.
 #include "../../include/lbm.h"
 #include "body_map.h"
+#include "dp_host.h"
 #include "dp_kernels.h"
 #include "host_common.h"
 
@@ -46,6 +47,8 @@ struct lbm_dp {
   double *cells[2] = {nullptr, nullptr};
   uint8_t *mask = nullptr;        // [ny][nx]: 0 fluid, 1 blocked and counted in the force, 2 blocked outside the body
   BodyMap body;                   // the host's copy of what the mask was made of (body_map.h)
+  DpMember *members = nullptr;    // [1]: this grid's constants as the helper kernels read them (dp_kernels.h); the step kernels
+                                  // take omega, omega_m, aw1, aw2 as arguments, and the table's omega, omega_m are not read
   double *seg = nullptr;          // [ring][ny][nseg]
   double *red = nullptr;          // [ring][red_blocks]: first reduction stage
   double *av_sum = nullptr;       // [max_iters]
@@ -84,6 +87,7 @@ void free_dp(lbm_dp *d) {
   for (double *c : d->cells)
     if (c) (void)hipFree(c);
   if (d->mask) (void)hipFree(d->mask);
+  if (d->members) (void)hipFree(d->members);
   if (d->seg) (void)hipFree(d->seg);
   if (d->red) (void)hipFree(d->red);
   if (d->av_sum) (void)hipFree(d->av_sum);
@@ -130,7 +134,7 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
     return lbm_fail(LBM_ERR_ARG, "a grid of %dx%d cells is beyond the 2^31 lanes of one launch", nx, ny);
 
   const size_t grid_bytes = (9 * d->plane_stride * ny + 32) * sizeof(double);
-  const size_t need = 2 * grid_bytes + cells + 64 + (size_t)d->ring * per_step * sizeof(double) +
+  const size_t need = 2 * grid_bytes + cells + 64 + sizeof(DpMember) + (size_t)d->ring * per_step * sizeof(double) +
                       (size_t)d->ring * d->red_blocks * sizeof(double) + (size_t)d->p.max_iters * sizeof(double) +
                       (size_t)d->fin_blocks * sizeof(double);
   size_t free_b = 0, total_b = 0;
@@ -148,26 +152,12 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
   if (int rc = alloc_ring(d)) return rc;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->av_sum), (size_t)d->p.max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->fin_partials), (size_t)d->fin_blocks * sizeof(double)));
+  // a table of one member: aw1, aw2 are run_dp_impl's statements, and the rest state's w0..w2 come from here alone
+  const DpMember m = member_constants<DpMember>(d->p);
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->members), sizeof(DpMember)));
+  HIP_TRY(hipMemcpy(d->members, &m, sizeof(DpMember), hipMemcpyHostToDevice));
   body_reset(d->body, obstacles, cells);
   return upload_mask(d->mask, obstacles, cells);
-}
-
-// Second reduction stage (kernels.cl:234-290 counterpart): the per_step segment sums of each of `steps` steps, `in_stride`
-// apart from `in`, into out[r * out_stride], in one stage or, where a step has many segments, in two
-int reduce_steps(lbm_dp *d, const double *in, size_t in_stride, int steps, double *out, unsigned long long out_stride) {
-  const size_t per_step = (size_t)d->p.ny * d->nseg;
-  if (d->red_blocks > 1) {
-    hipLaunchKernelGGL(dp_reduce, dim3(d->red_blocks, steps), dim3(kBlock), 0, d->q.st, in, (unsigned long long)in_stride,
-                       (long)per_step, d->red, (unsigned long long)d->red_blocks);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(dp_reduce, dim3(1, steps), dim3(kBlock), 0, d->q.st, (const double *)d->red,
-                       (unsigned long long)d->red_blocks, (long)d->red_blocks, out, out_stride);
-  } else {
-    hipLaunchKernelGGL(dp_reduce, dim3(1, steps), dim3(kBlock), 0, d->q.st, in, (unsigned long long)in_stride, (long)per_step, out,
-                       out_stride);
-  }
-  HIP_TRY(hipGetLastError());
-  return LBM_OK;
 }
 
 // The instance the options choose: FORCE from "force", TRT from lbm_dtrt_set, OPEN from lbm_dopen_set, WALL from lbm_dwall_set.
@@ -217,8 +207,8 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   // prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53); later steps get theirs fused into
   // the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
   if (!d->open) {
-    hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(nx, 128)), dim3(128), 0, d->q.st, d->cells[d->cur], d->plane_stride, d->mask,
-                       nx, ny - 2, aw1, aw2);
+    hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(nx, 128), 1), dim3(128), 0, d->q.st, d->cells[d->cur], d->plane_stride, 0ull,
+                       (const uint8_t *)d->mask, (const DpMember *)d->members, nx, ny, (const int *)nullptr);
     HIP_TRY(hipGetLastError());
   }
 
@@ -229,7 +219,9 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
     // |u| into av_sum and, with "force", F_x and F_y into their records: the same launches on each value's segments
     for (int v = 0; v < nval; v++) {
       double *record = (v == 0 ? d->av_sum : d->force_rec + (size_t)(v - 1) * d->p.max_iters) + batch_first;
-      if (int rc = reduce_steps(d, d->seg + (size_t)v * per_step, slot, d->ring_fill, record, 1ull)) return rc;
+      if (int rc = reduce_steps(d->q.st, d->seg + (size_t)v * per_step, slot, per_step, d->ring_fill, 1, d->red, d->red_blocks, record,
+                                0ull, nullptr))
+        return rc;
     }
     batch_first += d->ring_fill;
     d->ring_fill = 0;
@@ -303,8 +295,9 @@ int run_dp(lbm_dp *d, int nsteps, bool timed, double *ms) {
 // the output stage into `d[0..3]` (any may be NULL) and the per-block sums of u
 int final_fields_dp(lbm_dp *d, double *const (&dst)[4]) {
   const size_t n = (size_t)d->p.nx * d->p.ny;
-  hipLaunchKernelGGL(dp_final_fields, dim3(d->fin_blocks), dim3(kBlock), 0, d->q.st, (const double *)d->cells[d->cur], d->plane_stride,
-                     d->p.nx, (const uint8_t *)d->mask, n, d->p.density, dst[0], dst[1], dst[2], dst[3], d->fin_partials);
+  hipLaunchKernelGGL(dp_final_fields, dim3(d->fin_blocks, 1), dim3(kBlock), 0, d->q.st, (const double *)d->cells[d->cur],
+                     (const double *)nullptr, (const int *)nullptr, d->plane_stride, 0ull, d->p.nx, (const uint8_t *)d->mask, n,
+                     (const DpMember *)d->members, dst[0], dst[1], dst[2], dst[3], d->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
 }
@@ -350,11 +343,12 @@ int lbm_dp_upload(lbm_dp *d, const double *cells) {
     // one transfer of the caller's double[9][ny][nx] into the second grid array (9 nx ny <= its size), then one launch that
     // scatters the planes into the first (d2q9-bgk.c:200-203)
     HIP_TRY(hipMemcpyAsync(d->cells[1], cells, 9 * n * sizeof(double), hipMemcpyHostToDevice, d->q.st));
-    hipLaunchKernelGGL(dp_pack_planes<true>, grid, dim3(256), 0, d->q.st, d->cells[0], d->plane_stride, d->p.nx, n, d->cells[1]);
+    hipLaunchKernelGGL(dp_pack_planes<true>, grid, dim3(256), 0, d->q.st, d->cells[0], (double *)nullptr, (const int *)nullptr,
+                       d->plane_stride, 0ull, d->p.nx, n, d->cells[1]);
   } else {
-    // d2q9-bgk.c:529-550 in double
-    const double w0 = d->p.density * 4.0 / 9.0, w1 = d->p.density / 9.0, w2 = d->p.density / 36.0;
-    hipLaunchKernelGGL(dp_init_cells, grid, dim3(256), 0, d->q.st, d->cells[0], d->plane_stride, d->p.nx, n, w0, w1, w2);
+    // d2q9-bgk.c:529-550 in double: the member table's w0, w1, w2
+    hipLaunchKernelGGL(dp_init_cells, grid, dim3(256), 0, d->q.st, d->cells[0], d->plane_stride, 0ull, (const DpMember *)d->members,
+                       d->p.nx, n);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(d->q.st));
@@ -400,8 +394,8 @@ int lbm_dp_download(lbm_dp *d, double *cells_out, double *av_vels_out) {
   if (cells_out) {
     // the grid array that is not current is scratch between runs: repack there, then one contiguous transfer
     double *stage = d->cells[d->cur ^ 1];
-    hipLaunchKernelGGL(dp_pack_planes<false>, dim3((unsigned)std::min(div_up((long)n, 256), 4096L)), dim3(256), 0, d->q.st,
-                       d->cells[d->cur], d->plane_stride, d->p.nx, n, stage);
+    hipLaunchKernelGGL(dp_pack_planes<false>, dim3((unsigned)std::min(div_up((long)n, 256), 4096L), 1), dim3(256), 0, d->q.st,
+                       d->cells[d->cur], (double *)nullptr, (const int *)nullptr, d->plane_stride, 0ull, d->p.nx, n, stage);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(cells_out, stage, 9 * n * sizeof(double), hipMemcpyDeviceToHost, d->q.st));
     HIP_TRY(hipStreamSynchronize(d->q.st));
@@ -510,25 +504,15 @@ int lbm_dforce(lbm_dp *d, double *fx, double *fy) {
   if (!fx && !fy) return lbm_fail(LBM_ERR_ARG, "fx and fy are both NULL");
   if (int rc = queue_sync(d->q)) return rc;
   if (!d->force_now) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->force_now), 2 * sizeof(double)));
-  // between runs the ring is empty (every run ends with its reduction): its first two blocks of ny * nseg take the
-  // segment sums of F_x and F_y, which then go the way a step's go
-  const size_t per_step = (size_t)d->p.ny * d->nseg;
   DpForceArgs a{};
   a.cells = d->cells[d->cur];
   a.mask = d->mask;
-  a.seg_x = d->seg;
-  a.seg_y = d->seg + per_step;
+  a.members = d->members;
   a.plane_stride = d->plane_stride;
   a.nx = d->p.nx;
   a.ny = d->p.ny;
-  a.lanes_per_row = d->lanes_per_row;
-  a.aw1 = d->p.density * d->p.accel / 9.0;   // kernels.cl:14-15, run_dp_impl's statements
-  a.aw2 = d->p.density * d->p.accel / 36.0;
   a.no_accel = d->open ? 1 : 0;
-  hipLaunchKernelGGL(dp_force_state, dim3((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock), 1), dim3(kBlock), 0, d->q.st, a);
-  HIP_TRY(hipGetLastError());
-  for (int c = 0; c < 2; c++)
-    if (int rc = reduce_steps(d, d->seg + (size_t)c * per_step, per_step, 1, d->force_now + c, 1ull)) return rc;
+  if (int rc = force_state(d->q.st, a, d->nseg, 1, d->seg, d->red, d->red_blocks, d->force_now)) return rc;
   double f[2] = {0.0, 0.0};
   HIP_TRY(hipMemcpyAsync(f, d->force_now, sizeof(f), hipMemcpyDeviceToHost, d->q.st));
   HIP_TRY(hipStreamSynchronize(d->q.st));

@@ -96,6 +96,10 @@ ENSEMBLES = {
 }
 DOUBLE = {"127x129": case(127, 129, 40), "1030x511": case(1030, 511, 41)}
 DOUBLE_ENSEMBLE = [case(37, 29, 50 + m, density=d, omega=o, reynolds_dim=r) for m, (d, o, r) in enumerate(MEMBER_CONSTANTS[:3])]
+# 272x256: 256 x ceil(272 / 16) = 4352 row segments a step, the smallest convenient grid above the 4096 up to which the fp64
+# families add a step's segments in one stage: two blocks, then one (section (b) only)
+DOUBLE_TWO_STAGE = case(272, 256, 42)
+DOUBLE_ENSEMBLE_TWO_STAGE = [case(272, 256, 53 + m, density=d, omega=o, reynolds_dim=r) for m, (d, o, r) in enumerate(MEMBER_CONSTANTS[:2])]
 # the ragged ensemble: the channel sweep of tests/test_steady_gpu.py from rest (stops 208 / 304 / 400 / 400 on the fp32 oracle)
 RAGGED = dict(nx=48, ny=32, omegas=(0.6, 1.0, 1.4, 1.7), window=16, rel_tol=2e-2, max_steps=400, density=0.1, accel=0.005,
               reynolds_dim=10)

@@ -332,25 +332,28 @@ def f64_av_gate(f32_forms, c, nsteps):
 
 @pytest.mark.parametrize("multistep", [0, 8])
 def test_av_vels_double(lbm, f32_forms, multistep):
-    c, nsteps = F.AV_CASES["127x129"]
-    ob, cells0 = F.inputs(c, np.float64)
-    with lbm.LBMDouble(params(lbm.make_dparams, c, nsteps, ob), ob) as sim:
-        sim.set_option("multistep", multistep)
-        sim.upload(cells0)
-        sim.run(nsteps)
-        cells, av = sim.download()
-    check_av("fp64 multistep %d" % multistep, av[nsteps - 1], cells, ob, c, f64_av_gate(f32_forms, c, nsteps), np.float64)
+    for c, nsteps in (F.AV_CASES["127x129"], (F.DOUBLE_TWO_STAGE, 8)):      # one reduction stage, and two (tests/_fields_ref.py)
+        name = "%dx%d" % (c["nx"], c["ny"])
+        ob, cells0 = F.inputs(c, np.float64)
+        with lbm.LBMDouble(params(lbm.make_dparams, c, nsteps, ob), ob) as sim:
+            sim.set_option("multistep", multistep)
+            sim.upload(cells0)
+            sim.run(nsteps)
+            cells, av = sim.download()
+        check_av("fp64 %s multistep %d" % (name, multistep), av[nsteps - 1], cells, ob, c, f64_av_gate(f32_forms, c, nsteps), np.float64)
 
 
 def test_av_vels_double_ensemble(lbm, f32_forms):
-    cases, nsteps = F.DOUBLE_ENSEMBLE, 8
-    ps, obs, cells0 = members(lbm.make_dparams, cases, nsteps, np.float64)
-    with lbm.EnsembleDouble(ps, obs) as ens:
-        ens.upload(cells0)
-        ens.run(nsteps)
-        cells, av = ens.download()
-    for m, c in enumerate(cases):
-        check_av("fp64 ensemble member %d" % m, av[m, nsteps - 1], cells[m], obs[m], c, f64_av_gate(f32_forms, c, nsteps), np.float64)
+    nsteps = 8
+    for cases in (F.DOUBLE_ENSEMBLE, F.DOUBLE_ENSEMBLE_TWO_STAGE):      # one reduction stage, and two
+        ps, obs, cells0 = members(lbm.make_dparams, cases, nsteps, np.float64)
+        with lbm.EnsembleDouble(ps, obs) as ens:
+            ens.upload(cells0)
+            ens.run(nsteps)
+            cells, av = ens.download()
+        for m, c in enumerate(cases):
+            check_av("fp64 ensemble %dx%d member %d" % (c["nx"], c["ny"], m), av[m, nsteps - 1], cells[m], obs[m], c,
+                     f64_av_gate(f32_forms, c, nsteps), np.float64)
 
 
 # ---- (c) read-back does not disturb the run ------------------------------------------------------------------------------------
