@@ -944,6 +944,72 @@ int lbm_dwall_get(const lbm_dp *d, int *on_out, double *u_x_out, double *u_y_out
 int lbm_dwall_ens_set(lbm_dens *e, const double *u_x /*[n][ny][nx]*/, const double *u_y, const double *rho_wall /*[n]*/);
 int lbm_dwall_ens_get(const lbm_dens *e, int *on_out, double *u_x_out, double *u_y_out, double *rho_wall_out /*[n]*/);
 
+/*
+ * ---- Subgrid viscosity: the Smagorinsky model for the double-precision families ---------------------------------------------
+ *
+ * Every run so far is laminar: the relaxation rate is one constant per grid, and as omega approaches 2, which is what a high
+ * Reynolds number on an affordable grid means, BGK and TRT with bounce-back go unstable (a 32 x 32 lid-driven cavity at omega =
+ * 1.99 and lid speed 0.1 is non-finite after a few hundred steps).  With the Smagorinsky subgrid model (Hou et al. 1996) a cell
+ * relaxes with its own rate: the eddy viscosity nu_t = (c Delta)^2 |S| comes from the non-equilibrium momentum flux the cell
+ * already holds, so the model is local and a pure change of the collision.  Off by default: one rate per grid keeps every bit.
+ * The reference has no counterpart.
+ *
+ * Definition.  The host computes two constants per context or member from omega and the Smagorinsky constant c, in double,
+ * separate statements without contraction; sqrt(2.0) is the correctly rounded double, and the factor follows from nu_t =
+ * (c Delta)^2 |S| with c_s^2 = 1/3:
+ *     tau0  = 1.0 / omega;
+ *     les_k = (18.0 * sqrt(2.0)) * (c * c);
+ * A fluid cell, after the gather and after the boundary fix where open boundaries are on, forms its rate from its gathered values
+ * g[0..8] and the moments the collision forms anyway: dens, densinv = 1.0 / dens and the momenta u_x, u_y (the BGK statements,
+ * unchanged).  All in double, contraction off, one IEEE operation per written operator, in this order; 1.0 / 3.0 is a double
+ * constant and sqrt is the correctly rounded square root:
+ *     d57 = g[5] + g[7];  d68 = g[6] + g[8];  dgs = d57 + d68;
+ *     p   = dens * (1.0 / 3.0);
+ *     pxx = ((g[1] + g[3]) + dgs) - (p + (u_x * u_x) * densinv);
+ *     pyy = ((g[2] + g[4]) + dgs) - (p + (u_y * u_y) * densinv);
+ *     pxy = (d57 - d68) - (u_x * u_y) * densinv;
+ *     q   = sqrt((pxx * pxx + pyy * pyy) + 2.0 * (pxy * pxy));
+ *     tau = 0.5 * (tau0 + sqrt(tau0 * tau0 + les_k * (q * densinv)));
+ *     om  = 1.0 / tau;
+ * The second moment of the equilibrium is analytic, so the stress needs no eq[k] - g[k].  BGK: the relaxation lines read om where
+ * they read omega.  TRT: rp = om * sp, out[0] uses om, and the second rate is recomputed per cell from the magic parameter by the
+ * three statements of "Two relaxation times" with tp = tau - 0.5 in place of 1.0 / omega - 0.5:
+ *     tp = tau - 0.5;
+ *     tm = magic / tp + 0.5;
+ *     omega_m = 1.0 / tm;
+ * A cell with q == 0 gets om = 1.0 / (1.0 / omega), which is not omega to the bit: with any c > 0 the model is promised BGK's
+ * bits nowhere; only c == 0.0, which is off, is.
+ *
+ * Nothing else moves: accelerate_flow, bounce-back and moving walls, the force and its body maps, the order of every sum, the
+ * four fields, the Reynolds number, whose viscosity stays the molecular one from omega, and both steady runs.  Every bit identity
+ * stated for the existing flow holds with the model on: between the kernel forms ("multistep"), launch splits and runs; between a
+ * double-precision context and a member of a double-precision ensemble with the same c; between a member stopped by
+ * lbm_dsteady_run or lbm_dbody_steady_run at count c and a plain run of c steps.  It composes with "force", body maps, TRT, open
+ * boundaries and moving walls; it and TRT may be set in either order.
+ *
+ * When it is accepted.  Only while steps_done is 0, the rule of lbm_dtrt_set: otherwise LBM_ERR_STATE.  lbm_dp_upload,
+ * lbm_dens_upload and lbm_dp_upload_obstacles keep the setting.  An ensemble has the model on for all members, each with its
+ * own c, or off.  Everything is checked before anything changes: after a refusal nothing has changed, on the host or on the
+ * device.
+ *
+ * Names: lbm_dles_*, on both double-precision handles.  Out of scope: fp32 contexts and fp32 ensembles, which get nothing; a
+ * downloadable field of the eddy viscosity; wall damping of c; any other subgrid model.
+ */
+
+/* Set the subgrid model of a double-precision context: c == 0.0 is off (the default), c > 0 and finite is on with that Smagorinsky
+ * constant.  LBM_ERR_ARG, before the context is read: a NULL context, c negative, NaN or infinite.  LBM_ERR_STATE: steps done. */
+int lbm_dles_set(lbm_dp *d, double c);
+
+/* The Smagorinsky constant in force (0.0: off) and les_k as the host statements give it.  Either output may be NULL; both NULL
+ * (c_out and les_k_out), or a NULL context: LBM_ERR_ARG. */
+int lbm_dles_get(const lbm_dp *d, double *c_out, double *les_k_out);
+
+/* The same for a double-precision ensemble: c = double[n], every entry > 0 and finite, members may differ; NULL: off for all
+ * members.  LBM_ERR_ARG, the message names the member: an entry that is 0, negative, NaN or infinite; nothing on the device
+ * changes after a refusal.  LBM_ERR_STATE: steps done.  Synchronises. */
+int lbm_dles_ens_set(lbm_dens *e, const double *c /*[n]*/);
+int lbm_dles_ens_get(const lbm_dens *e, double *c_out /*[n]*/, double *les_k_out /*[n]*/);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "lbm_dtrt_set", "lbm_dtrt_get", "lbm_dtrt_ens_set", "lbm_dtrt_ens_get",
     "lbm_dopen_set", "lbm_dopen_get", "lbm_dopen_ens_set", "lbm_dopen_ens_get",
     "lbm_dwall_set", "lbm_dwall_get", "lbm_dwall_ens_set", "lbm_dwall_ens_get",
+    "lbm_dles_set", "lbm_dles_get", "lbm_dles_ens_set", "lbm_dles_ens_get",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -176,6 +177,10 @@ def load_library():
     L.lbm_dwall_get.argtypes = [vp, ctypes.POINTER(ci), vp, vp, ctypes.POINTER(ctypes.c_double)]
     L.lbm_dwall_ens_set.argtypes = [vp, vp, vp, vp]
     L.lbm_dwall_ens_get.argtypes = [vp, ctypes.POINTER(ci), vp, vp, vp]
+    L.lbm_dles_set.argtypes = [vp, ctypes.c_double]
+    L.lbm_dles_get.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    L.lbm_dles_ens_set.argtypes = [vp, vp]
+    L.lbm_dles_ens_get.argtypes = [vp, vp, vp]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -640,6 +645,18 @@ class LBMDouble(_Handle):
         _check(self.lib.lbm_dwall_get(self.ctx, ctypes.byref(on), ux.ctypes.data, uy.ctypes.data, ctypes.byref(rho)), "lbm_dwall_get")
         return (ux, uy, rho.value) if on.value else None
 
+    def set_les(self, c):
+        """Subgrid viscosity (lbm_dles_set): c > 0 = the Smagorinsky model with that constant (0.1 .. 0.2 is usual), every fluid
+        cell relaxes with its own rate; 0.0 = off, the default.  Only before the first step."""
+        _check(self.lib.lbm_dles_set(self.ctx, float(c)), "lbm_dles_set")
+
+    def les(self):
+        """(c, les_k): the Smagorinsky constant in force (0.0: off) and (18 sqrt 2) c^2 as the library computes it
+        (lbm_dles_get)"""
+        c, k = ctypes.c_double(), ctypes.c_double()
+        _check(self.lib.lbm_dles_get(self.ctx, ctypes.byref(c), ctypes.byref(k)), "lbm_dles_get")
+        return c.value, k.value
+
     def force_record(self):
         """(F_x float64[steps_done], F_y float64[steps_done]): the force of every step since the upload; needs
         set_option("force", 1) before the first step."""
@@ -887,6 +904,26 @@ class EnsembleDouble(_EnsembleOf):
         _check(self.lib.lbm_dwall_ens_get(self.ens, ctypes.byref(on), ux.ctypes.data, uy.ctypes.data, r.ctypes.data),
                "lbm_dwall_ens_get")
         return (ux, uy, r) if on.value else None
+
+    def set_les(self, c):
+        """Subgrid viscosity of all members (lbm_dles_ens_set): one Smagorinsky constant for all, or an array-like of n, every
+        entry > 0; None or 0.0 = off, the default.  Only before the first step."""
+        if c is None or (np.ndim(c) == 0 and float(c) == 0.0):
+            _check(self.lib.lbm_dles_ens_set(self.ens, None), "lbm_dles_ens_set")
+            return
+        v = np.asarray(c, dtype=np.float64)
+        if v.ndim == 0:
+            v = np.full(self.n, float(v), dtype=np.float64)
+        v = np.ascontiguousarray(v)
+        assert v.shape == (self.n,)
+        _check(self.lib.lbm_dles_ens_set(self.ens, v.ctypes.data), "lbm_dles_ens_set")
+
+    def les(self):
+        """(c float64[n], les_k float64[n]): per member the Smagorinsky constant in force (0.0: off) and (18 sqrt 2) c^2 as the
+        library computes it (lbm_dles_ens_get)"""
+        c, k = np.zeros(self.n, dtype=np.float64), np.zeros(self.n, dtype=np.float64)
+        _check(self.lib.lbm_dles_ens_get(self.ens, c.ctypes.data, k.ctypes.data), "lbm_dles_ens_get")
+        return c, k
 
     def run_until(self, max_steps, window=64, rel_tol=1e-4, on="av_vels"):
         """_EnsembleOf.run_until with a choice of criterion: on="av_vels" (lbm_dsteady_run), or on="drag"

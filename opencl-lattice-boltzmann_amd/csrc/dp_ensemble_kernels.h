@@ -19,7 +19,8 @@ struct DensArgs {
   const double *src;         // member m: src + m * member_stride
   double *dst;
   const uint8_t *mask;       // member m: mask + m * nx * ny
-  const DpMember *members; // [members], and behind them the open-boundary table (OPEN: dens_open_table)
+  const DpMember *members; // [members], and behind them the open-boundary table (OPEN: dens_open_table), the wall densities
+                           // (WALL: dens_wall_table) and the subgrid constants (LES: dens_les_table)
   double *seg;               // [T][members][ny][nseg]: the segment sums of each of the T steps; FORCE:
                              // [T][3][members][ny][nseg], |u|, F_x, F_y
   unsigned long long plane_stride, member_stride;   // row_stride = 9 * plane_stride
@@ -47,12 +48,17 @@ __host__ __device__ inline const double *dens_open_table(const DpMember *members
 __host__ __device__ inline const double *dens_wall_table(const DpMember *members, int n, int ny) {
   return dens_open_table(members, n) + (size_t)n * (ny + 1);
 }
+// Subgrid viscosity: member m's DpLes (tau0, les_k, magic; dp_kernels.h) is entry m of a fourth table, behind the wall table
+__host__ __device__ inline const DpLes *dens_les_table(const DpMember *members, int n, int ny) {
+  return reinterpret_cast<const DpLes *>(dens_wall_table(members, n, ny) + n);
+}
 
 // Member blockIdx.y as dp_tile takes it (dp_tile.h): its arrays a member stride into the ensemble's, its constants from the
-// DpMember load, its profile, rho_out and rho_wall from the tables behind the members
+// DpMember load, its profile, rho_out, rho_wall and subgrid constants from the tables behind the members
 template <bool WALL>
 struct DensGrid {
   static constexpr bool kStageRhoOut = true;   // rho_out lies in a table in global memory: no load under the outlet's branch
+  static constexpr bool kStageLes = true;      // the subgrid constants too, and six SGPRs across the loops are six too many here
   const DensArgsOf<WALL> &a;
   int member;
   size_t cells, cell0;   // nx * ny, and this member's cell (0,0) among all members' cells: mask and wall velocities
@@ -79,6 +85,7 @@ struct DensGrid {
   __device__ __forceinline__ const double *wall_u_x() const { return a.wall_u; }
   __device__ __forceinline__ const double *wall_u_y() const { return a.wall_u + (size_t)gridDim.y * cells; }
   __device__ __forceinline__ double rho_wall() const { return dens_wall_table(a.members, (int)gridDim.y, a.ny)[member]; }
+  __device__ __forceinline__ DpLes les() const { return dens_les_table(a.members, (int)gridDim.y, a.ny)[member]; }
 };
 
 // grid = (tiles per member, members), NT threads: dp_tile (dp_tile.h) on member blockIdx.y, tile blockIdx.x.
@@ -104,9 +111,25 @@ struct DensGrid {
 // The FORCE instance states its two workgroups per CU (NT / 128 waves per SIMD) to the compiler: 60 VGPRs, 78 SGPRs, 0 scratch.
 // So do the TRT, OPEN and WALL instances (DESIGN.md section 3.7 holds their tables).  The gated kernel of a steady run
 // (dp_steady_kernels.h) calls dp_tile the same way and so advances a member with the very same instructions.
-template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL = false>
-__global__ __launch_bounds__(NT, (FORCE || TRT || OPEN || WALL) ? NT / 128 : 1) void d2q9_dp_ensemble(const DensArgsOf<WALL> a) {
-  dp_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN, WALL, DensGrid<WALL>>(a);
+//
+// LES: two fp64 square roots and one division more per cell, with TRT three divisions, in a kernel at 60-63 of 64 VGPRs and at its
+// 80 SGPRs.  What keeps 31 of the 32 LES instances of either ensemble kernel at two workgroups per CU with 0 scratch: the rate is
+// formed before the equilibrium and fenced, with TRT one division and one pair of speeds after the other (dp_collide_cell: without
+// these two the TRT + WALL + LES instance spills 8 B); the
+// three constants lie in LDS (kStageLes, 24 B) and are addressed from an opaque zero; the collision loop takes its cell from an
+// opaque copy of the loop index; store_segments' lane is opaque (dp_tile.h).  The one instance that still spilled 8 B per lane
+// under the hint, TRT + OPEN + WALL + LES without FORCE (with FORCE it fits), does not state it: left to itself the compiler
+// schedules it into 64 VGPRs with 0 scratch, so it, too, runs two workgroups per CU (74 680 B of LDS).  Cross-compiled figures
+// of all 32: DESIGN.md section 3.7, profiles/les_throughput.txt.
+template <int NT, bool FORCE, bool TRT, bool OPEN, bool WALL, bool LES>
+constexpr int dens_waves_per_simd() {
+  if (!FORCE && TRT && OPEN && WALL && LES) return 1;
+  return (FORCE || TRT || OPEN || WALL || LES) ? NT / 128 : 1;
+}
+
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false>
+__global__ __launch_bounds__(NT, (dens_waves_per_simd<NT, FORCE, TRT, OPEN, WALL, LES>())) void d2q9_dp_ensemble(const DensArgsOf<WALL> a) {
+  dp_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN, WALL, LES, DensGrid<WALL>>(a);
 }
 
 }  // namespace lbm

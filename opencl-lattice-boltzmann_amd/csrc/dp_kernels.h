@@ -22,6 +22,7 @@
 #pragma once
 #include "d2q9_kernels.h"
 
+#include <cmath>
 #include <type_traits>
 
 namespace lbm {
@@ -41,15 +42,32 @@ inline double dp_trt_omega_minus(double omega, double magic) {
   return omega_m;
 }
 
+// Subgrid viscosity (include/lbm.h, "Subgrid viscosity"): what an LES instance takes beyond omega and omega_m.  tau0 and les_k
+// are the header's two host statements on the context's or member's omega and Smagorinsky constant; magic is read by the
+// TRT instances alone, which recompute the second rate per cell.
+struct DpLes {
+  double tau0, les_k, magic;
+};
+inline DpLes dp_les_constants(double omega, double c, double magic) {
+#pragma clang fp contract(off)
+  const double tau0 = 1.0 / omega;
+  const double les_k = (18.0 * std::sqrt(2.0)) * (c * c);
+  return DpLes{tau0, les_k, magic};
+}
+
 // Collision of one cell in fp64.  TRT = false: BGK (kernels.cl:119-198), the statements of the fp64 oracle
 // (oracle/d2q9_oracle.c, timestep_row) with pairwise momenta, contraction off: every kernel that inlines this rounds
 // identically, and the cell equals the oracle's pairwise no-FMA build bit for bit; omega_m is not read.  TRT = true: the
 // two-relaxation-time operator of include/lbm.h ("Two relaxation times") - moments, equilibrium and the obstacle branch are
 // the same statements, only the relaxation lines differ: of each pair of opposite speeds the symmetric part of eq - g relaxes
 // with omega, the antisymmetric part with omega_m.  Returns |u| = sqrt(j^2)/rho of a fluid cell, 0 for an obstacle.
-template <bool TRT>
+// LES = true: the Smagorinsky rate of include/lbm.h ("Subgrid viscosity") in place of omega, and with TRT the second rate
+// recomputed from it; the header's statements, from g and the moments alone, BEFORE the equilibrium and fenced: nothing of uvec
+// or eq is alive under the two square roots and the divisions (placed behind the equilibrium, seven of the eight BGK ensemble
+// instances spilled 8-36 B per lane).  omega and omega_m are not read.  LES = false: the kernel without it, `les` is not read.
+template <bool TRT, bool LES = false>
 __device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obstacle, double omega, double omega_m,
-                                                  double (&out)[9]) {
+                                                  [[maybe_unused]] const DpLes &les, double (&out)[9]) {
 #pragma clang fp contract(off)
   if (obstacle) {
     // bounce-back: the un-relaxed value leaves through the opposite speed (kernels.cl:69, 187-197)
@@ -62,10 +80,28 @@ __device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obs
   double dens = g[0];
 #pragma unroll
   for (int k = 1; k < 9; k++) dens += g[k];
-  const double densinv = 1.0 / dens;
+  std::conditional_t<LES, double, const double> densinv = 1.0 / dens;
   const double diag_a = g[5] - g[7], diag_b = g[8] - g[6];
-  const double u_x = (g[1] - g[3]) + (diag_a + diag_b);
-  const double u_y = (g[2] - g[4]) + (diag_a - diag_b);
+  std::conditional_t<LES, double, const double> u_x = (g[1] - g[3]) + (diag_a + diag_b);
+  std::conditional_t<LES, double, const double> u_y = (g[2] - g[4]) + (diag_a - diag_b);
+  if constexpr (LES) {
+    const double d57 = g[5] + g[7], d68 = g[6] + g[8], dgs = d57 + d68;
+    const double p = dens * (1.0 / 3.0);
+    const double pxx = ((g[1] + g[3]) + dgs) - (p + (u_x * u_x) * densinv);
+    const double pyy = ((g[2] + g[4]) + dgs) - (p + (u_y * u_y) * densinv);
+    const double pxy = (d57 - d68) - (u_x * u_y) * densinv;
+    const double q = __builtin_sqrt((pxx * pxx + pyy * pyy) + 2.0 * (pxy * pxy));
+    const double tau = 0.5 * (les.tau0 + __builtin_sqrt(les.tau0 * les.tau0 + les.les_k * (q * densinv)));
+    omega = 1.0 / tau;
+    if constexpr (TRT) {
+      double tp = tau - 0.5;
+      asm volatile("" : "+v"(omega), "+v"(tp));   // one division after the other
+      const double tm = les.magic / tp + 0.5;
+      omega_m = 1.0 / tm;
+      asm volatile("" : "+v"(omega_m));
+    }
+    asm volatile("" : "+v"(omega), "+v"(dens), "+v"(u_x), "+v"(u_y), "+v"(densinv));
+  }
   const double u_sq = u_x * u_x + u_y * u_y;
   double uvec[9];
   uvec[0] = 0.0;
@@ -93,6 +129,8 @@ __device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obs
       const double rp = omega * sp, rm = omega_m * sm;
       out[k] = g[k] + (rp + rm);
       out[q] = g[q] + (rp - rm);
+      // with both rates in VGPRs, one pair after the other: four in flight together do not fit 64 VGPRs
+      if constexpr (LES) asm volatile("" : "+v"(out[k]), "+v"(out[q]), "+v"(dens));
     }
   } else {
 #pragma unroll
@@ -245,13 +283,15 @@ __device__ __forceinline__ void dp_output_cell(const double (&f)[9], double &ux,
   pr = local_density * (1.0 / 3.0);
 }
 
-// Host side: the instance four run-time options choose.  f(force, trt, open, wall) is called once, with the std::bool_constant
-// of each option, so a launch site names its kernel's template flags as decltype(force)::value, ... and widens its argument
-// struct where wall is true.  Every launch site goes through here: the sixteen instances of a kernel are these sixteen.
+// Host side: the instance five run-time options choose.  f(force, trt, open, wall, les) is called once, with the
+// std::bool_constant of each option, so a launch site names its kernel's template flags as decltype(force)::value, ... and widens
+// its argument struct where wall or les is true.  Every launch site goes through here: the 32 instances of a kernel are these 32.
 template <class F>
-inline void dp_with_flags(bool force, bool trt, bool open, bool wall, F &&f) {
+inline void dp_with_flags(bool force, bool trt, bool open, bool wall, bool les, F &&f) {
   auto pick = [](bool on, auto &&g) { on ? g(std::true_type{}) : g(std::false_type{}); };
-  pick(force, [&](auto fo) { pick(trt, [&](auto tr) { pick(open, [&](auto op) { pick(wall, [&](auto wa) { f(fo, tr, op, wa); }); }); }); });
+  pick(force, [&](auto fo) {
+    pick(trt, [&](auto tr) { pick(open, [&](auto op) { pick(wall, [&](auto wa) { pick(les, [&](auto le) { f(fo, tr, op, wa, le); }); }); }); });
+  });
 }
 
 struct DpStepArgs {
@@ -271,8 +311,17 @@ struct DpStepArgs {
 struct DpStepWallArgs : DpStepArgs {
   DpWall wall;
 };
-template <bool WALL>
-using DpStepArgsOf = std::conditional_t<WALL, DpStepWallArgs, DpStepArgs>;
+// LES: the three constants behind whatever the instance without it takes; the LES = false structs are those of a library
+// without the option
+struct DpStepLesArgs : DpStepArgs {
+  DpLes les;
+};
+struct DpStepWallLesArgs : DpStepWallArgs {
+  DpLes les;
+};
+template <bool WALL, bool LES = false>
+using DpStepArgsOf = std::conditional_t<LES, std::conditional_t<WALL, DpStepWallLesArgs, DpStepLesArgs>,
+                                        std::conditional_t<WALL, DpStepWallArgs, DpStepArgs>>;
 
 // One timestep, lane = cells x0, x0+1 of one row.  x-1 / x+1 neighbours: aligned 16-B loads plus one scalar load per
 // streamed plane at the wrap column (an L1 hit).  A lane past the row's end (x0 >= nx) only joins the segment sum with 0.
@@ -284,9 +333,10 @@ using DpStepArgsOf = std::conditional_t<WALL, DpStepWallArgs, DpStepArgs>;
 // -1.  The false instances are the kernels without it.
 // WALL: a lane with a blocked cell loads that cell's two wall velocities under the branch it takes for the obstacle, and a
 // cell that moves goes through dp_wall_cell after its bounce-back.  The false instances are the kernels without it.
+// LES: dp_collide_cell<TRT, true> on a.les, nothing else.  The false instances are the kernels without it.
 // static, like the helper kernels below: two translation units include this header (lbm_dp.cpp, lbm_dens.cpp).
-template <bool FORCE, bool TRT, bool OPEN, bool WALL = false>
-static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgsOf<WALL> a) {
+template <bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false>
+static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgsOf<WALL, LES> a) {
   const unsigned t = blockIdx.x * kBlock + threadIdx.x;
   const unsigned lpr = (unsigned)a.lanes_per_row;
   const int y = (int)(t / lpr);
@@ -344,8 +394,10 @@ static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgsOf
       }
     }
     double oa[9], ob[9];
-    const double ta = dp_collide_cell<TRT>(ga, ob_a, a.omega, a.omega_m, oa);
-    const double tb = dp_collide_cell<TRT>(gb, ob_b, a.omega, a.omega_m, ob);
+    DpLes les{};
+    if constexpr (LES) les = a.les;
+    const double ta = dp_collide_cell<TRT, LES>(ga, ob_a, a.omega, a.omega_m, les, oa);
+    const double tb = dp_collide_cell<TRT, LES>(gb, ob_b, a.omega, a.omega_m, les, ob);
     if constexpr (WALL) {
       const size_t at = (size_t)y * a.nx + x0;   // ob_b implies has_b: at + 1 is a cell of this row
       if (ob_a) {
@@ -408,24 +460,32 @@ struct DpMultiArgs {
 struct DpMultiWallArgs : DpMultiArgs {
   DpWall wall;
 };
-template <bool WALL>
-using DpMultiArgsOf = std::conditional_t<WALL, DpMultiWallArgs, DpMultiArgs>;
+struct DpMultiLesArgs : DpMultiArgs {
+  DpLes les;
+};
+struct DpMultiWallLesArgs : DpMultiWallArgs {
+  DpLes les;
+};
+template <bool WALL, bool LES = false>
+using DpMultiArgsOf = std::conditional_t<LES, std::conditional_t<WALL, DpMultiWallLesArgs, DpMultiLesArgs>,
+                                         std::conditional_t<WALL, DpMultiWallArgs, DpMultiArgs>>;
 
 }  // namespace lbm
 #include "dp_tile.h"   // dp_tile, on the per-cell functions above
 namespace lbm {
 
 // The one grid of a context as dp_tile takes it (dp_tile.h): the argument struct's own fields
-template <bool WALL>
+template <bool WALL, bool LES = false>
 struct DpMultiGrid {
   static constexpr bool kStageRhoOut = false;   // rho_out is a kernel argument, in SGPRs already; in LDS it cost two VGPRs
-  const DpMultiArgsOf<WALL> &a;
+  static constexpr bool kStageLes = false;      // so are the subgrid constants, and this kernel has SGPRs to spare
+  const DpMultiArgsOf<WALL, LES> &a;
   const double *src;
   double *dst;
   const uint8_t *mask;
   double *seg_out;
   double omega, omega_m, aw1, aw2;
-  __device__ __forceinline__ explicit DpMultiGrid(const DpMultiArgsOf<WALL> &a_)
+  __device__ __forceinline__ explicit DpMultiGrid(const DpMultiArgsOf<WALL, LES> &a_)
       : a(a_), src(a_.src), dst(a_.dst), mask(a_.mask), seg_out(a_.seg), omega(a_.omega), omega_m(a_.omega_m),
         aw1(a_.aw1), aw2(a_.aw2) {}
   __device__ __forceinline__ unsigned comp() const { return (unsigned)(a.ny * a.nseg); }
@@ -435,6 +495,7 @@ struct DpMultiGrid {
   __device__ __forceinline__ const double *wall_u_x() const { return a.wall.u_x; }
   __device__ __forceinline__ const double *wall_u_y() const { return a.wall.u_y; }
   __device__ __forceinline__ double rho_wall() const { return a.wall.rho_wall; }
+  __device__ __forceinline__ DpLes les() const { return a.les; }
 };
 
 // T <= TMAX timesteps per launch on one grid: dp_tile (dp_tile.h) with kMultiThreads threads, tile = blockIdx.x.
@@ -445,9 +506,9 @@ struct DpMultiGrid {
 //   16x16, T <= 4 (85 KB)                                2.13 / 2.99 / 8.43
 // and one step per launch (d2q9_dp_step) 3.78 / 4.45 / 9.53, at 1024^2 23.8 against this kernel's 28.2: auto up to 300K cells.
 // With every option on the tile holds about 152 of the 160 KB of LDS.
-template <int TX, int TY, int TMAX, bool FORCE, bool TRT, bool OPEN, bool WALL = false>
-__global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgsOf<WALL> a) {
-  dp_tile<TX, TY, TMAX, kMultiThreads, FORCE, TRT, OPEN, WALL, DpMultiGrid<WALL>>(a);
+template <int TX, int TY, int TMAX, bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false>
+__global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgsOf<WALL, LES> a) {
+  dp_tile<TX, TY, TMAX, kMultiThreads, FORCE, TRT, OPEN, WALL, LES, DpMultiGrid<WALL, LES>>(a);
 }
 
 // What differs from member to member, in device memory, read by member index (a wave-uniform load), as EnsMember.  An

@@ -12,6 +12,8 @@
 //   u_in(), rho_out()                 OPEN: its inlet profile [ny] and its outlet density
 //   wall_u_x(), wall_u_y()            WALL: the arrays that hold its wall velocities,
 //   wall_cell0(), rho_wall()                its cell (0,0) in them, and its wall density
+//   les()                             LES: its tau0, les_k and magic parameter (DpLes)
+//   kStageLes                         LES: they go to LDS with the region, or are held in SGPRs
 //   kStageRhoOut                      the one switch: rho_out goes to LDS with the profile, or is read where it is used
 // The option members are functions: an instance without the option never evaluates them, and one with it evaluates them where
 // it uses them, under the branch of a marked cell, so no register holds a table's address across the loops (the ensemble runs
@@ -59,8 +61,10 @@ namespace lbm {
 // VGPRs, issued the nine plane loads of the region load one after the other: 29.5 against 19.5 us/step on 64 x 128x128 with a
 // spinning disc, 25.8 now (tools/wall_ab.py).
 //
+// LES (the Smagorinsky subgrid viscosity): dp_collide_cell<TRT, true> on g.les() in the collision loop, nothing else.
+//
 // The false instance of each flag is the kernel without it, instruction for instruction.
-template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL, class Grid, class Args>
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL, bool LES, class Grid, class Args>
 __device__ __forceinline__ void dp_tile(const Args a) {
   constexpr bool MARKED = OPEN || WALL;   // lmask bytes carry marks above the low two bits
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
@@ -76,6 +80,20 @@ __device__ __forceinline__ void dp_tile(const Args a) {
   const int gx0 = tile_x * TX - T, gy0 = tile_y * TY - T;  // region cell (0,0)
   const size_t ps = a.plane_stride, rs = 9 * ps;
   const Grid g(a);   // here, not in the kernel: see the head of this file
+  // LES: the three constants, read once, before the kernel's first store to global memory (behind one, a load by member index
+  // is a vector load under the collision loop's branch, every cell: four VGPRs and twenty scalar instructions of address
+  // arithmetic).  kStageLes: into LDS with the region, where six more SGPRs held across the loops would be spilled to the lanes
+  // of a VGPR that the kernel does not have (the ensemble's instances are at their 80 SGPRs); else into SGPRs here.
+  [[maybe_unused]] DpLes les{};
+  [[maybe_unused]] double *lles = nullptr;
+  if constexpr (LES) {
+    if constexpr (Grid::kStageLes) {
+      __shared__ double les_consts[3];
+      lles = les_consts;
+    } else {
+      les = g.les();
+    }
+  }
   // OPEN: the profile on the region's rows and, behind them, rho_out (kStageRhoOut), staged in LDS with the region: a marked cell
   // reads them under its branch without a global load on a step's critical path, and no register holds an address across the loops
   [[maybe_unused]] double *lopen = nullptr;
@@ -100,7 +118,7 @@ __device__ __forceinline__ void dp_tile(const Args a) {
     constexpr int kSegs = TY * (TX / kDpSeg);
     int lane = tid;
     // as in the force pass below: nothing of this is kept across the collision loop (WALL: its branch needs the registers)
-    if constexpr (FORCE || WALL) asm volatile("" : "+v"(lane));
+    if constexpr (FORCE || WALL || LES) asm volatile("" : "+v"(lane));
     if (lane < kSegs) {
       const int oy = lane / (TX / kDpSeg), sx = lane - oy * (TX / kDpSeg);
       const int gy = tile_y * TY + oy;
@@ -149,6 +167,12 @@ __device__ __forceinline__ void dp_tile(const Args a) {
     if (tid < RY) lopen[tid] = u_in[grid_row(tid)];
     if constexpr (Grid::kStageRhoOut)
       if (tid == RY) lopen[kRY] = g.rho_out();
+  }
+  if constexpr (LES && Grid::kStageLes) {
+    if (tid == 0) {
+      const DpLes l = g.les();
+      lles[0] = l.tau0, lles[1] = l.les_k, lles[2] = l.magic;
+    }
   }
   if constexpr (WALL) {
     // The marks, in a pass of its own: every lane revisits the bytes it wrote itself (no barrier) and reads the two velocities
@@ -229,8 +253,12 @@ __device__ __forceinline__ void dp_tile(const Args a) {
     [[maybe_unused]] const bool accel_step = (s < T) || a.accel_next;
     const float inv = 1.0f / (float)w;
     for (int i = tid; i < w * h; i += NT) {
-      const int q = (int)(((float)i + 0.5f) * inv);
-      const int rx = s + (i - q * w), ry = s + q;
+      // LES: the cell from an opaque copy of i.  Otherwise the compiler carries four sums of the lane index, the step and a
+      // constant across the step loop, one for each use below, and the instance with all five options is one VGPR short.
+      int at = i;
+      if constexpr (LES) asm volatile("" : "+v"(at));
+      const int q = (int)(((float)at + 0.5f) * inv);
+      const int rx = s + (at - q * w), ry = s + q;
       const int c = ry * kRX + rx;
       double gth[9], o[9];
       gth[0] = lds[in][0][c];
@@ -248,7 +276,14 @@ __device__ __forceinline__ void dp_tile(const Args a) {
         if (mb & kOpenInlet) dp_open_inlet(gth, lopen[ry]);
         else if (mb & kOpenOutlet) dp_open_outlet(gth, Grid::kStageRhoOut ? lopen[kRY] : g.rho_out());
       }
-      const double t = dp_collide_cell<TRT>(gth, obst, g.omega, g.omega_m, o);
+      if constexpr (LES && Grid::kStageLes) {
+        // from an opaque zero: the address is formed here, per cell; as constants the compiler holds it across the loops, in
+        // two VGPRs (one for tau0 and les_k, one for magic)
+        int zero = 0;
+        asm volatile("" : "+v"(zero));
+        les = DpLes{lles[zero], lles[zero + 1], TRT ? lles[zero + 2] : 0.0};
+      }
+      const double t = dp_collide_cell<TRT, LES>(gth, obst, g.omega, g.omega_m, les, o);
       if constexpr (!OPEN)
         if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, g.aw1, g.aw2);
 #pragma unroll

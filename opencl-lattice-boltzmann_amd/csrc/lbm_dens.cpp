@@ -62,7 +62,7 @@ struct lbm_dens {
   uint8_t *mask = nullptr;         // [n][ny][nx]: 0 fluid, 1 blocked and counted in the force, 2 blocked outside the body
   BodyMap body;                    // the host's copy of what the mask was made of (body_map.h)
   DpMember *members = nullptr;     // [n], then the open-boundary table double[n][ny + 1] (dens_open_table), then rho_wall[n]
-                                   // (dens_wall_table)
+                                   // (dens_wall_table), then DpLes[n] (dens_les_table)
   double *seg = nullptr;           // [ring][n][ny][nseg]
   double *red = nullptr;           // [ring][n][red_blocks]: first reduction stage
   double *av_sum = nullptr;        // [n][max_iters]
@@ -79,6 +79,8 @@ struct lbm_dens {
   std::vector<double> wall_u;      // [2][n][ny][nx]: the host's copy of the wall velocities, u_x then u_y (empty while off)
   std::vector<double> rho_wall;    // [n]: the members' wall densities (empty while off); on the device behind the open table
   double *wall_dev = nullptr;      // [2][n][ny][nx] (allocated by the first lbm_dwall_ens_set that switches on)
+  bool les = false;                // lbm_dles_ens_set: the kernels' LES instances, for all members
+  std::vector<double> les_c;       // [n]: every member's Smagorinsky constant, 0 while the setting is off
   int nseg = 1, red_blocks = 1, fin_blocks = 1;
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
@@ -144,6 +146,17 @@ int upload_members(lbm_dens *e, const std::vector<double> &omega_m) {
   return LBM_OK;
 }
 
+// The table of per-member subgrid constants for these Smagorinsky constants and magic parameters, to the device: tau0 and
+// les_k by the header's host statements.  Written by lbm_dles_ens_set and again by lbm_dtrt_ens_set, so that the two may be
+// set in either order.
+int upload_les(lbm_dens *e, const std::vector<double> &c, const std::vector<double> &magic) {
+  std::vector<DpLes> t(e->n);
+  for (int i = 0; i < e->n; i++) t[i] = dp_les_constants(e->p[i].omega, c[i], magic[i]);
+  HIP_TRY(hipMemcpy(const_cast<DpLes *>(dens_les_table(e->members, e->n, e->ny)), t.data(), t.size() * sizeof(DpLes),
+                    hipMemcpyHostToDevice));
+  return LBM_OK;
+}
+
 int build_dens(lbm_dens *e, const int32_t *obstacles) {
   const int n = e->n, nx = e->nx, ny = e->ny;
   const size_t cells_per = (size_t)nx * ny;
@@ -162,7 +175,8 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
 
   // what the ensemble needs against what the device has free: refuse here rather than fail half-way through
   const size_t cells_bytes = ((size_t)n * e->member_stride + 32) * sizeof(double);
-  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + (size_t)n * (sizeof(DpMember) + (size_t)(ny + 2) * sizeof(double)) +
+  const size_t tables = (size_t)n * (sizeof(DpMember) + (size_t)(ny + 2) * sizeof(double) + sizeof(DpLes));
+  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + tables +
                       (size_t)e->ring * all_step * sizeof(double) + (size_t)e->ring * n * e->red_blocks * sizeof(double) +
                       (size_t)n * e->max_iters * sizeof(double) + (size_t)n * e->fin_blocks * sizeof(double);
   size_t free_b = 0, total_b = 0;
@@ -177,7 +191,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
     HIP_TRY(hipMemset(e->cells[i], 0, cells_bytes));
   }
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->mask), (size_t)n * cells_per + 64));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), (size_t)n * (sizeof(DpMember) + (size_t)(ny + 2) * sizeof(double))));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), tables));
   if (int rc = alloc_ring(e)) return rc;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->av_sum), (size_t)n * e->max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->fin_partials), (size_t)n * e->fin_blocks * sizeof(double)));
@@ -186,25 +200,29 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
   body_reset(e->body, obstacles, (size_t)n * cells_per);
   // in double these are lbm_dp.cpp's own statements (run_dp_impl, lbm_dp_upload): a member's constants are a context's
   e->magic.assign(n, 0.0);
+  e->les_c.assign(n, 0.0);
   e->omega_m.resize(n);
   for (int i = 0; i < n; i++) e->omega_m[i] = e->p[i].omega;
   return upload_members(e, e->omega_m);
 }
 
-// FORCE from the option "force", TRT from lbm_dtrt_ens_set, OPEN from lbm_dopen_ens_set, WALL from lbm_dwall_ens_set: with all
+// FORCE from the option "force", TRT from lbm_dtrt_ens_set, OPEN from lbm_dopen_ens_set, WALL from lbm_dwall_ens_set, LES from
+// lbm_dles_ens_set: with all
 // off these are the launches of a library without any of them.  active: NULL for an ordinary run, the members' words for a
 // leg of a steady run
 void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
   const dim3 grid(e->tiles, e->n), block(kDensThreads);
-  dp_with_flags(e->force, e->trt, e->open, e->wall, [&](auto force, auto trt, auto open, auto wall) {
-    constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value;
+  dp_with_flags(e->force, e->trt, e->open, e->wall, e->les, [&](auto force, auto trt, auto open, auto wall, auto les) {
+    constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value,
+                   LES = decltype(les)::value;
     DensArgsOf<WALL> w{};
     static_cast<DensArgs &>(w) = a;
     if constexpr (WALL) w.wall_u = e->wall_dev;
     if (!active)
-      hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL>), grid, block, 0, e->q.st, w);
+      hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL, LES>), grid, block, 0, e->q.st,
+                         w);
     else
-      hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL>), grid, block, 0,
+      hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL, LES>), grid, block, 0,
                          e->q.st, w, active);
   });
 }
@@ -684,6 +702,8 @@ int lbm_dtrt_ens_set(lbm_dens *e, const double *magic) {
   if (magic) e->magic.assign(magic, magic + e->n);
   else e->magic.assign(e->n, 0.0);
   e->omega_m = omega_m;
+  // the subgrid table carries the magic parameter: the TRT + LES instances recompute the second rate per cell
+  if (e->les) return upload_les(e, e->les_c, e->magic);
   return LBM_OK;
 }
 
@@ -792,6 +812,41 @@ int lbm_dwall_ens_get(const lbm_dens *e, int *on_out, double *u_x_out, double *u
   if (u_x_out) std::copy(e->wall_u.begin(), e->wall_u.begin() + all, u_x_out);
   if (u_y_out) std::copy(e->wall_u.begin() + all, e->wall_u.end(), u_y_out);
   if (rho_wall_out) std::copy(e->rho_wall.begin(), e->rho_wall.end(), rho_wall_out);
+  return LBM_OK;
+}
+
+int lbm_dles_ens_set(lbm_dens *e, const double *c) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  // every member is checked before anything changes, on the host or on the device
+  if (c)
+    for (int m = 0; m < e->n; m++)
+      if (!(c[m] > 0.0) || !std::isfinite(c[m]))
+        return lbm_fail(LBM_ERR_ARG, "member %d: the Smagorinsky constant c must be finite and positive (got %g); an ensemble has the "
+                        "subgrid viscosity on for all members or, with a NULL array, off", m, c[m]);
+  if (e->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "the subgrid viscosity is set before the first step (%d done): one record holds one operator",
+                    e->steps_done);
+  if (!c) {
+    e->les = false;
+    e->les_c.assign(e->n, 0.0);
+    return LBM_OK;
+  }
+  if (int rc = queue_sync(e->q)) return rc;
+  HIP_TRY(hipSetDevice(e->q.dev));
+  const std::vector<double> cs(c, c + e->n);
+  if (int rc = upload_les(e, cs, e->magic)) return rc;
+  e->les = true;
+  e->les_c = cs;
+  return LBM_OK;
+}
+
+int lbm_dles_ens_get(const lbm_dens *e, double *c_out, double *les_k_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!c_out && !les_k_out) return lbm_fail(LBM_ERR_ARG, "c_out and les_k_out are both NULL");
+  for (int m = 0; m < e->n; m++) {
+    if (c_out) c_out[m] = e->les_c[m];
+    if (les_k_out) les_k_out[m] = dp_les_constants(e->p[m].omega, e->les_c[m], 0.0).les_k;
+  }
   return LBM_OK;
 }
 

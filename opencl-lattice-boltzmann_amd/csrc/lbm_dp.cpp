@@ -70,6 +70,7 @@ struct lbm_dp {
   std::vector<double> wall_u;     // [2][ny][nx]: the host's copy of the wall velocities, u_x then u_y (empty while off)
   double rho_wall = 0.0;          // the wall density
   double *wall_dev = nullptr;     // [2][ny][nx] (allocated by the first lbm_dwall_set that switches on)
+  double les_c = 0.0;             // lbm_dles_set: 0 = off, > 0 = the LES instances with this Smagorinsky constant
   int cur = 0, steps_done = 0;
   bool failed = false;
 };
@@ -160,7 +161,8 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
   return upload_mask(d->mask, obstacles, cells);
 }
 
-// The instance the options choose: FORCE from "force", TRT from lbm_dtrt_set, OPEN from lbm_dopen_set, WALL from lbm_dwall_set.
+// The instance the options choose: FORCE from "force", TRT from lbm_dtrt_set, OPEN from lbm_dopen_set, WALL from lbm_dwall_set,
+// LES from lbm_dles_set.
 // With all off these are the launches of a library without any of them.
 // what a WALL instance takes beyond the arguments of the kernel without it
 DpWall wall_args(const lbm_dp *d) {
@@ -168,24 +170,32 @@ DpWall wall_args(const lbm_dp *d) {
   return DpWall{d->wall_dev, d->wall_dev + n, d->rho_wall};
 }
 
+// what an LES instance takes beyond them: the header's two host statements, and the magic parameter as set (either order)
+DpLes les_args(const lbm_dp *d) { return dp_les_constants(d->p.omega, d->les_c, d->magic); }
+
 void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
-  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, [&](auto force, auto trt, auto open, auto wall) {
-    constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value;
-    DpMultiArgsOf<WALL> w{};
+  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, [&](auto force, auto trt, auto open, auto wall, auto les) {
+    constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value,
+                   LES = decltype(les)::value;
+    DpMultiArgsOf<WALL, LES> w{};
     static_cast<DpMultiArgs &>(w) = a;
     if constexpr (WALL) w.wall = wall_args(d);
-    hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT, OPEN, WALL>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st, w);
+    if constexpr (LES) w.les = les_args(d);
+    hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT, OPEN, WALL, LES>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st,
+                       w);
   });
 }
 
 void launch_step(const lbm_dp *d, const DpStepArgs &a) {
   const dim3 grid((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock));
-  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, [&](auto force, auto trt, auto open, auto wall) {
-    constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value;
-    DpStepArgsOf<WALL> w{};
+  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, [&](auto force, auto trt, auto open, auto wall, auto les) {
+    constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value,
+                   LES = decltype(les)::value;
+    DpStepArgsOf<WALL, LES> w{};
     static_cast<DpStepArgs &>(w) = a;
     if constexpr (WALL) w.wall = wall_args(d);
-    hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT, OPEN, WALL>), grid, dim3(kBlock), 0, d->q.st, w);
+    if constexpr (LES) w.les = les_args(d);
+    hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT, OPEN, WALL, LES>), grid, dim3(kBlock), 0, d->q.st, w);
   });
 }
 
@@ -638,6 +648,26 @@ int lbm_dwall_get(const lbm_dp *d, int *on_out, double *u_x_out, double *u_y_out
   if (u_x_out) std::copy(d->wall_u.begin(), d->wall_u.begin() + n, u_x_out);
   if (u_y_out) std::copy(d->wall_u.begin() + n, d->wall_u.end(), u_y_out);
   if (rho_wall_out) *rho_wall_out = d->rho_wall;
+  return LBM_OK;
+}
+
+int lbm_dles_set(lbm_dp *d, double c) {
+  // argument errors before anything of the context is read
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!(c >= 0.0) || !std::isfinite(c))
+    return lbm_fail(LBM_ERR_ARG, "the Smagorinsky constant c must be 0 (off) or finite and positive (got %g)", c);
+  if (d->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "the subgrid viscosity is set before the first step (%d done): one record holds one operator",
+                    d->steps_done);
+  d->les_c = c;
+  return LBM_OK;
+}
+
+int lbm_dles_get(const lbm_dp *d, double *c_out, double *les_k_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!c_out && !les_k_out) return lbm_fail(LBM_ERR_ARG, "c_out and les_k_out are both NULL");
+  if (c_out) *c_out = d->les_c;
+  if (les_k_out) *les_k_out = les_args(d).les_k;
   return LBM_OK;
 }
 
