@@ -1010,6 +1010,91 @@ int lbm_dles_get(const lbm_dp *d, double *c_out, double *les_k_out);
 int lbm_dles_ens_set(lbm_dens *e, const double *c /*[n]*/);
 int lbm_dles_ens_get(const lbm_dens *e, double *c_out /*[n]*/, double *les_k_out /*[n]*/);
 
+/*
+ * ---- Body force: a uniform driving force by Guo forcing, for the double-precision families ------------------------------------
+ *
+ * Two things set a double-precision flow moving so far: accelerate_flow, which nudges three populations on the one row ny - 2
+ * where a guard allows it, a first-order trick without a continuum meaning, and a velocity inlet.  A channel driven by a
+ * pressure gradient, gravity in a closed box, a permeability sweep with one force per member cannot be run.  With a body force a
+ * context, or each member of an ensemble, carries a constant force density F = (F_x, F_y) per cell volume; it is NOT multiplied
+ * by the cell's density (the convention of the reference's density * accel constants, kernels.cl:14-15).  Every fluid cell takes
+ * it up by Guo's scheme (Guo, Zheng, Shi 2002): the momenta the collision reads are shifted by half the force, and the
+ * relaxation lines gain a source whose even and odd parts relax with the two rates of the collision.  Off by default: (0, 0)
+ * keeps every bit.  The reference has no counterpart.
+ *
+ * Definition.  With the force on, every FLUID cell does the following after the gather and after the boundary fix where open
+ * boundaries are on.  All in double, contraction off, one IEEE operation per written operator, in this order; w[0] = 4.0 / 9.0,
+ * w[1..4] = 1.0 / 9.0, w[5..8] = 1.0 / 36.0, s[1..4] = 1.0 / 3.0 and s[5..8] = 1.0 / 12.0 (three times w) are double constants.
+ * dens and densinv are the BGK statements, unchanged.  The momenta gain half the force:
+ *     u_x = ((g[1] - g[3]) + (diag_a + diag_b)) + 0.5 * F_x;
+ *     u_y = ((g[2] - g[4]) + (diag_a - diag_b)) + 0.5 * F_y;
+ * with diag_a = g[5] - g[7] and diag_b = g[8] - g[6] as in the BGK statements.  Everything downstream reads these shifted
+ * momenta: the statements of "Subgrid viscosity" where the model is on, u_sq, uvec[k], the equilibrium eq[k], and the
+ * |u| = sqrt(u_sq) * densinv the cell adds to av_vels.  The source, with cF[k] = c_k . F formed in the pattern of uvec[k]
+ * (cF[1] = F_x, cF[2] = F_y, cF[3] = -F_x, cF[4] = -F_y, cF[5] = F_x + F_y, cF[6] = -F_x + F_y, cF[7] = -F_x - F_y,
+ * cF[8] = F_x - F_y):
+ *     v_x = u_x * densinv;            v_y = u_y * densinv;
+ *     uF = v_x * F_x + v_y * F_y;     t3 = 3.0 * uF;
+ *     se[0] = w[0] * (0.0 - t3);
+ *     for k = 1..8:
+ *         cv = uvec[k] * densinv;
+ *         se[k] = w[k] * (9.0 * (cv * cF[k]) - t3);
+ *         so[k] = s[k] * cF[k];
+ * se is the even part (the same bits on the two speeds of a pair), so the odd part (so[q] = -so[k] on the opposite speed q).
+ * The relaxation lines, with pe = 1.0 - 0.5 * omega:
+ *     BGK:  out[0] = (g[0] + omega * (eq[0] - g[0])) + pe * se[0];
+ *           out[k] = (g[k] + omega * (eq[k] - g[k])) + pe * (se[k] + so[k]);          k = 1..8
+ *     TRT:  out[0] as under BGK, and with po = 1.0 - 0.5 * omega_m, for (k, q) in (1,3), (2,4), (5,7), (6,8):
+ *           fe = pe * se[k];          fo = po * so[k];
+ *           out[k] = (g[k] + (rp + rm)) + (fe + fo);
+ *           out[q] = (g[q] + (rp - rm)) + (fe - fo);
+ * The parenthesised first terms are the lines of the operator without the force.  The split of the source over the two rates is
+ * what makes a force-driven Poiseuille profile exact at Lambda = 3/16.  With the subgrid model on, the cell's own om and, with
+ * TRT, its own omega_m stand in pe and po where omega and omega_m stand.  The model reads the stress as it does without the
+ * force, from the shifted momenta: the -1/2 (uF + Fu) correction of the stress estimate is out of scope.
+ *
+ * Reported velocity.  The physical velocity of a forced cell is (sum of c_k g[k] + F / 2) / rho on the values g the cell
+ * gathers, which is what the shifted momenta are and what av_vels sums.  The library stores the values BEHIND a collision, and
+ * the collision above adds the whole force to a cell's momentum: sum of c_k out[k] = sum of c_k g[k] + F.  So on a stored state
+ * the physical velocity is (sum of c_k f_k - F / 2) / rho, and with the force on the output stage (lbm_dp_final_state,
+ * lbm_dens_final_state and the Reynolds numbers) subtracts 0.5 * F_x and 0.5 * F_y from the two momentum sums of a fluid cell
+ * before the division by its density; with it off the statements are untouched.  A state that was uploaded and not yet stepped
+ * is read the same way.
+ *
+ * Nothing else moves: blocked cells bounce back, or go through the statements of "Moving walls", and take no force;
+ * accelerate_flow stays and composes (accel = 0 switches it off); the boundary fix, the momentum-exchange force and the body
+ * maps, the order of every sum, the Reynolds number's viscosity and both steady criteria are unchanged.  Every bit identity stated
+ * for the existing flow holds with the force on: between the kernel forms ("multistep"), launch splits and runs; between a
+ * double-precision context and a member of a double-precision ensemble with the same force; between a member stopped by
+ * lbm_dsteady_run or lbm_dbody_steady_run at count c and a plain run of c steps.  It composes with "force", body maps, TRT, open
+ * boundaries, moving walls and the subgrid model, set in any order.
+ *
+ * When it is accepted.  Only while steps_done is 0, the rule of lbm_dles_set: otherwise LBM_ERR_STATE.  lbm_dp_upload,
+ * lbm_dens_upload and lbm_dp_upload_obstacles keep the setting.  An ensemble has the force on for all members, each with its own
+ * pair, or off.  Everything is checked before anything changes: after a refusal nothing has changed, on the host or on the
+ * device.
+ *
+ * Names: lbm_ddrive_*, on both double-precision handles ("body" is the body map, "force" the measured force).  Out of scope: fp32
+ * contexts and fp32 ensembles, which get nothing; a force that varies in space or time; a force proportional to the local density.
+ */
+
+/* Set the body force of a double-precision context: (0, 0) is off (the default).  LBM_ERR_ARG, before the context is read: a NULL
+ * context, a component that is NaN or infinite.  LBM_ERR_STATE: steps done.  Synchronises. */
+int lbm_ddrive_set(lbm_dp *d, double f_x, double f_y);
+
+/* The force in force ((0, 0): off).  Either output may be NULL; both NULL (f_x_out and f_y_out), or a NULL context: LBM_ERR_ARG. */
+int lbm_ddrive_get(const lbm_dp *d, double *f_x_out, double *f_y_out);
+
+/* The same for a double-precision ensemble: f = double[n][2], F_x then F_y of every member, members may differ; NULL: off for all
+ * members.  LBM_ERR_ARG, the message names the member: a component that is NaN or infinite, a member whose two components are both
+ * zero (its context twin would run the kernels without the force); nothing on the device changes after a refusal.  LBM_ERR_STATE:
+ * steps done.  Synchronises. */
+int lbm_ddrive_ens_set(lbm_dens *e, const double *f /*[n][2]*/);
+
+/* on_out: 1 while the force is on, else 0; f_out = double[n][2], zeros while it is off.  Either output may be NULL; both NULL
+ * (on_out and f_out), or a NULL ensemble: LBM_ERR_ARG. */
+int lbm_ddrive_ens_get(const lbm_dens *e, int *on_out, double *f_out /*[n][2]*/);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

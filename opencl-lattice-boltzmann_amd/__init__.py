@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "lbm_dopen_set", "lbm_dopen_get", "lbm_dopen_ens_set", "lbm_dopen_ens_get",
     "lbm_dwall_set", "lbm_dwall_get", "lbm_dwall_ens_set", "lbm_dwall_ens_get",
     "lbm_dles_set", "lbm_dles_get", "lbm_dles_ens_set", "lbm_dles_ens_get",
+    "lbm_ddrive_set", "lbm_ddrive_get", "lbm_ddrive_ens_set", "lbm_ddrive_ens_get",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -181,6 +182,10 @@ def load_library():
     L.lbm_dles_get.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     L.lbm_dles_ens_set.argtypes = [vp, vp]
     L.lbm_dles_ens_get.argtypes = [vp, vp, vp]
+    L.lbm_ddrive_set.argtypes = [vp, ctypes.c_double, ctypes.c_double]
+    L.lbm_ddrive_get.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    L.lbm_ddrive_ens_set.argtypes = [vp, vp]
+    L.lbm_ddrive_ens_get.argtypes = [vp, ctypes.POINTER(ci), vp]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -657,6 +662,18 @@ class LBMDouble(_Handle):
         _check(self.lib.lbm_dles_get(self.ctx, ctypes.byref(c), ctypes.byref(k)), "lbm_dles_get")
         return c.value, k.value
 
+    def set_drive(self, f):
+        """Body force (lbm_ddrive_set): f = (F_x, F_y), a constant force density per cell volume that every fluid cell takes up
+        by Guo forcing; (0, 0) = off, the default.  Only before the first step."""
+        f_x, f_y = f
+        _check(self.lib.lbm_ddrive_set(self.ctx, float(f_x), float(f_y)), "lbm_ddrive_set")
+
+    def drive(self):
+        """(F_x, F_y): the body force in force, (0.0, 0.0) while it is off (lbm_ddrive_get)"""
+        f_x, f_y = ctypes.c_double(), ctypes.c_double()
+        _check(self.lib.lbm_ddrive_get(self.ctx, ctypes.byref(f_x), ctypes.byref(f_y)), "lbm_ddrive_get")
+        return f_x.value, f_y.value
+
     def force_record(self):
         """(F_x float64[steps_done], F_y float64[steps_done]): the force of every step since the upload; needs
         set_option("force", 1) before the first step."""
@@ -924,6 +941,26 @@ class EnsembleDouble(_EnsembleOf):
         c, k = np.zeros(self.n, dtype=np.float64), np.zeros(self.n, dtype=np.float64)
         _check(self.lib.lbm_dles_ens_get(self.ens, c.ctypes.data, k.ctypes.data), "lbm_dles_ens_get")
         return c, k
+
+    def set_drive(self, f):
+        """Body force of all members (lbm_ddrive_ens_set): one pair (F_x, F_y) for all, or an array-like [n, 2], no member (0, 0);
+        None = off, the default.  Only before the first step."""
+        if f is None:
+            _check(self.lib.lbm_ddrive_ens_set(self.ens, None), "lbm_ddrive_ens_set")
+            return
+        v = np.asarray(f, dtype=np.float64)
+        if v.ndim == 1:
+            v = np.broadcast_to(v, (self.n, 2))
+        v = np.ascontiguousarray(v)
+        assert v.shape == (self.n, 2)
+        _check(self.lib.lbm_ddrive_ens_set(self.ens, v.ctypes.data), "lbm_ddrive_ens_set")
+
+    def drive(self):
+        """float64[n, 2]: per member the body force in force, zeros while it is off (lbm_ddrive_ens_get)"""
+        on = ctypes.c_int()
+        f = np.zeros((self.n, 2), dtype=np.float64)
+        _check(self.lib.lbm_ddrive_ens_get(self.ens, ctypes.byref(on), f.ctypes.data), "lbm_ddrive_ens_get")
+        return f
 
     def run_until(self, max_steps, window=64, rel_tol=1e-4, on="av_vels"):
         """_EnsembleOf.run_until with a choice of criterion: on="av_vels" (lbm_dsteady_run), or on="drag"

@@ -20,7 +20,8 @@ struct DensArgs {
   double *dst;
   const uint8_t *mask;       // member m: mask + m * nx * ny
   const DpMember *members; // [members], and behind them the open-boundary table (OPEN: dens_open_table), the wall densities
-                           // (WALL: dens_wall_table) and the subgrid constants (LES: dens_les_table)
+                           // (WALL: dens_wall_table), the subgrid constants (LES: dens_les_table) and the body forces (DRIVE:
+                           // dens_drive_table)
   double *seg;               // [T][members][ny][nseg]: the segment sums of each of the T steps; FORCE:
                              // [T][3][members][ny][nseg], |u|, F_x, F_y
   unsigned long long plane_stride, member_stride;   // row_stride = 9 * plane_stride
@@ -53,12 +54,18 @@ __host__ __device__ inline const DpLes *dens_les_table(const DpMember *members, 
   return reinterpret_cast<const DpLes *>(dens_wall_table(members, n, ny) + n);
 }
 
+// Body force: member m's F_x, F_y are entry m of a fifth table, double[n][2], behind the subgrid table
+__host__ __device__ inline const double *dens_drive_table(const DpMember *members, int n, int ny) {
+  return reinterpret_cast<const double *>(dens_les_table(members, n, ny) + n);
+}
+
 // Member blockIdx.y as dp_tile takes it (dp_tile.h): its arrays a member stride into the ensemble's, its constants from the
 // DpMember load, its profile, rho_out, rho_wall and subgrid constants from the tables behind the members
 template <bool WALL>
 struct DensGrid {
   static constexpr bool kStageRhoOut = true;   // rho_out lies in a table in global memory: no load under the outlet's branch
   static constexpr bool kStageLes = true;      // the subgrid constants too, and six SGPRs across the loops are six too many here
+  static constexpr bool kStageDrive = true;    // and the body force, for the same reason
   const DensArgsOf<WALL> &a;
   int member;
   size_t cells, cell0;   // nx * ny, and this member's cell (0,0) among all members' cells: mask and wall velocities
@@ -86,6 +93,10 @@ struct DensGrid {
   __device__ __forceinline__ const double *wall_u_y() const { return a.wall_u + (size_t)gridDim.y * cells; }
   __device__ __forceinline__ double rho_wall() const { return dens_wall_table(a.members, (int)gridDim.y, a.ny)[member]; }
   __device__ __forceinline__ DpLes les() const { return dens_les_table(a.members, (int)gridDim.y, a.ny)[member]; }
+  __device__ __forceinline__ DpDrive drive() const {
+    const double *f = dens_drive_table(a.members, (int)gridDim.y, a.ny) + 2 * (size_t)member;
+    return DpDrive{f[0], f[1]};
+  }
 };
 
 // grid = (tiles per member, members), NT threads: dp_tile (dp_tile.h) on member blockIdx.y, tile blockIdx.x.
@@ -121,15 +132,20 @@ struct DensGrid {
 // under the hint, TRT + OPEN + WALL + LES without FORCE (with FORCE it fits), does not state it: left to itself the compiler
 // schedules it into 64 VGPRs with 0 scratch, so it, too, runs two workgroups per CU (74 680 B of LDS).  Cross-compiled figures
 // of all 32: DESIGN.md section 3.7, profiles/les_throughput.txt.
-template <int NT, bool FORCE, bool TRT, bool OPEN, bool WALL, bool LES>
+//
+// DRIVE: the source of the body force is added behind the relaxation lines and fenced, the two components lie in 16 B of LDS
+// (kStageDrive) and are read at each of their two uses (dp_collide_cell, dp_tile.h).  26 of the 32 DRIVE instances of either
+// ensemble kernel have 64 VGPRs, 0 scratch; the six with LES and without OPEN that also have FORCE or WALL spill 8 B per lane under
+// the hint and keep it: without it they take 66-68 VGPRs, which is one workgroup per CU.
+template <int NT, bool FORCE, bool TRT, bool OPEN, bool WALL, bool LES, bool DRIVE = false>
 constexpr int dens_waves_per_simd() {
-  if (!FORCE && TRT && OPEN && WALL && LES) return 1;
-  return (FORCE || TRT || OPEN || WALL || LES) ? NT / 128 : 1;
+  if (!DRIVE && !FORCE && TRT && OPEN && WALL && LES) return 1;
+  return (FORCE || TRT || OPEN || WALL || LES || DRIVE) ? NT / 128 : 1;
 }
 
-template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false>
-__global__ __launch_bounds__(NT, (dens_waves_per_simd<NT, FORCE, TRT, OPEN, WALL, LES>())) void d2q9_dp_ensemble(const DensArgsOf<WALL> a) {
-  dp_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN, WALL, LES, DensGrid<WALL>>(a);
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false, bool DRIVE = false>
+__global__ __launch_bounds__(NT, (dens_waves_per_simd<NT, FORCE, TRT, OPEN, WALL, LES, DRIVE>())) void d2q9_dp_ensemble(const DensArgsOf<WALL> a) {
+  dp_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN, WALL, LES, DRIVE, DensGrid<WALL>>(a);
 }
 
 }  // namespace lbm

@@ -55,6 +55,19 @@ inline DpLes dp_les_constants(double omega, double c, double magic) {
   return DpLes{tau0, les_k, magic};
 }
 
+// Body force (include/lbm.h, "Body force"): what a DRIVE instance takes beyond that, the constant force density of the context
+// or member.  Everything else the statements need (the two halves, c_k . F, the odd source) a cell forms from these two.
+struct DpDrive {
+  double f_x, f_y;
+};
+inline bool dp_drive_on(double f_x, double f_y) { return !(f_x == 0.0 && f_y == 0.0); }
+// dp_collide_cell asks for the two components where it uses them, twice per cell, through a callable: one that reads them from
+// LDS holds no register in between.  This one returns a pair held in SGPRs; the DRIVE = false instances pass it empty.
+struct DpDriveHeld {
+  DpDrive f{};
+  __device__ __forceinline__ DpDrive operator()() const { return f; }
+};
+
 // Collision of one cell in fp64.  TRT = false: BGK (kernels.cl:119-198), the statements of the fp64 oracle
 // (oracle/d2q9_oracle.c, timestep_row) with pairwise momenta, contraction off: every kernel that inlines this rounds
 // identically, and the cell equals the oracle's pairwise no-FMA build bit for bit; omega_m is not read.  TRT = true: the
@@ -65,9 +78,16 @@ inline DpLes dp_les_constants(double omega, double c, double magic) {
 // recomputed from it; the header's statements, from g and the moments alone, BEFORE the equilibrium and fenced: nothing of uvec
 // or eq is alive under the two square roots and the divisions (placed behind the equilibrium, seven of the eight BGK ensemble
 // instances spilled 8-36 B per lane).  omega and omega_m are not read.  LES = false: the kernel without it, `les` is not read.
-template <bool TRT, bool LES = false>
+// DRIVE = true: Guo forcing of include/lbm.h ("Body force") - the two momenta gain half the force before anything reads them, and
+// the relaxation lines gain the source, its even part under 1 - omega / 2, its odd part, with TRT, under 1 - omega_m / 2.  The
+// source is added in a pass of its own BEHIND the relaxation lines and fenced from them: there nothing of the equilibrium is
+// alive, only out[], the two momenta, densinv and the rates, so the peak of the equilibrium loop is the DRIVE = false one plus
+// nothing (formed inside that loop, as the header's order of statements suggests, all 32 ensemble instances spilled 40-68 B per
+// lane).  drv() is called twice, before the shift and before the source.  DRIVE = false: the kernel without it, `drv` is not read.
+template <bool TRT, bool LES = false, bool DRIVE = false, class Drv = DpDriveHeld>
 __device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obstacle, double omega, double omega_m,
-                                                  [[maybe_unused]] const DpLes &les, double (&out)[9]) {
+                                                  [[maybe_unused]] const DpLes &les, [[maybe_unused]] const Drv &drv,
+                                                  double (&out)[9]) {
 #pragma clang fp contract(off)
   if (obstacle) {
     // bounce-back: the un-relaxed value leaves through the opposite speed (kernels.cl:69, 187-197)
@@ -80,10 +100,15 @@ __device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obs
   double dens = g[0];
 #pragma unroll
   for (int k = 1; k < 9; k++) dens += g[k];
-  std::conditional_t<LES, double, const double> densinv = 1.0 / dens;
+  std::conditional_t<LES || DRIVE, double, const double> densinv = 1.0 / dens;
   const double diag_a = g[5] - g[7], diag_b = g[8] - g[6];
-  std::conditional_t<LES, double, const double> u_x = (g[1] - g[3]) + (diag_a + diag_b);
-  std::conditional_t<LES, double, const double> u_y = (g[2] - g[4]) + (diag_a - diag_b);
+  std::conditional_t<LES || DRIVE, double, const double> u_x = (g[1] - g[3]) + (diag_a + diag_b);
+  std::conditional_t<LES || DRIVE, double, const double> u_y = (g[2] - g[4]) + (diag_a - diag_b);
+  if constexpr (DRIVE) {
+    const DpDrive f = drv();
+    u_x = u_x + 0.5 * f.f_x;
+    u_y = u_y + 0.5 * f.f_y;
+  }
   if constexpr (LES) {
     const double d57 = g[5] + g[7], d68 = g[6] + g[8], dgs = d57 + d68;
     const double p = dens * (1.0 / 3.0);
@@ -118,8 +143,8 @@ __device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obs
     const double tsq = t * uvec[k];
     eq[k] = ((k < 5) ? w1 : w2) * (dens + t + half_densinv_icsq * (tsq - u_sq));
   }
+  constexpr int pairs[4][2] = {{1, 3}, {2, 4}, {5, 7}, {6, 8}};
   if constexpr (TRT) {
-    constexpr int pairs[4][2] = {{1, 3}, {2, 4}, {5, 7}, {6, 8}};
     out[0] = g[0] + omega * (eq[0] - g[0]);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -135,6 +160,42 @@ __device__ __forceinline__ double dp_collide_cell(const double (&g)[9], bool obs
   } else {
 #pragma unroll
     for (int k = 0; k < 9; k++) out[k] = g[k] + omega * (eq[k] - g[k]);
+  }
+  if constexpr (DRIVE) {
+    // the source, behind the relaxation lines: se[k] is the same value on the two speeds of a pair and so[q] = -so[k], so a pair
+    // forms them once; under BGK pe * (se[q] + so[q]) is pe * (se[k] - so[k]), the same bits
+    asm volatile("" : "+v"(out[0]), "+v"(out[1]), "+v"(out[2]), "+v"(out[3]), "+v"(out[4]), "+v"(out[5]), "+v"(out[6]), "+v"(out[7]),
+                 "+v"(out[8]));
+    // |u| here: u_sq is not held across the source
+    double speed = __builtin_sqrt(u_sq) * densinv;
+    asm volatile("" : "+v"(u_x), "+v"(u_y), "+v"(densinv), "+v"(speed));
+    const DpDrive f = drv();
+    const double v_x = u_x * densinv, v_y = u_y * densinv;
+    const double uF = v_x * f.f_x + v_y * f.f_y;
+    const double t3 = 3.0 * uF;
+    const double pe = 1.0 - 0.5 * omega;
+    [[maybe_unused]] double po = 0.0;
+    if constexpr (TRT) po = 1.0 - 0.5 * omega_m;
+    out[0] = out[0] + pe * (w0 * (0.0 - t3));
+    const double cF[9] = {0.0, f.f_x, f.f_y, -f.f_x, -f.f_y, f.f_x + f.f_y, -f.f_x + f.f_y, -f.f_x - f.f_y, f.f_x - f.f_y};
+    // uvec[k] again, from the fenced momenta: the same bits, and nothing of uvec is held across the relaxation lines
+    const double uv[9] = {0.0, u_x, u_y, -u_x, -u_y, u_x + u_y, -u_x + u_y, -u_x - u_y, u_x - u_y};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int k = pairs[i][0], q = pairs[i][1];
+      const double cv = uv[k] * densinv;
+      const double se = ((k < 5) ? w1 : w2) * (9.0 * (cv * cF[k]) - t3);
+      const double so = ((k < 5) ? 1.0 / 3.0 : 1.0 / 12.0) * cF[k];   // 3 w_k
+      if constexpr (TRT) {
+        const double fe = pe * se, fo = po * so;
+        out[k] = out[k] + (fe + fo);
+        out[q] = out[q] + (fe - fo);
+      } else {
+        out[k] = out[k] + pe * (se + so);
+        out[q] = out[q] + pe * (se - so);
+      }
+    }
+    return speed;
   }
   return __builtin_sqrt(u_sq) * densinv;
 }
@@ -271,28 +332,49 @@ __device__ __forceinline__ double dp_block_sum(double v) {
 }
 
 // Output stage, one fluid cell from its nine values: the columns of final_state.dat (d2q9-bgk.c:787-832, 396-442) in double,
-// the oracle's statements (cell_moments), contraction off
-__device__ __forceinline__ void dp_output_cell(const double (&f)[9], double &ux, double &uy, double &uu, double &pr) {
+// the oracle's statements (cell_moments), contraction off.  drv: NULL, or the body force of the grid (include/lbm.h, "Body
+// force"): the reported velocity is the physical one.  f is a STORED state, the values behind a collision, whose momentum is the
+// collided cell's plus the whole force: each momentum sum less half the force before the division.
+__device__ __forceinline__ void dp_output_cell(const double (&f)[9], const double *drv, double &ux, double &uy, double &uu,
+                                               double &pr) {
 #pragma clang fp contract(off)
   double local_density = 0.0;
 #pragma unroll
   for (int k = 0; k < 9; k++) local_density += f[k];
-  ux = (f[1] + f[5] + f[8] - f[3] - f[6] - f[7]) / local_density;
-  uy = (f[2] + f[5] + f[6] - f[4] - f[7] - f[8]) / local_density;
+  double jx = f[1] + f[5] + f[8] - f[3] - f[6] - f[7];
+  double jy = f[2] + f[5] + f[6] - f[4] - f[7] - f[8];
+  if (drv) {
+    jx = jx - 0.5 * drv[0];
+    jy = jy - 0.5 * drv[1];
+  }
+  ux = jx / local_density;
+  uy = jy / local_density;
   uu = __builtin_sqrt(ux * ux + uy * uy);
   pr = local_density * (1.0 / 3.0);
 }
 
-// Host side: the instance five run-time options choose.  f(force, trt, open, wall, les) is called once, with the
+// Host side: the instance six run-time options choose.  f(force, trt, open, wall, les, drive) is called once, with the
 // std::bool_constant of each option, so a launch site names its kernel's template flags as decltype(force)::value, ... and widens
-// its argument struct where wall or les is true.  Every launch site goes through here: the 32 instances of a kernel are these 32.
+// its argument struct where wall, les or drive is true.  Every launch site goes through here: the 64 instances of a kernel are
+// these 64.
 template <class F>
-inline void dp_with_flags(bool force, bool trt, bool open, bool wall, bool les, F &&f) {
+inline void dp_with_flags(bool force, bool trt, bool open, bool wall, bool les, bool drive, F &&f) {
   auto pick = [](bool on, auto &&g) { on ? g(std::true_type{}) : g(std::false_type{}); };
   pick(force, [&](auto fo) {
-    pick(trt, [&](auto tr) { pick(open, [&](auto op) { pick(wall, [&](auto wa) { pick(les, [&](auto le) { f(fo, tr, op, wa, le); }); }); }); });
+    pick(trt, [&](auto tr) {
+      pick(open, [&](auto op) {
+        pick(wall, [&](auto wa) { pick(les, [&](auto le) { pick(drive, [&](auto dr) { f(fo, tr, op, wa, le, dr); }); }); });
+      });
+    });
   });
 }
+
+// DRIVE: the two components behind whatever the instance without it takes; the DRIVE = false structs are those of a library
+// without the option
+template <class Base>
+struct DpDriveArgs : Base {
+  DpDrive drive;
+};
 
 struct DpStepArgs {
   const double *src;
@@ -320,8 +402,10 @@ struct DpStepWallLesArgs : DpStepWallArgs {
   DpLes les;
 };
 template <bool WALL, bool LES = false>
-using DpStepArgsOf = std::conditional_t<LES, std::conditional_t<WALL, DpStepWallLesArgs, DpStepLesArgs>,
-                                        std::conditional_t<WALL, DpStepWallArgs, DpStepArgs>>;
+using DpStepPlainArgsOf = std::conditional_t<LES, std::conditional_t<WALL, DpStepWallLesArgs, DpStepLesArgs>,
+                                             std::conditional_t<WALL, DpStepWallArgs, DpStepArgs>>;
+template <bool WALL, bool LES = false, bool DRIVE = false>
+using DpStepArgsOf = std::conditional_t<DRIVE, DpDriveArgs<DpStepPlainArgsOf<WALL, LES>>, DpStepPlainArgsOf<WALL, LES>>;
 
 // One timestep, lane = cells x0, x0+1 of one row.  x-1 / x+1 neighbours: aligned 16-B loads plus one scalar load per
 // streamed plane at the wrap column (an L1 hit).  A lane past the row's end (x0 >= nx) only joins the segment sum with 0.
@@ -334,9 +418,10 @@ using DpStepArgsOf = std::conditional_t<LES, std::conditional_t<WALL, DpStepWall
 // WALL: a lane with a blocked cell loads that cell's two wall velocities under the branch it takes for the obstacle, and a
 // cell that moves goes through dp_wall_cell after its bounce-back.  The false instances are the kernels without it.
 // LES: dp_collide_cell<TRT, true> on a.les, nothing else.  The false instances are the kernels without it.
+// DRIVE: dp_collide_cell<TRT, LES, true> on a.drive, nothing else.  The false instances are the kernels without it.
 // static, like the helper kernels below: two translation units include this header (lbm_dp.cpp, lbm_dens.cpp).
-template <bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false>
-static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgsOf<WALL, LES> a) {
+template <bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false, bool DRIVE = false>
+static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgsOf<WALL, LES, DRIVE> a) {
   const unsigned t = blockIdx.x * kBlock + threadIdx.x;
   const unsigned lpr = (unsigned)a.lanes_per_row;
   const int y = (int)(t / lpr);
@@ -396,8 +481,10 @@ static __global__ __launch_bounds__(kBlock) void d2q9_dp_step(const DpStepArgsOf
     double oa[9], ob[9];
     DpLes les{};
     if constexpr (LES) les = a.les;
-    const double ta = dp_collide_cell<TRT, LES>(ga, ob_a, a.omega, a.omega_m, les, oa);
-    const double tb = dp_collide_cell<TRT, LES>(gb, ob_b, a.omega, a.omega_m, les, ob);
+    DpDriveHeld drv{};
+    if constexpr (DRIVE) drv.f = a.drive;
+    const double ta = dp_collide_cell<TRT, LES, DRIVE>(ga, ob_a, a.omega, a.omega_m, les, drv, oa);
+    const double tb = dp_collide_cell<TRT, LES, DRIVE>(gb, ob_b, a.omega, a.omega_m, les, drv, ob);
     if constexpr (WALL) {
       const size_t at = (size_t)y * a.nx + x0;   // ob_b implies has_b: at + 1 is a cell of this row
       if (ob_a) {
@@ -467,25 +554,28 @@ struct DpMultiWallLesArgs : DpMultiWallArgs {
   DpLes les;
 };
 template <bool WALL, bool LES = false>
-using DpMultiArgsOf = std::conditional_t<LES, std::conditional_t<WALL, DpMultiWallLesArgs, DpMultiLesArgs>,
-                                         std::conditional_t<WALL, DpMultiWallArgs, DpMultiArgs>>;
+using DpMultiPlainArgsOf = std::conditional_t<LES, std::conditional_t<WALL, DpMultiWallLesArgs, DpMultiLesArgs>,
+                                              std::conditional_t<WALL, DpMultiWallArgs, DpMultiArgs>>;
+template <bool WALL, bool LES = false, bool DRIVE = false>
+using DpMultiArgsOf = std::conditional_t<DRIVE, DpDriveArgs<DpMultiPlainArgsOf<WALL, LES>>, DpMultiPlainArgsOf<WALL, LES>>;
 
 }  // namespace lbm
 #include "dp_tile.h"   // dp_tile, on the per-cell functions above
 namespace lbm {
 
 // The one grid of a context as dp_tile takes it (dp_tile.h): the argument struct's own fields
-template <bool WALL, bool LES = false>
+template <bool WALL, bool LES = false, bool DRIVE = false>
 struct DpMultiGrid {
   static constexpr bool kStageRhoOut = false;   // rho_out is a kernel argument, in SGPRs already; in LDS it cost two VGPRs
   static constexpr bool kStageLes = false;      // so are the subgrid constants, and this kernel has SGPRs to spare
-  const DpMultiArgsOf<WALL, LES> &a;
+  static constexpr bool kStageDrive = false;    // and the body force
+  const DpMultiArgsOf<WALL, LES, DRIVE> &a;
   const double *src;
   double *dst;
   const uint8_t *mask;
   double *seg_out;
   double omega, omega_m, aw1, aw2;
-  __device__ __forceinline__ explicit DpMultiGrid(const DpMultiArgsOf<WALL, LES> &a_)
+  __device__ __forceinline__ explicit DpMultiGrid(const DpMultiArgsOf<WALL, LES, DRIVE> &a_)
       : a(a_), src(a_.src), dst(a_.dst), mask(a_.mask), seg_out(a_.seg), omega(a_.omega), omega_m(a_.omega_m),
         aw1(a_.aw1), aw2(a_.aw2) {}
   __device__ __forceinline__ unsigned comp() const { return (unsigned)(a.ny * a.nseg); }
@@ -496,6 +586,7 @@ struct DpMultiGrid {
   __device__ __forceinline__ const double *wall_u_y() const { return a.wall.u_y; }
   __device__ __forceinline__ double rho_wall() const { return a.wall.rho_wall; }
   __device__ __forceinline__ DpLes les() const { return a.les; }
+  __device__ __forceinline__ DpDrive drive() const { return a.drive; }
 };
 
 // T <= TMAX timesteps per launch on one grid: dp_tile (dp_tile.h) with kMultiThreads threads, tile = blockIdx.x.
@@ -506,9 +597,9 @@ struct DpMultiGrid {
 //   16x16, T <= 4 (85 KB)                                2.13 / 2.99 / 8.43
 // and one step per launch (d2q9_dp_step) 3.78 / 4.45 / 9.53, at 1024^2 23.8 against this kernel's 28.2: auto up to 300K cells.
 // With every option on the tile holds about 152 of the 160 KB of LDS.
-template <int TX, int TY, int TMAX, bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false>
-__global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgsOf<WALL, LES> a) {
-  dp_tile<TX, TY, TMAX, kMultiThreads, FORCE, TRT, OPEN, WALL, LES, DpMultiGrid<WALL, LES>>(a);
+template <int TX, int TY, int TMAX, bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false, bool DRIVE = false>
+__global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgsOf<WALL, LES, DRIVE> a) {
+  dp_tile<TX, TY, TMAX, kMultiThreads, FORCE, TRT, OPEN, WALL, LES, DRIVE, DpMultiGrid<WALL, LES, DRIVE>>(a);
 }
 
 // What differs from member to member, in device memory, read by member index (a wave-uniform load), as EnsMember.  An
@@ -606,12 +697,14 @@ static __global__ void dp_pack_planes(double *cells, double *cells_alt, const in
 
 // output stage per member: the columns of final_state.dat and the velocity sum (dp_output_cell: d2q9-bgk.c:787-832, 396-442, in
 // double, the oracle's statements); obstacle cells give 0, 0, 0, density/3.  Outputs are double[members][ny][nx], partials
-// double[members][gridDim.x]: the per-block sums of u.  cells_alt, par: as dp_pack_planes
+// double[members][gridDim.x]: the per-block sums of u.  cells_alt, par: as dp_pack_planes.  drive: NULL, or the members' body
+// forces, double[members][2] (include/lbm.h, "Body force": the reported velocity is corrected by half of it)
 static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *cells, const double *cells_alt, const int *par,
                                                                  unsigned long long plane_stride,
                                                                  unsigned long long member_stride, int nx, const uint8_t *mask,
-                                                                 size_t n, const DpMember *members, double *u_x, double *u_y,
-                                                                 double *u, double *pressure, double *partials) {
+                                                                 size_t n, const DpMember *members, const double *drive,
+                                                                 double *u_x, double *u_y, double *u, double *pressure,
+                                                                 double *partials) {
 #pragma clang fp contract(off)
   const double c_sq = 1.0 / 3.0;
   const double density = members[blockIdx.y].density;
@@ -619,6 +712,7 @@ static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *c
   cells += (size_t)blockIdx.y * member_stride;
   mask += (size_t)blockIdx.y * n;
   const size_t off = (size_t)blockIdx.y * n;
+  if (drive) drive += 2 * (size_t)blockIdx.y;
   double tot_u = 0.0;
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     double ux = 0.0, uy = 0.0, uu = 0.0, pr = density * c_sq;
@@ -628,7 +722,7 @@ static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *c
       const size_t cell = y * 9 * plane_stride + (i - y * nx);
 #pragma unroll
       for (int k = 0; k < 9; k++) f[k] = cells[k * plane_stride + cell];
-      dp_output_cell(f, ux, uy, uu, pr);
+      dp_output_cell(f, drive, ux, uy, uu, pr);
       tot_u += uu;
     }
     if (u_x) u_x[off + i] = ux;

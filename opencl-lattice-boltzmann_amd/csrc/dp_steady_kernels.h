@@ -14,11 +14,11 @@
 
 namespace lbm {
 
-template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false>
-__global__ __launch_bounds__(NT, (dens_waves_per_simd<NT, FORCE, TRT, OPEN, WALL, LES>())) void d2q9_dp_ensemble_gated(const DensArgsOf<WALL> a,
-                                                                                                                    const int *active) {
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL = false, bool LES = false, bool DRIVE = false>
+__global__ __launch_bounds__(NT, (dens_waves_per_simd<NT, FORCE, TRT, OPEN, WALL, LES, DRIVE>())) void d2q9_dp_ensemble_gated(
+    const DensArgsOf<WALL> a, const int *active) {
   if (active[blockIdx.y] == 0) return;  // uniform over the workgroup, before the first barrier or LDS access
-  dp_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN, WALL, LES, DensGrid<WALL>>(a);
+  dp_tile<TX, TY, TMAX, NT, FORCE, TRT, OPEN, WALL, LES, DRIVE, DensGrid<WALL>>(a);
 }
 
 // After a leg that ended at step count s on parity cur: the members that were active during it are now at s.  With

@@ -14,6 +14,8 @@
 //   wall_cell0(), rho_wall()                its cell (0,0) in them, and its wall density
 //   les()                             LES: its tau0, les_k and magic parameter (DpLes)
 //   kStageLes                         LES: they go to LDS with the region, or are held in SGPRs
+//   drive()                           DRIVE: its body force F_x, F_y (DpDrive)
+//   kStageDrive                       DRIVE: they go to LDS with the region, or are held in SGPRs
 //   kStageRhoOut                      the one switch: rho_out goes to LDS with the profile, or is read where it is used
 // The option members are functions: an instance without the option never evaluates them, and one with it evaluates them where
 // it uses them, under the branch of a marked cell, so no register holds a table's address across the loops (the ensemble runs
@@ -63,8 +65,12 @@ namespace lbm {
 //
 // LES (the Smagorinsky subgrid viscosity): dp_collide_cell<TRT, true> on g.les() in the collision loop, nothing else.
 //
+// DRIVE (a uniform body force, Guo forcing): dp_collide_cell<TRT, LES, true> on g.drive() in the collision loop, nothing else.  The
+// two components are wave-uniform: held in SGPRs, or, where the kernel has none to spare (kStageDrive), in 16 B of LDS beside the
+// subgrid constants and read per cell from an opaque zero, as those are.
+//
 // The false instance of each flag is the kernel without it, instruction for instruction.
-template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL, bool LES, class Grid, class Args>
+template <int TX, int TY, int TMAX, int NT, bool FORCE, bool TRT, bool OPEN, bool WALL, bool LES, bool DRIVE, class Grid, class Args>
 __device__ __forceinline__ void dp_tile(const Args a) {
   constexpr bool MARKED = OPEN || WALL;   // lmask bytes carry marks above the low two bits
   static_assert(TX % kDpSeg == 0, "a tile row is whole segments");
@@ -94,6 +100,17 @@ __device__ __forceinline__ void dp_tile(const Args a) {
       les = g.les();
     }
   }
+  // DRIVE: the two components, read once like the subgrid constants, into LDS (kStageDrive) or into SGPRs
+  [[maybe_unused]] DpDrive drv{};
+  [[maybe_unused]] double *ldrv = nullptr;
+  if constexpr (DRIVE) {
+    if constexpr (Grid::kStageDrive) {
+      __shared__ double drive_consts[2];
+      ldrv = drive_consts;
+    } else {
+      drv = g.drive();
+    }
+  }
   // OPEN: the profile on the region's rows and, behind them, rho_out (kStageRhoOut), staged in LDS with the region: a marked cell
   // reads them under its branch without a global load on a step's critical path, and no register holds an address across the loops
   [[maybe_unused]] double *lopen = nullptr;
@@ -118,7 +135,7 @@ __device__ __forceinline__ void dp_tile(const Args a) {
     constexpr int kSegs = TY * (TX / kDpSeg);
     int lane = tid;
     // as in the force pass below: nothing of this is kept across the collision loop (WALL: its branch needs the registers)
-    if constexpr (FORCE || WALL || LES) asm volatile("" : "+v"(lane));
+    if constexpr (FORCE || WALL || LES || DRIVE) asm volatile("" : "+v"(lane));
     if (lane < kSegs) {
       const int oy = lane / (TX / kDpSeg), sx = lane - oy * (TX / kDpSeg);
       const int gy = tile_y * TY + oy;
@@ -172,6 +189,12 @@ __device__ __forceinline__ void dp_tile(const Args a) {
     if (tid == 0) {
       const DpLes l = g.les();
       lles[0] = l.tau0, lles[1] = l.les_k, lles[2] = l.magic;
+    }
+  }
+  if constexpr (DRIVE && Grid::kStageDrive) {
+    if (tid == 64) {   // the second wave's first lane: the first's stages the subgrid constants
+      const DpDrive d = g.drive();
+      ldrv[0] = d.f_x, ldrv[1] = d.f_y;
     }
   }
   if constexpr (WALL) {
@@ -256,7 +279,7 @@ __device__ __forceinline__ void dp_tile(const Args a) {
       // LES: the cell from an opaque copy of i.  Otherwise the compiler carries four sums of the lane index, the step and a
       // constant across the step loop, one for each use below, and the instance with all five options is one VGPR short.
       int at = i;
-      if constexpr (LES) asm volatile("" : "+v"(at));
+      if constexpr (LES || DRIVE) asm volatile("" : "+v"(at));
       const int q = (int)(((float)at + 0.5f) * inv);
       const int rx = s + (at - q * w), ry = s + q;
       const int c = ry * kRX + rx;
@@ -283,7 +306,18 @@ __device__ __forceinline__ void dp_tile(const Args a) {
         asm volatile("" : "+v"(zero));
         les = DpLes{lles[zero], lles[zero + 1], TRT ? lles[zero + 2] : 0.0};
       }
-      const double t = dp_collide_cell<TRT, LES>(gth, obst, g.omega, g.omega_m, les, o);
+      double t;
+      if constexpr (DRIVE && Grid::kStageDrive) {
+        // from an opaque zero, at each of the collision's two uses: no register holds the pair, or its address, in between
+        auto staged = [ldrv]() {
+          int zero = 0;
+          asm volatile("" : "+v"(zero));
+          return DpDrive{ldrv[zero], ldrv[zero + 1]};
+        };
+        t = dp_collide_cell<TRT, LES, DRIVE>(gth, obst, g.omega, g.omega_m, les, staged, o);
+      } else {
+        t = dp_collide_cell<TRT, LES, DRIVE>(gth, obst, g.omega, g.omega_m, les, DpDriveHeld{drv}, o);
+      }
       if constexpr (!OPEN)
         if (accel_step && grid_row(ry) == a.ny - 2) dp_accelerate_cell(o, obst, g.aw1, g.aw2);
 #pragma unroll

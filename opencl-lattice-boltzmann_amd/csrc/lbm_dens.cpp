@@ -62,7 +62,8 @@ struct lbm_dens {
   uint8_t *mask = nullptr;         // [n][ny][nx]: 0 fluid, 1 blocked and counted in the force, 2 blocked outside the body
   BodyMap body;                    // the host's copy of what the mask was made of (body_map.h)
   DpMember *members = nullptr;     // [n], then the open-boundary table double[n][ny + 1] (dens_open_table), then rho_wall[n]
-                                   // (dens_wall_table), then DpLes[n] (dens_les_table)
+                                   // (dens_wall_table), then DpLes[n] (dens_les_table), then the body forces double[n][2]
+                                   // (dens_drive_table)
   double *seg = nullptr;           // [ring][n][ny][nseg]
   double *red = nullptr;           // [ring][n][red_blocks]: first reduction stage
   double *av_sum = nullptr;        // [n][max_iters]
@@ -81,6 +82,8 @@ struct lbm_dens {
   double *wall_dev = nullptr;      // [2][n][ny][nx] (allocated by the first lbm_dwall_ens_set that switches on)
   bool les = false;                // lbm_dles_ens_set: the kernels' LES instances, for all members
   std::vector<double> les_c;       // [n]: every member's Smagorinsky constant, 0 while the setting is off
+  bool drive = false;              // lbm_ddrive_ens_set: the kernels' DRIVE instances, for all members
+  std::vector<double> drive_f;     // [n][2]: every member's force density, 0 while the setting is off
   int nseg = 1, red_blocks = 1, fin_blocks = 1;
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
@@ -175,7 +178,7 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
 
   // what the ensemble needs against what the device has free: refuse here rather than fail half-way through
   const size_t cells_bytes = ((size_t)n * e->member_stride + 32) * sizeof(double);
-  const size_t tables = (size_t)n * (sizeof(DpMember) + (size_t)(ny + 2) * sizeof(double) + sizeof(DpLes));
+  const size_t tables = (size_t)n * (sizeof(DpMember) + (size_t)(ny + 2) * sizeof(double) + sizeof(DpLes) + sizeof(DpDrive));
   const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + tables +
                       (size_t)e->ring * all_step * sizeof(double) + (size_t)e->ring * n * e->red_blocks * sizeof(double) +
                       (size_t)n * e->max_iters * sizeof(double) + (size_t)n * e->fin_blocks * sizeof(double);
@@ -201,29 +204,30 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
   // in double these are lbm_dp.cpp's own statements (run_dp_impl, lbm_dp_upload): a member's constants are a context's
   e->magic.assign(n, 0.0);
   e->les_c.assign(n, 0.0);
+  e->drive_f.assign(2 * (size_t)n, 0.0);
   e->omega_m.resize(n);
   for (int i = 0; i < n; i++) e->omega_m[i] = e->p[i].omega;
   return upload_members(e, e->omega_m);
 }
 
 // FORCE from the option "force", TRT from lbm_dtrt_ens_set, OPEN from lbm_dopen_ens_set, WALL from lbm_dwall_ens_set, LES from
-// lbm_dles_ens_set: with all
+// lbm_dles_ens_set, DRIVE from lbm_ddrive_ens_set: with all
 // off these are the launches of a library without any of them.  active: NULL for an ordinary run, the members' words for a
 // leg of a steady run
 void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
   const dim3 grid(e->tiles, e->n), block(kDensThreads);
-  dp_with_flags(e->force, e->trt, e->open, e->wall, e->les, [&](auto force, auto trt, auto open, auto wall, auto les) {
+  dp_with_flags(e->force, e->trt, e->open, e->wall, e->les, e->drive, [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
     constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value,
-                   LES = decltype(les)::value;
+                   LES = decltype(les)::value, DRIVE = decltype(drive)::value;
     DensArgsOf<WALL> w{};
     static_cast<DensArgs &>(w) = a;
     if constexpr (WALL) w.wall_u = e->wall_dev;
     if (!active)
-      hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL, LES>), grid, block, 0, e->q.st,
-                         w);
+      hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL, LES, DRIVE>), grid, block, 0,
+                         e->q.st, w);
     else
-      hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL, LES>), grid, block, 0,
-                         e->q.st, w, active);
+      hipLaunchKernelGGL((d2q9_dp_ensemble_gated<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL, LES, DRIVE>), grid, block,
+                         0, e->q.st, w, active);
   });
 }
 
@@ -386,8 +390,9 @@ int stage_of(lbm_dens *e, double **stage) {
 int final_fields_dens(lbm_dens *e, double *const (&d)[4]) {
   hipLaunchKernelGGL(dp_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->q.st,
                      (const double *)e->cells[e->ragged ? 0 : e->cur], (const double *)e->cells[1], member_parity(e), e->plane_stride,
-                     e->member_stride, e->nx, (const uint8_t *)e->mask, (size_t)e->nx * e->ny, (const DpMember *)e->members, d[0],
-                     d[1], d[2], d[3], e->fin_partials);
+                     e->member_stride, e->nx, (const uint8_t *)e->mask, (size_t)e->nx * e->ny, (const DpMember *)e->members,
+                     e->drive ? dens_drive_table(e->members, e->n, e->ny) : (const double *)nullptr, d[0], d[1], d[2], d[3],
+                     e->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
 }
@@ -847,6 +852,42 @@ int lbm_dles_ens_get(const lbm_dens *e, double *c_out, double *les_k_out) {
     if (c_out) c_out[m] = e->les_c[m];
     if (les_k_out) les_k_out[m] = dp_les_constants(e->p[m].omega, e->les_c[m], 0.0).les_k;
   }
+  return LBM_OK;
+}
+
+int lbm_ddrive_ens_set(lbm_dens *e, const double *f) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  // every member is checked before anything changes, on the host or on the device
+  if (f)
+    for (int m = 0; m < e->n; m++) {
+      const double f_x = f[2 * (size_t)m], f_y = f[2 * (size_t)m + 1];
+      if (!std::isfinite(f_x) || !std::isfinite(f_y))
+        return lbm_fail(LBM_ERR_ARG, "member %d: the body force must be finite (got f_x = %g, f_y = %g)", m, f_x, f_y);
+      if (!dp_drive_on(f_x, f_y))
+        return lbm_fail(LBM_ERR_ARG, "member %d: the body force is (0, 0); an ensemble has the body force on for all members or, "
+                        "with a NULL array, off", m);
+    }
+  if (e->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "the body force is set before the first step (%d done): one record holds one flow", e->steps_done);
+  if (!f) {
+    e->drive = false;
+    e->drive_f.assign(2 * (size_t)e->n, 0.0);
+    return LBM_OK;
+  }
+  if (int rc = queue_sync(e->q)) return rc;
+  HIP_TRY(hipSetDevice(e->q.dev));
+  HIP_TRY(hipMemcpy(const_cast<double *>(dens_drive_table(e->members, e->n, e->ny)), f, 2 * (size_t)e->n * sizeof(double),
+                    hipMemcpyHostToDevice));
+  e->drive = true;
+  e->drive_f.assign(f, f + 2 * (size_t)e->n);
+  return LBM_OK;
+}
+
+int lbm_ddrive_ens_get(const lbm_dens *e, int *on_out, double *f_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!on_out && !f_out) return lbm_fail(LBM_ERR_ARG, "on_out and f_out are both NULL");
+  if (on_out) *on_out = e->drive ? 1 : 0;
+  if (f_out) std::copy(e->drive_f.begin(), e->drive_f.end(), f_out);
   return LBM_OK;
 }
 

@@ -48,7 +48,8 @@ struct lbm_dp {
   uint8_t *mask = nullptr;        // [ny][nx]: 0 fluid, 1 blocked and counted in the force, 2 blocked outside the body
   BodyMap body;                   // the host's copy of what the mask was made of (body_map.h)
   DpMember *members = nullptr;    // [1]: this grid's constants as the helper kernels read them (dp_kernels.h); the step kernels
-                                  // take omega, omega_m, aw1, aw2 as arguments, and the table's omega, omega_m are not read
+                                  // take omega, omega_m, aw1, aw2 as arguments, and the table's omega, omega_m are not read;
+                                  // behind it double[2], the body force as dp_final_fields reads it (drive_dev)
   double *seg = nullptr;          // [ring][ny][nseg]
   double *red = nullptr;          // [ring][red_blocks]: first reduction stage
   double *av_sum = nullptr;       // [max_iters]
@@ -71,6 +72,7 @@ struct lbm_dp {
   double rho_wall = 0.0;          // the wall density
   double *wall_dev = nullptr;     // [2][ny][nx] (allocated by the first lbm_dwall_set that switches on)
   double les_c = 0.0;             // lbm_dles_set: 0 = off, > 0 = the LES instances with this Smagorinsky constant
+  double drive[2] = {0.0, 0.0};   // lbm_ddrive_set: (0, 0) = off, else the DRIVE instances with this force density
   int cur = 0, steps_done = 0;
   bool failed = false;
 };
@@ -135,7 +137,7 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
     return lbm_fail(LBM_ERR_ARG, "a grid of %dx%d cells is beyond the 2^31 lanes of one launch", nx, ny);
 
   const size_t grid_bytes = (9 * d->plane_stride * ny + 32) * sizeof(double);
-  const size_t need = 2 * grid_bytes + cells + 64 + sizeof(DpMember) + (size_t)d->ring * per_step * sizeof(double) +
+  const size_t need = 2 * grid_bytes + cells + 64 + sizeof(DpMember) + sizeof(DpDrive) + (size_t)d->ring * per_step * sizeof(double) +
                       (size_t)d->ring * d->red_blocks * sizeof(double) + (size_t)d->p.max_iters * sizeof(double) +
                       (size_t)d->fin_blocks * sizeof(double);
   size_t free_b = 0, total_b = 0;
@@ -155,14 +157,15 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->fin_partials), (size_t)d->fin_blocks * sizeof(double)));
   // a table of one member: aw1, aw2 are run_dp_impl's statements, and the rest state's w0..w2 come from here alone
   const DpMember m = member_constants<DpMember>(d->p);
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->members), sizeof(DpMember)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->members), sizeof(DpMember) + sizeof(DpDrive)));
   HIP_TRY(hipMemcpy(d->members, &m, sizeof(DpMember), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d->members + 1, 0, sizeof(DpDrive)));
   body_reset(d->body, obstacles, cells);
   return upload_mask(d->mask, obstacles, cells);
 }
 
 // The instance the options choose: FORCE from "force", TRT from lbm_dtrt_set, OPEN from lbm_dopen_set, WALL from lbm_dwall_set,
-// LES from lbm_dles_set.
+// LES from lbm_dles_set, DRIVE from lbm_ddrive_set.
 // With all off these are the launches of a library without any of them.
 // what a WALL instance takes beyond the arguments of the kernel without it
 DpWall wall_args(const lbm_dp *d) {
@@ -173,29 +176,37 @@ DpWall wall_args(const lbm_dp *d) {
 // what an LES instance takes beyond them: the header's two host statements, and the magic parameter as set (either order)
 DpLes les_args(const lbm_dp *d) { return dp_les_constants(d->p.omega, d->les_c, d->magic); }
 
+// whether the body force is on, and where dp_final_fields reads it (NULL while it is off)
+bool drive_on(const lbm_dp *d) { return dp_drive_on(d->drive[0], d->drive[1]); }
+const double *drive_dev(const lbm_dp *d) { return drive_on(d) ? reinterpret_cast<const double *>(d->members + 1) : nullptr; }
+
 void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
-  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, [&](auto force, auto trt, auto open, auto wall, auto les) {
+  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, drive_on(d),
+                [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
     constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value,
-                   LES = decltype(les)::value;
-    DpMultiArgsOf<WALL, LES> w{};
+                   LES = decltype(les)::value, DRIVE = decltype(drive)::value;
+    DpMultiArgsOf<WALL, LES, DRIVE> w{};
     static_cast<DpMultiArgs &>(w) = a;
     if constexpr (WALL) w.wall = wall_args(d);
     if constexpr (LES) w.les = les_args(d);
-    hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT, OPEN, WALL, LES>), dim3(d->tiles), dim3(kMultiThreads), 0, d->q.st,
-                       w);
+    if constexpr (DRIVE) w.drive = DpDrive{d->drive[0], d->drive[1]};
+    hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT, OPEN, WALL, LES, DRIVE>), dim3(d->tiles), dim3(kMultiThreads), 0,
+                       d->q.st, w);
   });
 }
 
 void launch_step(const lbm_dp *d, const DpStepArgs &a) {
   const dim3 grid((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock));
-  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, [&](auto force, auto trt, auto open, auto wall, auto les) {
+  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, drive_on(d),
+                [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
     constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value,
-                   LES = decltype(les)::value;
-    DpStepArgsOf<WALL, LES> w{};
+                   LES = decltype(les)::value, DRIVE = decltype(drive)::value;
+    DpStepArgsOf<WALL, LES, DRIVE> w{};
     static_cast<DpStepArgs &>(w) = a;
     if constexpr (WALL) w.wall = wall_args(d);
     if constexpr (LES) w.les = les_args(d);
-    hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT, OPEN, WALL, LES>), grid, dim3(kBlock), 0, d->q.st, w);
+    if constexpr (DRIVE) w.drive = DpDrive{d->drive[0], d->drive[1]};
+    hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT, OPEN, WALL, LES, DRIVE>), grid, dim3(kBlock), 0, d->q.st, w);
   });
 }
 
@@ -307,7 +318,7 @@ int final_fields_dp(lbm_dp *d, double *const (&dst)[4]) {
   const size_t n = (size_t)d->p.nx * d->p.ny;
   hipLaunchKernelGGL(dp_final_fields, dim3(d->fin_blocks, 1), dim3(kBlock), 0, d->q.st, (const double *)d->cells[d->cur],
                      (const double *)nullptr, (const int *)nullptr, d->plane_stride, 0ull, d->p.nx, (const uint8_t *)d->mask, n,
-                     (const DpMember *)d->members, dst[0], dst[1], dst[2], dst[3], d->fin_partials);
+                     (const DpMember *)d->members, drive_dev(d), dst[0], dst[1], dst[2], dst[3], d->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
 }
@@ -668,6 +679,31 @@ int lbm_dles_get(const lbm_dp *d, double *c_out, double *les_k_out) {
   if (!c_out && !les_k_out) return lbm_fail(LBM_ERR_ARG, "c_out and les_k_out are both NULL");
   if (c_out) *c_out = d->les_c;
   if (les_k_out) *les_k_out = les_args(d).les_k;
+  return LBM_OK;
+}
+
+int lbm_ddrive_set(lbm_dp *d, double f_x, double f_y) {
+  // argument errors before anything of the context is read
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!std::isfinite(f_x) || !std::isfinite(f_y))
+    return lbm_fail(LBM_ERR_ARG, "the body force must be finite (got f_x = %g, f_y = %g)", f_x, f_y);
+  if (d->steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "the body force is set before the first step (%d done): one record holds one flow", d->steps_done);
+  if (int rc = queue_sync(d->q)) return rc;
+  HIP_TRY(hipSetDevice(d->q.dev));
+  // the copy the output stage reads; the step kernels take the two components as arguments
+  const double f[2] = {f_x, f_y};
+  HIP_TRY(hipMemcpy(d->members + 1, f, sizeof(f), hipMemcpyHostToDevice));
+  d->drive[0] = f_x;
+  d->drive[1] = f_y;
+  return LBM_OK;
+}
+
+int lbm_ddrive_get(const lbm_dp *d, double *f_x_out, double *f_y_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!f_x_out && !f_y_out) return lbm_fail(LBM_ERR_ARG, "f_x_out and f_y_out are both NULL");
+  if (f_x_out) *f_x_out = d->drive[0];
+  if (f_y_out) *f_y_out = d->drive[1];
   return LBM_OK;
 }
 
