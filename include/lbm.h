@@ -1095,6 +1095,93 @@ int lbm_ddrive_ens_set(lbm_dens *e, const double *f /*[n][2]*/);
  * (on_out and f_out), or a NULL ensemble: LBM_ERR_ARG. */
 int lbm_ddrive_ens_get(const lbm_dens *e, int *on_out, double *f_out /*[n][2]*/);
 
+/*
+ * ---- Scalar transport: a passive scalar carried by the flow, for the double-precision families -------------------------------
+ *
+ * The double-precision families compute a flow; nothing so far is carried by it.  With a scalar on, a context, or each member of
+ * an ensemble, carries one field C(x, y) - dye, a concentration, a temperature that does not act back - that the flow advects
+ * and that diffuses with a diffusivity D of its own.  The scalar is PASSIVE: the flow never reads it, and the flow with a scalar
+ * on equals the flow without it bit for bit (cells, av_vels, the force record).  It is advanced by a kernel of its own
+ * (dp_scalar_step); no flow kernel, argument struct or launch changes.  Off by default.  The reference has no counterpart.
+ *
+ * The lattice.  D2Q5: speeds k = 0..4 are the flow's speeds 0..4 (rest, E, N, W, S), the opposites are 1 <-> 3 and 2 <-> 4, the
+ * weights 1/3 (rest) and 1/6.  A handle holds five populations g_k per cell in the row-interleaved layout of the flow (g_k(x, y) at
+ * y * 5 * plane_stride + k * plane_stride + x), in two arrays.  The host computes, in double, contraction off,
+ *     omega_s = 1.0 / (3.0 * D + 0.5);
+ *
+ * When a step happens.  Scalar step n runs BEFORE flow step n, on the state that flow step n streams: the current cells after
+ * step n's accelerate_flow, whether the run's prologue applied it or the previous launch's fused write did.  So run(10) and
+ * run(3); run(7) see the same velocities.  While a scalar is on every launch of a run advances ONE step (the scalar needs each
+ * step's velocities); the option "multistep" still chooses the kernel form, and every form computes the same bits.
+ *
+ * Definition.  A FLUID cell x does the following; all in double, contraction off, one IEEE operation per written operator, in this
+ * order.  (u_x, u_y) is the output stage's velocity of the cell's nine stored values (the statements of lbm_dp_final_state; with a
+ * body force on, the physical velocity, less half the force).  The gather, with q = x - c_k, periodic in both axes:
+ *     h[0] = g[0](x);
+ *     for k = 1..4:
+ *         q fluid:                           h[k] = g[k](q);
+ *         q blocked, c_wall(q) NaN:          h[k] = g[opp(k)](x);
+ *         q blocked, c_wall(q) finite:       h[k] = (1.0 / 3.0) * c_wall(q) - g[opp(k)](x);
+ * A blocked neighbour with NaN is an insulating wall (half-way bounce-back), one with a finite value a wall held at that value.
+ * With open boundaries on ("Open boundaries"), behind the gather:
+ *     column 0:         h[1] = c_in(y) - (((h[0] + h[2]) + h[3]) + h[4]);
+ *     column nx - 1:    h[3] = g[3](x);
+ * the inlet carries the value c_in(y), the outlet the cell's own stored value (zero gradient).  The collision:
+ *     C = (((h[0] + h[1]) + h[2]) + h[3]) + h[4];
+ *     a_x = 3.0 * (C * u_x);          a_y = 3.0 * (C * u_y);
+ *     e[0] = (1.0 / 3.0) * C;
+ *     e[1] = (1.0 / 6.0) * (C + a_x);
+ *     e[3] = (1.0 / 6.0) * (C - a_x);
+ *     e[2] = (1.0 / 6.0) * (C + a_y);
+ *     e[4] = (1.0 / 6.0) * (C - a_y);
+ *     for k = 0..4:
+ *         g'[k] = h[k] + omega_s * (e[k] - h[k]);
+ * A BLOCKED cell's five values are copied through unchanged.
+ *
+ * Reported field.  A fluid cell reports (((g[0] + g[1]) + g[2]) + g[3]) + g[4] of its stored values, a blocked cell 0.0.
+ * Setting a scalar initialises g[k] = w_k * c0(x) on every cell: (1.0 / 3.0) * c0 for k = 0, (1.0 / 6.0) * c0 for the others.
+ *
+ * Bit identities.  A member of a double-precision ensemble equals a double-precision context with the same scalar, flow and
+ * obstacles; the kernel forms ("multistep") and launch splits agree; a download followed by an upload changes nothing.
+ *
+ * When it is accepted.  Between runs at any step count: a scalar is often released into a developed flow.  lbm_dp_upload,
+ * lbm_dens_upload and lbm_dp_upload_obstacles keep the scalar and its state; c_wall is only ever read at blocked cells.  An ensemble
+ * has the scalar on for all members, each with its own D, c_wall and c_in, or off.  Everything is checked before anything changes:
+ * after a refusal nothing has changed, on the host or on the device.  lbm_dsteady_run and lbm_dbody_steady_run are refused
+ * (LBM_ERR_ARG) while a scalar is on: a member that stops would need a gated scalar kernel, which is out of scope.
+ *
+ * Names: lbm_dscalar_*, on both double-precision handles.  Out of scope: fp32 contexts and fp32 ensembles, which get nothing; a
+ * scalar that acts back on the flow (buoyancy); more than one scalar per handle; a scalar step fused into the LDS-tile kernels.
+ */
+
+/* Set the scalar of a double-precision context: diffusivity > 0 switches it on from the field c0 = double[ny][nx]; c_wall =
+ * double[ny][nx] (NaN: insulating, finite: held at that value; read at blocked cells only) or NULL: all insulating; c_in =
+ * double[ny], read with open boundaries on, or NULL: zeros.  diffusivity == 0 switches it off: the handle then runs as one that never
+ * had a scalar, multi-step launches included.  LBM_ERR_ARG: a NULL context, a negative or non-finite diffusivity, a NULL c0 with a
+ * positive diffusivity (these before the context is read), a non-finite c0 or c_in, an infinite c_wall.  Synchronises first. */
+int lbm_dscalar_set(lbm_dp *d, double diffusivity, const double *c0 /*[ny][nx]*/, const double *c_wall /*[ny][nx] or NULL*/,
+                    const double *c_in /*[ny] or NULL*/);
+
+/* on_out: 1 while the scalar is on, else 0; the diffusivity and omega_s in force, 0.0 while it is off.  Any output may be NULL; all
+ * NULL (on_out, diffusivity_out and omega_s_out), or a NULL context: LBM_ERR_ARG. */
+int lbm_dscalar_get(const lbm_dp *d, int *on_out, double *diffusivity_out, double *omega_s_out);
+
+/* The reported field, the five populations as double[5][ny][nx], and the populations back.  LBM_ERR_ARG: a NULL argument, or the
+ * scalar is off.  Synchronise. */
+int lbm_dscalar_field(lbm_dp *d, double *c_out /*[ny][nx]*/);
+int lbm_dscalar_download(lbm_dp *d, double *g_out /*[5][ny][nx]*/);
+int lbm_dscalar_upload(lbm_dp *d, const double *g /*[5][ny][nx]*/);
+
+/* The same for a double-precision ensemble, every array with a leading member axis: diffusivity = double[n], every entry > 0 and
+ * finite, members may differ; NULL: off for all members.  LBM_ERR_ARG, the message names the member: as above, and an entry of
+ * diffusivity that is 0.  LBM_ERR_STATE: the ensemble is ragged (lbm_dsteady_run). */
+int lbm_dscalar_ens_set(lbm_dens *e, const double *diffusivity /*[n] or NULL*/, const double *c0 /*[n][ny][nx]*/,
+                        const double *c_wall /*[n][ny][nx] or NULL*/, const double *c_in /*[n][ny] or NULL*/);
+int lbm_dscalar_ens_get(const lbm_dens *e, int *on_out, double *diffusivity_out /*[n]*/, double *omega_s_out /*[n]*/);
+int lbm_dscalar_ens_field(lbm_dens *e, double *c_out /*[n][ny][nx]*/);
+int lbm_dscalar_ens_download(lbm_dens *e, double *g_out /*[n][5][ny][nx]*/);
+int lbm_dscalar_ens_upload(lbm_dens *e, const double *g /*[n][5][ny][nx]*/);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "lbm_dwall_set", "lbm_dwall_get", "lbm_dwall_ens_set", "lbm_dwall_ens_get",
     "lbm_dles_set", "lbm_dles_get", "lbm_dles_ens_set", "lbm_dles_ens_get",
     "lbm_ddrive_set", "lbm_ddrive_get", "lbm_ddrive_ens_set", "lbm_ddrive_ens_get",
+    "lbm_dscalar_set", "lbm_dscalar_get", "lbm_dscalar_field", "lbm_dscalar_download", "lbm_dscalar_upload",
+    "lbm_dscalar_ens_set", "lbm_dscalar_ens_get", "lbm_dscalar_ens_field", "lbm_dscalar_ens_download", "lbm_dscalar_ens_upload",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -186,6 +188,16 @@ def load_library():
     L.lbm_ddrive_get.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     L.lbm_ddrive_ens_set.argtypes = [vp, vp]
     L.lbm_ddrive_ens_get.argtypes = [vp, ctypes.POINTER(ci), vp]
+    L.lbm_dscalar_set.argtypes = [vp, ctypes.c_double, vp, vp, vp]
+    L.lbm_dscalar_get.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    L.lbm_dscalar_field.argtypes = [vp, vp]
+    L.lbm_dscalar_download.argtypes = [vp, vp]
+    L.lbm_dscalar_upload.argtypes = [vp, vp]
+    L.lbm_dscalar_ens_set.argtypes = [vp, vp, vp, vp, vp]
+    L.lbm_dscalar_ens_get.argtypes = [vp, ctypes.POINTER(ci), vp, vp]
+    L.lbm_dscalar_ens_field.argtypes = [vp, vp]
+    L.lbm_dscalar_ens_download.argtypes = [vp, vp]
+    L.lbm_dscalar_ens_upload.argtypes = [vp, vp]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -674,6 +686,44 @@ class LBMDouble(_Handle):
         _check(self.lib.lbm_ddrive_get(self.ctx, ctypes.byref(f_x), ctypes.byref(f_y)), "lbm_ddrive_get")
         return f_x.value, f_y.value
 
+    def set_scalar(self, D, c0=0.0, wall=None, inlet=None):
+        """Passive scalar (lbm_dscalar_set): D > 0 = a scalar of that diffusivity, started from the field c0 (float64[ny, nx] or one
+        value); wall float64[ny, nx], the value a blocked cell is held at, NaN = insulating (None: all insulating); inlet
+        float64[ny] or one value, the inlet value with open boundaries on (None: zeros).  set_scalar(None) or 0.0 = off, the
+        default.  Between runs at any step count."""
+        if D is None or float(D) == 0.0:
+            _check(self.lib.lbm_dscalar_set(self.ctx, 0.0, None, None, None), "lbm_dscalar_set")
+            return
+        c = np.ascontiguousarray(np.broadcast_to(np.asarray(c0, dtype=np.float64), (self.ny, self.nx)))
+        w = None if wall is None else np.ascontiguousarray(np.broadcast_to(np.asarray(wall, dtype=np.float64), (self.ny, self.nx)))
+        i = None if inlet is None else np.ascontiguousarray(np.broadcast_to(np.asarray(inlet, dtype=np.float64), (self.ny,)))
+        _check(self.lib.lbm_dscalar_set(self.ctx, float(D), c.ctypes.data, None if w is None else w.ctypes.data,
+                                        None if i is None else i.ctypes.data), "lbm_dscalar_set")
+
+    def scalar(self):
+        """(D, omega_s) while a scalar is on, None while it is off (lbm_dscalar_get)"""
+        on, D, om = ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
+        _check(self.lib.lbm_dscalar_get(self.ctx, ctypes.byref(on), ctypes.byref(D), ctypes.byref(om)), "lbm_dscalar_get")
+        return (D.value, om.value) if on.value else None
+
+    def scalar_field(self):
+        """float64[ny, nx]: the scalar of every fluid cell, 0.0 on blocked cells (lbm_dscalar_field)"""
+        c = np.zeros((self.ny, self.nx), dtype=np.float64)
+        _check(self.lib.lbm_dscalar_field(self.ctx, c.ctypes.data), "lbm_dscalar_field")
+        return c
+
+    def scalar_cells(self):
+        """float64[5, ny, nx]: the scalar's five populations (lbm_dscalar_download)"""
+        g = np.zeros((5, self.ny, self.nx), dtype=np.float64)
+        _check(self.lib.lbm_dscalar_download(self.ctx, g.ctypes.data), "lbm_dscalar_download")
+        return g
+
+    def upload_scalar(self, g):
+        """the scalar's five populations, float64[5, ny, nx] (lbm_dscalar_upload); the scalar is on"""
+        a = np.ascontiguousarray(g, dtype=np.float64)
+        assert a.shape == (5, self.ny, self.nx)
+        _check(self.lib.lbm_dscalar_upload(self.ctx, a.ctypes.data), "lbm_dscalar_upload")
+
     def force_record(self):
         """(F_x float64[steps_done], F_y float64[steps_done]): the force of every step since the upload; needs
         set_option("force", 1) before the first step."""
@@ -961,6 +1011,49 @@ class EnsembleDouble(_EnsembleOf):
         f = np.zeros((self.n, 2), dtype=np.float64)
         _check(self.lib.lbm_ddrive_ens_get(self.ens, ctypes.byref(on), f.ctypes.data), "lbm_ddrive_ens_get")
         return f
+
+    def _per_member(self, a, shape):
+        """`a` as a contiguous float64 array with a leading member axis: given with it, or broadcast over the members"""
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (self.n,) + shape))
+
+    def set_scalar(self, D, c0=0.0, wall=None, inlet=None):
+        """Passive scalars of all members (lbm_dscalar_ens_set): D one diffusivity for all or an array-like of n, every entry > 0;
+        c0 float64[n, ny, nx], wall float64[n, ny, nx] (NaN = insulating; None: all insulating) and inlet float64[n, ny] (None:
+        zeros) with the member axis or broadcast over it.  set_scalar(None) = off, the default.  Between runs at any step count."""
+        if D is None:
+            _check(self.lib.lbm_dscalar_ens_set(self.ens, None, None, None, None), "lbm_dscalar_ens_set")
+            return
+        d = self._per_member(D, ())
+        c = self._per_member(c0, (self.ny, self.nx))
+        w = None if wall is None else self._per_member(wall, (self.ny, self.nx))
+        i = None if inlet is None else self._per_member(inlet, (self.ny,))
+        _check(self.lib.lbm_dscalar_ens_set(self.ens, d.ctypes.data, c.ctypes.data, None if w is None else w.ctypes.data,
+                                            None if i is None else i.ctypes.data), "lbm_dscalar_ens_set")
+
+    def scalar(self):
+        """(D float64[n], omega_s float64[n]) while the scalars are on, None while they are off (lbm_dscalar_ens_get)"""
+        on = ctypes.c_int()
+        D, om = np.zeros(self.n, dtype=np.float64), np.zeros(self.n, dtype=np.float64)
+        _check(self.lib.lbm_dscalar_ens_get(self.ens, ctypes.byref(on), D.ctypes.data, om.ctypes.data), "lbm_dscalar_ens_get")
+        return (D, om) if on.value else None
+
+    def scalar_field(self):
+        """float64[n, ny, nx]: every member's scalar on its fluid cells, 0.0 on blocked cells (lbm_dscalar_ens_field)"""
+        c = np.zeros((self.n, self.ny, self.nx), dtype=np.float64)
+        _check(self.lib.lbm_dscalar_ens_field(self.ens, c.ctypes.data), "lbm_dscalar_ens_field")
+        return c
+
+    def scalar_cells(self):
+        """float64[n, 5, ny, nx]: every member's five populations (lbm_dscalar_ens_download)"""
+        g = np.zeros((self.n, 5, self.ny, self.nx), dtype=np.float64)
+        _check(self.lib.lbm_dscalar_ens_download(self.ens, g.ctypes.data), "lbm_dscalar_ens_download")
+        return g
+
+    def upload_scalar(self, g):
+        """every member's five populations, float64[n, 5, ny, nx] (lbm_dscalar_ens_upload); the scalars are on"""
+        a = np.ascontiguousarray(g, dtype=np.float64)
+        assert a.shape == (self.n, 5, self.ny, self.nx)
+        _check(self.lib.lbm_dscalar_ens_upload(self.ens, a.ctypes.data), "lbm_dscalar_ens_upload")
 
     def run_until(self, max_steps, window=64, rel_tol=1e-4, on="av_vels"):
         """_EnsembleOf.run_until with a choice of criterion: on="av_vels" (lbm_dsteady_run), or on="drag"

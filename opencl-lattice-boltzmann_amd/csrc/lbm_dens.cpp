@@ -84,6 +84,7 @@ struct lbm_dens {
   std::vector<double> les_c;       // [n]: every member's Smagorinsky constant, 0 while the setting is off
   bool drive = false;              // lbm_ddrive_ens_set: the kernels' DRIVE instances, for all members
   std::vector<double> drive_f;     // [n][2]: every member's force density, 0 while the setting is off
+  ScalarState scalar;              // lbm_dscalar_ens_set: the members' passive scalars (dp_host.h), off by default
   int nseg = 1, red_blocks = 1, fin_blocks = 1;
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
@@ -117,6 +118,7 @@ void free_dens(lbm_dens *e) {
   if (e->steady_inv) (void)hipFree(e->steady_inv);
   if (e->steady_count_host) (void)hipHostFree(e->steady_count_host);
   if (e->stage) (void)hipFree(e->stage);
+  scalar_free(e->scalar);
   queue_destroy(e->q);
   delete e;
 }
@@ -231,12 +233,22 @@ void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
   });
 }
 
+// the members' grids as the scalar's helpers take them (dp_host.h), and where the scalar reads the members' body forces
+ScalarGrid scalar_grid(const lbm_dens *e) { return ScalarGrid{e->n, e->nx, e->ny, e->plane_stride, e->member_stride}; }
+const double *scalar_drive(const lbm_dens *e) { return e->drive ? dens_drive_table(e->members, e->n, e->ny) : nullptr; }
+
 // nsteps steps from step count `first` on, enqueued: the prologue, the launches, the reductions into the record.  Flips
 // e->cur per launch; the caller counts the steps.  active: as launch_dens.
 int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   const size_t per_step = (size_t)e->ny * e->nseg, all_step = (size_t)e->n * per_step;
   const int nval = seg_values(e);
   const size_t slot = all_step * nval;   // one step in the ring: [nval][n][ny][nseg]
+  // with a scalar on every launch advances one step: the scalar reads each step's velocities (never during a steady run, which
+  // is refused while a scalar is on)
+  const bool scalar = e->scalar.on;
+  const ScalarGrid sgrid = scalar_grid(e);
+  if (scalar)
+    if (int rc = scalar_begin_run(e->scalar, sgrid, scalar_drive(e), 2ull)) return rc;
   // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
   // into the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
   if (!e->open) {
@@ -265,9 +277,12 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   while (i < nsteps) {
     // the remaining steps in as few launches as possible, of equal depth (8 steps at 3 a launch: 3 + 3 + 2)
     const int rem = nsteps - i;
-    const int adv = equal_depth(rem, kDensTMax);
+    const int adv = scalar ? 1 : equal_depth(rem, kDensTMax);
     if (e->ring_fill + adv > e->ring)
       if (int rc = flush()) return rc;
+    // scalar step n before flow step n, on the state that flow step streams
+    if (scalar)
+      if (int rc = scalar_step(e->scalar, sgrid, e->q.st, e->cells[e->cur], e->mask, e->open)) return rc;
     DensArgs a{};
     a.src = e->cells[e->cur];
     a.dst = e->cells[e->cur ^ 1];
@@ -290,6 +305,11 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
     i += adv;
   }
   return flush();
+}
+
+int refuse_steady_scalar(const char *what) {
+  return lbm_fail(LBM_ERR_ARG, "%s: the members carry a scalar (lbm_dscalar_ens_set): a member that stops would need a gated scalar "
+                  "kernel, which is out of scope; switch the scalar off for a steady run", what);
 }
 
 int refuse_ragged(const lbm_dens *e) {
@@ -559,6 +579,7 @@ int lbm_dsteady_run(lbm_dens *e, int max_steps, int window, double rel_tol) {
   // every argument error is reported before the ensemble or a device is touched
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
+  if (e->scalar.on) return refuse_steady_scalar("lbm_dsteady_run");
   bool launched = false;
   const int rc = steady_impl(e, max_steps, window, rel_tol, nullptr, &launched);
   return latch_failure(rc, launched, e->q.st, &e->failed);
@@ -675,6 +696,7 @@ int lbm_dbody_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol)
   // every argument error is reported before the ensemble or a device is touched
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
+  if (e->scalar.on) return refuse_steady_scalar("lbm_dbody_steady_run");
   if (!e->force)
     return lbm_fail(LBM_ERR_STATE, "the drag criterion reads the force record: option \"force\" is off (lbm_dforce_ens_set_option "
                     "switches it on before the first step)");
@@ -889,6 +911,61 @@ int lbm_ddrive_ens_get(const lbm_dens *e, int *on_out, double *f_out) {
   if (on_out) *on_out = e->drive ? 1 : 0;
   if (f_out) std::copy(e->drive_f.begin(), e->drive_f.end(), f_out);
   return LBM_OK;
+}
+
+int lbm_dscalar_ens_set(lbm_dens *e, const double *diffusivity, const double *c0, const double *c_wall, const double *c_in) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (diffusivity && !c0) return lbm_fail(LBM_ERR_ARG, "c0 is NULL (diffusivity is not: a scalar starts from a field)");
+  // every member is checked before anything changes, on the host or on the device
+  const ScalarGrid gr = scalar_grid(e);
+  if (diffusivity)
+    if (int rc = scalar_check(gr, true, diffusivity, c0, c_wall, c_in)) return rc;
+  if (diffusivity && e->ragged) return refuse_ragged(e);
+  if (int rc = queue_sync(e->q)) return rc;
+  if (!diffusivity) {
+    // the arrays stay until the ensemble goes; the handle runs as one that never had a scalar
+    e->scalar.on = false;
+    e->scalar.diffusivity.clear();
+    e->scalar.omega_s.clear();
+    return LBM_OK;
+  }
+  return scalar_set(e->scalar, gr, e->q.st, diffusivity, c0, c_wall, c_in, scalar_drive(e), 2ull);
+}
+
+int lbm_dscalar_ens_get(const lbm_dens *e, int *on_out, double *diffusivity_out, double *omega_s_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!on_out && !diffusivity_out && !omega_s_out)
+    return lbm_fail(LBM_ERR_ARG, "on_out, diffusivity_out and omega_s_out are all NULL");
+  if (on_out) *on_out = e->scalar.on ? 1 : 0;
+  for (int m = 0; m < e->n; m++) {
+    if (diffusivity_out) diffusivity_out[m] = e->scalar.on ? e->scalar.diffusivity[m] : 0.0;
+    if (omega_s_out) omega_s_out[m] = e->scalar.on ? e->scalar.omega_s[m] : 0.0;
+  }
+  return LBM_OK;
+}
+
+int lbm_dscalar_ens_field(lbm_dens *e, double *c_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!c_out) return lbm_fail(LBM_ERR_ARG, "c_out is NULL");
+  if (!e->scalar.on) return scalar_refuse_off("lbm_dscalar_ens_field");
+  if (int rc = queue_sync(e->q)) return rc;
+  return scalar_field(e->scalar, scalar_grid(e), e->q.st, e->mask, c_out);
+}
+
+int lbm_dscalar_ens_download(lbm_dens *e, double *g_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!g_out) return lbm_fail(LBM_ERR_ARG, "g_out is NULL");
+  if (!e->scalar.on) return scalar_refuse_off("lbm_dscalar_ens_download");
+  if (int rc = queue_sync(e->q)) return rc;
+  return scalar_download(e->scalar, scalar_grid(e), e->q.st, g_out);
+}
+
+int lbm_dscalar_ens_upload(lbm_dens *e, const double *g) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!g) return lbm_fail(LBM_ERR_ARG, "g is NULL");
+  if (!e->scalar.on) return scalar_refuse_off("lbm_dscalar_ens_upload");
+  if (int rc = queue_sync(e->q)) return rc;
+  return scalar_upload(e->scalar, scalar_grid(e), e->q.st, g);
 }
 
 void lbm_dens_destroy(lbm_dens *e) {

@@ -73,6 +73,7 @@ struct lbm_dp {
   double *wall_dev = nullptr;     // [2][ny][nx] (allocated by the first lbm_dwall_set that switches on)
   double les_c = 0.0;             // lbm_dles_set: 0 = off, > 0 = the LES instances with this Smagorinsky constant
   double drive[2] = {0.0, 0.0};   // lbm_ddrive_set: (0, 0) = off, else the DRIVE instances with this force density
+  ScalarState scalar;             // lbm_dscalar_set: the passive scalar (dp_host.h), off by default
   int cur = 0, steps_done = 0;
   bool failed = false;
 };
@@ -99,6 +100,7 @@ void free_dp(lbm_dp *d) {
   if (d->force_now) (void)hipFree(d->force_now);
   if (d->u_in_dev) (void)hipFree(d->u_in_dev);
   if (d->wall_dev) (void)hipFree(d->wall_dev);
+  scalar_free(d->scalar);
   queue_destroy(d->q);
   delete d;
 }
@@ -180,6 +182,9 @@ DpLes les_args(const lbm_dp *d) { return dp_les_constants(d->p.omega, d->les_c, 
 bool drive_on(const lbm_dp *d) { return dp_drive_on(d->drive[0], d->drive[1]); }
 const double *drive_dev(const lbm_dp *d) { return drive_on(d) ? reinterpret_cast<const double *>(d->members + 1) : nullptr; }
 
+// the grid as the scalar's helpers take it (dp_host.h): a context is one member
+ScalarGrid scalar_grid(const lbm_dp *d) { return ScalarGrid{1, d->p.nx, d->p.ny, d->plane_stride, 0}; }
+
 void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
   dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, drive_on(d),
                 [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
@@ -224,6 +229,11 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   const int nval = seg_values(d);
   const size_t slot = per_step * nval;   // one step in the ring: [nval][ny][nseg]
   const int T = multistep_effective(d);
+  // with a scalar on every launch advances one step, in the kernel form "multistep" chooses: the scalar reads each step's velocities
+  const bool scalar = d->scalar.on;
+  const ScalarGrid sgrid = scalar_grid(d);
+  if (scalar)
+    if (int rc = scalar_begin_run(d->scalar, sgrid, drive_dev(d), 0ull)) return rc;
   if (int rc = timed_begin(d->q, timed)) return rc;
   // prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53); later steps get theirs fused into
   // the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
@@ -252,9 +262,12 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   while (i < nsteps) {
     // the LDS-tile form: the remaining steps in as few launches as possible, of equal depth (20 steps at T = 8: 7 + 7 + 6)
     const int rem = nsteps - i;
-    const int adv = T > 0 ? equal_depth(rem, T) : 1;
+    const int adv = (T > 0 && !scalar) ? equal_depth(rem, T) : 1;
     if (d->ring_fill + adv > d->ring)
       if (int rc = flush()) return rc;
+    // scalar step n before flow step n, on the state that flow step streams
+    if (scalar)
+      if (int rc = scalar_step(d->scalar, sgrid, d->q.st, d->cells[d->cur], d->mask, d->open)) return rc;
     const bool accel_next = !d->open && i + adv < nsteps;
     double *seg = d->seg + (size_t)d->ring_fill * slot;
     if (T > 0) {
@@ -385,7 +398,7 @@ int lbm_dp_upload_obstacles(lbm_dp *d, const int32_t *obstacles) {
   // the body map, if one was set, described the old map's blocked cells: every blocked cell counts again
   if (int rc = upload_mask(d->mask, obstacles, (size_t)d->p.nx * d->p.ny)) return rc;
   body_reset(d->body, obstacles, (size_t)d->p.nx * d->p.ny);
-  // wall velocities stay as set: a kernel reads one only while its cell is blocked
+  // wall velocities stay as set: a kernel reads one only while its cell is blocked; so do the scalar's state and its c_wall
   // open boundaries stay on: the blocked cells of columns 0 and nx - 1 are outside every body
   if (d->open) return body_rewrite(d->body, d->mask, d->p.nx, true);
   return LBM_OK;
@@ -705,6 +718,60 @@ int lbm_ddrive_get(const lbm_dp *d, double *f_x_out, double *f_y_out) {
   if (f_x_out) *f_x_out = d->drive[0];
   if (f_y_out) *f_y_out = d->drive[1];
   return LBM_OK;
+}
+
+int lbm_dscalar_set(lbm_dp *d, double diffusivity, const double *c0, const double *c_wall, const double *c_in) {
+  // argument errors before anything of the context is read
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!std::isfinite(diffusivity) || diffusivity < 0.0)
+    return lbm_fail(LBM_ERR_ARG, "the diffusivity must be finite and positive, or 0 (off) (got %g)", diffusivity);
+  if (diffusivity > 0.0 && !c0) return lbm_fail(LBM_ERR_ARG, "c0 is NULL (the diffusivity is positive: a scalar starts from a field)");
+  const ScalarGrid gr = scalar_grid(d);
+  if (diffusivity > 0.0)
+    if (int rc = scalar_check(gr, false, &diffusivity, c0, c_wall, c_in)) return rc;
+  if (int rc = queue_sync(d->q)) return rc;
+  if (diffusivity == 0.0) {
+    // the arrays stay until the context goes; the handle runs as one that never had a scalar
+    d->scalar.on = false;
+    d->scalar.diffusivity.clear();
+    d->scalar.omega_s.clear();
+    return LBM_OK;
+  }
+  return scalar_set(d->scalar, gr, d->q.st, &diffusivity, c0, c_wall, c_in, drive_dev(d), 0ull);
+}
+
+int lbm_dscalar_get(const lbm_dp *d, int *on_out, double *diffusivity_out, double *omega_s_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!on_out && !diffusivity_out && !omega_s_out)
+    return lbm_fail(LBM_ERR_ARG, "on_out, diffusivity_out and omega_s_out are all NULL");
+  if (on_out) *on_out = d->scalar.on ? 1 : 0;
+  if (diffusivity_out) *diffusivity_out = d->scalar.on ? d->scalar.diffusivity[0] : 0.0;
+  if (omega_s_out) *omega_s_out = d->scalar.on ? d->scalar.omega_s[0] : 0.0;
+  return LBM_OK;
+}
+
+int lbm_dscalar_field(lbm_dp *d, double *c_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!c_out) return lbm_fail(LBM_ERR_ARG, "c_out is NULL");
+  if (!d->scalar.on) return scalar_refuse_off("lbm_dscalar_field");
+  if (int rc = queue_sync(d->q)) return rc;
+  return scalar_field(d->scalar, scalar_grid(d), d->q.st, d->mask, c_out);
+}
+
+int lbm_dscalar_download(lbm_dp *d, double *g_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!g_out) return lbm_fail(LBM_ERR_ARG, "g_out is NULL");
+  if (!d->scalar.on) return scalar_refuse_off("lbm_dscalar_download");
+  if (int rc = queue_sync(d->q)) return rc;
+  return scalar_download(d->scalar, scalar_grid(d), d->q.st, g_out);
+}
+
+int lbm_dscalar_upload(lbm_dp *d, const double *g) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!g) return lbm_fail(LBM_ERR_ARG, "g is NULL");
+  if (!d->scalar.on) return scalar_refuse_off("lbm_dscalar_upload");
+  if (int rc = queue_sync(d->q)) return rc;
+  return scalar_upload(d->scalar, scalar_grid(d), d->q.st, g);
 }
 
 void lbm_dp_destroy(lbm_dp *d) {
