@@ -12,6 +12,7 @@ import numpy as np
 import _open_ref
 import _trt_ref
 import _wall_ref
+from _force_ref import body_restatement
 
 THIRD = np.float64(1.0) / np.float64(3.0)
 HALF, ONE, TWO = np.float64(0.5), np.float64(1.0), np.float64(2.0)
@@ -90,25 +91,10 @@ def effective_omega(f, ob, omega, c, u_in=None, rho_out=None):
     return rates(gathered(f, ob, u_in, rho_out), omega, c)[1]
 
 
-def reference_step(oracle_f64, p, ob, body, f, trt_magic, open_setting, wall, c):
-    """_wall_ref.reference_step with the model: the same routing of the state and of the force, step() above in place of the
-    step it routes to"""
-    from test_body_gpu import body_restatement
-    from test_force_gpu import accelerated, restatement
-    if open_setting is not None:
-        u_in, rho_out = open_setting
-        cells, u = step(f, ob, p.omega, trt_magic, u_in, rho_out, wall, c)
-        force = _open_ref.force(f, ob, body)
-    else:
-        fa = accelerated(oracle_f64, p, ob, f)
-        cells, u = step(fa, ob, p.omega, trt_magic, wall=wall, c=c)
-        force = restatement(fa, ob) if body is None else body_restatement(fa, ob, body)
-    return cells, u, (force if np.any(ob) else None)
-
-
 # ---- the two flows of the tests -------------------------------------------------------------------------------------------
 
 COUETTE_C = 2.0     # |S| = U / H is tiny in the Couette case: a constant this large makes the eddy viscosity 12.9 % of the total
+GATE = 1e-4         # the Couette case's wall force and profile against the formula, on the CPU and on the GPU
 
 CAVITY = dict(nx=32, ny=32, U=0.1, rho=0.1, omega=1.99, c=0.17, steps=3000, bgk_limit=2000)
 
@@ -117,6 +103,24 @@ def couette_force(nx, ny, U, rho, omega, c):
     """rho (nu + c^2 U / H) U nx / H: a steady shear has |S| = U / H, so nu_t = c^2 U / H everywhere; nu = (1 / omega - 1 / 2) / 3"""
     h = float(ny - 2)
     return rho * ((1.0 / omega - 0.5) / 3.0 + c * c * U / h) * U * nx / h
+
+
+def couette_figures(before, f):
+    """(relative error of F_x on the top wall, on the bottom wall, the same against the molecular viscosity alone, profile error
+    over U) from the state the last step streamed and the settled state"""
+    c = _wall_ref.COUETTE
+    ob, _, _ = _wall_ref.couette_maps()
+    want = couette_force(c["nx"], c["ny"], c["U"], c["rho"], c["omega"], COUETTE_C)
+    plain = _wall_ref.couette_force(c["nx"], c["ny"], c["U"], c["rho"], c["omega"])
+    rel = []
+    for row, sign in ((c["ny"] - 1, -1.0), (0, +1.0)):
+        body = np.zeros_like(ob)
+        body[row] = 1
+        fx, _, links, _ = body_restatement(before, ob, body)
+        assert links == 3 * c["nx"]
+        rel.append((abs(fx - sign * want) / want, abs(fx - sign * plain) / plain))
+    err = float(np.max(np.abs(_wall_ref.column_velocity(f, c["nx"] // 2) - _wall_ref.couette_profile(c["ny"], c["U"])))) / c["U"]
+    return rel[0][0], rel[1][0], min(rel[0][1], rel[1][1]), err
 
 
 def cavity_maps(nx=CAVITY["nx"], ny=CAVITY["ny"], U=CAVITY["U"]):

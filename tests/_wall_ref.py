@@ -6,8 +6,8 @@ statements on the blocked cells that move.  After that step a blocked cell holds
 so `out[1] = g[3] + a` is cells[1] + a there: one ufunc per written operator, np.where on the moving cells.  With no cell
 moving (no setting, or every velocity +-0.0 on the blocked cells) the arrays of _open_ref.step are returned untouched.
 
-The force needs no restatement of its own: _open_ref.force, test_force_gpu.restatement and test_body_gpu.body_restatement read
-the stored state, which already carries what the wall added."""
+The force needs no restatement of its own: _open_ref.force, _force_ref.restatement and _force_ref.body_restatement read the
+stored state, which already carries what the wall added."""
 import numpy as np
 
 import _open_ref
@@ -64,23 +64,6 @@ def step(f, ob, omega, omega_m=None, u_in=None, rho_out=None, wall=None):
     return apply(cells, ob, wall), u
 
 
-def reference_step(oracle_f64, p, ob, body, f, trt_magic, open_setting, wall):
-    """_dp_matrix.reference_step with walls moving: the same routing of the state and of the force, step() above in place of
-    the step it routes to"""
-    from test_body_gpu import body_restatement
-    from test_force_gpu import accelerated, restatement
-    om = _trt_ref.omega_minus(p.omega, trt_magic) if trt_magic else None
-    if open_setting is not None:
-        u_in, rho_out = open_setting
-        cells, u = step(f, ob, p.omega, om, u_in, rho_out, wall)
-        force = _open_ref.force(f, ob, body)
-    else:
-        fa = accelerated(oracle_f64, p, ob, f)
-        cells, u = step(fa, ob, p.omega, om, wall=wall)
-        force = restatement(fa, ob) if body is None else body_restatement(fa, ob, body)
-    return cells, u, (force if np.any(ob) else None)
-
-
 # ---- the Couette case of the tests: 16 x 16, walls on rows 0 and ny - 1, the top wall moving ----------------------------------
 
 COUETTE = dict(nx=16, ny=16, U=0.05, rho=0.1, omega=1.2, steps=6000, magic=3.0 / 16.0)
@@ -112,3 +95,22 @@ def column_velocity(f, x):
 def couette_force(nx, ny, U, rho, omega):
     """rho nu U nx / H, the shear force on either wall of the settled flow; nu = (1 / omega - 1 / 2) / 3"""
     return rho * ((1.0 / omega - 0.5) / 3.0) * U * nx / float(ny - 2)
+
+
+_couette = {}
+
+
+def couette_run(trt):
+    """the settled state of the Couette case and the state one step before it (what the last step streamed), once per
+    operator"""
+    if trt not in _couette:
+        c = COUETTE
+        ob, u_x, u_y = couette_maps()
+        om = _trt_ref.omega_minus(c["omega"], c["magic"]) if trt else None
+        f = _open_ref.rest_state(c["rho"], c["ny"], c["nx"])
+        before = f
+        for _ in range(c["steps"]):
+            before = f
+            f, u = step(f, ob, c["omega"], om, wall=(u_x, u_y, c["rho"]))
+        _couette[trt] = (before, f, u)
+    return _couette[trt]

@@ -29,6 +29,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import _drive_ref as ref  # noqa: E402
 import _open_ref  # noqa: E402
+from _force_ref import restatement  # noqa: E402
 
 BGK_OMEGAS = (0.6, 1.0, 1.7)
 
@@ -49,7 +50,6 @@ def hydrostatic_entry(omega, magic, steps=ref.HYDROSTATIC["steps"]):
 
 def balance_entry(omega, magic, sign=1.0, steps=ref.BALANCE["steps"]):
     """the force record's last entry: the force of the step that streams the state after steps - 1 steps"""
-    from test_force_gpu import restatement
     ob = ref.balance_mask()
     drive = (sign * ref.BALANCE["force"][0], 0.0)
     fx, fy = restatement(ref.run(ob, omega, magic, drive, steps - 1), ob)[:2]

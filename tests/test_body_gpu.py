@@ -1,14 +1,14 @@
 """Drag of a body on the GPU: the force on chosen blocked cells (lbm_dbody_*, LBMDouble / EnsembleDouble .set_body() and
 .body()) and steady runs that stop each member on its body's drag (run_until(on="drag")).
 
-The reference value is `body_restatement` below: test_force_gpu.restatement with `counted &= body`, on states downloaded from
-the GPU and accelerated with the fp64 oracle's accelerate_flow.  Gates:
+The reference value is tests/_force_ref.py's `body_restatement`: its `restatement` with `counted &= body`, on states downloaded
+from the GPU and accelerated with the fp64 oracle's accelerate_flow.  Gates:
   1. record against the restatement, per component 8 L 2^-53 sum|link terms| with L and the sum over the BODY's links (the
      gate of test_force_gpu, derived there: four times the bound between two summation orders of the same terms);
   2. additivity of two disjoint bodies on one state: the same gate over all links;
   3. - 6. bit identity (np.array_equal), stop counts and error codes: no tolerance.
 Shapes 16x16, 33x19, 48x35 and 3x3 at multistep 0, 3 and 8: a wrap in x and y, rows ny-1 .. ny-3, a tile seam at 15 | 16, a row
-shorter than a segment and a lone cell.  Bodies per shape, on test_force_gpu.force_mask:
+shorter than a segment and a lone cell.  Bodies per shape, on _force_ref.force_mask:
   a  the cells of the 4x5 block (on 3x3: the lone blocked cell, which is then every blocked cell)
   b  the other blocked cells
   c  every blocked cell
@@ -20,8 +20,8 @@ a plain EnsembleDouble run to the cap."""
 import numpy as np
 import pytest
 
-from test_dp_steady_gpu import OMEGAS, TOL, channel, rule, sweep
-from test_force_gpu import CX, CY, OPP, SHAPES, U, accelerated, case, force_mask, restatement, single_steps
+from _force_ref import SHAPES, U, accelerated, block_body, body_restatement, case, force_mask, restatement, single_steps
+from _steady_rule import OMEGAS, TOL, rule, sweep
 
 pytestmark = pytest.mark.gpu
 
@@ -72,24 +72,6 @@ def bodies(nx, ny):
     assert not np.any(out["a"] & out["b"]) and np.array_equal(out["a"] | out["b"], out["c"])
     assert np.count_nonzero(out["a"]) > 0 and not np.any(out["d"])
     return out
-
-
-def body_restatement(f, ob, body):
-    """test_force_gpu.restatement with the outer sum over the blocked cells of the body only: counted &= body"""
-    assert f.dtype == np.float64
-    blocked = ob != 0
-    fx = fy = 0.0
-    links, mag = 0, 0.0
-    for k in range(1, 9):
-        shift = (CY[k], CX[k])
-        counted = blocked & np.roll(~blocked, shift, axis=(0, 1))
-        counted &= body != 0
-        term = (np.roll(f[k], shift, axis=(0, 1)) + f[OPP[k]])[counted]
-        fx += CX[k] * float(np.sum(term))
-        fy += CY[k] * float(np.sum(term))
-        links += int(term.size)
-        mag += float(np.sum(np.abs(term)))
-    return fx, fy, links, mag
 
 
 @pytest.fixture(scope="module")
@@ -391,14 +373,6 @@ def test_state_rules(lbm):
 
 
 # ---- 6. drag criterion -------------------------------------------------------------------------------------------------
-
-def block_body(nx, ny):
-    """the 4x4 block of test_dp_steady_gpu.channel, without the walls"""
-    body = np.zeros((ny, nx), dtype=np.int32)
-    body[ny // 2 - 2:ny // 2 + 2, nx // 4:nx // 4 + 4] = 1
-    ob = channel(nx, ny)
-    assert np.count_nonzero(body) == 16 and not np.any(body & (ob == 0)) and np.count_nonzero(ob) == 16 + 2 * nx
-    return body
 
 
 def drag_ensemble(lbm, nx, ny, body):

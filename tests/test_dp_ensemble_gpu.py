@@ -13,36 +13,18 @@ import numpy as np
 import pytest
 
 from conftest import golden_cols, input_files
-from test_dp_gpu import FULL, PRINT_PRECISION_PCNT, RE_REL, VEL_ABS, max_pcnt, random_state, reynolds_ref
+from _dp_states import (CASES, CHECKPOINTS, FULL, PRINT_PRECISION_PCNT, RE_REL, RUNS, VEL_ABS, make_members, max_pcnt,
+                        reynolds_ref)
 
 pytestmark = pytest.mark.gpu
 
 LBM_ERR_STATE = 3
-CHECKPOINTS = [1, 2, 11, 1000]
-# runs between the checkpoints: 1, 1, 9, then 2..8 (with at most 8 steps a launch: one launch of every depth; with fewer,
-# every depth up to that and two-launch splits), 20 (7 + 7 + 6) and the tail
-RUNS = [1, 1, 9, 2, 3, 4, 5, 6, 7, 8, 20, 1000 - 11 - 35 - 20]
-assert sum(RUNS) == CHECKPOINTS[-1]
 
 
 def same(a, b):
     """bit-identical values; a NaN in both at the same place (av_vels and Reynolds number of a member without a free cell:
     0 * inf) counts equal, as in max_abs of test_dp_gpu.py"""
     return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
-
-
-def make_members(lbm, nx, ny, n, seed, max_iters=CHECKPOINTS[-1], masks=None):
-    """n members that differ in omega, accel, density, obstacle map and initial state"""
-    rng = np.random.default_rng(seed)
-    params, obs, cells = [], [], []
-    for k in range(n):
-        ob = masks[k] if masks is not None else (rng.random((ny, nx)) < 0.05 + 0.03 * k).astype(np.int32)
-        density = 0.1 * (1.0 + 0.05 * k)
-        params.append(lbm.make_dparams(nx, ny, max_iters, density=density, accel=0.005 * (1.0 + 0.2 * k),
-                                       omega=1.0 + 0.85 * (k + 1) / n, obstacles=ob))
-        obs.append(ob)
-        cells.append(random_state(rng, density, ny, nx))
-    return params, np.stack(obs), np.stack(cells)
 
 
 def snapshot(sim):
@@ -77,32 +59,6 @@ def assert_member_equals(ens_snap, k, ref_snap, what):
 
 
 # ---- 1. members equal double-precision contexts, bit for bit -----------------------------------------------------------
-
-def blocked_and_free_masks(nx, ny):
-    rng = np.random.default_rng(99)
-    ordinary = [(rng.random((ny, nx)) < 0.1).astype(np.int32) for _ in range(2)]
-    return [ordinary[0], np.ones((ny, nx), dtype=np.int32), np.zeros((ny, nx), dtype=np.int32), ordinary[1]]
-
-
-def one_blocked_cell(n):
-    """3x3: member k has cell k blocked (without any obstacle nothing opposes the acceleration on nine cells)"""
-    masks = []
-    for k in range(n):
-        m = np.zeros(9, dtype=np.int32)
-        m[k] = 1
-        masks.append(m.reshape(3, 3))
-    return masks
-
-
-CASES = {
-    "128x128": (128, 128, 5, None),
-    "128x256": (128, 256, 3, None),
-    "256x256": (256, 256, 3, None),
-    "ragged 100x37": (100, 37, 4, None),
-    "3x3": (3, 3, 3, one_blocked_cell(3)),
-    "near the bound 1024x300": (1024, 300, 2, None),
-    "all-blocked and all-free members 64x48": (64, 48, 4, blocked_and_free_masks(64, 48)),
-}
 
 
 @pytest.mark.parametrize("name", list(CASES))

@@ -22,25 +22,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from _dp_states import (FULL, LDS, MASS_REL, ORACLE_FORMS_FACTOR, PRESSURE_ABS_256, PRINT_PRECISION_PCNT, RE_REL, VEL_ABS, gpu_track,
+                        max_abs, max_pcnt, oracle_params, oracle_track, random_state, reynolds_ref)
 from conftest import GOLDEN, ROOT, golden_cols, golden_path, input_files
 
 pytestmark = pytest.mark.gpu
-
-PRINT_PRECISION_PCNT = 1e-8       # % (tests/test_oracle_golden.py): the golden files carry 13 significant digits
-VEL_ABS = 1e-12                   # u_x, u_y, u: 9x the 1.1e-13 the oracle's forms differ by
-PRESSURE_ABS_256 = 1e-12
-RE_REL = 1e-10                    # the oracle's forms: <= 8e-13
-ORACLE_FORMS_FACTOR = 4.0         # section 3: gate = 4x the largest difference between the oracle's two fp64 forms
-MASS_REL = 1e-12                  # the fp64 oracle alone, 256x256 after 1000 steps: 1.8e-13
-LDS = 8                           # "multistep" of the LDS-tile form
-W = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4, dtype=np.float64).reshape(9, 1, 1)
-
-FULL = {"128x128": 40000, "128x256": 40000, "256x256": 80000, "1024x1024": 20000}
-
-
-def max_pcnt(ref, sim):
-    diff = ref - sim
-    return float(np.max(np.abs(100.0 * diff / (ref - diff))))
 
 
 # ---- the oracle's second fp64 form ---------------------------------------------------------------------------------
@@ -67,48 +53,6 @@ def oracle_fma(oracle_f64_omp, tmp_path_factory):
     return o
 
 
-def oracle_params(orc, p):
-    q = orc.Params()
-    q.nx, q.ny, q.max_iters, q.reynolds_dim = p.nx, p.ny, p.max_iters, p.reynolds_dim
-    q.density, q.accel, q.omega, q.free_cells_inv = p.density, p.accel, p.omega, p.free_cells_inv
-    return q
-
-
-def oracle_track(orc, p, ob, cells0, checkpoints):
-    """the oracle's cells and av_vels at each checkpoint (cumulative steps)"""
-    q = oracle_params(orc, p)
-    cells = np.array(cells0, dtype=np.float64, copy=True)
-    av_all, out, done = [], [], 0
-    with np.errstate(invalid="ignore"):
-        for n in checkpoints:
-            av_all.append(orc.run(q, cells, ob, n - done))
-            done = n
-            out.append((cells.copy(), np.concatenate(av_all)))
-    return out
-
-
-def gpu_track(lbm, p, ob, cells0, checkpoints, multistep):
-    out, done = [], 0
-    with lbm.LBMDouble(p, ob) as sim:
-        sim.set_option("multistep", multistep)
-        sim.upload(cells0)
-        for n in checkpoints:
-            sim.run(n - done)
-            done = n
-            c, av = sim.download()
-            out.append((c, av))
-    return out
-
-
-def max_abs(a, b):
-    """max |a - b|; a NaN in both at the same place (av_vels of a grid without a free cell: 0 * inf) counts 0"""
-    a, b = np.asarray(a), np.asarray(b)
-    na, nb = np.isnan(a), np.isnan(b)
-    if not np.array_equal(na, nb):
-        return math.inf
-    return float(np.max(np.abs(a[~na] - b[~nb]), initial=0.0))
-
-
 # ---- 1. golden data at full length ---------------------------------------------------------------------------------
 
 def full_run(lbm, size):
@@ -121,15 +65,6 @@ def full_run(lbm, size):
         fields = sim.final_state()
         re = sim.reynolds()
     return p, ob, av, fields, re
-
-
-def reynolds_ref(size):
-    with open(os.path.join(GOLDEN, "transcripts.json")) as f:
-        tr = json.load(f)
-    if size in tr["reynolds"]:
-        return tr["reynolds"][size]
-    with open(os.path.join(GOLDEN, "generated", "oracle_f64_scalars.json")) as f:
-        return json.load(f)[size]["reynolds"]
 
 
 @pytest.mark.parametrize("size", ["128x128", "128x256"])
@@ -215,10 +150,6 @@ def test_run_double_tool_writes_the_reference_files(tmp_path):
 # ---- 3. against the fp64 oracle --------------------------------------------------------------------------------------
 
 CHECKPOINTS = [1, 2, 11, 1000]
-
-
-def random_state(rng, density, ny, nx):
-    return W * density * (1.0 + 0.2 * (rng.random((9, ny, nx)) - 0.5))
 
 
 def make_case(lbm, name):

@@ -19,11 +19,15 @@ import pytest
 
 import _dp_matrix as dm
 import _open_ref
-from test_dp_gpu import oracle_params
-from test_trt_restatement_cpu import oracle_nofma  # noqa: F401  (a fixture)
+from _dp_states import build_oracle_nofma, oracle_params
 
 SHAPES = [(33, 19), (17, 16), (48, 35)]
 STEADY_SHAPE = (48, 32)
+
+
+@pytest.fixture(scope="module")
+def oracle_nofma(tmp_path_factory):
+    return build_oracle_nofma(tmp_path_factory)
 
 
 @pytest.fixture(scope="module")

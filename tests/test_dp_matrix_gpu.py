@@ -3,8 +3,9 @@
 FORCE (option "force"), TRT (set_trt) and OPEN (set_open) are template flags of d2q9_dp_step, d2q9_dp_multi (LBMDouble at
 "multistep" 0 and 8), d2q9_dp_ensemble (EnsembleDouble.run) and d2q9_dp_ensemble_gated (EnsembleDouble.run_until): 32
 separately compiled kernels, chosen by launch_step / launch_multi (lbm_dp.cpp) and launch_dens (lbm_dens.cpp).  The reference
-is tests/_dp_matrix.reference_step, which only routes a state to tests/_open_ref.py, tests/_trt_ref.py, test_force_gpu.restatement
-and test_body_gpu.body_restatement; tests/test_dp_matrix_cpu.py holds the inputs to what these comparisons need of them.
+is tests/_dp_matrix.reference_step, which only routes a state to tests/_open_ref.py, tests/_trt_ref.py (through the steps of the
+options that are off here) and tests/_force_ref.py's restatement and body_restatement; tests/test_dp_matrix_cpu.py holds the
+inputs to what these comparisons need of them.  The cases, the drivers, the gates and the cache (dm.Once) are tests/_dp_matrix.py's.
 
 Gates, all taken from the suite as it stands:
   cells after every run            np.array_equal with the reference applied that many times
@@ -40,94 +41,29 @@ named where it is the first test to launch the instance, and it launches every o
 Seven instances had no launch before this module.  Two that were suspected of none had one: d2q9_dp_ensemble<0,1,0> runs two
 steps in test_trt_gpu.test_errors_and_what_keeps_the_setting, and d2q9_dp_ensemble_gated<1,1,0> runs under both criteria in
 test_trt_gpu.test_run_until_stops_every_member_where_the_rule_says."""
-import itertools
-
 import numpy as np
 import pytest
 
 import _dp_matrix as dm
 import _open_ref
-from test_dp_steady_gpu import CAP, OMEGAS, TOL, rule
+from _dp_matrix import assert_equals_the_reference, assert_same_bits, plus_zero
+from _steady_rule import CAP, OMEGAS, TOL, rule
 
 pytestmark = pytest.mark.gpu
 
 U = dm.U
-SHAPES = [(33, 19), (17, 16)]
+SHAPES = dm.SHAPES
 BODY_SHAPES = SHAPES + [(48, 35)]
-RUNS = [1, 1, 1, 7]
-FLAGS = list(itertools.product((0, 1), repeat=3))
-_refs, _runs = {}, {}
+RUNS = dm.RUNS
+FLAGS = dm.flags(3)
+once = dm.Once()
+reference_of, run_of, _runs = once.reference_of, once.run_of, once.runs
 
 
 @pytest.fixture(scope="module")
 def oracle_f64():
     from oracle.oracle import Oracle
     return Oracle("f64")
-
-
-def reference_of(oracle_f64, key, case, steps):
-    """the chained reference of every member, computed once per key; the force tuples are those of the case's bodies"""
-    if key not in _refs:
-        _refs[key] = [dm.reference_run(oracle_f64, m, steps) for m in case.members]
-    return _refs[key]
-
-
-def run_of(lbm, key, family, case, runs):
-    if (family,) + key not in _runs:
-        _runs[(family,) + key] = dm.drive(lbm, family, case, runs)
-    return _runs[(family,) + key]
-
-
-def plus_zero(v):
-    v = np.asarray(v)
-    return bool(np.all(v == 0.0) and not np.any(np.signbit(v)))
-
-
-def assert_equals_the_reference(case, refs, results, runs, what):
-    nx, ny = case.nx, case.ny
-    for k, (m, ref, got) in enumerate(zip(case.members, refs, results)):
-        steps = sum(runs)
-        assert got.av.shape == (steps,) and len(got.states) == len(runs)
-        done, worst_av, worst_f = 0, 0.0, 0.0
-        for i, r in enumerate(runs):
-            done += r
-            differs = int(np.count_nonzero(got.states[i] != ref.states[done]))
-            assert np.array_equal(got.states[i], ref.states[done]), (what, k, done, differs)
-        for t in range(steps):
-            total = ref.totals[t]
-            err, tol = abs(got.av[t] - total * m.p.free_cells_inv), nx * ny * U * total
-            worst_av = max(worst_av, err / tol)
-            assert total > 0.0 and err <= tol, (what, k, t, got.av[t], total * m.p.free_cells_inv, tol)
-            if not case.force:
-                continue
-            if ref.forces[t] is None:
-                assert plus_zero(got.fx[t]) and plus_zero(got.fy[t]), (what, k, t)
-                continue
-            rx, ry, links, mag = ref.forces[t]
-            ftol = 8.0 * links * U * mag
-            worst_f = max(worst_f, abs(got.fx[t] - rx) / ftol, abs(got.fy[t] - ry) / ftol)
-            assert abs(got.fx[t] - rx) <= ftol and abs(got.fy[t] - ry) <= ftol, (what, k, t, got.fx[t], rx, got.fy[t], ry, ftol)
-            assert links > 0 and mag > 0.0 and max(abs(got.fx[t]), abs(got.fy[t])) > 1e-5
-        for i, r in enumerate(runs):
-            if case.force:
-                # the output stage: force() of the state before a run equals the entry the run's first step writes
-                first = sum(runs[:i])
-                assert got.now[i] == (got.fx[first], got.fy[first]), (what, k, first)
-        print("%s member %d: cells equal after runs of %s steps; av_vels within %.1e of its gate, force within %.1e of its gate" %
-              (what, k, runs, worst_av, worst_f))
-
-
-def assert_same_bits(a, b, what):
-    """two results of one case, member by member: states, av_vels, force() and, where both have it, the record"""
-    assert len(a) == len(b)
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert all(np.array_equal(s, t) for s, t in zip(x.states, y.states)), (what, k)
-        assert np.array_equal(x.av, y.av), (what, k)
-        assert x.now == y.now, (what, k)
-        assert all(np.signbit(u) == np.signbit(v) for p, q in zip(x.now, y.now) for u, v in zip(p, q)), (what, k)
-        if x.fx is not None and y.fx is not None:
-            assert np.array_equal(x.fx, y.fx) and np.array_equal(x.fy, y.fy), (what, k)
-            assert np.array_equal(np.signbit(x.fx), np.signbit(y.fx)) and np.array_equal(np.signbit(x.fy), np.signbit(y.fy)), (what, k)
 
 
 # ---- 1. the instance matrix --------------------------------------------------------------------------------------------

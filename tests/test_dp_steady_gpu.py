@@ -17,30 +17,16 @@ threshold is 1.7e-4 of rel_tol against rounding differences of order 1e-16, so t
 import numpy as np
 import pytest
 
+from _steady_rule import CAP, OMEGAS, TOL, channel, rule, sweep
+
 pytestmark = pytest.mark.gpu
 
 LBM_ERR_STATE = 3
-TOL, CAP = 2e-2, 400
-OMEGAS = {4: (0.6, 1.0, 1.4, 1.7), 24: tuple(float(v) for v in np.linspace(0.6, 1.7, 24))}
 # (nx, ny, window, max_steps) -> the 4-member stops on the fp64 oracle
 STOPS = {(48, 32, 7, 400): [119, 168, 196, 210], (48, 32, 16, 400): [208, 304, 400, 400], (48, 32, 20, 400): [220, 340, 400, 400],
          (48, 32, 7, 200): [119, 168, 196, 200], (37, 29, 7, 400): [112, 161, 196, 210], (37, 29, 16, 400): [176, 272, 368, 400],
          (37, 29, 20, 400): [200, 300, 400, 400], (37, 29, 7, 200): [112, 161, 196, 200]}
 _cache = {}
-
-
-def channel(nx, ny):
-    """rows 0 and ny-1 blocked plus a 4x4 block"""
-    ob = np.zeros((ny, nx), dtype=np.int32)
-    ob[0] = ob[ny - 1] = 1
-    ob[ny // 2 - 2:ny // 2 + 2, nx // 4:nx // 4 + 4] = 1
-    return ob
-
-
-def sweep(lbm, nx, ny, omegas, max_iters=CAP):
-    ob = channel(nx, ny)
-    base = lbm.make_dparams(nx, ny, max_iters, density=0.1, accel=0.005, omega=omegas[0], obstacles=ob)
-    return lbm.sweep_dparams(base, omega=list(omegas)), ob
 
 
 def members(lbm, nx, ny, omegas, ob=None, inv=None):
@@ -49,24 +35,6 @@ def members(lbm, nx, ny, omegas, ob=None, inv=None):
     for m, v in (inv or {}).items():
         params[m].free_cells_inv = v
     return params, (ob0 if ob is None else ob)
-
-
-def rule(av, s0, max_steps, window, rel_tol):
-    """the header's criterion on a downloaded record av float64[n, >= s0 + max_steps]: (steps, converged)"""
-    assert av.dtype == np.float64
-    n = av.shape[0]
-    steps, conv = np.full(n, s0 + max_steps, dtype=np.int32), np.zeros(n, dtype=bool)
-    for m in range(n):
-        for s in range(s0 + window, s0 + max_steps + 1, window):
-            if s - window < 1:
-                continue
-            a_now, a_then = av[m, s - 1], av[m, s - window - 1]
-            diff = np.abs(a_now - a_then)
-            bound = np.float64(rel_tol) * np.abs(a_now)
-            if diff <= bound:   # False for a NaN on either side
-                steps[m], conv[m] = s, True
-                break
-    return steps, conv
 
 
 def snapshot(sim):

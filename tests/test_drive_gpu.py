@@ -3,9 +3,9 @@ families against tests/_drive_ref.py, and the three force-driven flows with exac
 
 DRIVE is a sixth template flag beside FORCE, TRT, OPEN, WALL and LES of d2q9_dp_step, d2q9_dp_multi (LBMDouble at "multistep" 0
 and 8), d2q9_dp_ensemble (EnsembleDouble.run) and d2q9_dp_ensemble_gated (EnsembleDouble.run_until): 128 more separately
-compiled kernels.  The cases, the drivers and the gates are those of tests/_dp_matrix.py, tests/test_dp_matrix_gpu.py,
-tests/test_wall_gpu.py and tests/test_les_gpu.py, imported and not edited; `driven` hands the drivers an LBMDouble /
-EnsembleDouble that has had set_drive called on it, behind test_les_gpu.lesed, which calls set_les and set_wall.
+compiled kernels.  The cases (make_case with `wall`, `les` and `drive`), the drivers, the gates and the bodies of the tests that
+every option repeats are tests/_dp_matrix.py's; its open_context and open_ensemble call set_wall, set_les and then set_drive on a
+handle before anything else happens to it.  The fixture and the gates of the three flows are tests/_drive_ref.py's.
 
   1. the matrix: the 32 FORCE x TRT x OPEN x WALL x LES combinations x the 4 families x 33x19 and 17x16, three members each with
      its own force (both components non-zero, mixed signs, 1e-6 to 1e-4), runs of 1, 1, 1 and 7 steps.  Compared with _drive_ref:
@@ -19,7 +19,7 @@ EnsembleDouble that has had set_drive called on it, behind test_les_gpu.lesed, w
      by run_until on "av_vels" and on "drag" against a plain run to its count (37x29, four members, four forces);
   5. the reported velocity: the fields of final_state equal _drive_ref.fields bit for bit, and av_vels of a step is the mean |u|
      of the state behind it under the matrix's bound; errors and what keeps the setting;
-  6. the three flows of tests/test_drive_restatement_cpu.py end to end under that module's gates, the figures held to the fixture's
+  6. the three flows of tests/test_drive_restatement_cpu.py end to end under _drive_ref's gates, the figures held to the fixture's
      to 1e-9 relative, the cells after the first 200 steps to 200 restated steps;
   7. a sweep to steady state: eight members, F_x = 1e-7 .. 8e-7, run_until on "av_vels": every member converges and av_vels / F_x
      is one constant.
@@ -29,28 +29,20 @@ asked for, and bits hold: on an MI355X the cells of all 256 matrix cases, of the
 restatement by np.array_equal after every run, and no looser bound is in this module.  The flows of 6 give the fixture's figures
 to the digit (deviation 1.462e-12 / 7.082e-13 / 8.729e-13 at Lambda 3/16, 4.115e-03 at 1/4, max |u| 3.93e-16 in the box, sum F_x
 5.92e-04 to 1.1e-14), the sweep stops every member at 512 steps with a spread of 4.68e-08.  295 cases, 5.4 s."""
-import itertools
-from types import SimpleNamespace
-
 import numpy as np
 import pytest
 
 import _dp_matrix as dm
 import _drive_ref as ref
-import test_drive_restatement_cpu as cpu
-from test_dp_matrix_gpu import assert_equals_the_reference, assert_same_bits
-from test_dp_steady_gpu import TOL, channel, rule
-from test_les_gpu import lesed, with_les
-from test_wall_gpu import narrow_case
+from _dp_matrix import FORCES
 
 pytestmark = pytest.mark.gpu
 
 U = dm.U
-SHAPES = [(33, 19), (17, 16)]
-RUNS = [1, 1, 1, 7]
-FLAGS = list(itertools.product((0, 1), repeat=5))
-FORCES = [(1e-6, -3e-5), (-1e-4, 2e-6), (4e-5, 1e-5), (-2e-5, -6e-6)]
-_refs, _runs = {}, {}
+SHAPES = dm.SHAPES
+RUNS = dm.RUNS
+FLAGS = dm.flags(5)
+once = dm.Once()
 
 
 @pytest.fixture(scope="module")
@@ -61,78 +53,14 @@ def oracle_f64():
 
 @pytest.fixture(scope="module")
 def fix():
-    return cpu.fixture()
-
-
-def driven(lbm, case):
-    """`lbm` as the drivers of _dp_matrix use it: the handles of test_les_gpu.lesed, which then call set_drive with the members'
-    `drive` (None: never called; "off": set to the member's drive_on, then turned off)"""
-    inner = lesed(lbm, case)
-
-    def set_on(handle, members, one):
-        mode = members[0].drive
-        if mode is None:
-            return handle
-        fs = [m.drive_on if mode == "off" else m.drive for m in members]
-        handle.set_drive(fs[0] if one else fs)
-        assert np.array_equal(np.atleast_2d(handle.drive()), fs)
-        if mode == "off":
-            handle.set_drive((0.0, 0.0) if one else None)
-            assert not np.any(handle.drive())
-        return handle
-
-    def context(p, ob):
-        return set_on(inner.LBMDouble(p, ob), [next(m for m in case.members if m.p is p)], True)
-
-    def ensemble(params, obs):
-        return set_on(inner.EnsembleDouble(params, obs), case.members, False)
-
-    return SimpleNamespace(LBMDouble=context, EnsembleDouble=ensemble)
-
-
-def with_drive(case, mode="on", wall=False, les=False):
-    """the case with a force per member (mode "on": FORCES; None: never set; "off": set and turned off), the velocities of
-    test_wall_gpu.member_wall (wall) and the constants of test_les_gpu.CS (les), else those never set"""
-    with_les(case, "on" if les else None, wall)
-    for k, m in enumerate(case.members):
-        m.drive_on = FORCES[k]
-        m.drive = FORCES[k] if mode == "on" else mode
-    return case
-
-
-def reference_run(oracle_f64, m, steps):
-    """_dp_matrix.reference_run through _drive_ref.reference_step"""
-    wall = m.wall if isinstance(m.wall, tuple) else None
-    c = m.les if isinstance(m.les, float) else None
-    drive = m.drive if isinstance(m.drive, tuple) else None
-    states, totals, forces = [m.cells0], [], []
-    for _ in range(steps):
-        cells, u, force = ref.reference_step(oracle_f64, m.p, m.ob, m.body, states[-1], m.magic, m.open, wall, c, drive)
-        states.append(cells)
-        totals.append(float(np.sum(u)))
-        forces.append(force)
-    return SimpleNamespace(states=states, totals=totals, forces=forces)
-
-
-def reference_of(oracle_f64, key, case, steps):
-    if key not in _refs:
-        _refs[key] = [reference_run(oracle_f64, m, steps) for m in case.members]
-    return _refs[key]
-
-
-def run_of(lbm, key, family, case, runs):
-    if (family,) + key not in _runs:
-        if isinstance(family, int):
-            _runs[(family,) + key] = dm.drive_context(driven(lbm, case), case, runs, family)     # LBMDouble at that "multistep"
-        else:
-            _runs[(family,) + key] = dm.drive(driven(lbm, case), family, case, runs)
-    return _runs[(family,) + key]
+    return ref.fixture()
 
 
 # ---- 1. the instance matrix --------------------------------------------------------------------------------------------
 
 def matrix_case(lbm, nx, ny, force, trt, opened, wall, les, mode="on"):
-    return with_drive(dm.make_case(lbm, nx, ny, 3, sum(RUNS), force, trt, opened), mode, wall, les)
+    return dm.make_case(lbm, nx, ny, 3, sum(RUNS), force, trt, opened, wall="on" if wall else None, les="on" if les else None,
+                        drive=mode)
 
 
 def test_the_forces_hold_what_they_promise():
@@ -148,35 +76,18 @@ def test_every_drive_instance_equals_the_reference(lbm, oracle_f64, force, trt, 
     what = "%s<%d,%d,%d,%d,%d,1> %dx%d" % (family, force, trt, opened, wall, les, nx, ny)
     case = matrix_case(lbm, nx, ny, force, trt, opened, wall, les)
     assert [m.drive for m in case.members] == FORCES[:3]
-    refs = reference_of(oracle_f64, ("matrix", nx, ny, trt, opened, wall, les), case, sum(RUNS))
-    got = run_of(lbm, ("matrix", nx, ny, force, trt, opened, wall, les), family, case, RUNS)
-    assert_equals_the_reference(case, refs, got, RUNS, what)
-    assert len({r.states[-1].tobytes() for r in got}) == case.n                   # the members are different flows
-    # the force changes the flow: the reference without it differs from the first step on, in the fluid cells alone
-    plain = reference_of(oracle_f64, ("plain", nx, ny, trt, opened, wall, les), matrix_case(lbm, nx, ny, force, trt, opened, wall, les, None), 1)
-    for m, a, b in zip(case.members, refs, plain):
-        assert not np.array_equal(a.states[1], b.states[1])
-        assert np.array_equal(a.states[1][:, m.ob != 0], b.states[1][:, m.ob != 0])
-    if family in ("ensemble", "gated"):
-        # a member is the LBMDouble with its force, at "multistep" 0 and 8, bit for bit
-        for other in ("dp_step", "dp_multi"):
-            assert_same_bits(got, run_of(lbm, ("matrix", nx, ny, force, trt, opened, wall, les), other, case, RUNS), what)
+    # the force changes the flow in the fluid cells alone
+    dm.check_every_instance(once, matrix_case, lbm, oracle_f64, case, (force, trt, opened, wall, les), family, nx, ny, what,
+                            fluid_alone=True)
 
 
 # ---- 2. a region wider than the grid -------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("family", ["dp_multi", "ensemble", "gated"])
 def test_region_wider_than_the_grid(lbm, oracle_f64, family):
-    runs = [1] * 6
-    case = narrow_case(lbm)
-    for k, m in enumerate(case.members):
-        m.les = None
-        m.drive_on = m.drive = FORCES[k]
-    assert (case.nx, case.ny) == (6, 5)
-    refs = reference_of(oracle_f64, ("narrow",), case, len(runs))
-    got = run_of(lbm, ("narrow",), family, case, runs)
-    assert_equals_the_reference(case, refs, got, runs, "%s 6x5" % family)
-    assert len({r.states[-1].tobytes() for r in got}) == case.n
+    case = dm.narrow_case(lbm, drive="on")
+    assert [m.les for m in case.members] == [None] * 3 and [m.drive for m in case.members] == FORCES[:3]
+    dm.check_region_wider_than_the_grid(once, lbm, oracle_f64, family, case)
 
 
 # ---- 3. off is off, on is on ---------------------------------------------------------------------------------------------
@@ -186,17 +97,12 @@ def test_region_wider_than_the_grid(lbm, oracle_f64, family):
 @pytest.mark.parametrize("force,trt,opened,wall,les", [(1, 0, 0, 0, 0), (1, 1, 1, 1, 1)])
 def test_off_is_off_and_on_is_on(lbm, force, trt, opened, wall, les, family, nx, ny):
     what = "%s<%d,%d,%d,%d,%d> %dx%d" % (family, force, trt, opened, wall, les, nx, ny)
-    flags = (nx, ny, force, trt, opened, wall, les)
-    never = run_of(lbm, ("never",) + flags, family, matrix_case(lbm, *flags, None), RUNS)
-    off = run_of(lbm, ("off",) + flags, family, matrix_case(lbm, *flags, "off"), RUNS)
-    assert_same_bits(off, never, what + " off")
+    flags = (force, trt, opened, wall, les)
     # with F = (1e-5, 0) in every member the cells differ from the plain run's after one step
-    case = matrix_case(lbm, *flags)
+    case = matrix_case(lbm, nx, ny, *flags)
     for m in case.members:
         m.drive_on = m.drive = (1e-5, 0.0)
-    on = run_of(lbm, ("on",) + flags, family, case, RUNS)
-    assert all(not np.array_equal(a.states[0], b.states[0]) for a, b in zip(on, never))
-    assert all(np.all(np.isfinite(a.states[-1])) for a in on)
+    dm.check_off_is_off(once, matrix_case, lbm, flags, family, nx, ny, what, ("off",), "on", case, finite=True)
 
 
 # ---- 4. identities -------------------------------------------------------------------------------------------------------
@@ -204,75 +110,22 @@ def test_off_is_off_and_on_is_on(lbm, force, trt, opened, wall, les, family, nx,
 @pytest.mark.parametrize("trt,wall,les", [(0, 0, 0), (1, 1, 1)])
 def test_multistep_0_3_and_8_agree(lbm, trt, wall, les):
     nx, ny = SHAPES[0]
-    key = ("forms", trt, wall, les)
-    results = [run_of(lbm, key, ms, matrix_case(lbm, nx, ny, 1, trt, 0, wall, les), RUNS) for ms in (0, 3, 8)]
-    assert_same_bits(results[0], results[1], "multistep 0 against 3")
-    assert_same_bits(results[0], results[2], "multistep 0 against 8")
-    members = run_of(lbm, key, "ensemble", matrix_case(lbm, nx, ny, 1, trt, 0, wall, les), RUNS)
-    assert_same_bits(members, results[1], "member against context")
+    dm.check_multistep_0_3_and_8_agree(once, lbm, ("forms", trt, wall, les), lambda: matrix_case(lbm, nx, ny, 1, trt, 0, wall, les))
 
 
 @pytest.mark.parametrize("family", dm.FAMILIES)
 def test_one_run_of_ten_against_three_and_seven(lbm, family):
     nx, ny = SHAPES[0]
-    whole = run_of(lbm, ("ten", 10), family, matrix_case(lbm, nx, ny, 1, 1, 0, 1, 0), [10])
-    split = run_of(lbm, ("ten", 3, 7), family, matrix_case(lbm, nx, ny, 1, 1, 0, 1, 0), [3, 7])
-    for k, (a, b) in enumerate(zip(whole, split)):
-        assert np.array_equal(a.states[-1], b.states[-1]), (family, k)
-        assert np.array_equal(a.av, b.av) and np.array_equal(a.fx, b.fx) and np.array_equal(a.fy, b.fy), (family, k)
-        assert b.now[1] == (b.fx[3], b.fy[3])
+    dm.check_one_run_of_ten_against_three_and_seven(once, lbm, family, lambda: matrix_case(lbm, nx, ny, 1, 1, 0, 1, 0))
 
 
 @pytest.mark.parametrize("on", ["av_vels", "drag"])
 def test_a_member_stopped_by_run_until_is_a_plain_run_to_its_count(lbm, on):
-    nx, ny, window, cap = 37, 29, 7, 200
-    omegas = (0.6, 1.0, 1.4, 1.7)
-    ob = channel(nx, ny)
-    base = lbm.make_dparams(nx, ny, cap, density=0.1, accel=0.005, omega=omegas[0], obstacles=ob)
-    params = lbm.sweep_dparams(base, omega=list(omegas))
     forces = np.array([(3e-5, 1e-6), (-1e-5, 2e-6), (6e-5, -4e-6), (2e-5, 8e-6)])
-
-    def ensemble():
-        ens = lbm.EnsembleDouble(params, ob)
-        ens.set_option("force", 1)
-        ens.set_drive(forces)
-        ens.upload(None)
-        return ens
-
-    with ensemble() as ens:
-        ens.run(cap)
-        whole = ens.download(cells=False)[1] if on == "av_vels" else ens.force_record()[0]
-    want_steps, want_conv = rule(whole, 0, cap, window, TOL)
-    print("channel %dx%d with four forces, window %d on %s: stops %s converged %s" %
-          (nx, ny, window, on, want_steps.tolist(), want_conv.tolist()))
-    assert np.any(want_conv) and len(set(want_steps.tolist())) >= 2
-    with ensemble() as ens:
-        steps, conv = ens.run_until(cap, window=window, rel_tol=TOL, on=on)
-        assert steps.tolist() == want_steps.tolist() and conv.tolist() == want_conv.tolist()
-        cells, av = ens.download()
-        fx, fy = ens.force_record()
-        now = ens.force()
-        fields = ens.final_state()
-    for k, p in enumerate(params):
-        c = int(steps[k])
-        with lbm.LBMDouble(p, ob) as sim:
-            sim.set_option("force", 1)
-            sim.set_drive(forces[k])
-            sim.upload(None)
-            sim.run(c)
-            rc, rav = sim.download()
-            rfx, rfy = sim.force_record()
-            assert np.array_equal(cells[k], rc), k
-            assert np.array_equal(av[k, :c], rav), k
-            assert np.array_equal(fx[k, :c], rfx) and np.array_equal(fy[k, :c], rfy), k
-            assert (now[0][k], now[1][k]) == sim.force(), k
-            assert all(np.array_equal(a[k], b) for a, b in zip(fields, sim.final_state())), k
-    # the force changes it: with another force the member is another flow
-    with lbm.LBMDouble(params[3], ob) as sim:
-        sim.set_drive(forces[0])
-        sim.upload(None)
-        sim.run(int(steps[3]))
-        assert not np.array_equal(sim.download(av_vels=False)[0], cells[3])
+    # the force changes it: with another force member 3 is another flow
+    dm.check_a_member_stopped_by_run_until(lbm, on, lambda ens: ens.set_drive(forces), lambda sim, k: sim.set_drive(forces[k]),
+                                           "channel %dx%d with four forces", (3, lambda sim: sim.set_drive(forces[0])),
+                                           final_state=True)
 
 
 # ---- 5. the reported velocity; errors and what keeps the setting -----------------------------------------------------------
@@ -281,9 +134,9 @@ def test_a_member_stopped_by_run_until_is_a_plain_run_to_its_count(lbm, on):
 def test_reported_velocity_is_the_physical_one(lbm, oracle_f64, trt):
     nx, ny = 33, 19
     case = matrix_case(lbm, nx, ny, 0, trt, 0, 0, 0)
-    refs = reference_of(oracle_f64, ("matrix", nx, ny, trt, 0, 0, 0), case, sum(RUNS))
+    refs = once.reference_of(oracle_f64, ("matrix", nx, ny, trt, 0, 0, 0), case, sum(RUNS))
     ms = case.members
-    with dm.open_ensemble(driven(lbm, case), case) as ens:
+    with dm.open_ensemble(lbm, case) as ens:
         for t in range(3):
             ens.run(1)
             got = ens.final_state()
@@ -302,7 +155,7 @@ def test_reported_velocity_is_the_physical_one(lbm, oracle_f64, trt):
                 assert abs(re[k] - total * m.p.free_cells_inv * m.p.reynolds_dim / viscosity) <= nx * ny * U * abs(re[k])
     # a context reports what the member reports
     m = ms[1]
-    with dm.open_context(driven(lbm, case), case, m, 8) as sim:
+    with dm.open_context(lbm, case, m, 8) as sim:
         sim.run(3)
         assert all(np.array_equal(a, b[1]) for a, b in zip(sim.final_state(), got))
         assert sim.reynolds() == re[1]
@@ -319,7 +172,7 @@ def test_errors_and_what_keeps_the_setting(lbm, oracle_f64):
     F = (4e-5, -1e-5)
 
     def one(magic=None, c=None, drive=F, q=m):
-        return ref.reference_step(oracle_f64, q.p, q.ob, None, q.cells0, magic, None, None, c, drive)[0]
+        return dm.reference_step(oracle_f64, q.p, q.ob, None, q.cells0, magic, None, None, c, drive)[0]
 
     want, plain = one(), one(drive=None)
     assert not np.array_equal(want, plain)
@@ -412,9 +265,9 @@ def held(got, want):
 
 def restated(ob, omega, magic, drive):
     key = ("start", ob.tobytes(), omega, magic, drive)
-    if key not in _refs:
-        _refs[key] = ref.run(ob, omega, magic, drive, ref.START)
-    return _refs[key]
+    if key not in once.refs:
+        once.refs[key] = ref.run(ob, omega, magic, drive, ref.START)
+    return once.refs[key]
 
 
 def context_run(lbm, ob, omega, magic, drive, steps, multistep, force=False):
@@ -451,12 +304,12 @@ def test_poiseuille_flow_one_ensemble_per_magic_parameter(lbm, fix, magic):
     p = ref.POISEUILLE
     ob, drive, omegas = ref.channel_mask(p["nx"], p["ny"]), p["force"], p["omegas"]
     early, _, fields, _ = ensemble_run(lbm, ob, omegas, magic, drive, p["steps"])
-    stored = cpu.poiseuille_table(fix)
+    stored = ref.poiseuille_table(fix)
     fig = {}
     for k, w in enumerate(omegas):
         assert np.array_equal(early[k], restated(ob, w, magic, drive)), w
         fig[(magic, w)] = ref.poiseuille_figures(fields[0][k], fields[1][k], fields[3][k], w)
-    print("\n".join(cpu.poiseuille_gates(fig, stored)))
+    print("\n".join(ref.poiseuille_gates(fig, stored)))
     for key in fig:
         assert all(held(a, b) for a, b in zip(fig[key], stored[key])), (key, fig[key], stored[key])
 
@@ -467,9 +320,9 @@ def test_poiseuille_flow_with_bgk_moves_the_wall(lbm, fix, omega, multistep):
     ob, drive = ref.channel_mask(p["nx"], p["ny"]), p["force"]
     early, _, fields, _ = context_run(lbm, ob, omega, None, drive, p["steps"], multistep)
     assert np.array_equal(early, restated(ob, omega, None, drive))
-    stored = cpu.poiseuille_table(fix)
+    stored = ref.poiseuille_table(fix)
     fig = {(None, omega): ref.poiseuille_figures(fields[0], fields[1], fields[3], omega)}
-    print("\n".join(cpu.poiseuille_gates(fig, stored)))
+    print("\n".join(ref.poiseuille_gates(fig, stored)))
     assert fig[(None, omega)][0] >= 4e-3                                          # not the parabola
     assert all(held(a, b) for a, b in zip(fig[(None, omega)], stored[(None, omega)]))
 
@@ -477,7 +330,7 @@ def test_poiseuille_flow_with_bgk_moves_the_wall(lbm, fix, omega, multistep):
 def test_hydrostatic_balance(lbm, fix):
     h = ref.HYDROSTATIC
     ob, drive = ref.box_mask(h["nx"], h["ny"]), h["force"]
-    stored = cpu.case_table(fix, "hydrostatic", ("umax", "step_error"))
+    stored = ref.case_table(fix, "hydrostatic", ("umax", "step_error"))
     (w0, m0), (w1, m1) = h["cases"]
     # TRT 3/16 through LBMDouble at "multistep" 8 and as a member; BGK through LBMDouble
     runs = {"context TRT": (context_run(lbm, ob, w0, m0, drive, h["steps"], 8), w0, m0),
@@ -487,7 +340,7 @@ def test_hydrostatic_balance(lbm, fix):
     for name, ((early, _, fields, _), w, magic) in runs.items():
         assert np.array_equal(early, restated(ob, w, magic, drive)), name
         umax, err = ref.hydrostatic_figures(fields[2], fields[3])
-        print(name, cpu.hydrostatic_gates(umax, err, stored[(magic, w)][0]))
+        print(name, ref.hydrostatic_gates(umax, err, stored[(magic, w)][0]))
         assert held(umax, stored[(magic, w)][0]) and held(err, stored[(magic, w)][1]), (name, umax, err, stored[(magic, w)])
     assert np.array_equal(runs["member TRT"][0][1], runs["context TRT"][0][1])
     # the second member carries twice the weight: twice the density step, at rest as well
@@ -498,13 +351,13 @@ def test_hydrostatic_balance(lbm, fix):
 def test_momentum_balance(lbm, fix):
     b = ref.BALANCE
     ob, drive = ref.balance_mask(), b["force"]
-    stored = cpu.case_table(fix, "balance", ("rel", "lift", "fx"))
+    stored = ref.case_table(fix, "balance", ("rel", "lift", "fx"))
     bal = fix["balance"]
     for w, magic in b["cases"]:
         early, _, _, (fx, fy) = context_run(lbm, ob, w, magic, drive, b["steps"], -1, force=True)   # "force" on, no body map
         assert np.array_equal(early, restated(ob, w, magic, drive))
         rel, lift = ref.balance_figures(fx[-1], fy[-1])
-        print("omega %.1f %s: sum F_x %.16e" % (w, "BGK" if magic is None else "TRT", fx[-1]), cpu.balance_gates(rel, lift, stored[(magic, w)][0]))
+        print("omega %.1f %s: sum F_x %.16e" % (w, "BGK" if magic is None else "TRT", fx[-1]), ref.balance_gates(rel, lift, stored[(magic, w)][0]))
         assert held(fx[-1], stored[(magic, w)][2])
     # two members, the second with the mirrored force
     w, magic = b["cases"][0]
@@ -512,8 +365,8 @@ def test_momentum_balance(lbm, fix):
     assert np.array_equal(early[0], restated(ob, w, magic, drive))
     for k in range(2):
         rel, lift = ref.balance_figures(fx[k, -1], fy[k, -1], (1 - 2 * k) * drive[0])
-        print("member %d" % k, cpu.balance_gates(rel, lift, stored[(magic, w)][0]))
-    print(cpu.mirror_gate(fx[0, -1], fx[1, -1], max(bal["mirror_sum"], stored[(magic, w)][0])))
+        print("member %d" % k, ref.balance_gates(rel, lift, stored[(magic, w)][0]))
+    print(ref.mirror_gate(fx[0, -1], fx[1, -1], max(bal["mirror_sum"], stored[(magic, w)][0])))
     assert held(fx[0, -1], stored[(magic, w)][2]) and held(fx[1, -1], bal["mirrored"]["fx"])
 
 
@@ -532,6 +385,6 @@ def test_sweep_to_steady_state(lbm, fix):
     print("sweep: stops %s" % steps.tolist())
     assert conv.all() and np.all(steps < s["max_steps"])                          # every member converges
     last = [av[k, steps[k] - 1] for k in range(n)]
-    print(cpu.sweep_gate(last, s["forces"], fix["sweep"]["spread"]))
+    print(ref.sweep_gate(last, s["forces"], fix["sweep"]["spread"]))
     for k, e in enumerate(fix["sweep"]["entries"]):
         assert abs(last[k] - e["av"]) <= 1e-6 * e["av"], (k, last[k], e)          # the restatement's steady value, stops apart

@@ -6,7 +6,7 @@ exact, all from rest at density 0.1 with accel = 0, and on a sweep to steady sta
   2. the fixture is this restatement's: the Poiseuille entry omega 1.0, Lambda 3/16 is computed again and equals the fixture;
   3. the inputs hold what the gates assume: nine fluid rows, a block that touches no wall, 296 fluid cells;
   4. the gates that tests/test_drive_gpu.py applies to the library's figures are applied to the fixture's: `poiseuille_gates`,
-     `hydrostatic_gates`, `balance_gates`, `mirror_gate` and `sweep_gate` below are the ones it imports.
+     `hydrostatic_gates`, `balance_gates`, `mirror_gate` and `sweep_gate` of tests/_drive_ref.py, which both modules import.
 
 The gates are conditions the known answers set, not figures of the code under test:
   Poiseuille   with two relaxation times at Lambda = 3/16 a force-driven flow between bounce-back walls is the parabola with the
@@ -16,8 +16,6 @@ The gates are conditions the known answers set, not figures of the code under te
   hydrostatic  a closed box under gravity is at rest, and its density falls by 3 F_y from row to row.
   balance      in steady state the walls and the block take up exactly the momentum the force feeds in, F_x x N_fluid per step:
                the new term and the existing force record held against each other."""
-import json
-import os
 import sys
 
 import numpy as np
@@ -25,15 +23,8 @@ import numpy as np
 import _drive_ref as ref
 import _les_ref
 import _open_ref
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-GATED_OMEGAS = (0.6, 1.0, 1.7)
-CAP = 1e-9
-
-
-def fixture():
-    with open(os.path.join(GOLDEN, "drive.json")) as f:
-        return json.load(f)
+from _drive_ref import (GATED_OMEGAS, GOLDEN, balance_gates, fixture, hydrostatic_gates, mirror_gate, poiseuille_gates, poiseuille_table,
+                        sweep_gate)
 
 
 def make_drive():
@@ -43,75 +34,6 @@ def make_drive():
     finally:
         sys.path.remove(GOLDEN)
     return module
-
-
-def poiseuille_table(fix):
-    """{(magic or None, omega): (deviation, spread, max |u_y|)} of the fixture"""
-    return {(e["magic"], e["omega"]): (e["deviation"], e["spread"], e["uy"]) for e in fix["poiseuille"]["entries"]}
-
-
-def case_table(fix, flow, keys):
-    return {(e["magic"], e["omega"]): tuple(e[k] for k in keys) for e in fix[flow]["entries"]}
-
-
-# ---- the gates -----------------------------------------------------------------------------------------------------------
-
-def poiseuille_gates(fig, stored):
-    """fig, stored: {(magic or None, omega): (deviation, spread, max |u_y|)}, the figures under test and the fixture's; fig may
-    hold any subset of the fixture's runs, and each gate is applied to the runs it has"""
-    lines = []
-    for key, (dev, spread, uy) in sorted(fig.items(), key=str):
-        magic, w = key
-        name = "BGK" if magic is None else "Lambda %.4f" % magic
-        lines.append("%s omega %.1f: deviation %.3e (fixture %.3e), density spread %.2e (gate %.2e), |u_y| %.2e (gate %.2e)" % (
-            name, w, dev, stored[key][0], spread, 100.0 * stored[key][1], uy, 100.0 * stored[key][2]))
-        assert 0.0 <= spread <= 100.0 * stored[key][1], lines[-1]
-        assert 0.0 <= uy <= 100.0 * stored[key][2], lines[-1]
-        if magic == ref.L316 and w in GATED_OMEGAS:                              # omega 1.9 has not settled: printed, not gated
-            bound = min(100.0 * stored[key][0], CAP)
-            assert dev <= bound, (lines[-1], bound)
-    if (ref.L14, 1.0) in fig and (ref.L14, 1.7) in fig:
-        a, b = fig[(ref.L14, 1.0)][0], fig[(ref.L14, 1.7)][0]
-        lines.append("Lambda 1/4: deviation %.9e at omega 1.0, %.9e at 1.7 (gates: equal to 1e-6 relative, >= 1e-3)" % (a, b))
-        assert abs(a - b) <= 1e-6 * abs(b) and min(a, b) >= 1e-3, lines[-1]
-    if (None, 0.6) in fig:
-        other = fig[(ref.L316, 0.6)][0] if (ref.L316, 0.6) in fig else stored[(ref.L316, 0.6)][0]
-        lines.append("BGK omega 0.6: deviation %.3e against %.3e at Lambda 3/16 (gate >= 10 x)" % (fig[(None, 0.6)][0], other))
-        assert fig[(None, 0.6)][0] >= 10.0 * other, lines[-1]
-    return lines
-
-
-def hydrostatic_gates(umax, step_error, stored_umax):
-    bound = min(100.0 * stored_umax, 1e-12)
-    line = "hydrostatic: max |u| %.2e (gate %.2e), density steps against 3 F_y %.2e (gate 1e-9)" % (umax, bound, step_error)
-    assert 0.0 <= umax <= bound and step_error <= 1e-9, line
-    return line
-
-
-def balance_gates(rel, lift, stored_rel):
-    """rel = |sum F_x / (F_x N_fluid) - 1|, lift = |sum F_y| / (F_x N_fluid)"""
-    bound = min(100.0 * stored_rel, CAP)
-    line = "balance: |sum F_x / (F_x N) - 1| %.2e, |sum F_y| / (F_x N) %.2e (gate %.2e on both)" % (rel, lift, bound)
-    assert rel <= bound and lift <= bound, line
-    return line
-
-
-def mirror_gate(fx, fx_mirrored, stored_rel):
-    """the member with the mirrored force: the opposite sum F_x, within the margin of the balance gate"""
-    total = ref.BALANCE["force"][0] * ref.BALANCE["fluid"]
-    bound = min(100.0 * stored_rel, CAP)
-    line = "mirrored force: |sum F_x + sum F_x'| / (F_x N) %.2e (gate %.2e)" % (abs(fx + fx_mirrored) / total, bound)
-    assert fx > 0.0 > fx_mirrored and abs(fx + fx_mirrored) <= bound * total, line
-    return line
-
-
-def sweep_gate(av, forces, stored_spread):
-    """Stokes regime: the settled av_vels over F_x is one constant across the members, within 10 x the spread the restatement shows"""
-    ratio = np.asarray(av, dtype=np.float64) / np.asarray(forces, dtype=np.float64)
-    spread = float((ratio.max() - ratio.min()) / ratio.mean())
-    line = "sweep: av_vels / F_x %.6e .. %.6e, spread %.2e (gate %.2e)" % (ratio.min(), ratio.max(), spread, 10.0 * stored_spread)
-    assert np.all(ratio > 0.0) and spread <= 10.0 * stored_spread, line
-    return line
 
 
 # ---- 1. the restatement's own lines ----------------------------------------------------------------------------------------

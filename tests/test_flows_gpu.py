@@ -4,8 +4,9 @@ bounce-back wall under two relaxation times, and the drag and lift of Schaefer a
 The other fp64 modules hold every kernel instance to a numpy restatement of include/lbm.h's statements bit for bit; a wrong
 statement (a Zou-He coefficient, the link set or a sign of the force, the relation between omega_minus and Lambda) passes
 them, because restatement and kernel share it.  Here the library's own long runs are gated on what the flow must give.  The
-gates are tests/test_flows_restatement_cpu.py's (channel_gates, cylinder_gates, mirror_gates, finer_gates), which that
-module applies to the restatement's recorded figures in tests/golden/flows.json; and kernel and restatement are compared:
+gates are tests/_flows_ref.py's (channel_gates, cylinder_gates, mirror_gates, finer_gates), which
+tests/test_flows_restatement_cpu.py applies to the restatement's recorded figures in tests/golden/flows.json; the stop rule is
+tests/_steady_rule.py's; and kernel and restatement are compared:
 cells after the first 200 steps with np.array_equal, final figures with the fixture's to 1e-9 relative, force records with
 the fixture's within 8 L 2^-53 sum|link terms| (the gate of test_force_gpu between two summation orders, L links).
 
@@ -51,9 +52,9 @@ import pytest
 import _flows_ref as flows
 import _open_ref
 import _trt_ref
-from test_dp_steady_gpu import rule
-from test_flows_restatement_cpu import (BGK_OMEGAS, L14, L316, channel_gates, channel_table, cylinder_gates, finer_gates, fixture,
-                                        mirror_gates, tail_of)
+from _flows_ref import (BGK_OMEGAS, L14, L316, channel_gates, channel_table, cylinder_gates, finer_gates, fixture, mirror_gates,
+                        tail_of)
+from _steady_rule import rule
 
 pytestmark = pytest.mark.gpu
 

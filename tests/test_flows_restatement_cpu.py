@@ -5,7 +5,7 @@ tests/golden/flows.json holds what tests/golden/make_flows.py recorded with test
      cylinder are computed again and equal the fixture to 1e-12 relative;
   2. the geometry holds what _flows_ref promises;
   3. the gates that tests/test_flows_gpu.py applies to the library's figures are applied to the fixture's: `channel_gates`,
-     `cylinder_gates`, `mirror_gates` and `finer_gates` below are the ones it imports.
+     `cylinder_gates`, `mirror_gates` and `finer_gates` of tests/_flows_ref.py, which both modules import.
 
 The gates are conditions that the answer known from outside sets, not figures of the code under test:
   channel   with two relaxation times at a fixed magic parameter Lambda the place of a bounce-back wall does not depend on
@@ -14,7 +14,6 @@ The gates are conditions that the answer known from outside sets, not figures of
             = 1/4); with BGK it moves with omega.
   cylinder  Schaefer-Turek 2D-1: C_d 5.57 - 5.59, C_l 0.0104 - 0.0110.  A disc of ten cells is a staircase: 7 % of 5.58 and
             25 % of 0.0107 are what that resolution is given; twenty cells must come closer, within 5 %."""
-import json
 import os
 import sys
 
@@ -22,23 +21,10 @@ import numpy as np
 
 import _flows_ref as flows
 import _open_ref
+from _flows_ref import BGK_OMEGAS, L316, channel_gates, channel_table, cylinder_gates, finer_gates, fixture, mirror_gates
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 U = 2.0 ** -53
-L316, L14 = 3.0 / 16.0, 0.25
-BGK_OMEGAS = (0.6, 1.0, 1.7)
-
-
-def fixture():
-    with open(os.path.join(GOLDEN, "flows.json")) as f:
-        return json.load(f)
-
-
-def channel_table(fix):
-    """{(magic or None, omega): (spread, shape)} of the fixture; the diverged BGK entry holds NaNs"""
-    nan = float("nan")
-    return {(e["magic"], e["omega"]): (nan if e["spread"] is None else e["spread"], nan if e["shape"] is None else e["shape"])
-            for e in fix["channel"]["entries"]}
 
 
 def make_flows():
@@ -48,73 +34,6 @@ def make_flows():
     finally:
         sys.path.remove(GOLDEN)
     return module
-
-
-# ---- the gates -----------------------------------------------------------------------------------------------------------
-
-def channel_gates(fig):
-    """fig {(magic or None, omega): (spread, shape)} with Lambda = 3/16 and 1/4 at the four omegas and BGK at 0.6, 1.0, 1.7"""
-    lines = []
-    for magic in (L316, L14):
-        shapes = [fig[(magic, w)][1] for w in flows.CH_OMEGAS]
-        assert all(s > 0.0 for s in shapes)
-        lines.append("Lambda %.4f: shape %s, max / min %.4f (gate 1.1)" % (magic, " ".join("%.4e" % s for s in shapes),
-                                                                          max(shapes) / min(shapes)))
-        assert max(shapes) / min(shapes) <= 1.1, (magic, shapes)                 # the wall does not move with omega
-    bgk = [fig[(None, w)][1] for w in BGK_OMEGAS]
-    lines.append("BGK: shape %s, max / min %.2f (gate >= 10)" % (" ".join("%.4e" % s for s in bgk), max(bgk) / min(bgk)))
-    assert min(bgk) > 0.0 and max(bgk) / min(bgk) >= 10.0, bgk                   # the figure is not blind: with BGK it moves
-    for w in flows.CH_OMEGAS:
-        s316, s14 = fig[(L316, w)][1], fig[(L14, w)][1]
-        lines.append("omega %.1f: shape at 3/16 %.4e (gate 1e-4), at 1/4 %.4e, ratio %.1f (gate >= 100), 1/4 against BGK at 1: %.2e "
-                     "(gate 1e-3)" % (w, s316, s14, s14 / s316, abs(s14 - fig[(None, 1.0)][1]) / fig[(None, 1.0)][1]))
-        assert s316 <= 1e-4, (w, s316)                                           # half-way: the parabola itself
-        assert s14 >= 100.0 * s316, (w, s14, s316)
-        assert abs(s14 - fig[(None, 1.0)][1]) <= 1e-3 * fig[(None, 1.0)][1], (w, s14, fig[(None, 1.0)][1])
-    for (magic, w), (spread, _) in sorted(fig.items(), key=str):
-        if w <= 1.7:
-            lines.append("%s omega %.1f: spread %.2e (gate 1e-9)" % ("BGK" if magic is None else "Lambda %.4f" % magic, w, spread))
-            assert abs(spread) <= 1e-9, (magic, w, spread)                       # one flux through every column: settled
-    return lines
-
-
-def tail_of(fx, fy, D, tail=6000):
-    """the figures of a record's last `tail` entries, as the fixture's "tail" holds them"""
-    cd, cl = flows.coefficients(fx[-tail:], fy[-tail:], D)
-    assert cd.shape == (tail,)
-    return {"cd_mean": float(cd.mean()), "cd_min": float(cd.min()), "cd_max": float(cd.max()), "cl_mean": float(cl.mean())}
-
-
-def cylinder_gates(t):
-    """t: the figures of the last 6 000 steps at D = 10"""
-    cd, cl, swing = t["cd_mean"], t["cl_mean"], (t["cd_max"] - t["cd_min"]) / t["cd_mean"]
-    line = ("D 10: C_d %.4f (%+.2f %% of 5.58, gate 7 %%), max - min %.3f %% (gate 0.2 %%), C_l %.5f (%+.1f %% of 0.0107, gate 25 %%)"
-            % (cd, 100.0 * (cd / flows.CD_PUBLISHED - 1.0), 100.0 * swing, cl, 100.0 * (cl / flows.CL_PUBLISHED - 1.0)))
-    assert abs(cd - flows.CD_PUBLISHED) <= 0.07 * flows.CD_PUBLISHED, line
-    assert 0.0 <= swing <= 2e-3, line
-    assert cl > 0.0 and abs(cl - flows.CL_PUBLISHED) <= 0.25 * flows.CL_PUBLISHED, line   # the disc is nearer the lower wall
-    return line
-
-
-def mirror_gates(t0, t1, stored):
-    """the mirrored member: the same C_d, the opposite C_l, each within 100 x what the restatement's two runs differ by and
-    1e-6 of C_d at the most (a flipped sign or a wrong member's record is 1e-2)"""
-    d_cd, d_cl = abs(t0["cd_mean"] - t1["cd_mean"]), abs(t0["cl_mean"] + t1["cl_mean"])
-    cap = 1e-6 * t0["cd_mean"]
-    g_cd, g_cl = min(100.0 * stored["d_cd"], cap), min(100.0 * stored["d_cl"], cap)
-    line = "mirrored member: |C_d - C_d'| %.2e (gate %.2e), |C_l + C_l'| %.2e (gate %.2e)" % (d_cd, g_cd, d_cl, g_cl)
-    assert d_cd <= g_cd and d_cl <= g_cl, line
-    return line
-
-
-def finer_gates(t20, t10):
-    """D = 20 against D = 10: nearer the published drag, and within 5 % of it"""
-    e20, e10 = abs(t20["cd_mean"] - flows.CD_PUBLISHED), abs(t10["cd_mean"] - flows.CD_PUBLISHED)
-    line = "D 20: C_d %.4f (%+.2f %% of 5.58, gate 5 %% and below D 10's %+.2f %%), C_l %.5f" % (
-        t20["cd_mean"], 100.0 * (t20["cd_mean"] / flows.CD_PUBLISHED - 1.0), 100.0 * (t10["cd_mean"] / flows.CD_PUBLISHED - 1.0),
-        t20["cl_mean"])
-    assert e20 < e10 and e20 <= 0.05 * flows.CD_PUBLISHED, line
-    return line
 
 
 # ---- 1. the fixture is this restatement's --------------------------------------------------------------------------------

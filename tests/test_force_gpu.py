@@ -1,8 +1,9 @@
 """Drag and lift on the GPU: the momentum-exchange force on the blocked cells (option "force", lbm_dforce_*,
 LBMDouble / EnsembleDouble .force() and .force_record()).
 
-The reference value is `restatement` below: include/lbm.h's definition in numpy float64, np.roll per speed over the mask,
-evaluated on states downloaded from the GPU and accelerated with the fp64 oracle's accelerate_flow.  Gates:
+The reference value is tests/_force_ref.py's `restatement`: include/lbm.h's definition in numpy float64, np.roll per speed over the
+mask, evaluated on states downloaded from the GPU and accelerated with the fp64 oracle's accelerate_flow; the masks, cases and
+single-step states are that module's too.  Gates:
   1. record against the restatement, per component 8 L 2^-53 sum|link terms| (L links): four times the bound between two
      summation orders of the same terms; a missing or doubled link is 1e-3 to 1e-2 of the total, ten orders above it;
   2. momentum balance, independent of the restatement: fluid momentum after step t minus fluid momentum of the accelerated
@@ -14,113 +15,13 @@ all eight neighbours blocked, blocked cells at x = 15 | 16 and y = 15 | 16 (tile
 import numpy as np
 import pytest
 
-from test_dp_ensemble_gpu import CASES, RUNS, make_members
-from test_dp_gpu import oracle_params, random_state
-from test_dp_steady_gpu import OMEGAS, TOL, sweep
+from _dp_states import CASES, RUNS, make_members
+from _force_ref import SHAPES, SINGLE_STEPS, U, accelerated, case, fluid_momentum, force_mask, restatement, single_steps
+from _steady_rule import OMEGAS, TOL, sweep
 
 pytestmark = pytest.mark.gpu
 
 LBM_ERR_ARG, LBM_ERR_STATE = 1, 3
-U = 2.0 ** -53
-# speed k: c_k = (CX[k], CY[k]); OPP[k] the opposite speed (include/lbm.h)
-CX = [0, 1, 0, -1, 0, 1, -1, -1, 1]
-CY = [0, 0, 1, 0, -1, 1, 1, -1, -1]
-OPP = [0, 3, 4, 1, 2, 7, 8, 5, 6]
-SHAPES = [(16, 16), (33, 19), (48, 35), (128, 128), (3, 3)]
-SINGLE_STEPS = 12
-
-
-def force_mask(nx, ny, seed=7):
-    """the masks of the module docstring, as far as the grid has room for them"""
-    ob = np.zeros((ny, nx), dtype=np.int32)
-    if nx == 3 and ny == 3:
-        ob[1, 1] = 1
-        return ob
-    rng = np.random.default_rng(seed)
-    ob[:] = rng.random((ny, nx)) < 0.03
-    ob[0, : 3 * nx // 4] = 1                                  # a wall on row 0, open at its east end
-    ob[ny - 1, :] = 0
-    ob[ny - 1, nx // 2:nx // 2 + 3] = 1                       # rows ny-1, ny-2, ny-3, fluid beside them on ny-2
-    ob[ny - 2, nx // 2 + 1] = 1
-    ob[ny - 2, [nx // 2, nx // 2 + 2]] = 0
-    ob[ny - 3, nx // 2:nx // 2 + 2] = 1
-    ob[ny // 2 - 2:ny // 2 + 2, nx // 4:nx // 4 + 5] = 1      # a 4x5 block
-    ob[ny // 2, 0] = 1                                        # x = 0 facing fluid at x = nx-1 across the wrap
-    ob[ny // 2 - 1:ny // 2 + 2, nx - 1] = 0
-    ob[0, 1] = 1                                              # y = 0 facing fluid at y = ny-1 (row ny-1 is fluid there)
-    if nx >= 16 and ny >= 12:
-        y, x = ny - 7, nx - 5                                 # an isolated blocked cell
-        ob[y - 1:y + 2, x - 1:x + 2] = 0
-        ob[y, x] = 1
-        ob[3:6, nx - 7:nx - 4] = 1                            # 3x3: its centre has all eight neighbours blocked
-    for y in (15, 16):                                        # tile seams
-        for x in (15, 16):
-            if x < nx and y < ny - 3:
-                ob[y, x] = 1
-    if nx > 20 and ny > 20:
-        ob[15, 14] = ob[16, 17] = 0
-    assert 0 < np.count_nonzero(ob) < ob.size
-    return ob
-
-
-def restatement(f, ob):
-    """include/lbm.h's definition on the accelerated state f float64[9, ny, nx]: (F_x, F_y, links, sum of |link terms|)"""
-    assert f.dtype == np.float64
-    blocked = ob != 0
-    fx = fy = 0.0
-    links, mag = 0, 0.0
-    for k in range(1, 9):
-        # at o: the neighbour x = o - c_k (periodic), np.roll(a, s)[i] = a[i - s]
-        shift = (CY[k], CX[k])
-        counted = blocked & np.roll(~blocked, shift, axis=(0, 1))
-        term = (np.roll(f[k], shift, axis=(0, 1)) + f[OPP[k]])[counted]
-        fx += CX[k] * float(np.sum(term))
-        fy += CY[k] * float(np.sum(term))
-        links += int(term.size)
-        mag += float(np.sum(np.abs(term)))
-    return fx, fy, links, mag
-
-
-def fluid_momentum(f, ob):
-    fluid = ob == 0
-    return (sum(CX[k] * float(np.sum(f[k][fluid])) for k in range(1, 9)),
-            sum(CY[k] * float(np.sum(f[k][fluid])) for k in range(1, 9)))
-
-
-def case(lbm, nx, ny, max_iters, seed=11):
-    ob = force_mask(nx, ny)
-    p = lbm.make_dparams(nx, ny, max_iters, density=0.1, accel=0.005, omega=1.7, obstacles=ob)
-    return p, ob, random_state(np.random.default_rng(seed + nx), 0.1, ny, nx)
-
-
-_single = {}
-
-
-def single_steps(lbm, nx, ny, multistep):
-    """12 steps one at a time: the state before each step and after the last, and the record.  Computed once per case."""
-    key = (nx, ny, multistep)
-    if key not in _single:
-        p, ob, cells0 = case(lbm, nx, ny, SINGLE_STEPS)
-        states = []
-        with lbm.LBMDouble(p, ob) as sim:
-            sim.set_option("multistep", multistep)
-            sim.set_option("force", 1)
-            assert sim.get_option("force") == 1
-            sim.upload(cells0)
-            for _ in range(SINGLE_STEPS):
-                states.append(sim.download(av_vels=False)[0])
-                sim.run(1)
-            states.append(sim.download(av_vels=False)[0])
-            fx, fy = sim.force_record()
-        assert fx.shape == fy.shape == (SINGLE_STEPS,)
-        _single[key] = (p, ob, states, fx, fy)
-    return _single[key]
-
-
-def accelerated(orc, p, ob, cells):
-    f = np.array(cells, dtype=np.float64, copy=True)
-    orc.accelerate_flow(oracle_params(orc, p), f, ob)
-    return f
 
 
 @pytest.fixture(scope="module")

@@ -30,7 +30,7 @@ import numpy as np
 import pytest
 
 import _guard_case as G
-from test_dp_gpu import ORACLE_FORMS_FACTOR
+from _dp_states import ORACLE_FORMS_FACTOR
 from test_gpu_parity import SINGLE, max_rel, random_case
 
 pytestmark = pytest.mark.gpu
@@ -360,7 +360,7 @@ def test_gated_ensemble_members(lbm, forms):
 
 
 def test_double_precision_ensemble_members(lbm, forms):
-    from test_dp_gpu import max_abs, oracle_track
+    from _dp_states import max_abs, oracle_track
     _, f64, f64_fma = forms
     nsteps = 13
     ps, obs, cells0 = members(lbm, nsteps, lbm.make_dparams, np.float64)
@@ -385,7 +385,7 @@ def test_double_precision_ensemble_members(lbm, forms):
 def test_double_precision_against_the_oracle(lbm, forms, name):
     """the pattern of test_against_fp64_oracle (gate: 4 x what the fp64 oracle's two forms differ by, max |a - b| over cells and
     av_vels) at checkpoints 1, 2, 11 and 19, and the two kernel forms bit-identical (section 4 of that file)"""
-    from test_dp_gpu import gpu_track, max_abs, oracle_track
+    from _dp_states import gpu_track, max_abs, oracle_track
     _, oracle_f64_omp, fma = forms
     checkpoints = [1, 2, 11, 19]
     nx, ny, _, _ = G.CASES[name]

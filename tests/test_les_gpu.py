@@ -3,9 +3,9 @@ double-precision kernel families against tests/_les_ref.py.
 
 LES is a fifth template flag beside FORCE, TRT, OPEN and WALL of d2q9_dp_step, d2q9_dp_multi (LBMDouble at "multistep" 0 and 8),
 d2q9_dp_ensemble (EnsembleDouble.run) and d2q9_dp_ensemble_gated (EnsembleDouble.run_until): 64 more separately compiled
-kernels.  The cases, the drivers and the gates are those of tests/_dp_matrix.py, tests/test_dp_matrix_gpu.py and
-tests/test_wall_gpu.py, imported and not edited; `lesed` hands the drivers an LBMDouble / EnsembleDouble that has had set_les
-called on it, behind test_wall_gpu.walled, which calls set_wall.
+kernels.  The cases (make_case with `wall` and `les`), the drivers, the gates and the bodies of the tests that every option
+repeats are tests/_dp_matrix.py's; its open_context and open_ensemble call set_wall and then set_les on a handle before anything
+else happens to it.  The Couette gate and figures are tests/_les_ref.py's.
 
   1. the matrix: the 16 FORCE x TRT x OPEN x WALL combinations x the 4 families x 33x19 and 17x16, three members with c = 0.1,
      0.17 and 0.3, runs of 1, 1, 1 and 7 steps.  Compared with _les_ref: cells after each run, av_vels under the bound of the
@@ -28,27 +28,21 @@ comparisons between device forms in 3 and 4 do not.  Bits are asked for, and bit
 cases, of the 6x5 cases and of the error tests equal the restatement by np.array_equal after every run, so the largest distance
 seen is 0 ulps of om, and no looser bound is in this module.  The Couette runs of 6 give the CPU module's figures to the digit
 (3.6e-06 and 5.5e-06 on the force, 2.68e-06 U and 4.06e-06 U on the profile), the cavity its max |u| of 0.0811."""
-import itertools
-from types import SimpleNamespace
-
 import numpy as np
 import pytest
 
 import _dp_matrix as dm
 import _les_ref
 import _wall_ref
-from test_dp_matrix_gpu import assert_equals_the_reference, assert_same_bits
-from test_dp_steady_gpu import TOL, channel, rule
-from test_les_restatement_cpu import GATE, couette_figures
-from test_wall_gpu import narrow_case, walled, with_walls
+from _dp_matrix import CS
+from _les_ref import GATE
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(33, 19), (17, 16)]
-RUNS = [1, 1, 1, 7]
-FLAGS = list(itertools.product((0, 1), repeat=4))
-CS = [0.1, 0.17, 0.3, 0.17]
-_refs, _runs = {}, {}
+SHAPES = dm.SHAPES
+RUNS = dm.RUNS
+FLAGS = dm.flags(4)
+once = dm.Once()
 
 
 @pytest.fixture(scope="module")
@@ -57,74 +51,10 @@ def oracle_f64():
     return Oracle("f64")
 
 
-def lesed(lbm, case):
-    """`lbm` as the drivers of _dp_matrix use it: the handles of test_wall_gpu.walled, which then call set_les with the members'
-    `les` (None: never called; "off": set to the member's les_on, then to 0.0)"""
-    inner = walled(lbm, case)
-
-    def set_on(handle, members):
-        mode = members[0].les
-        if mode is None:
-            return handle
-        cs = [m.les_on if mode == "off" else m.les for m in members]
-        handle.set_les(cs[0] if len(cs) == 1 else cs)
-        assert np.array_equal(np.atleast_1d(handle.les()[0]), cs)
-        if mode == "off":
-            handle.set_les(0.0)
-            assert not np.any(handle.les()[0]) and not np.any(handle.les()[1])
-        return handle
-
-    def context(p, ob):
-        return set_on(inner.LBMDouble(p, ob), [next(m for m in case.members if m.p is p)])
-
-    def ensemble(params, obs):
-        return set_on(inner.EnsembleDouble(params, obs), case.members)
-
-    return SimpleNamespace(LBMDouble=context, EnsembleDouble=ensemble)
-
-
-def with_les(case, mode="on", wall=False):
-    """the case with a Smagorinsky constant per member (mode "on": CS; None: never set; "off": set and turned off) and, wall,
-    the velocities of test_wall_gpu.member_wall (else walls never set)"""
-    with_walls(case, "on" if wall else None)
-    for k, m in enumerate(case.members):
-        m.les_on = CS[k]
-        m.les = CS[k] if mode == "on" else mode
-    return case
-
-
-def reference_run(oracle_f64, m, steps):
-    """_dp_matrix.reference_run through _les_ref.reference_step"""
-    wall = m.wall if isinstance(m.wall, tuple) else None
-    c = m.les if isinstance(m.les, float) else None
-    states, totals, forces = [m.cells0], [], []
-    for _ in range(steps):
-        cells, u, force = _les_ref.reference_step(oracle_f64, m.p, m.ob, m.body, states[-1], m.magic, m.open, wall, c)
-        states.append(cells)
-        totals.append(float(np.sum(u)))
-        forces.append(force)
-    return SimpleNamespace(states=states, totals=totals, forces=forces)
-
-
-def reference_of(oracle_f64, key, case, steps):
-    if key not in _refs:
-        _refs[key] = [reference_run(oracle_f64, m, steps) for m in case.members]
-    return _refs[key]
-
-
-def run_of(lbm, key, family, case, runs):
-    if (family,) + key not in _runs:
-        if isinstance(family, int):
-            _runs[(family,) + key] = dm.drive_context(lesed(lbm, case), case, runs, family)      # LBMDouble at that "multistep"
-        else:
-            _runs[(family,) + key] = dm.drive(lesed(lbm, case), family, case, runs)
-    return _runs[(family,) + key]
-
-
 # ---- 1. the instance matrix --------------------------------------------------------------------------------------------
 
 def matrix_case(lbm, nx, ny, force, trt, opened, wall, mode="on"):
-    return with_les(dm.make_case(lbm, nx, ny, 3, sum(RUNS), force, trt, opened), mode, wall)
+    return dm.make_case(lbm, nx, ny, 3, sum(RUNS), force, trt, opened, wall="on" if wall else None, les=mode)
 
 
 @pytest.mark.parametrize("nx,ny", SHAPES)
@@ -134,32 +64,16 @@ def test_every_les_instance_equals_the_reference(lbm, oracle_f64, force, trt, op
     what = "%s<%d,%d,%d,%d,1> %dx%d" % (family, force, trt, opened, wall, nx, ny)
     case = matrix_case(lbm, nx, ny, force, trt, opened, wall)
     assert [m.les for m in case.members] == [0.1, 0.17, 0.3]
-    refs = reference_of(oracle_f64, ("matrix", nx, ny, trt, opened, wall), case, sum(RUNS))
-    got = run_of(lbm, ("matrix", nx, ny, force, trt, opened, wall), family, case, RUNS)
-    assert_equals_the_reference(case, refs, got, RUNS, what)
-    assert len({r.states[-1].tobytes() for r in got}) == case.n                   # the members are different flows
-    # the model changes the flow: the reference without it differs from the first step on
-    plain = reference_of(oracle_f64, ("plain", nx, ny, trt, opened, wall), matrix_case(lbm, nx, ny, force, trt, opened, wall, None), 1)
-    assert all(not np.array_equal(a.states[1], b.states[1]) for a, b in zip(refs, plain))
-    if family in ("ensemble", "gated"):
-        # a member is the LBMDouble with its c, at "multistep" 0 and 8, bit for bit
-        for other in ("dp_step", "dp_multi"):
-            assert_same_bits(got, run_of(lbm, ("matrix", nx, ny, force, trt, opened, wall), other, case, RUNS), what)
+    dm.check_every_instance(once, matrix_case, lbm, oracle_f64, case, (force, trt, opened, wall), family, nx, ny, what)
 
 
 # ---- 2. a region wider than the grid -------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("family", ["dp_multi", "ensemble", "gated"])
 def test_region_wider_than_the_grid(lbm, oracle_f64, family):
-    runs = [1] * 6
-    case = narrow_case(lbm)
-    for k, m in enumerate(case.members):
-        m.les_on = m.les = CS[k]
-    assert (case.nx, case.ny) == (6, 5)
-    refs = reference_of(oracle_f64, ("narrow",), case, len(runs))
-    got = run_of(lbm, ("narrow",), family, case, runs)
-    assert_equals_the_reference(case, refs, got, runs, "%s 6x5" % family)
-    assert len({r.states[-1].tobytes() for r in got}) == case.n
+    case = dm.narrow_case(lbm, les="on")
+    assert [m.les for m in case.members] == CS[:3]
+    dm.check_region_wider_than_the_grid(once, lbm, oracle_f64, family, case)
 
 
 # ---- 3. off is off, on is on ---------------------------------------------------------------------------------------------
@@ -169,16 +83,11 @@ def test_region_wider_than_the_grid(lbm, oracle_f64, family):
 @pytest.mark.parametrize("force,trt,opened,wall", [(1, 0, 0, 0), (1, 1, 1, 1)])
 def test_off_is_off_and_on_is_on(lbm, force, trt, opened, wall, family, nx, ny):
     what = "%s<%d,%d,%d,%d> %dx%d" % (family, force, trt, opened, wall, nx, ny)
-    never = run_of(lbm, ("never", nx, ny, force, trt, opened, wall), family, matrix_case(lbm, nx, ny, force, trt, opened, wall, None), RUNS)
-    off = run_of(lbm, ("off", nx, ny, force, trt, opened, wall), family, matrix_case(lbm, nx, ny, force, trt, opened, wall, "off"), RUNS)
-    assert_same_bits(off, never, what + " off")
     # with c = 0.17 in every member the cells differ from those of the flow without the model
     case = matrix_case(lbm, nx, ny, force, trt, opened, wall)
     for m in case.members:
         m.les_on = m.les = 0.17
-    on = run_of(lbm, ("on", nx, ny, force, trt, opened, wall), family, case, RUNS)
-    assert all(not np.array_equal(a.states[0], b.states[0]) for a, b in zip(on, never))
-    assert all(np.all(np.isfinite(a.states[-1])) for a in on)
+    dm.check_off_is_off(once, matrix_case, lbm, (force, trt, opened, wall), family, nx, ny, what, ("off",), "on", case, finite=True)
 
 
 # ---- 4. identities -------------------------------------------------------------------------------------------------------
@@ -186,77 +95,33 @@ def test_off_is_off_and_on_is_on(lbm, force, trt, opened, wall, family, nx, ny):
 @pytest.mark.parametrize("trt,wall", [(0, 0), (1, 1)])
 def test_multistep_0_3_and_8_agree(lbm, trt, wall):
     nx, ny = SHAPES[0]
-    key = ("forms", trt, wall)
-    results = [run_of(lbm, key, ms, matrix_case(lbm, nx, ny, 1, trt, 0, wall), RUNS) for ms in (0, 3, 8)]
-    assert_same_bits(results[0], results[1], "multistep 0 against 3")
-    assert_same_bits(results[0], results[2], "multistep 0 against 8")
-    members = run_of(lbm, key, "ensemble", matrix_case(lbm, nx, ny, 1, trt, 0, wall), RUNS)
-    assert_same_bits(members, results[1], "member against context")
+    dm.check_multistep_0_3_and_8_agree(once, lbm, ("forms", trt, wall), lambda: matrix_case(lbm, nx, ny, 1, trt, 0, wall))
 
 
 @pytest.mark.parametrize("family", dm.FAMILIES)
 def test_one_run_of_ten_against_three_and_seven(lbm, family):
     nx, ny = SHAPES[0]
-    whole = run_of(lbm, ("ten", 10), family, matrix_case(lbm, nx, ny, 1, 1, 0, 1), [10])
-    split = run_of(lbm, ("ten", 3, 7), family, matrix_case(lbm, nx, ny, 1, 1, 0, 1), [3, 7])
-    for k, (a, b) in enumerate(zip(whole, split)):
-        assert np.array_equal(a.states[-1], b.states[-1]), (family, k)
-        assert np.array_equal(a.av, b.av) and np.array_equal(a.fx, b.fx) and np.array_equal(a.fy, b.fy), (family, k)
-        assert b.now[1] == (b.fx[3], b.fy[3])
+    dm.check_one_run_of_ten_against_three_and_seven(once, lbm, family, lambda: matrix_case(lbm, nx, ny, 1, 1, 0, 1))
 
 
 @pytest.mark.parametrize("on", ["av_vels", "drag"])
 def test_a_member_stopped_by_run_until_is_a_plain_run_to_its_count(lbm, on):
-    nx, ny, window, cap = 37, 29, 7, 200
-    omegas = (0.6, 1.0, 1.4, 1.7)
-    ob = channel(nx, ny)
-    base = lbm.make_dparams(nx, ny, cap, density=0.1, accel=0.005, omega=omegas[0], obstacles=ob)
-    params = lbm.sweep_dparams(base, omega=list(omegas))
+    nx, ny = 37, 29
     u_x, u_y = np.zeros((ny, nx)), np.zeros((ny, nx))
     u_x[ny - 1] = 0.04                                                            # the lid
     rhos = np.array([0.1, 0.0985, 0.102, 0.1])
 
-    def ensemble():
-        ens = lbm.EnsembleDouble(params, ob)
-        ens.set_option("force", 1)
+    def set_ensemble(ens):
         ens.set_wall(u_x, u_y, rhos)
         ens.set_les(CS)
-        ens.upload(None)
-        return ens
 
-    with ensemble() as ens:
-        ens.run(cap)
-        whole = ens.download(cells=False)[1] if on == "av_vels" else ens.force_record()[0]
-    want_steps, want_conv = rule(whole, 0, cap, window, TOL)
-    print("moving lid %dx%d with the model, window %d on %s: stops %s converged %s" %
-          (nx, ny, window, on, want_steps.tolist(), want_conv.tolist()))
-    assert np.any(want_conv) and len(set(want_steps.tolist())) >= 2
-    with ensemble() as ens:
-        steps, conv = ens.run_until(cap, window=window, rel_tol=TOL, on=on)
-        assert steps.tolist() == want_steps.tolist() and conv.tolist() == want_conv.tolist()
-        cells, av = ens.download()
-        fx, fy = ens.force_record()
-        now = ens.force()
-    for k, p in enumerate(params):
-        c = int(steps[k])
-        with lbm.LBMDouble(p, ob) as sim:
-            sim.set_option("force", 1)
-            sim.set_wall(u_x, u_y, rhos[k])
-            sim.set_les(CS[k])
-            sim.upload(None)
-            sim.run(c)
-            rc, rav = sim.download()
-            rfx, rfy = sim.force_record()
-            assert np.array_equal(cells[k], rc), k
-            assert np.array_equal(av[k, :c], rav), k
-            assert np.array_equal(fx[k, :c], rfx) and np.array_equal(fy[k, :c], rfy), k
-            assert (now[0][k], now[1][k]) == sim.force(), k
-    # the model changes it: without the setting the member is another flow
-    with lbm.LBMDouble(params[3], ob) as sim:
-        sim.set_wall(u_x, u_y, rhos[3])
-        sim.upload(None)
-        sim.run(int(steps[3]))
-        assert not np.array_equal(sim.download(av_vels=False)[0], cells[3])
+    def set_member(sim, k):
+        sim.set_wall(u_x, u_y, rhos[k])
+        sim.set_les(CS[k])
+
+    # the model changes it: with the lid alone member 3 is another flow
+    dm.check_a_member_stopped_by_run_until(lbm, on, set_ensemble, set_member, "moving lid %dx%d with the model",
+                                           (3, lambda sim: sim.set_wall(u_x, u_y, rhos[3])))
 
 
 # ---- 5. errors and what keeps the setting --------------------------------------------------------------------------------
@@ -269,8 +134,8 @@ def test_errors_and_what_keeps_the_setting(lbm, oracle_f64):
     nx, ny = 17, 16
     case = matrix_case(lbm, nx, ny, 0, 0, 0, 0, None)
     m = case.members[0]
-    want = _les_ref.reference_step(oracle_f64, m.p, m.ob, None, m.cells0, None, None, None, 0.17)[0]
-    plain = _les_ref.reference_step(oracle_f64, m.p, m.ob, None, m.cells0, None, None, None, None)[0]
+    want = dm.reference_step(oracle_f64, m.p, m.ob, None, m.cells0, None, None, None, 0.17)[0]
+    plain = dm.reference_step(oracle_f64, m.p, m.ob, None, m.cells0, None, None, None, None)[0]
     assert not np.array_equal(want, plain)
     with lbm.LBMDouble(m.p, m.ob) as sim:
         assert sim.les() == (0.0, 0.0)                                            # off by default
@@ -297,7 +162,7 @@ def test_errors_and_what_keeps_the_setting(lbm, oracle_f64):
         assert np.array_equal(sim.download(av_vels=False)[0], want)
         # the model and TRT in either order
         magic = 3.0 / 16.0
-        both = _les_ref.reference_step(oracle_f64, m.p, m.ob, None, m.cells0, magic, None, None, 0.17)[0]
+        both = dm.reference_step(oracle_f64, m.p, m.ob, None, m.cells0, magic, None, None, 0.17)[0]
         sim.upload(m.cells0)
         sim.set_trt(magic)                                                        # the model first, TRT second
         sim.run(1)
@@ -312,7 +177,7 @@ def test_errors_and_what_keeps_the_setting(lbm, oracle_f64):
     ms = case.members
     cs = np.array([0.1, 0.17, 0.3])
     start = np.stack([q.cells0 for q in ms])
-    wants = np.stack([_les_ref.reference_step(oracle_f64, q.p, q.ob, None, q.cells0, None, None, None, float(c))[0] for q, c in zip(ms, cs)])
+    wants = np.stack([dm.reference_step(oracle_f64, q.p, q.ob, None, q.cells0, None, None, None, float(c))[0] for q, c in zip(ms, cs)])
     with lbm.EnsembleDouble([q.p for q in ms], np.stack([q.ob for q in ms])) as ens:
         assert not np.any(ens.les()[0])
         ens.set_les(cs)

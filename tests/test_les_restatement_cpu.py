@@ -20,10 +20,10 @@ import _les_ref
 import _open_ref
 import _trt_ref
 import _wall_ref
+from _les_ref import GATE, couette_figures
 from _wall_ref import COUETTE
 
 U53 = 2.0 ** -53
-GATE = 1e-4
 _couette, _cavity = {}, {}
 
 
@@ -88,25 +88,6 @@ def couette_run(trt):
             f, _ = _les_ref.step(f, ob, c["omega"], c["magic"] if trt else None, wall=(u_x, u_y, c["rho"]), c=_les_ref.COUETTE_C)
         _couette[trt] = (before, f)
     return _couette[trt]
-
-
-def couette_figures(before, f):
-    """(relative error of F_x on the top wall, on the bottom wall, the same against the molecular viscosity alone, profile error
-    over U) from the state the last step streamed and the settled state"""
-    from test_body_gpu import body_restatement
-    c = COUETTE
-    ob, _, _ = _wall_ref.couette_maps()
-    want = _les_ref.couette_force(c["nx"], c["ny"], c["U"], c["rho"], c["omega"], _les_ref.COUETTE_C)
-    plain = _wall_ref.couette_force(c["nx"], c["ny"], c["U"], c["rho"], c["omega"])
-    rel = []
-    for row, sign in ((c["ny"] - 1, -1.0), (0, +1.0)):
-        body = np.zeros_like(ob)
-        body[row] = 1
-        fx, _, links, _ = body_restatement(before, ob, body)
-        assert links == 3 * c["nx"]
-        rel.append((abs(fx - sign * want) / want, abs(fx - sign * plain) / plain))
-    err = float(np.max(np.abs(_wall_ref.column_velocity(f, c["nx"] // 2) - _wall_ref.couette_profile(c["ny"], c["U"])))) / c["U"]
-    return rel[0][0], rel[1][0], min(rel[0][1], rel[1][1]), err
 
 
 @pytest.mark.parametrize("trt", [False, True])

@@ -18,11 +18,9 @@ import pytest
 
 import _open_ref
 import _trt_ref
-from test_body_gpu import block_body
-from test_dp_ensemble_gpu import RUNS
-from test_dp_gpu import random_state
-from test_dp_steady_gpu import CAP, OMEGAS, TOL, rule, sweep
-from test_force_gpu import accelerated
+from _dp_states import RUNS, random_state
+from _force_ref import accelerated, block_body
+from _steady_rule import CAP, OMEGAS, TOL, rule, sweep
 
 pytestmark = pytest.mark.gpu
 

@@ -19,7 +19,7 @@ import pytest
 
 import _open_ref
 import _trt_ref
-from test_dp_gpu import random_state
+from _dp_states import random_state
 
 MAGIC = 3.0 / 16.0
 ULP1 = 2.0 ** -52

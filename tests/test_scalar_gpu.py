@@ -1,9 +1,10 @@
 """The passive scalar (include/lbm.h, "Scalar transport"; lbm_dscalar_*) on the GPU: dp_scalar_step and its helper kernels against
 tests/_scalar_ref.py, the flow beside it against the flow without it, and the flows with known answers end to end.
 
-The cases, masks, inputs and handle factories of the flow are those of tests/_dp_matrix.py and tests/test_drive_gpu.py, imported and
-not edited: a case has three members, each with its own obstacle map (walls, a block, lips and isolated cells), omega and state, and
-here its own diffusivity (0.01, 1/6, 0.4), first field, c_wall (NaN and finite values mixed) and inlet values.
+The cases, masks, inputs and drivers of the flow are tests/_dp_matrix.py's (make_case with `scalar`; open_context and open_ensemble
+set the scalar last, behind the upload): a case has three members, each with its own obstacle map (walls, a block, lips and isolated
+cells), omega and state, and here its own diffusivity (0.01, 1/6, 0.4), first field, c_wall (NaN and finite values mixed) and inlet
+values.
 
   1. bits: 33x19 and 17x16 (odd nx, a lane without its second cell, a last segment that is not full), the flow with all options
      off, each of FORCE, TRT, OPEN, WALL, LES and DRIVE alone and all on, LBMDouble at "multistep" 0 and 8 and EnsembleDouble, runs
@@ -37,16 +38,14 @@ import pytest
 
 import _dp_matrix as dm
 import _scalar_ref as sref
-import test_drive_gpu as tdg
-from test_force_gpu import accelerated
-from test_wall_gpu import narrow_case
+from _dp_matrix import DS, set_scalars
+from _force_ref import accelerated
 
 pytestmark = pytest.mark.gpu
 
 LBM_ERR_ARG, LBM_ERR_STATE = 1, 3
-SHAPES = [(33, 19), (17, 16)]
-RUNS = [1, 1, 1, 7]
-DS = [0.01, 1.0 / 6.0, 0.4]
+SHAPES = dm.SHAPES
+RUNS = dm.RUNS
 #          force trt open wall les drive
 OPTIONS = [(0, 0, 0, 0, 0, 0), (1, 0, 0, 0, 0, 0), (0, 1, 0, 0, 0, 0), (0, 0, 1, 0, 0, 0), (0, 0, 0, 1, 0, 0), (0, 0, 0, 0, 1, 0),
            (0, 0, 0, 0, 0, 1), (1, 1, 1, 1, 1, 1)]
@@ -66,38 +65,24 @@ def fix():
         return json.load(f)
 
 
-def with_scalar(case):
-    """the case with a scalar per member: D, c0 in 0.5 .. 1.5, c_wall NaN on half the cells and 0 .. 2 on the others, c_in per row"""
-    for k, m in enumerate(case.members):
-        rng = np.random.default_rng(9000 + 100 * case.nx + 10 * case.ny + k)
-        wall = 2.0 * rng.random((case.ny, case.nx))
-        wall[rng.random((case.ny, case.nx)) < 0.5] = np.nan
-        m.scalar = SimpleNamespace(D=DS[k], c0=0.5 + rng.random((case.ny, case.nx)), wall=wall, inlet=0.5 + rng.random(case.ny))
-        blocked = m.ob != 0
-        assert np.any(np.isnan(wall[blocked])) and np.any(np.isfinite(wall[blocked]))
-    return case
-
-
 def make_case(lbm, nx, ny, opts, steps=sum(RUNS)):
+    """the matrix case with a scalar per member (dm.member_scalar)"""
     force, trt, opened, wall, les, drive = opts
-    return with_scalar(tdg.with_drive(dm.make_case(lbm, nx, ny, 3, steps, force, trt, opened), "on" if drive else None, wall, les))
+    return dm.make_case(lbm, nx, ny, 3, steps, force, trt, opened, wall="on" if wall else None, les="on" if les else None,
+                        drive="on" if drive else None, scalar=True)
 
 
 def narrow(lbm):
-    case = narrow_case(lbm)
-    for k, m in enumerate(case.members):
-        m.les = None
-        m.drive_on = m.drive = tdg.FORCES[k]
-    return with_scalar(case)
+    return dm.narrow_case(lbm, drive="on", scalar=True)
 
 
 def reference_of(oracle_f64, key, case, steps):
-    """per member: the flow's reference states (test_drive_gpu.reference_run) and the scalar's populations after every step"""
+    """per member: the flow's reference states (dm.reference_run) and the scalar's populations after every step"""
     if key in _refs:
         return _refs[key]
     out = []
     for m in case.members:
-        flow = tdg.reference_run(oracle_f64, m, steps)
+        flow = dm.reference_run(oracle_f64, m, steps)
         drive = m.drive if isinstance(m.drive, tuple) else None
         g = [sref.init(m.scalar.c0)]
         for n in range(steps):
@@ -115,26 +100,13 @@ def reference_of(oracle_f64, key, case, steps):
     return out
 
 
-def set_scalars(handle, members):
-    s = [m.scalar for m in members]
-    if len(s) == 1:
-        handle.set_scalar(s[0].D, s[0].c0, s[0].wall, s[0].inlet)
-    else:
-        handle.set_scalar([x.D for x in s], np.stack([x.c0 for x in s]), np.stack([x.wall for x in s]), np.stack([x.inlet for x in s]))
-    D, om = handle.scalar()
-    assert np.array_equal(np.atleast_1d(D), [x.D for x in s])
-    assert np.array_equal(np.atleast_1d(om), [sref.omega_s(x.D) for x in s])
-
-
 def drive(lbm, family, case, runs, scalar=True, between=None):
-    """per member: the flow's state after each run, av_vels, the force record, force() before each run, and with a scalar its
-    populations and field after each run.  between(handle): called behind every run but the last"""
-    inner = tdg.driven(lbm, case)
+    """per member: the flow's state after each run, av_vels, the force record, force() before each run, and with a scalar
+    (set behind the upload by dm.open_context / dm.open_ensemble) its populations and field after each run.  between(handle):
+    called behind every run but the last"""
     results = []
 
-    def loop(handle, members):
-        if scalar:
-            set_scalars(handle, members)
+    def loop(handle):
         states, now, g, c = [], [], [], []
         for i, r in enumerate(runs):
             now.append(handle.force())
@@ -149,16 +121,16 @@ def drive(lbm, family, case, runs, scalar=True, between=None):
         return states, now, g, c, av, (handle.force_record() if case.force else None)
 
     if family == "ensemble":
-        with dm.open_ensemble(inner, case) as ens:
-            states, now, g, c, av, rec = loop(ens, case.members)
+        with dm.open_ensemble(lbm, case, scalar=scalar) as ens:
+            states, now, g, c, av, rec = loop(ens)
         for k in range(case.n):
             results.append(SimpleNamespace(states=[s[k] for s in states], av=av[k], fx=None if rec is None else rec[0][k],
                                            fy=None if rec is None else rec[1][k], now=[(float(a[k]), float(b[k])) for a, b in now],
                                            g=[x[k] for x in g], c=[x[k] for x in c]))
     else:
         for m in case.members:
-            with dm.open_context(inner, case, m, family) as sim:
-                states, now, g, c, av, rec = loop(sim, [m])
+            with dm.open_context(lbm, case, m, family, scalar=scalar) as sim:
+                states, now, g, c, av, rec = loop(sim)
             results.append(SimpleNamespace(states=states, av=av, fx=None if rec is None else rec[0], fy=None if rec is None else rec[1],
                                            now=now, g=g, c=c))
     return results
@@ -263,8 +235,7 @@ def test_off_is_off_and_on_is_on(lbm, family):
     opts = (1, 0, 0, 0, 0, 0)
     case = make_case(lbm, nx, ny, opts)
     never = run_of(lbm, (nx, ny) + opts, family, case, RUNS, scalar=False)
-    inner = tdg.driven(lbm, case)
-    handles = ([dm.open_ensemble(inner, case)] if family == "ensemble" else [dm.open_context(inner, case, m, family) for m in case.members])
+    handles = ([dm.open_ensemble(lbm, case)] if family == "ensemble" else [dm.open_context(lbm, case, m, family) for m in case.members])
     for i, h in enumerate(handles):
         members = case.members if family == "ensemble" else [case.members[i]]
         with h:

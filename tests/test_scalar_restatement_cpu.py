@@ -65,8 +65,8 @@ def test_the_pieces():
 
 def test_accelerate_is_the_oracles():
     from oracle.oracle import Oracle
-    from test_dp_gpu import random_state
-    from test_force_gpu import accelerated, oracle_params    # noqa: F401
+    from _dp_states import random_state
+    from _force_ref import accelerated
     from types import SimpleNamespace
     orc = Oracle("f64")
     ny, nx = 12, 13

@@ -16,11 +16,9 @@ import numpy as np
 import pytest
 
 import _trt_ref
-from test_body_gpu import block_body
-from test_dp_ensemble_gpu import RUNS
-from test_dp_gpu import MASS_REL, random_state
-from test_dp_steady_gpu import CAP, OMEGAS, TOL, rule, sweep
-from test_force_gpu import accelerated, case, force_mask
+from _dp_states import MASS_REL, RUNS, random_state
+from _force_ref import accelerated, block_body, case, force_mask
+from _steady_rule import CAP, OMEGAS, TOL, rule, sweep
 
 pytestmark = pytest.mark.gpu
 

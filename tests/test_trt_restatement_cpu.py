@@ -2,24 +2,20 @@
 control that makes the bit comparison of tests/test_trt_gpu.py mean something.
 
   1. in BGK mode it equals the fp64 oracle's pairwise no-FMA build (the statements dp_collide_cell restates) bit for bit;
-  2. in TRT mode a step conserves mass to test_dp_gpu's MASS_REL;
-  3. in TRT mode the fluid momentum it takes out of a step is the momentum-exchange force of test_force_gpu.restatement, within
-     that file's gate 2 (2 9N 2^-53 sum|f|);
+  2. in TRT mode a step conserves mass to _dp_states.MASS_REL;
+  3. in TRT mode the fluid momentum it takes out of a step is the momentum-exchange force of _force_ref.restatement, within
+     gate 2 of tests/test_force_gpu.py (2 9N 2^-53 sum|f|);
   4. Lambda = 1/4 at omega = 1 gives omega_m = 1 exactly, and that degenerate TRT step stays within 2^-53 (2|out| + 6|out - g|)
      of the BGK step: five more roundings of the increment (a + b, a - b, their halves are exact, rp + rm; |a + b| / 2 and
      |a - b| / 2 counted with |out - g| each, hence 6 with the BGK increment's own) and the two final additions."""
-import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import _trt_ref
-from conftest import ROOT
-from test_dp_gpu import MASS_REL, oracle_params
-from test_force_gpu import case, fluid_momentum, restatement
+from _dp_states import MASS_REL, build_oracle_nofma, oracle_params
+from _force_ref import accelerated, case, fluid_momentum, restatement
 
 U = 2.0 ** -53
 SHAPES = [(3, 3), (16, 16), (33, 19), (48, 35)]
@@ -29,27 +25,7 @@ STEPS = 40
 
 @pytest.fixture(scope="module")
 def oracle_nofma(tmp_path_factory):
-    """oracle/d2q9_oracle.c in double with pairwise momenta and contraction off, built as test_dp_gpu.oracle_fma builds its
-    contracted twin"""
-    out = str(tmp_path_factory.mktemp("oracle_nofma") / "liboracle_f64_pairwise.so")
-    src = os.path.join(ROOT, "oracle", "d2q9_oracle.c")
-    subprocess.run(["gcc", "-std=c99", "-O3", "-march=native", "-fPIC", "-DREAL=double", "-DORACLE_PAIRWISE=1",
-                    "-ffp-contract=off", "-shared", src, "-o", out, "-lm"], check=True)
-    from oracle.oracle import Oracle
-    o = Oracle("f64")
-    base = o.lib
-    o.lib = ctypes.CDLL(out)
-    for name in ("oracle_accelerate_flow", "oracle_timestep"):
-        f, g = getattr(o.lib, name), getattr(base, name)
-        f.argtypes, f.restype = g.argtypes, g.restype
-    assert o.lib.oracle_pairwise_momentum() == 1 and o.lib.oracle_real_size() == 8
-    return o
-
-
-def accelerated(orc, p, ob, cells):
-    f = np.array(cells, dtype=np.float64, copy=True)
-    orc.accelerate_flow(oracle_params(orc, p), f, ob)
-    return f
+    return build_oracle_nofma(tmp_path_factory)
 
 
 @pytest.mark.parametrize("nx,ny", SHAPES)

@@ -6,7 +6,7 @@ that is not finite and positive and four NULL outputs, before anything of the ha
 
 On the GPU (marked): every refusal that needs a handle - an entry that is not finite, a non-zero entry on a fluid cell (the
 message names the cell, and the member), a bad rho_wall per member, LBM_ERR_STATE after a step.  After each refusal wall()
-returns the previous setting and a step equals the previous setting's reference (tests/_wall_ref.py), bit for bit.  Set, get,
+returns the previous setting and a step equals the previous setting's reference (tests/_dp_matrix.reference_step), bit for bit.  Set, get,
 off round trip; upload and upload_obstacles keep the setting, and a velocity is read only while its cell is blocked."""
 import ctypes
 import os
@@ -15,7 +15,7 @@ import re
 import numpy as np
 import pytest
 
-import _wall_ref
+import _dp_matrix as dm
 from conftest import ROOT
 
 LBM_ERR_ARG, LBM_ERR_STATE = 1, 3
@@ -138,7 +138,7 @@ def oracle_f64():
 
 def wall_case(lbm, steps=8):
     """walls on rows 0 and NY - 1 and a block; every blocked cell moves but the bottom wall"""
-    from test_dp_gpu import random_state
+    from _dp_states import random_state
     rng = np.random.default_rng(99)
     ob = np.zeros((NY, NX), dtype=np.int32)
     ob[0] = ob[NY - 1] = 1
@@ -164,8 +164,8 @@ def test_context_refusals_leave_the_setting(lbm, oracle_f64):
     p, ob, cells0, u_x, u_y = wall_case(lbm)
     rho = 0.0985
     wall = (u_x, u_y, rho)
-    want, _, _ = _wall_ref.reference_step(oracle_f64, p, ob, None, cells0, None, None, wall)
-    plain, _, _ = _wall_ref.reference_step(oracle_f64, p, ob, None, cells0, None, None, None)
+    want, _, _ = dm.reference_step(oracle_f64, p, ob, None, cells0, None, None, wall)
+    plain, _, _ = dm.reference_step(oracle_f64, p, ob, None, cells0, None, None, None)
     assert not np.array_equal(want, plain)
     on = ctypes.c_int()
     with lbm.LBMDouble(p, ob) as sim:
@@ -222,7 +222,7 @@ def test_context_refusals_leave_the_setting(lbm, oracle_f64):
 @pytest.mark.gpu
 def test_context_round_trip_and_what_keeps_the_setting(lbm, oracle_f64):
     p, ob, cells0, u_x, u_y = wall_case(lbm)
-    plain, _, _ = _wall_ref.reference_step(oracle_f64, p, ob, None, cells0, None, None, None)
+    plain, _, _ = dm.reference_step(oracle_f64, p, ob, None, cells0, None, None, None)
     with lbm.LBMDouble(p, ob) as sim:
         sim.set_wall(u_x, u_y)                                                    # rho_wall None: the params' density
         assert same_setting(sim.wall(), u_x, u_y, p.density)
@@ -234,7 +234,7 @@ def test_context_round_trip_and_what_keeps_the_setting(lbm, oracle_f64):
         assert np.array_equal(sim.download(av_vels=False)[0], plain)
         sim.upload(cells0)
         sim.set_wall(u_x, u_y, 0.102)
-        want, _, _ = _wall_ref.reference_step(oracle_f64, p, ob, None, cells0, None, None, (u_x, u_y, 0.102))
+        want, _, _ = dm.reference_step(oracle_f64, p, ob, None, cells0, None, None, (u_x, u_y, 0.102))
         sim.run(1)
         assert np.array_equal(sim.download(av_vels=False)[0], want)
         sim.upload(cells0)                                                        # uploads keep the setting
@@ -251,7 +251,7 @@ def test_context_round_trip_and_what_keeps_the_setting(lbm, oracle_f64):
         sim.upload_obstacles(other)
         assert same_setting(sim.wall(), u_x, u_y, 0.102)
         po = lbm.make_dparams(NX, NY, 8, density=0.1, accel=0.005, omega=1.3, obstacles=other)
-        moved, _, _ = _wall_ref.reference_step(oracle_f64, po, other, None, cells0, None, None, (u_x, u_y, 0.102))
+        moved, _, _ = dm.reference_step(oracle_f64, po, other, None, cells0, None, None, (u_x, u_y, 0.102))
         sim.run(1)
         assert np.array_equal(sim.download(av_vels=False)[0], moved)
 
@@ -266,7 +266,7 @@ def test_ensemble_refusals_round_trip_and_uploads(lbm, oracle_f64):
     uy = np.stack([u_y, u_y, 0.25 * u_y])
     rhos = np.array([0.1, 0.102, 0.099])
     start = np.stack([cells0] * n)
-    want = np.stack([_wall_ref.reference_step(oracle_f64, params[m], ob, None, cells0, None, None, (ux[m], uy[m], rhos[m]))[0]
+    want = np.stack([dm.reference_step(oracle_f64, params[m], ob, None, cells0, None, None, (ux[m], uy[m], rhos[m]))[0]
                      for m in range(n)])
     with lbm.EnsembleDouble(params, ob) as ens:
         assert ens.wall() is None
@@ -318,5 +318,5 @@ def test_ensemble_refusals_round_trip_and_uploads(lbm, oracle_f64):
         ens.set_wall(None, None)
         assert ens.wall() is None
         ens.run(1)
-        plain = np.stack([_wall_ref.reference_step(oracle_f64, params[m], ob, None, cells0, None, None, None)[0] for m in range(n)])
+        plain = np.stack([dm.reference_step(oracle_f64, params[m], ob, None, cells0, None, None, None)[0] for m in range(n)])
         assert np.array_equal(ens.download(av_vels=False)[0], plain)

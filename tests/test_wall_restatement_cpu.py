@@ -15,25 +15,8 @@ import pytest
 import _open_ref
 import _trt_ref
 import _wall_ref
-from _wall_ref import COUETTE
-
-_couette = {}
-
-
-def couette_run(trt):
-    """the settled state of the Couette case and the state one step before it (what the last step streamed), once per
-    operator"""
-    if trt not in _couette:
-        c = COUETTE
-        ob, u_x, u_y = _wall_ref.couette_maps()
-        om = _trt_ref.omega_minus(c["omega"], c["magic"]) if trt else None
-        f = _open_ref.rest_state(c["rho"], c["ny"], c["nx"])
-        before = f
-        for _ in range(c["steps"]):
-            before = f
-            f, u = _wall_ref.step(f, ob, c["omega"], om, wall=(u_x, u_y, c["rho"]))
-        _couette[trt] = (before, f, u)
-    return _couette[trt]
+from _force_ref import body_restatement
+from _wall_ref import COUETTE, couette_run
 
 
 @pytest.mark.parametrize("trt", [False, True])
@@ -54,7 +37,6 @@ def test_couette_profile_is_linear(trt):
 
 @pytest.mark.parametrize("trt", [False, True])
 def test_couette_wall_forces_are_the_shear(trt):
-    from test_body_gpu import body_restatement
     c = COUETTE
     before, _, _ = couette_run(trt)
     ob, _, _ = _wall_ref.couette_maps()
