@@ -1182,6 +1182,74 @@ int lbm_dscalar_ens_field(lbm_dens *e, double *c_out /*[n][ny][nx]*/);
 int lbm_dscalar_ens_download(lbm_dens *e, double *g_out /*[n][5][ny][nx]*/);
 int lbm_dscalar_ens_upload(lbm_dens *e, const double *g /*[n][5][ny][nx]*/);
 
+/*
+ * ---- Buoyancy: the scalar acts back on the flow, for the double-precision families ------------------------------------------------
+ *
+ * "Body force" carries one constant force per grid and "Scalar transport" a field the flow never reads; each names the other's
+ * missing half as out of scope ("a force proportional to the local density" was the nearest wording there, "a scalar that acts
+ * back on the flow (buoyancy)" here).  This section lifts those two remarks: a handle with a scalar on may carry a buoyancy
+ * b = (b_x, b_y) and a reference value c_ref, and every fluid cell then takes a force density that follows its own scalar value,
+ * the Boussinesq coupling.  That is natural convection in double precision: Rayleigh-Benard layers, heated cavities, plumes, and a
+ * sweep over Rayleigh numbers in one ensemble.  Off by default.  The reference has no counterpart.
+ *
+ * Definition.  All in double, contraction off, one IEEE operation per written operator, in this order.  With g[0..4] the cell's
+ * five STORED scalar values (the reported field of "Scalar transport") and F0 = (F0_x, F0_y) the body force of lbm_ddrive_set,
+ * (0.0, 0.0) while that is off, every FLUID cell takes the force density
+ *     C = (((g[0] + g[1]) + g[2]) + g[3]) + g[4];
+ *     d = C - c_ref;
+ *     F_x = F0_x + b_x * d;
+ *     F_y = F0_y + b_y * d;
+ * As with lbm_ddrive_*, the force is NOT multiplied by the cell's density: the acceleration is b d / rho, and a layer of H fluid
+ * rows between half-way walls held dC apart has Ra = (|b| dC / rho0) H^3 / (nu kappa).  F stands wherever "Body force" has its
+ * constant F: in the half shift of the two momenta, in the source (uF, cF[k], se[k], so[k]), under pe and po; the subgrid rates read
+ * the shifted momenta.  Blocked cells take no force.
+ *
+ * Which scalar state is read.  Everything is a function of the two current states.  Scalar step n still runs before flow step n.
+ * Scalar step n forms each cell's F from the scalar array it reads, state n - the force the flow's stored state n already carries -
+ * and the velocity it advects with is the output stage's, less half of this F.  Flow step n then forms F from the scalar array
+ * that scalar step n has just written, state n + 1.  So after any number of steps the stored flow state carries the force of the
+ * scalar state that is current, and the output stage (lbm_dp_final_state, lbm_dens_final_state and the Reynolds numbers) subtracts
+ * 0.5 * F_x and 0.5 * F_y of the current scalar state, per cell, from the two momentum sums.  An uploaded state that has not yet
+ * been stepped is read the same way, the rule of "Body force".
+ *
+ * Kernels.  While buoyancy is on the scalar step is dp_scalar_step<true> and the flow step d2q9_dp_buoyant, one step per launch
+ * in both families: there is ONE kernel form, and the option "multistep" chooses nothing.  Nothing else moves: accelerate_flow, the
+ * boundary fix, moving walls, the subgrid model, TRT, the momentum-exchange force and its record, the order of every sum.  With
+ * buoyancy off the passive path runs and keeps every bit.  Bit identities: a member of a double-precision ensemble equals a
+ * double-precision context with the same settings; launch splits agree; a download followed by an upload of both states changes
+ * nothing; with C == c_ref on every cell for ever (c0 = 0, c_ref = 0, insulating walls) the flow equals the flow under the body
+ * force F0 alone, bit for bit.
+ *
+ * When it is accepted.  Only with a scalar on, and only while steps_done is 0 (the rule of lbm_ddrive_set): otherwise
+ * LBM_ERR_STATE.  (0, 0) on a context means off, and is accepted with the scalar off too.  An ensemble has buoyancy on for all
+ * members, each with its own triple (b_x, b_y, c_ref), or off (NULL); a member whose b is (0, 0) is refused, the twin rule of
+ * lbm_ddrive_ens_set.  Switching the scalar off while buoyancy is on is LBM_ERR_STATE; setting the scalar again, or
+ * lbm_dscalar_upload, while buoyancy is on is allowed.  lbm_dp_upload, lbm_dens_upload and lbm_dp_upload_obstacles keep the
+ * setting.  Everything is checked before anything changes.  Steady runs stay refused while a scalar is on.
+ *
+ * Names: lbm_dbuoy_*, on both double-precision handles.  Out of scope: fp32 contexts and fp32 ensembles, which get nothing; the
+ * LDS-tile kernels, a fused scalar + flow tile form included; more than one scalar; a density-weighted force; a viscosity that
+ * depends on the scalar; switching buoyancy on into a developed flow.
+ */
+
+/* Set the buoyancy of a double-precision context: b = (0, 0) is off (the default).  LBM_ERR_ARG, before the context is read: a
+ * NULL context, a component or c_ref that is NaN or infinite.  LBM_ERR_STATE: b is not (0, 0) and the scalar is off; steps done.
+ * Synchronises. */
+int lbm_dbuoy_set(lbm_dp *d, double b_x, double b_y, double c_ref);
+
+/* on_out: 1 while buoyancy is on, else 0; b_out = double[2] and c_ref_out, zeros while it is off.  Any output may be NULL; all NULL
+ * (on_out, b_out and c_ref_out), or a NULL context: LBM_ERR_ARG. */
+int lbm_dbuoy_get(const lbm_dp *d, int *on_out, double *b_out /*[2]*/, double *c_ref_out);
+
+/* The same for a double-precision ensemble: b = double[n][3], b_x, b_y, c_ref of every member, members may differ; NULL: off for
+ * all members.  LBM_ERR_ARG, the message names the member: a value that is NaN or infinite, a member whose b is (0, 0).
+ * LBM_ERR_STATE: the scalar is off; steps done.  Synchronises. */
+int lbm_dbuoy_ens_set(lbm_dens *e, const double *b /*[n][3] or NULL*/);
+
+/* on_out: 1 while buoyancy is on, else 0; b_out = double[n][3], zeros while it is off.  Either output may be NULL; both NULL (on_out
+ * and b_out), or a NULL ensemble: LBM_ERR_ARG. */
+int lbm_dbuoy_ens_get(const lbm_dens *e, int *on_out, double *b_out /*[n][3]*/);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "lbm_ddrive_set", "lbm_ddrive_get", "lbm_ddrive_ens_set", "lbm_ddrive_ens_get",
     "lbm_dscalar_set", "lbm_dscalar_get", "lbm_dscalar_field", "lbm_dscalar_download", "lbm_dscalar_upload",
     "lbm_dscalar_ens_set", "lbm_dscalar_ens_get", "lbm_dscalar_ens_field", "lbm_dscalar_ens_download", "lbm_dscalar_ens_upload",
+    "lbm_dbuoy_set", "lbm_dbuoy_get", "lbm_dbuoy_ens_set", "lbm_dbuoy_ens_get",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -198,6 +199,10 @@ def load_library():
     L.lbm_dscalar_ens_field.argtypes = [vp, vp]
     L.lbm_dscalar_ens_download.argtypes = [vp, vp]
     L.lbm_dscalar_ens_upload.argtypes = [vp, vp]
+    L.lbm_dbuoy_set.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+    L.lbm_dbuoy_get.argtypes = [vp, ctypes.POINTER(ci), vp, ctypes.POINTER(ctypes.c_double)]
+    L.lbm_dbuoy_ens_set.argtypes = [vp, vp]
+    L.lbm_dbuoy_ens_get.argtypes = [vp, ctypes.POINTER(ci), vp]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -724,6 +729,20 @@ class LBMDouble(_Handle):
         assert a.shape == (5, self.ny, self.nx)
         _check(self.lib.lbm_dscalar_upload(self.ctx, a.ctypes.data), "lbm_dscalar_upload")
 
+    def set_buoyancy(self, b, c_ref=0.0):
+        """Buoyancy (lbm_dbuoy_set): b = (b_x, b_y); every fluid cell takes the force density F0 + b (C - c_ref), C its scalar
+        value and F0 the body force of set_drive.  (0, 0) or None = off, the default.  Needs a scalar on; only before the first
+        step."""
+        b_x, b_y = (0.0, 0.0) if b is None else b
+        _check(self.lib.lbm_dbuoy_set(self.ctx, float(b_x), float(b_y), float(c_ref)), "lbm_dbuoy_set")
+
+    def buoyancy(self):
+        """((b_x, b_y), c_ref) while buoyancy is on, None while it is off (lbm_dbuoy_get)"""
+        on, c_ref = ctypes.c_int(), ctypes.c_double()
+        b = np.zeros(2, dtype=np.float64)
+        _check(self.lib.lbm_dbuoy_get(self.ctx, ctypes.byref(on), b.ctypes.data, ctypes.byref(c_ref)), "lbm_dbuoy_get")
+        return ((float(b[0]), float(b[1])), c_ref.value) if on.value else None
+
     def force_record(self):
         """(F_x float64[steps_done], F_y float64[steps_done]): the force of every step since the upload; needs
         set_option("force", 1) before the first step."""
@@ -1054,6 +1073,25 @@ class EnsembleDouble(_EnsembleOf):
         a = np.ascontiguousarray(g, dtype=np.float64)
         assert a.shape == (self.n, 5, self.ny, self.nx)
         _check(self.lib.lbm_dscalar_ens_upload(self.ens, a.ctypes.data), "lbm_dscalar_ens_upload")
+
+    def set_buoyancy(self, b, c_ref=0.0):
+        """Buoyancy of all members (lbm_dbuoy_ens_set): b one pair (b_x, b_y) for all or an array-like [n, 2], no member (0, 0);
+        c_ref one value for all or an array-like of n.  None = off, the default.  Needs the scalars on; only before the first
+        step."""
+        if b is None:
+            _check(self.lib.lbm_dbuoy_ens_set(self.ens, None), "lbm_dbuoy_ens_set")
+            return
+        v = np.empty((self.n, 3), dtype=np.float64)
+        v[:, :2] = np.asarray(b, dtype=np.float64)
+        v[:, 2] = np.asarray(c_ref, dtype=np.float64)
+        _check(self.lib.lbm_dbuoy_ens_set(self.ens, v.ctypes.data), "lbm_dbuoy_ens_set")
+
+    def buoyancy(self):
+        """float64[n, 3], per member b_x, b_y, c_ref, while buoyancy is on, None while it is off (lbm_dbuoy_ens_get)"""
+        on = ctypes.c_int()
+        b = np.zeros((self.n, 3), dtype=np.float64)
+        _check(self.lib.lbm_dbuoy_ens_get(self.ens, ctypes.byref(on), b.ctypes.data), "lbm_dbuoy_ens_get")
+        return b if on.value else None
 
     def run_until(self, max_steps, window=64, rel_tol=1e-4, on="av_vels"):
         """_EnsembleOf.run_until with a choice of criterion: on="av_vels" (lbm_dsteady_run), or on="drag"

@@ -1,13 +1,17 @@
 // Where lbm_dp.cpp and lbm_dens.cpp drive the helper kernels of dp_kernels.h with the same statements: the second reduction
-// stage, the force of the current state and the passive scalar (dp_scalar_kernels.h), for `members` grids (a context: 1).  Plain functions over the fields they need,
+// stage, the force of the current state, the scalar (dp_scalar_kernels.h) and buoyancy (dp_buoyant_kernels.h), for `members` grids
+// (a context: 1).  Plain functions over the fields they need,
 // as host_common.h's; static, because the kernels they launch are each unit's own copies.
 #pragma once
+#include "dp_buoyant_kernels.h"
 #include "dp_kernels.h"
 #include "dp_scalar_kernels.h"
 #include "host_common.h"
 
 #include <cstdio>
+#include <cstring>
 #include <limits>
+#include <vector>
 
 namespace lbm_host {
 
@@ -176,9 +180,11 @@ static inline int scalar_set(ScalarState &s, const ScalarGrid &gr, hipStream_t s
   return LBM_OK;
 }
 
-// One scalar step of all members on the flow state `flow` (the array the flow's next launch streams), enqueued; flips s.cur
-static inline int scalar_step(ScalarState &s, const ScalarGrid &gr, hipStream_t st, const double *flow, const uint8_t *mask, bool open) {
-  lbm::DpScalarArgs a{};
+// One scalar step of all members on the flow state `flow` (the array the flow's next launch streams), enqueued; flips s.cur.
+// buoy: NULL (the passive scalar), or the members' buoyant constants (dp_scalar_step<true>)
+static inline int scalar_step(ScalarState &s, const ScalarGrid &gr, hipStream_t st, const double *flow, const uint8_t *mask, bool open,
+                              const lbm::DpBuoyMember *buoy = nullptr) {
+  lbm::DpScalarBuoyArgs a{};
   a.flow = flow;
   a.src = s.g[s.cur];
   a.dst = s.g[s.cur ^ 1];
@@ -191,8 +197,10 @@ static inline int scalar_step(ScalarState &s, const ScalarGrid &gr, hipStream_t 
   a.ny = gr.ny;
   a.lanes_per_row = gr.lanes_per_row();
   a.open = open ? 1 : 0;
-  hipLaunchKernelGGL(lbm::dp_scalar_step, dim3((unsigned)div_up((long)a.lanes_per_row * gr.ny, lbm::kBlock), gr.members),
-                     dim3(lbm::kBlock), 0, st, a);
+  a.buoy = buoy;
+  const dim3 grid((unsigned)div_up((long)a.lanes_per_row * gr.ny, lbm::kBlock), gr.members);
+  if (buoy) hipLaunchKernelGGL(lbm::dp_scalar_step<true>, grid, dim3(lbm::kBlock), 0, st, a);
+  else hipLaunchKernelGGL(lbm::dp_scalar_step<false>, grid, dim3(lbm::kBlock), 0, st, static_cast<const lbm::DpScalarArgs &>(a));
   HIP_TRY(hipGetLastError());
   s.cur ^= 1;
   return LBM_OK;
@@ -237,6 +245,89 @@ static inline int scalar_upload(ScalarState &s, const ScalarGrid &gr, hipStream_
                      (unsigned long long)gr.member_stride(), gr.nx, gr.cells(), stage);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
+  return LBM_OK;
+}
+
+// ---- buoyancy (include/lbm.h, "Buoyancy"; lbm_dbuoy_*) -----------------------------------------------------------------------
+// What a handle holds of it, and what the two hosts say alike: the checks, the device table and the buoyant flow launch.
+struct BuoyState {
+  bool on = false;
+  std::vector<double> b;                     // [members][3]: b_x, b_y, c_ref; empty while off
+  lbm::DpBuoyMember *table = nullptr;        // device, [members] (allocated by the first set that switches on)
+  std::vector<lbm::DpBuoyMember> uploaded;   // what the device table holds
+};
+
+static inline void buoy_free(BuoyState &s) {
+  if (s.table) (void)hipFree(s.table);
+}
+
+// What lbm_dbuoy_set / lbm_dbuoy_ens_set refuse of their values, before the handle is read: b = double[members][3].  ens: the
+// message names the member, and a member whose b is (0, 0) is refused too (its context twin would run the passive path).
+static inline int buoy_check_values(const double *b, int members, bool ens) {
+  char who[32] = "";
+  for (int m = 0; m < members; m++) {
+    if (ens) snprintf(who, sizeof(who), "member %d: ", m);
+    const double *v = b + 3 * (size_t)m;
+    if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !std::isfinite(v[2]))
+      return lbm_fail(LBM_ERR_ARG, "%sthe buoyancy must be finite (got b_x = %g, b_y = %g, c_ref = %g)", who, v[0], v[1], v[2]);
+    if (ens && !lbm::dp_drive_on(v[0], v[1]))
+      return lbm_fail(LBM_ERR_ARG, "%sthe buoyancy is (0, 0); an ensemble has buoyancy on for all members or, with a NULL array, off", who);
+  }
+  return LBM_OK;
+}
+
+// What they refuse of the handle's state; switching_on: the call sets a b other than (0, 0)
+static inline int buoy_check_state(const ScalarState &scalar, int steps_done, bool switching_on) {
+  if (switching_on && !scalar.on)
+    return lbm_fail(LBM_ERR_STATE, "buoyancy needs a scalar: the scalar is off (lbm_dscalar_set / lbm_dscalar_ens_set switches it on first)");
+  if (steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "buoyancy is set before the first step (%d done): one record holds one flow", steps_done);
+  return LBM_OK;
+}
+
+static inline int buoy_refuse_scalar_off() {
+  return lbm_fail(LBM_ERR_STATE, "the scalar cannot be switched off while buoyancy is on: the flow reads it (lbm_dbuoy_set / "
+                  "lbm_dbuoy_ens_set switches buoyancy off first)");
+}
+
+// Behind the checks and the caller's synchronisation.  b NULL: off.
+static inline int buoy_set(BuoyState &s, const double *b, int members) {
+  if (!b) {
+    s.on = false;
+    s.b.clear();
+    return LBM_OK;
+  }
+  if (!s.table) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.table), (size_t)members * sizeof(lbm::DpBuoyMember)));
+  s.on = true;
+  s.b.assign(b, b + 3 * (size_t)members);
+  s.uploaded.clear();
+  return LBM_OK;
+}
+
+// The device table as the handle's settings stand now: t holds every member's flow constants and body force (the caller's),
+// b and c_ref come from s.  Written only where it differs from what the device holds, behind a synchronisation of the stream.
+static inline int buoy_table(BuoyState &s, hipStream_t st, std::vector<lbm::DpBuoyMember> &t) {
+  for (size_t m = 0; m < t.size(); m++) {
+    t[m].buoy.b_x = s.b[3 * m];
+    t[m].buoy.b_y = s.b[3 * m + 1];
+    t[m].buoy.c_ref = s.b[3 * m + 2];
+    t[m].pad = 0.0;
+  }
+  if (s.uploaded.size() == t.size() && !memcmp(s.uploaded.data(), t.data(), t.size() * sizeof(lbm::DpBuoyMember))) return LBM_OK;
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(s.table, t.data(), t.size() * sizeof(lbm::DpBuoyMember), hipMemcpyHostToDevice));
+  s.uploaded = t;
+  return LBM_OK;
+}
+
+// One buoyant flow step of all members, enqueued: the instance the five options choose
+static inline int buoy_launch(hipStream_t st, bool force, bool trt, bool open, bool wall, bool les, const lbm::DpBuoyArgs &a, int members) {
+  const dim3 grid((unsigned)div_up((long)a.lanes_per_row * a.ny, lbm::kBlock), members);
+  lbm::dp_with_flags(force, trt, open, wall, les, false, [&](auto fo, auto tr, auto op, auto wa, auto le, auto) {
+    hipLaunchKernelGGL((lbm::d2q9_dp_buoyant<decltype(fo)::value, decltype(tr)::value, decltype(op)::value, decltype(wa)::value,
+                                            decltype(le)::value>), grid, dim3(lbm::kBlock), 0, st, a);
+  });
+  HIP_TRY(hipGetLastError());
   return LBM_OK;
 }
 

@@ -353,6 +353,32 @@ __device__ __forceinline__ void dp_output_cell(const double (&f)[9], const doubl
   pr = local_density * (1.0 / 3.0);
 }
 
+// Buoyancy (include/lbm.h, "Buoyancy"): the force density of one cell from its five STORED scalar values, the header's four
+// statements, contraction off.  f0 is the body force of lbm_ddrive_set, (0.0, 0.0) while that is off.
+struct DpBuoy {
+  double b_x, b_y, c_ref;
+  double f0_x, f0_y;
+};
+__device__ __forceinline__ DpDrive dp_buoy_force(const double (&g)[5], const DpBuoy &b) {
+#pragma clang fp contract(off)
+  const double c = (((g[0] + g[1]) + g[2]) + g[3]) + g[4];
+  const double d = c - b.c_ref;
+  return DpDrive{b.f0_x + b.b_x * d, b.f0_y + b.b_y * d};
+}
+// What a buoyant handle's kernels read per member, in device memory, by member index (a wave-uniform load): a context holds a
+// table of one.  The scalar step and the output stage read `buoy` alone; the flow kernel (dp_buoyant_kernels.h) reads everything
+// d2q9_dp_step takes as arguments.  Written by dp_host.h (buoy_table) from the handle's settings before a run and before the
+// output stage.
+struct DpBuoyMember {
+  DpBuoy buoy;
+  double omega, omega_m, aw1, aw2;   // as DpMember
+  double rho_out, rho_wall;          // OPEN, WALL
+  DpLes les;                         // LES
+  const double *u_in;                // OPEN: the member's inlet profile, [ny]
+  double pad;
+};
+static_assert(sizeof(DpBuoyMember) == 128, "a member's buoyant constants are two 64-B lines");
+
 // Host side: the instance six run-time options choose.  f(force, trt, open, wall, les, drive) is called once, with the
 // std::bool_constant of each option, so a launch site names its kernel's template flags as decltype(force)::value, ... and widens
 // its argument struct where wall, les or drive is true.  Every launch site goes through here: the 64 instances of a kernel are
@@ -698,11 +724,14 @@ static __global__ void dp_pack_planes(double *cells, double *cells_alt, const in
 // output stage per member: the columns of final_state.dat and the velocity sum (dp_output_cell: d2q9-bgk.c:787-832, 396-442, in
 // double, the oracle's statements); obstacle cells give 0, 0, 0, density/3.  Outputs are double[members][ny][nx], partials
 // double[members][gridDim.x]: the per-block sums of u.  cells_alt, par: as dp_pack_planes.  drive: NULL, or the members' body
-// forces, double[members][2] (include/lbm.h, "Body force": the reported velocity is corrected by half of it)
+// forces, double[members][2] (include/lbm.h, "Body force": the reported velocity is corrected by half of it).  buoy: NULL, or the
+// members' buoyant constants, and scalar the current scalar array, member m 5 * plane_stride * ny doubles in (include/lbm.h,
+// "Buoyancy": the half-force of each cell is that of its own five stored scalar values; drive is not read)
 static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *cells, const double *cells_alt, const int *par,
                                                                  unsigned long long plane_stride,
                                                                  unsigned long long member_stride, int nx, const uint8_t *mask,
                                                                  size_t n, const DpMember *members, const double *drive,
+                                                                 const double *scalar, const DpBuoyMember *buoy,
                                                                  double *u_x, double *u_y, double *u, double *pressure,
                                                                  double *partials) {
 #pragma clang fp contract(off)
@@ -713,6 +742,11 @@ static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *c
   mask += (size_t)blockIdx.y * n;
   const size_t off = (size_t)blockIdx.y * n;
   if (drive) drive += 2 * (size_t)blockIdx.y;
+  DpBuoy bu{};
+  if (buoy) {
+    bu = buoy[blockIdx.y].buoy;
+    scalar += (size_t)blockIdx.y * (5 * plane_stride * (n / nx));
+  }
   double tot_u = 0.0;
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     double ux = 0.0, uy = 0.0, uu = 0.0, pr = density * c_sq;
@@ -722,7 +756,15 @@ static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *c
       const size_t cell = y * 9 * plane_stride + (i - y * nx);
 #pragma unroll
       for (int k = 0; k < 9; k++) f[k] = cells[k * plane_stride + cell];
-      dp_output_cell(f, drive, ux, uy, uu, pr);
+      if (buoy) {
+        const double *s = scalar + y * 5 * plane_stride + (i - y * nx);
+        const double g[5] = {s[0], s[plane_stride], s[2 * plane_stride], s[3 * plane_stride], s[4 * plane_stride]};
+        const DpDrive fo = dp_buoy_force(g, bu);
+        const double pair[2] = {fo.f_x, fo.f_y};
+        dp_output_cell(f, pair, ux, uy, uu, pr);
+      } else {
+        dp_output_cell(f, drive, ux, uy, uu, pr);
+      }
       tot_u += uu;
     }
     if (u_x) u_x[off + i] = ux;

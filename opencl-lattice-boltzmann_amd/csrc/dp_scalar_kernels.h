@@ -1,6 +1,7 @@
 // Passive scalar transport for the double-precision families (include/lbm.h, "Scalar transport"; lbm_dscalar_*): a D2Q5
 // advection-diffusion lattice carried by the flow of a context or of each member of an ensemble, advanced by a kernel of its own.
-// No flow kernel, argument struct or launch knows of it: the scalar reads the flow's state, the flow never reads the scalar.
+// No flow kernel, argument struct or launch knows of the passive scalar: it reads the flow's state, the flow never reads it.  With
+// buoyancy on (include/lbm.h, "Buoyancy") the flow step is a kernel of its own that does (dp_buoyant_kernels.h).
 //
 // Layout: five populations per cell in the flow's row-interleaved SoA - g_k(x, y) at y*5*plane_stride + k*plane_stride + x with the
 // flow's plane_stride, two arrays, double-buffered, member m's grid mc.state_off doubles in.  Speeds 0..4 are the flow's 0..4
@@ -8,7 +9,9 @@
 //
 //   dp_scalar_step    one scalar step per launch, lane = 2 neighbouring cells of a row (d2q9_dp_step's lanes), member axis on
 //                     blockIdx.y.  About 157 B per lattice update: 72 read from the flow, 40 + 40 of the scalar, the mask bytes.
-//                     No LDS, no atomics.
+//                     No LDS, no atomics.  <false>: the passive scalar.  <true>: a scalar that acts back (include/lbm.h,
+//                     "Buoyancy"): the velocity it advects with is less half of each cell's own force; two more 16-B loads per lane
+//                     (the cell's own g_2, g_4), about 173 B per update.
 //   dp_scalar_init    g_k = w_k c0 on every cell
 //   dp_scalar_field   output stage: the sum of a fluid cell's five stored values, 0.0 on a blocked cell
 //   dp_scalar_pack    device layout <-> double[members][5][ny][nx] (dp_pack_planes with five planes)
@@ -54,6 +57,13 @@ struct DpScalarArgs {
   int lanes_per_row;              // as DpStepArgs
   int open;                       // the flow has open boundaries: the inlet and outlet statements on columns 0 and nx - 1
 };
+// BUOY: the members' buoyant constants behind what the instance without it takes; the BUOY = false struct is that of a library
+// without the option
+struct DpScalarBuoyArgs : DpScalarArgs {
+  const DpBuoyMember *buoy;
+};
+template <bool BUOY>
+using DpScalarArgsOf = std::conditional_t<BUOY, DpScalarBuoyArgs, DpScalarArgs>;
 
 // What a fluid cell gathers along speed k from a blocked neighbour q: its own opposite value comes back (insulating, half-way
 // bounce-back), or the wall's value less it (a wall held at c_wall(q)).
@@ -83,7 +93,11 @@ __device__ __forceinline__ void dp_scalar_collide(const double (&h)[5], double u
 // row), g_4 (north row); the x-neighbours of g_1 and g_3 as d2q9_dp_step forms w1 and e3: the pair's other half plus one scalar
 // load at the wrap or edge column.  A lane past the row's end is idle.  A cell's own g_2, g_4 and a neighbour's c_wall are read
 // only under the branch of a blocked neighbour (or of a blocked cell, which copies its five values through).
-static __global__ __launch_bounds__(kBlock) void dp_scalar_step(const DpScalarArgs a) {
+// BUOY: the lane loads its two cells' own g_2 and g_4 always, forms each cell's force from its five stored values (dp_buoy_force on
+// the member's b, c_ref and F0) and hands dp_output_cell that pair in place of the member's body force, which is not read.  The
+// false instance is the kernel without it, instruction for instruction.
+template <bool BUOY>
+static __global__ __launch_bounds__(kBlock) void dp_scalar_step(const DpScalarArgsOf<BUOY> a) {
 #pragma clang fp contract(off)
   const unsigned t = blockIdx.x * kBlock + threadIdx.x;
   const unsigned lpr = (unsigned)a.lanes_per_row;
@@ -116,7 +130,7 @@ static __global__ __launch_bounds__(kBlock) void dp_scalar_step(const DpScalarAr
 
   // cell x of this row: own = its stored g_0, g_1, g_3; east / west: the streamed values and whether their cells are blocked
   auto cell = [&](int x, bool blocked, double own0, double own1, double own3, double from_w, bool w_blocked, int x_w, double from_e,
-                  bool e_blocked, int x_e, double from_s, double from_n, const double (&fl)[9], double (&out)[5]) {
+                  bool e_blocked, int x_e, double from_s, double from_n, const double (&fl)[9], const double *drv, double (&out)[5]) {
     if (blocked) {
       out[0] = own0; out[1] = own1; out[2] = gc[2 * ps + x]; out[3] = own3; out[4] = gc[4 * ps + x];
       return;
@@ -134,7 +148,7 @@ static __global__ __launch_bounds__(kBlock) void dp_scalar_step(const DpScalarAr
       if (x == a.nx - 1) h[3] = own3;
     }
     double u_x, u_y, uu, pr;
-    dp_output_cell(fl, mc.drive, u_x, u_y, uu, pr);
+    dp_output_cell(fl, drv, u_x, u_y, uu, pr);
     dp_scalar_collide(h, u_x, u_y, mc.omega_s, out);
   };
 
@@ -145,11 +159,24 @@ static __global__ __launch_bounds__(kBlock) void dp_scalar_step(const DpScalarAr
     fb[k] = f[k].y;
   }
   double oa[5], ob[5];
+  // the force of each cell's own five stored values; without BUOY the member's body force, or NULL
+  [[maybe_unused]] double pa[2], pb[2];
+  const double *drv_a = mc.drive, *drv_b = mc.drive;
+  if constexpr (BUOY) {
+    const DpBuoy bu = a.buoy[blockIdx.y].buoy;
+    const v2d o2 = *reinterpret_cast<const v2d *>(gc + 2 * ps + x0);
+    const v2d o4 = *reinterpret_cast<const v2d *>(gc + 4 * ps + x0);
+    const double sa[5] = {c0.x, c1.x, o2.x, c3.x, o4.x}, sb[5] = {c0.y, c1.y, o2.y, c3.y, o4.y};
+    const DpDrive fa_ = dp_buoy_force(sa, bu), fb_ = dp_buoy_force(sb, bu);
+    pa[0] = fa_.f_x, pa[1] = fa_.f_y;
+    pb[0] = fb_.f_x, pb[1] = fb_.f_y;
+    drv_a = pa, drv_b = pb;
+  }
   // cell a: its west neighbour is column xw, its east neighbour cell b or, where the lane has none, column xe
-  cell(x0, ob_a, c0.x, c1.x, c3.x, w1, blk_w, xw, has_b ? c3.y : e3, has_b ? ob_b : blk_e, has_b ? x0 + 1 : xe, c2.x, c4.x, fa, oa);
+  cell(x0, ob_a, c0.x, c1.x, c3.x, w1, blk_w, xw, has_b ? c3.y : e3, has_b ? ob_b : blk_e, has_b ? x0 + 1 : xe, c2.x, c4.x, fa, drv_a, oa);
   double *d = a.dst + mc.state_off + (size_t)y * grs + x0;
   if (has_b) {
-    cell(x0 + 1, ob_b, c0.y, c1.y, c3.y, c1.x, ob_a, x0, e3, blk_e, xe, c2.y, c4.y, fb, ob);
+    cell(x0 + 1, ob_b, c0.y, c1.y, c3.y, c1.x, ob_a, x0, e3, blk_e, xe, c2.y, c4.y, fb, drv_b, ob);
 #pragma unroll
     for (int k = 0; k < 5; k++) {
       v2d v = {oa[k], ob[k]};

@@ -84,7 +84,8 @@ struct lbm_dens {
   std::vector<double> les_c;       // [n]: every member's Smagorinsky constant, 0 while the setting is off
   bool drive = false;              // lbm_ddrive_ens_set: the kernels' DRIVE instances, for all members
   std::vector<double> drive_f;     // [n][2]: every member's force density, 0 while the setting is off
-  ScalarState scalar;              // lbm_dscalar_ens_set: the members' passive scalars (dp_host.h), off by default
+  ScalarState scalar;              // lbm_dscalar_ens_set: the members' scalars (dp_host.h), off by default
+  BuoyState buoy;                  // lbm_dbuoy_ens_set: the scalars act back on the members' flows (dp_host.h), off by default
   int nseg = 1, red_blocks = 1, fin_blocks = 1;
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
@@ -119,6 +120,7 @@ void free_dens(lbm_dens *e) {
   if (e->steady_count_host) (void)hipHostFree(e->steady_count_host);
   if (e->stage) (void)hipFree(e->stage);
   scalar_free(e->scalar);
+  buoy_free(e->buoy);
   queue_destroy(e->q);
   delete e;
 }
@@ -237,6 +239,27 @@ void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
 ScalarGrid scalar_grid(const lbm_dens *e) { return ScalarGrid{e->n, e->nx, e->ny, e->plane_stride, e->member_stride}; }
 const double *scalar_drive(const lbm_dens *e) { return e->drive ? dens_drive_table(e->members, e->n, e->ny) : nullptr; }
 
+// Buoyancy: the members' table as the settings stand now (dp_host.h: buoy_table), before a run and before the output stage.  The
+// flow constants are those the tables behind `members` hold, from the host's copies.
+int buoy_sync(lbm_dens *e) {
+  std::vector<DpBuoyMember> t(e->n, DpBuoyMember{});
+  const double *u_in = dens_open_table(e->members, e->n);
+  for (int i = 0; i < e->n; i++) {
+    const DpMember m = member_constants<DpMember>(e->p[i]);
+    t[i].buoy.f0_x = e->drive_f[2 * (size_t)i];
+    t[i].buoy.f0_y = e->drive_f[2 * (size_t)i + 1];
+    t[i].omega = e->p[i].omega;
+    t[i].omega_m = e->omega_m[i];
+    t[i].aw1 = m.aw1;
+    t[i].aw2 = m.aw2;
+    t[i].rho_out = e->open ? e->open_host[(size_t)i * (e->ny + 1) + e->ny] : 0.0;
+    t[i].rho_wall = e->wall ? e->rho_wall[i] : 0.0;
+    t[i].les = dp_les_constants(e->p[i].omega, e->les_c[i], e->magic[i]);
+    t[i].u_in = u_in + (size_t)i * (e->ny + 1);
+  }
+  return buoy_table(e->buoy, e->q.st, t);
+}
+
 // nsteps steps from step count `first` on, enqueued: the prologue, the launches, the reductions into the record.  Flips
 // e->cur per launch; the caller counts the steps.  active: as launch_dens.
 int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
@@ -249,6 +272,10 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   const ScalarGrid sgrid = scalar_grid(e);
   if (scalar)
     if (int rc = scalar_begin_run(e->scalar, sgrid, scalar_drive(e), 2ull)) return rc;
+  // with buoyancy on the flow step is d2q9_dp_buoyant, one step per launch (never during a steady run)
+  const bool buoy = scalar && e->buoy.on;
+  if (buoy)
+    if (int rc = buoy_sync(e)) return rc;
   // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
   // into the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
   if (!e->open) {
@@ -282,7 +309,29 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
       if (int rc = flush()) return rc;
     // scalar step n before flow step n, on the state that flow step streams
     if (scalar)
-      if (int rc = scalar_step(e->scalar, sgrid, e->q.st, e->cells[e->cur], e->mask, e->open)) return rc;
+      if (int rc = scalar_step(e->scalar, sgrid, e->q.st, e->cells[e->cur], e->mask, e->open, buoy ? e->buoy.table : nullptr)) return rc;
+    if (buoy) {
+      // flow step n reads the scalar array that scalar step n has just written
+      DpBuoyArgs b{};
+      b.src = e->cells[e->cur];
+      b.dst = e->cells[e->cur ^ 1];
+      b.mask = e->mask;
+      b.scalar = e->scalar.g[e->scalar.cur];
+      b.members = e->buoy.table;
+      b.wall_u = e->wall_dev;
+      b.seg = e->seg + (size_t)e->ring_fill * slot;
+      b.plane_stride = e->plane_stride;
+      b.member_stride = e->member_stride;
+      b.nx = e->nx;
+      b.ny = e->ny;
+      b.lanes_per_row = e->nseg * 8;
+      b.accel_row = (!e->open && i + adv < nsteps) ? e->ny - 2 : -1;
+      if (int rc = buoy_launch(e->q.st, e->force, e->trt, e->open, e->wall, e->les, b, e->n)) return rc;
+      e->cur ^= 1;
+      e->ring_fill += adv;
+      i += adv;
+      continue;
+    }
     DensArgs a{};
     a.src = e->cells[e->cur];
     a.dst = e->cells[e->cur ^ 1];
@@ -408,11 +457,16 @@ int stage_of(lbm_dens *e, double **stage) {
 // the output stage of all members, each from the array that holds it, into `d[0..3]` (any may be NULL) and the per-block
 // sums of u
 int final_fields_dens(lbm_dens *e, double *const (&d)[4]) {
+  // buoyancy: the half-force of the scalar state that is current, per cell (a scalar is never on while the ensemble is ragged)
+  const bool buoy = e->scalar.on && e->buoy.on;
+  if (buoy)
+    if (int rc = buoy_sync(e)) return rc;
   hipLaunchKernelGGL(dp_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->q.st,
                      (const double *)e->cells[e->ragged ? 0 : e->cur], (const double *)e->cells[1], member_parity(e), e->plane_stride,
                      e->member_stride, e->nx, (const uint8_t *)e->mask, (size_t)e->nx * e->ny, (const DpMember *)e->members,
-                     e->drive ? dens_drive_table(e->members, e->n, e->ny) : (const double *)nullptr, d[0], d[1], d[2], d[3],
-                     e->fin_partials);
+                     e->drive ? dens_drive_table(e->members, e->n, e->ny) : (const double *)nullptr,
+                     buoy ? (const double *)e->scalar.g[e->scalar.cur] : (const double *)nullptr,
+                     buoy ? (const DpBuoyMember *)e->buoy.table : (const DpBuoyMember *)nullptr, d[0], d[1], d[2], d[3], e->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
 }
@@ -921,6 +975,7 @@ int lbm_dscalar_ens_set(lbm_dens *e, const double *diffusivity, const double *c0
   if (diffusivity)
     if (int rc = scalar_check(gr, true, diffusivity, c0, c_wall, c_in)) return rc;
   if (diffusivity && e->ragged) return refuse_ragged(e);
+  if (!diffusivity && e->buoy.on) return buoy_refuse_scalar_off();
   if (int rc = queue_sync(e->q)) return rc;
   if (!diffusivity) {
     // the arrays stay until the ensemble goes; the handle runs as one that never had a scalar
@@ -966,6 +1021,28 @@ int lbm_dscalar_ens_upload(lbm_dens *e, const double *g) {
   if (!e->scalar.on) return scalar_refuse_off("lbm_dscalar_ens_upload");
   if (int rc = queue_sync(e->q)) return rc;
   return scalar_upload(e->scalar, scalar_grid(e), e->q.st, g);
+}
+
+int lbm_dbuoy_ens_set(lbm_dens *e, const double *b) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  // every member is checked before anything changes, on the host or on the device
+  if (b)
+    if (int rc = buoy_check_values(b, e->n, true)) return rc;
+  if (int rc = buoy_check_state(e->scalar, e->steps_done, b != nullptr)) return rc;
+  if (int rc = queue_sync(e->q)) return rc;
+  HIP_TRY(hipSetDevice(e->q.dev));
+  return buoy_set(e->buoy, b, e->n);
+}
+
+int lbm_dbuoy_ens_get(const lbm_dens *e, int *on_out, double *b_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!on_out && !b_out) return lbm_fail(LBM_ERR_ARG, "on_out and b_out are both NULL");
+  if (on_out) *on_out = e->buoy.on ? 1 : 0;
+  if (b_out) {
+    if (e->buoy.on) std::copy(e->buoy.b.begin(), e->buoy.b.end(), b_out);
+    else std::fill(b_out, b_out + 3 * (size_t)e->n, 0.0);
+  }
+  return LBM_OK;
 }
 
 void lbm_dens_destroy(lbm_dens *e) {

@@ -73,7 +73,8 @@ struct lbm_dp {
   double *wall_dev = nullptr;     // [2][ny][nx] (allocated by the first lbm_dwall_set that switches on)
   double les_c = 0.0;             // lbm_dles_set: 0 = off, > 0 = the LES instances with this Smagorinsky constant
   double drive[2] = {0.0, 0.0};   // lbm_ddrive_set: (0, 0) = off, else the DRIVE instances with this force density
-  ScalarState scalar;             // lbm_dscalar_set: the passive scalar (dp_host.h), off by default
+  ScalarState scalar;             // lbm_dscalar_set: the scalar (dp_host.h), off by default
+  BuoyState buoy;                 // lbm_dbuoy_set: the scalar acts back on the flow (dp_host.h), off by default
   int cur = 0, steps_done = 0;
   bool failed = false;
 };
@@ -101,6 +102,7 @@ void free_dp(lbm_dp *d) {
   if (d->u_in_dev) (void)hipFree(d->u_in_dev);
   if (d->wall_dev) (void)hipFree(d->wall_dev);
   scalar_free(d->scalar);
+  buoy_free(d->buoy);
   queue_destroy(d->q);
   delete d;
 }
@@ -185,6 +187,23 @@ const double *drive_dev(const lbm_dp *d) { return drive_on(d) ? reinterpret_cast
 // the grid as the scalar's helpers take it (dp_host.h): a context is one member
 ScalarGrid scalar_grid(const lbm_dp *d) { return ScalarGrid{1, d->p.nx, d->p.ny, d->plane_stride, 0}; }
 
+// Buoyancy: the table of one member as the settings stand now (dp_host.h: buoy_table), before a run and before the output stage
+int buoy_sync(lbm_dp *d) {
+  std::vector<DpBuoyMember> t(1, DpBuoyMember{});
+  const DpMember m = member_constants<DpMember>(d->p);
+  t[0].buoy.f0_x = d->drive[0];
+  t[0].buoy.f0_y = d->drive[1];
+  t[0].omega = d->p.omega;
+  t[0].omega_m = d->omega_m;
+  t[0].aw1 = m.aw1;
+  t[0].aw2 = m.aw2;
+  t[0].rho_out = d->rho_out;
+  t[0].rho_wall = d->rho_wall;
+  t[0].les = les_args(d);
+  t[0].u_in = d->u_in_dev;
+  return buoy_table(d->buoy, d->q.st, t);
+}
+
 void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
   dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, drive_on(d),
                 [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
@@ -234,6 +253,10 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   const ScalarGrid sgrid = scalar_grid(d);
   if (scalar)
     if (int rc = scalar_begin_run(d->scalar, sgrid, drive_dev(d), 0ull)) return rc;
+  // with buoyancy on there is one kernel form, d2q9_dp_buoyant: "multistep" chooses nothing
+  const bool buoy = scalar && d->buoy.on;
+  if (buoy)
+    if (int rc = buoy_sync(d)) return rc;
   if (int rc = timed_begin(d->q, timed)) return rc;
   // prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53); later steps get theirs fused into
   // the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
@@ -267,10 +290,27 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       if (int rc = flush()) return rc;
     // scalar step n before flow step n, on the state that flow step streams
     if (scalar)
-      if (int rc = scalar_step(d->scalar, sgrid, d->q.st, d->cells[d->cur], d->mask, d->open)) return rc;
+      if (int rc = scalar_step(d->scalar, sgrid, d->q.st, d->cells[d->cur], d->mask, d->open, buoy ? d->buoy.table : nullptr)) return rc;
     const bool accel_next = !d->open && i + adv < nsteps;
     double *seg = d->seg + (size_t)d->ring_fill * slot;
-    if (T > 0) {
+    if (buoy) {
+      // flow step n reads the scalar array that scalar step n has just written
+      DpBuoyArgs a{};
+      a.src = d->cells[d->cur];
+      a.dst = d->cells[d->cur ^ 1];
+      a.mask = d->mask;
+      a.scalar = d->scalar.g[d->scalar.cur];
+      a.members = d->buoy.table;
+      a.wall_u = d->wall_dev;
+      a.seg = seg;
+      a.plane_stride = d->plane_stride;
+      a.member_stride = 0;
+      a.nx = nx;
+      a.ny = ny;
+      a.lanes_per_row = d->lanes_per_row;
+      a.accel_row = accel_next ? ny - 2 : -1;
+      if (int rc = buoy_launch(d->q.st, d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, a, 1)) return rc;
+    } else if (T > 0) {
       DpMultiArgs a{};
       a.src = d->cells[d->cur];
       a.dst = d->cells[d->cur ^ 1];
@@ -329,9 +369,15 @@ int run_dp(lbm_dp *d, int nsteps, bool timed, double *ms) {
 // the output stage into `d[0..3]` (any may be NULL) and the per-block sums of u
 int final_fields_dp(lbm_dp *d, double *const (&dst)[4]) {
   const size_t n = (size_t)d->p.nx * d->p.ny;
+  // buoyancy: the half-force of the scalar state that is current, per cell
+  const bool buoy = d->scalar.on && d->buoy.on;
+  if (buoy)
+    if (int rc = buoy_sync(d)) return rc;
   hipLaunchKernelGGL(dp_final_fields, dim3(d->fin_blocks, 1), dim3(kBlock), 0, d->q.st, (const double *)d->cells[d->cur],
                      (const double *)nullptr, (const int *)nullptr, d->plane_stride, 0ull, d->p.nx, (const uint8_t *)d->mask, n,
-                     (const DpMember *)d->members, drive_dev(d), dst[0], dst[1], dst[2], dst[3], d->fin_partials);
+                     (const DpMember *)d->members, drive_dev(d), buoy ? (const double *)d->scalar.g[d->scalar.cur] : (const double *)nullptr,
+                     buoy ? (const DpBuoyMember *)d->buoy.table : (const DpBuoyMember *)nullptr, dst[0], dst[1], dst[2], dst[3],
+                     d->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
 }
@@ -729,6 +775,7 @@ int lbm_dscalar_set(lbm_dp *d, double diffusivity, const double *c0, const doubl
   const ScalarGrid gr = scalar_grid(d);
   if (diffusivity > 0.0)
     if (int rc = scalar_check(gr, false, &diffusivity, c0, c_wall, c_in)) return rc;
+  if (diffusivity == 0.0 && d->buoy.on) return buoy_refuse_scalar_off();
   if (int rc = queue_sync(d->q)) return rc;
   if (diffusivity == 0.0) {
     // the arrays stay until the context goes; the handle runs as one that never had a scalar
@@ -772,6 +819,30 @@ int lbm_dscalar_upload(lbm_dp *d, const double *g) {
   if (!d->scalar.on) return scalar_refuse_off("lbm_dscalar_upload");
   if (int rc = queue_sync(d->q)) return rc;
   return scalar_upload(d->scalar, scalar_grid(d), d->q.st, g);
+}
+
+int lbm_dbuoy_set(lbm_dp *d, double b_x, double b_y, double c_ref) {
+  // argument errors before anything of the context is read
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  const double b[3] = {b_x, b_y, c_ref};
+  if (int rc = buoy_check_values(b, 1, false)) return rc;
+  const bool on = dp_drive_on(b_x, b_y);
+  if (int rc = buoy_check_state(d->scalar, d->steps_done, on)) return rc;
+  if (int rc = queue_sync(d->q)) return rc;
+  HIP_TRY(hipSetDevice(d->q.dev));
+  return buoy_set(d->buoy, on ? b : nullptr, 1);
+}
+
+int lbm_dbuoy_get(const lbm_dp *d, int *on_out, double *b_out, double *c_ref_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!on_out && !b_out && !c_ref_out) return lbm_fail(LBM_ERR_ARG, "on_out, b_out and c_ref_out are all NULL");
+  if (on_out) *on_out = d->buoy.on ? 1 : 0;
+  if (b_out) {
+    b_out[0] = d->buoy.on ? d->buoy.b[0] : 0.0;
+    b_out[1] = d->buoy.on ? d->buoy.b[1] : 0.0;
+  }
+  if (c_ref_out) *c_ref_out = d->buoy.on ? d->buoy.b[2] : 0.0;
+  return LBM_OK;
 }
 
 void lbm_dp_destroy(lbm_dp *d) {

@@ -19,7 +19,7 @@ def kernels(path):
     """{(kernel, flags): normalised lines} of every fp64 step kernel in one assembly file"""
     out, name, body = {}, None, []
     for line in open(path):
-        m = re.match(r"^(_ZN3lbm\S*d2q9_dp_\S+):", line)
+        m = re.match(r"^(_ZN3lbm\S*d2q9_dp_(?:step|multi|ensemble)\S*):", line)   # not d2q9_dp_buoyant: it has no older twin
         if m:
             if name is not None:
                 out[name] = body
