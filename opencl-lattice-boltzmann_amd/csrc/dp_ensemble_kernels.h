@@ -19,9 +19,9 @@ struct DensArgs {
   const double *src;         // member m: src + m * member_stride
   double *dst;
   const uint8_t *mask;       // member m: mask + m * nx * ny
-  const DpMember *members; // [members], and behind them the open-boundary table (OPEN: dens_open_table), the wall densities
-                           // (WALL: dens_wall_table), the subgrid constants (LES: dens_les_table) and the body forces (DRIVE:
-                           // dens_drive_table)
+  const DpMember *members; // [members], and behind them the open-boundary table (OPEN: dens_open_table, dp_kernels.h), the wall
+                           // densities (WALL: dens_wall_table), the subgrid constants (LES: dens_les_table) and the body forces
+                           // (DRIVE: dens_drive_table)
   double *seg;               // [T][members][ny][nseg]: the segment sums of each of the T steps; FORCE:
                              // [T][3][members][ny][nseg], |u|, F_x, F_y
   unsigned long long plane_stride, member_stride;   // row_stride = 9 * plane_stride
@@ -39,25 +39,6 @@ struct DensWallArgs : DensArgs {
 };
 template <bool WALL>
 using DensArgsOf = std::conditional_t<WALL, DensWallArgs, DensArgs>;
-
-// Open boundaries: member m's inlet profile u_in[ny] and, behind it, its rho_out lie m * (ny + 1) doubles into a second table,
-// which starts where the table of DpMember ends: one allocation, and DensArgs is the struct of a library without it.
-__host__ __device__ inline const double *dens_open_table(const DpMember *members, int n) {
-  return reinterpret_cast<const double *>(members + n);
-}
-// Moving walls: member m's rho_wall is entry m of a third table, behind the open-boundary table
-__host__ __device__ inline const double *dens_wall_table(const DpMember *members, int n, int ny) {
-  return dens_open_table(members, n) + (size_t)n * (ny + 1);
-}
-// Subgrid viscosity: member m's DpLes (tau0, les_k, magic; dp_kernels.h) is entry m of a fourth table, behind the wall table
-__host__ __device__ inline const DpLes *dens_les_table(const DpMember *members, int n, int ny) {
-  return reinterpret_cast<const DpLes *>(dens_wall_table(members, n, ny) + n);
-}
-
-// Body force: member m's F_x, F_y are entry m of a fifth table, double[n][2], behind the subgrid table
-__host__ __device__ inline const double *dens_drive_table(const DpMember *members, int n, int ny) {
-  return reinterpret_cast<const double *>(dens_les_table(members, n, ny) + n);
-}
 
 // Member blockIdx.y as dp_tile takes it (dp_tile.h): its arrays a member stride into the ensemble's, its constants from the
 // DpMember load, its profile, rho_out, rho_wall and subgrid constants from the tables behind the members

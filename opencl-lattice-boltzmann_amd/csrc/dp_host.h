@@ -1,8 +1,9 @@
 // Where lbm_dp.cpp and lbm_dens.cpp drive the helper kernels of dp_kernels.h with the same statements: the second reduction
-// stage, the force of the current state, the scalar (dp_scalar_kernels.h) and buoyancy (dp_buoyant_kernels.h), for `members` grids
-// (a context: 1).  Plain functions over the fields they need,
-// as host_common.h's; static, because the kernels they launch are each unit's own copies.
+// stage, the force of the current state, the settings of the six flow options with their device tables, the scalar
+// (dp_scalar_kernels.h) and buoyancy (dp_buoyant_kernels.h), for `members` grids (a context: 1).  Plain functions over the fields
+// they need, as host_common.h's; static, because the kernels they launch are each unit's own copies.
 #pragma once
+#include "body_map.h"
 #include "dp_buoyant_kernels.h"
 #include "dp_kernels.h"
 #include "dp_scalar_kernels.h"
@@ -59,6 +60,349 @@ static inline int force_state(hipStream_t st, lbm::DpForceArgs a, int nseg, int 
   return LBM_OK;
 }
 
+// ---- the six flow options ("force", lbm_dtrt_*, lbm_dopen_*, lbm_dwall_*, lbm_dles_*, lbm_ddrive_*) ---------------------------
+// What a handle holds of them for its `members` grids.  The per-member constants lie on the device in the tables behind the
+// handle's DpMember table (dp_kernels.h: dens_*_table), a context's as an ensemble's of one member; the host copies here are
+// what the getters return and what a context's step kernels take as arguments (element 0).  "Off" is one spelling, a NULL
+// array: a context's entry point turns its 0 into that before it comes here.
+struct FlowState {
+  bool force = false;              // option "force": the kernels' FORCE instances, three values per segment
+  bool trt = false;                // the TRT instances, for all members
+  bool open = false;               // the OPEN instances for all members, no accelerate_flow
+  bool wall = false;               // the WALL instances for all members
+  bool les = false;                // the LES instances, for all members
+  bool drive = false;              // the DRIVE instances, for all members
+  std::vector<double> magic;       // [members]: every member's magic parameter, 0 while BGK
+  std::vector<double> omega_m;     // [members]: the host's copy of DpMember::omega_m (BGK: the member's omega)
+  std::vector<double> open_host;   // [members][ny + 1]: per member u_in[ny], then rho_out (zeros while off); dens_open_table
+  std::vector<double> wall_u;      // [2][members][ny][nx]: the host's copy of the wall velocities, u_x then u_y (empty while off)
+  std::vector<double> rho_wall;    // [members]: the wall densities, 0 while off; dens_wall_table
+  double *wall_dev = nullptr;      // [2][members][ny][nx] (allocated by the first wall_set that switches on)
+  std::vector<double> les_c;       // [members]: every member's Smagorinsky constant, 0 while off; DpLes in dens_les_table
+  std::vector<double> drive_f;     // [members][2]: every member's force density, 0 while off; dens_drive_table
+};
+
+// The grids a state belongs to, as both handles describe theirs when a setter is called, and their ring of segment sums: the
+// handle's own three fields, and the sizes that fix them
+struct FlowGrid {
+  int members;
+  const lbm_dparams *p;   // [members]; nx, ny and max_iters are those of p[0]
+  lbm::DpMember *table;   // the device table and the four behind it
+  const Queue &q;
+  int steps_done;
+  double *&seg, *&red;
+  int &ring;
+  size_t per_step;        // one member's segments of one step (ny * nseg)
+  int red_blocks, tmax;   // blocks of the first reduction stage a member and step; the steps of the unit's deepest launch
+};
+
+static inline size_t flow_table_bytes(int members, int ny) {
+  return (size_t)members * (sizeof(lbm::DpMember) + (size_t)(ny + 2) * sizeof(double) + sizeof(lbm::DpLes) + sizeof(lbm::DpDrive));
+}
+
+// The table of per-member constants with these second relaxation rates, to the device
+static inline int upload_members(lbm::DpMember *table, const lbm_dparams *p, int members, const std::vector<double> &omega_m) {
+  std::vector<lbm::DpMember> t(members);
+  for (int i = 0; i < members; i++) {
+    t[i] = member_constants<lbm::DpMember>(p[i]);
+    t[i].omega_m = omega_m[i];
+  }
+  HIP_TRY(hipMemcpy(table, t.data(), t.size() * sizeof(lbm::DpMember), hipMemcpyHostToDevice));
+  return LBM_OK;
+}
+
+// The table of per-member subgrid constants for these Smagorinsky constants and magic parameters, to the device: tau0 and
+// les_k by the header's host statements.  Written by les_set and again by trt_set, so that the two may be set in either order.
+static inline int upload_les(const FlowGrid &g, const std::vector<double> &c, const std::vector<double> &magic) {
+  std::vector<lbm::DpLes> t(g.members);
+  for (int i = 0; i < g.members; i++) t[i] = lbm::dp_les_constants(g.p[i].omega, c[i], magic[i]);
+  HIP_TRY(hipMemcpy(const_cast<lbm::DpLes *>(lbm::dens_les_table(g.table, g.members, g.p[0].ny)), t.data(), t.size() * sizeof(lbm::DpLes),
+                    hipMemcpyHostToDevice));
+  return LBM_OK;
+}
+
+// At creation: the device tables, every option off.  In double the member constants are lbm_dp.cpp's own statements of old
+// (run_dp_impl, lbm_dp_upload): a member's constants are a context's.
+static inline int flow_create(FlowState &s, lbm::DpMember **table, const lbm_dparams *p, int members) {
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(table), flow_table_bytes(members, p[0].ny)));
+  s.magic.assign(members, 0.0);
+  s.open_host.assign((size_t)members * (p[0].ny + 1), 0.0);
+  s.rho_wall.assign(members, 0.0);
+  s.les_c.assign(members, 0.0);
+  s.drive_f.assign(2 * (size_t)members, 0.0);
+  s.omega_m.resize(members);
+  for (int i = 0; i < members; i++) s.omega_m[i] = p[i].omega;
+  return upload_members(*table, p, members, s.omega_m);
+}
+
+// Every setter below is two functions.  *_check refuses the caller's values, every member before anything changes, and reads
+// of the handle no more than p (a context's entry point is called with a handle of zero bytes: tests/test_*_abi.py); ens: the
+// message names the member, and words "off" as an ensemble's caller spells it.  *_set refuses the handle's state, then
+// synchronises, writes the device, and changes the host copies last: after a refusal or a failed upload nothing has changed.
+
+// values per segment and step: |u|, and F_x, F_y with the option "force"
+static inline int seg_values(const FlowState &s) { return s.force ? 3 : 1; }
+
+// The ring of per-step segment sums of all members and the first reduction stage's partials, (re)allocated for the values a
+// segment carries: the ring holds as many steps as fit kRingBytes, at least the tmax steps of the unit's deepest launch.
+// How many steps lie between two reductions decides no sum.
+constexpr size_t kRingBytes = 32u << 20;
+constexpr int kRingMax = 256;
+static inline int ring_steps_of(int members, size_t per_step, int nval, int tmax) {
+  return ring_steps((size_t)members * per_step * nval * sizeof(double), tmax, kRingMax, kRingBytes);
+}
+static inline int alloc_ring(const FlowGrid &r, int nval) {
+  r.ring = ring_steps_of(r.members, r.per_step, nval, r.tmax);
+  if (r.seg) HIP_TRY(hipFree(r.seg));
+  r.seg = nullptr;
+  if (r.red) HIP_TRY(hipFree(r.red));
+  r.red = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&r.seg), (size_t)r.ring * r.members * r.per_step * nval * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&r.red), (size_t)r.ring * r.members * r.red_blocks * sizeof(double)));
+  return LBM_OK;
+}
+
+// Option "force" (the key is the entry point's to match): the ring for three values a segment, and the record
+// [2][members][max_iters], allocated by the first call that switches on.  failed: the handle's latch, set where the ring could
+// not be put back.
+static inline int force_check(long value) {
+  if (value != 0 && value != 1) return lbm_fail(LBM_ERR_ARG, "force must be 0 or 1 (got %ld)", value);
+  return LBM_OK;
+}
+
+static inline int force_set(FlowState &s, const FlowGrid &g, long value, bool ens, double *&force_rec, bool &failed) {
+  if (g.steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "\"force\" is set before the first step (%d done): the record holds every step since %s",
+                    g.steps_done, ens ? "lbm_dens_upload" : "lbm_dp_upload");
+  if ((value != 0) == s.force) return LBM_OK;
+  if (int rc = queue_sync(g.q)) return rc;
+  const bool before = s.force;
+  s.force = value != 0;
+  int rc = alloc_ring(g, seg_values(s));
+  if (rc == LBM_OK && s.force && !force_rec)
+    rc = hip_alloc(reinterpret_cast<void **>(&force_rec), 2 * (size_t)g.members * g.p[0].max_iters * sizeof(double));
+  if (rc != LBM_OK) {
+    // back to a ring that fits the option as it was
+    const std::string keep = lbm_last_error();
+    s.force = before;
+    if (alloc_ring(g, seg_values(s)) != LBM_OK) failed = true;
+    return fail_again(rc, keep);
+  }
+  return LBM_OK;
+}
+
+// Two relaxation times.  magic: double[members], or NULL for BGK.
+static inline int trt_check(const lbm_dparams *p, int members, const double *magic, bool ens) {
+  char who[32] = "";
+  for (int m = 0; magic && m < members; m++) {
+    if (ens) snprintf(who, sizeof(who), "member %d: ", m);
+    if (!(magic[m] > 0.0) || !std::isfinite(magic[m]))
+      return lbm_fail(LBM_ERR_ARG, "%smagic must be %sfinite and positive (got %g)%s", who, ens ? "" : "0 (BGK) or ", magic[m],
+                      ens ? "; an ensemble is all TRT or, with a NULL array, all BGK" : "");
+    if (!(1.0 / p[m].omega - 0.5 > 0.0))
+      return lbm_fail(LBM_ERR_ARG, "%sthe two-relaxation-time operator needs 1/omega - 1/2 > 0: omega is %g", who, p[m].omega);
+  }
+  return LBM_OK;
+}
+
+static inline int trt_set(FlowState &s, const FlowGrid &g, const double *magic) {
+  if (g.steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "the collision operator is set before the first step (%d done): one record holds one operator",
+                    g.steps_done);
+  std::vector<double> omega_m(g.members);
+  for (int m = 0; m < g.members; m++) omega_m[m] = magic ? lbm::dp_trt_omega_minus(g.p[m].omega, magic[m]) : g.p[m].omega;
+  if (int rc = queue_sync(g.q)) return rc;
+  if (int rc = upload_members(g.table, g.p, g.members, omega_m)) return rc;
+  s.trt = magic != nullptr;
+  if (magic) s.magic.assign(magic, magic + g.members);
+  else s.magic.assign(g.members, 0.0);
+  s.omega_m = omega_m;
+  // the subgrid table carries the magic parameter: the TRT + LES instances recompute the second rate per cell
+  if (s.les) return upload_les(g, s.les_c, s.magic);
+  return LBM_OK;
+}
+
+static inline void trt_get(const FlowState &s, double *magic_out, double *omega_minus_out) {
+  if (magic_out) std::copy(s.magic.begin(), s.magic.end(), magic_out);
+  if (omega_minus_out) std::copy(s.omega_m.begin(), s.omega_m.end(), omega_minus_out);
+}
+
+// Open boundaries.  u_in: double[members][ny] with rho_out: double[members], or NULL for periodic.
+static inline int open_check(const lbm_dparams *p, int members, const double *u_in, const double *rho_out, bool ens) {
+  char who[32] = "";
+  for (int m = 0; u_in && m < members; m++) {
+    if (ens) snprintf(who, sizeof(who), "member %d: ", m);
+    if (!positive_finite(rho_out[m])) return lbm_fail(LBM_ERR_ARG, "%srho_out must be finite and positive (got %g)", who, rho_out[m]);
+    const int ny = p[0].ny;
+    for (int y = 0; y < ny; y++) {
+      const double u = u_in[(size_t)m * ny + y];
+      if (!std::isfinite(u) || !(u < 1.0)) return lbm_fail(LBM_ERR_ARG, "%su_in of row %d must be finite and below 1 (got %g)", who, y, u);
+    }
+  }
+  return LBM_OK;
+}
+
+// body, mask: the handle's, rewritten under the column rule (body_map.h), or without it again
+static inline int open_set(FlowState &s, const FlowGrid &g, const BodyMap &body, uint8_t *mask, const double *u_in, const double *rho_out) {
+  if (g.steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "open boundaries are set before the first step (%d done): one record holds one flow", g.steps_done);
+  if (!u_in && !s.open) return LBM_OK;
+  if (int rc = queue_sync(g.q)) return rc;
+  HIP_TRY(hipSetDevice(g.q.dev));
+  const size_t ny = (size_t)g.p[0].ny;
+  std::vector<double> table((size_t)g.members * (ny + 1), 0.0);
+  if (u_in) {
+    for (int m = 0; m < g.members; m++) {
+      std::copy(u_in + (size_t)m * ny, u_in + (size_t)(m + 1) * ny, table.begin() + (size_t)m * (ny + 1));
+      table[(size_t)m * (ny + 1) + ny] = rho_out[m];
+    }
+    HIP_TRY(hipMemcpy(const_cast<double *>(lbm::dens_open_table(g.table, g.members)), table.data(), table.size() * sizeof(double),
+                      hipMemcpyHostToDevice));
+  }
+  if (int rc = body_rewrite(body, mask, g.p[0].nx, u_in != nullptr)) return rc;
+  s.open = u_in != nullptr;
+  s.open_host.swap(table);
+  return LBM_OK;
+}
+
+static inline void open_get(const FlowState &s, int members, int ny, int *on_out, double *u_in_out, double *rho_out_out) {
+  if (on_out) *on_out = s.open ? 1 : 0;
+  if (!s.open) return;
+  for (int m = 0; m < members; m++) {
+    const double *row = s.open_host.data() + (size_t)m * (ny + 1);
+    if (u_in_out) std::copy(row, row + ny, u_in_out + (size_t)m * ny);
+    if (rho_out_out) rho_out_out[m] = row[ny];
+  }
+}
+
+// Moving walls.  u_x, u_y: double[members][ny][nx] each with rho_wall: double[members], or both NULL for walls at rest (the
+// entry points have refused one without the other).
+static inline int wall_values_check(const BodyMap &body, const lbm_dparams *p, int members, const double *u_x, const double *u_y,
+                                    const double *rho_wall, bool ens) {
+  if (!u_x) return LBM_OK;
+  char who[32] = "";
+  for (int m = 0; m < members; m++) {
+    if (ens) snprintf(who, sizeof(who), "member %d: ", m);
+    if (!positive_finite(rho_wall[m])) return lbm_fail(LBM_ERR_ARG, "%srho_wall must be finite and positive (got %g)", who, rho_wall[m]);
+  }
+  return wall_check(body, u_x, u_y, members, p[0].ny, p[0].nx, ens);
+}
+
+static inline int wall_set(FlowState &s, const FlowGrid &g, const double *u_x, const double *u_y, const double *rho_wall) {
+  if (g.steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "wall velocities are set before the first step (%d done): one record holds one flow", g.steps_done);
+  if (!u_x) {
+    s.wall = false;
+    s.wall_u.clear();
+    s.rho_wall.assign(g.members, 0.0);
+    return LBM_OK;
+  }
+  if (int rc = queue_sync(g.q)) return rc;
+  HIP_TRY(hipSetDevice(g.q.dev));
+  const size_t all = (size_t)g.members * g.p[0].nx * g.p[0].ny;
+  if (!s.wall_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.wall_dev), 2 * all * sizeof(double)));
+  std::vector<double> u(2 * all);
+  std::copy(u_x, u_x + all, u.begin());
+  std::copy(u_y, u_y + all, u.begin() + all);
+  HIP_TRY(hipMemcpy(s.wall_dev, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(const_cast<double *>(lbm::dens_wall_table(g.table, g.members, g.p[0].ny)), rho_wall, (size_t)g.members * sizeof(double),
+                    hipMemcpyHostToDevice));
+  s.wall = true;
+  s.wall_u.swap(u);
+  s.rho_wall.assign(rho_wall, rho_wall + g.members);
+  return LBM_OK;
+}
+
+static inline void wall_get(const FlowState &s, int *on_out, double *u_x_out, double *u_y_out, double *rho_wall_out) {
+  if (on_out) *on_out = s.wall ? 1 : 0;
+  if (!s.wall) return;
+  const size_t all = s.wall_u.size() / 2;
+  if (u_x_out) std::copy(s.wall_u.begin(), s.wall_u.begin() + all, u_x_out);
+  if (u_y_out) std::copy(s.wall_u.begin() + all, s.wall_u.end(), u_y_out);
+  if (rho_wall_out) std::copy(s.rho_wall.begin(), s.rho_wall.end(), rho_wall_out);
+}
+
+// Subgrid viscosity.  c: double[members], or NULL for off.
+static inline int les_check(int members, const double *c, bool ens) {
+  char who[32] = "";
+  for (int m = 0; c && m < members; m++) {
+    if (ens) snprintf(who, sizeof(who), "member %d: ", m);
+    if (!(c[m] > 0.0) || !std::isfinite(c[m]))
+      return lbm_fail(LBM_ERR_ARG, "%sthe Smagorinsky constant c must be %sfinite and positive (got %g)%s", who, ens ? "" : "0 (off) or ", c[m],
+                      ens ? "; an ensemble has the subgrid viscosity on for all members or, with a NULL array, off" : "");
+  }
+  return LBM_OK;
+}
+
+static inline int les_set(FlowState &s, const FlowGrid &g, const double *c) {
+  if (g.steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "the subgrid viscosity is set before the first step (%d done): one record holds one operator",
+                    g.steps_done);
+  if (!c) {
+    s.les = false;
+    s.les_c.assign(g.members, 0.0);
+    return LBM_OK;
+  }
+  if (int rc = queue_sync(g.q)) return rc;
+  HIP_TRY(hipSetDevice(g.q.dev));
+  const std::vector<double> cs(c, c + g.members);
+  if (int rc = upload_les(g, cs, s.magic)) return rc;
+  s.les = true;
+  s.les_c = cs;
+  return LBM_OK;
+}
+
+// the constants a member's LES instances run with, from its omega and the two settings as they stand (either order)
+static inline lbm::DpLes les_constants(const FlowState &s, const lbm_dparams *p, int m) {
+  return lbm::dp_les_constants(p[m].omega, s.les_c[m], s.magic[m]);
+}
+
+static inline void les_get(const FlowState &s, const lbm_dparams *p, int members, double *c_out, double *les_k_out) {
+  for (int m = 0; m < members; m++) {
+    if (c_out) c_out[m] = s.les_c[m];
+    if (les_k_out) les_k_out[m] = les_constants(s, p, m).les_k;
+  }
+}
+
+// Body force.  f: double[members][2], or NULL for off.  ens: a member whose force is (0, 0) is refused too (a context's caller
+// has taken that as "off" before the set).
+static inline int drive_check(int members, const double *f, bool ens) {
+  char who[32] = "";
+  for (int m = 0; f && m < members; m++) {
+    if (ens) snprintf(who, sizeof(who), "member %d: ", m);
+    const double f_x = f[2 * (size_t)m], f_y = f[2 * (size_t)m + 1];
+    if (!std::isfinite(f_x) || !std::isfinite(f_y))
+      return lbm_fail(LBM_ERR_ARG, "%sthe body force must be finite (got f_x = %g, f_y = %g)", who, f_x, f_y);
+    if (ens && !lbm::dp_drive_on(f_x, f_y))
+      return lbm_fail(LBM_ERR_ARG, "%sthe body force is (0, 0); an ensemble has the body force on for all members or, "
+                      "with a NULL array, off", who);
+  }
+  return LBM_OK;
+}
+
+static inline int drive_set(FlowState &s, const FlowGrid &g, const double *f) {
+  if (g.steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "the body force is set before the first step (%d done): one record holds one flow", g.steps_done);
+  if (!f) {
+    s.drive = false;
+    s.drive_f.assign(2 * (size_t)g.members, 0.0);
+    return LBM_OK;
+  }
+  if (int rc = queue_sync(g.q)) return rc;
+  HIP_TRY(hipSetDevice(g.q.dev));
+  // the copy the ensemble's step kernels, the output stage and the scalar read
+  HIP_TRY(hipMemcpy(const_cast<double *>(lbm::dens_drive_table(g.table, g.members, g.p[0].ny)), f, 2 * (size_t)g.members * sizeof(double),
+                    hipMemcpyHostToDevice));
+  s.drive = true;
+  s.drive_f.assign(f, f + 2 * (size_t)g.members);
+  return LBM_OK;
+}
+
+static inline void drive_get(const FlowState &s, int *on_out, double *f_out) {
+  if (on_out) *on_out = s.drive ? 1 : 0;
+  if (f_out) std::copy(s.drive_f.begin(), s.drive_f.end(), f_out);
+}
+
 // ---- passive scalar (include/lbm.h, "Scalar transport"; lbm_dscalar_*) -------------------------------------------------------
 // What a handle holds of its scalar, and the grid it rides on as both families describe theirs.  Everything the two hosts say
 // alike is here: the checks, the set, the step launch, the output stage and the transfers.
@@ -71,7 +415,6 @@ struct ScalarState {
   double *c_in = nullptr;                     // [members][ny]
   lbm::DpScalarMember *table = nullptr;       // [members]
   const double *table_drive = nullptr;        // the body-force table the device table was written for
-  unsigned long long table_drive_stride = 0;
 };
 
 struct ScalarGrid {
@@ -123,9 +466,9 @@ static inline int scalar_check(const ScalarGrid &gr, bool ens, const double *dif
   return LBM_OK;
 }
 
-// The device table for these rates: member m's offsets, and its body force at drive + m * drive_stride (drive NULL: none)
-static inline int scalar_table(ScalarState &s, const ScalarGrid &gr, const std::vector<double> &omega_s, const double *drive,
-                               unsigned long long drive_stride) {
+// The device table for these rates: member m's offsets, and its body force at entry m of drive, double[members][2] (the table
+// behind the handle's members, dens_drive_table; NULL: none)
+static inline int scalar_table(ScalarState &s, const ScalarGrid &gr, const std::vector<double> &omega_s, const double *drive) {
   std::vector<lbm::DpScalarMember> t(gr.members);
   for (int m = 0; m < gr.members; m++) {
     t[m] = lbm::DpScalarMember{};
@@ -134,18 +477,17 @@ static inline int scalar_table(ScalarState &s, const ScalarGrid &gr, const std::
     t[m].flow_off = (unsigned long long)m * gr.flow_member_stride;
     t[m].cell_off = (unsigned long long)m * gr.cells();
     t[m].in_off = (unsigned long long)m * gr.ny;
-    t[m].drive = drive ? drive + (size_t)m * drive_stride : nullptr;
+    t[m].drive = drive ? drive + 2 * (size_t)m : nullptr;
   }
   HIP_TRY(hipMemcpy(s.table, t.data(), t.size() * sizeof(lbm::DpScalarMember), hipMemcpyHostToDevice));
   s.table_drive = drive;
-  s.table_drive_stride = drive_stride;
   return LBM_OK;
 }
 
 // Behind scalar_check and the caller's synchronisation: the scalar of every member on, from c0.  The arrays are allocated by the
 // first call; c_wall NULL: all insulating (NaN), c_in NULL: zeros.
 static inline int scalar_set(ScalarState &s, const ScalarGrid &gr, hipStream_t st, const double *diffusivity, const double *c0,
-                             const double *c_wall, const double *c_in, const double *drive, unsigned long long drive_stride) {
+                             const double *c_wall, const double *c_in, const double *drive) {
   const size_t n = gr.cells(), all = (size_t)gr.members * n;
   const size_t g_bytes = ((size_t)gr.members * gr.member_stride() + 32) * sizeof(double);
   for (double *&g : s.g)
@@ -158,7 +500,7 @@ static inline int scalar_set(ScalarState &s, const ScalarGrid &gr, hipStream_t s
   if (!s.table) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.table), (size_t)gr.members * sizeof(lbm::DpScalarMember)));
   std::vector<double> omega_s(gr.members);
   for (int m = 0; m < gr.members; m++) omega_s[m] = lbm::dp_scalar_omega(diffusivity[m]);
-  if (int rc = scalar_table(s, gr, omega_s, drive, drive_stride)) return rc;
+  if (int rc = scalar_table(s, gr, omega_s, drive)) return rc;
   if (c_wall) {
     HIP_TRY(hipMemcpy(s.c_wall, c_wall, all * sizeof(double), hipMemcpyHostToDevice));
   } else {
@@ -177,6 +519,14 @@ static inline int scalar_set(ScalarState &s, const ScalarGrid &gr, hipStream_t s
   s.on = true;
   s.diffusivity.assign(diffusivity, diffusivity + gr.members);
   s.omega_s = omega_s;
+  return LBM_OK;
+}
+
+// Off, behind the caller's synchronisation: the arrays stay until the handle goes; it runs as one that never had a scalar
+static inline int scalar_off(ScalarState &s) {
+  s.on = false;
+  s.diffusivity.clear();
+  s.omega_s.clear();
   return LBM_OK;
 }
 
@@ -207,9 +557,9 @@ static inline int scalar_step(ScalarState &s, const ScalarGrid &gr, hipStream_t 
 }
 
 // Before the first scalar step of a run: the device table names the body force as it is set now
-static inline int scalar_begin_run(ScalarState &s, const ScalarGrid &gr, const double *drive, unsigned long long drive_stride) {
-  if (s.table_drive == drive && s.table_drive_stride == drive_stride) return LBM_OK;
-  return scalar_table(s, gr, s.omega_s, drive, drive_stride);
+static inline int scalar_begin_run(ScalarState &s, const ScalarGrid &gr, const double *drive) {
+  if (s.table_drive == drive) return LBM_OK;
+  return scalar_table(s, gr, s.omega_s, drive);
 }
 
 static inline int scalar_refuse_off(const char *what) {
@@ -318,6 +668,28 @@ static inline int buoy_table(BuoyState &s, hipStream_t st, std::vector<lbm::DpBu
   HIP_TRY(hipMemcpy(s.table, t.data(), t.size() * sizeof(lbm::DpBuoyMember), hipMemcpyHostToDevice));
   s.uploaded = t;
   return LBM_OK;
+}
+
+// The members' table as the handle's settings stand now, before a run and before the output stage: the flow constants are those
+// the tables behind g.table hold, from the host's copies
+static inline int buoy_sync(BuoyState &b, const FlowState &s, const FlowGrid &g) {
+  std::vector<lbm::DpBuoyMember> t(g.members, lbm::DpBuoyMember{});
+  const double *u_in = lbm::dens_open_table(g.table, g.members);
+  const size_t row = (size_t)g.p[0].ny + 1;
+  for (int i = 0; i < g.members; i++) {
+    const lbm::DpMember m = member_constants<lbm::DpMember>(g.p[i]);
+    t[i].buoy.f0_x = s.drive_f[2 * (size_t)i];
+    t[i].buoy.f0_y = s.drive_f[2 * (size_t)i + 1];
+    t[i].omega = g.p[i].omega;
+    t[i].omega_m = s.omega_m[i];
+    t[i].aw1 = m.aw1;
+    t[i].aw2 = m.aw2;
+    t[i].rho_out = s.open_host[i * row + row - 1];
+    t[i].rho_wall = s.rho_wall[i];
+    t[i].les = les_constants(s, g.p, i);
+    t[i].u_in = u_in + i * row;
+  }
+  return buoy_table(b, g.q.st, t);
 }
 
 // One buoyant flow step of all members, enqueued: the instance the five options choose

@@ -630,7 +630,9 @@ __global__ __launch_bounds__(kMultiThreads) void d2q9_dp_multi(const DpMultiArgs
 
 // What differs from member to member, in device memory, read by member index (a wave-uniform load), as EnsMember.  An
 // ensemble holds a table of these (lbm_dens.cpp), a context a table of one (lbm_dp.cpp): the helper kernels below read a
-// grid's constants here in both families.
+// grid's constants here in both families.  Behind the table, in the same allocation, lie the four tables of the options'
+// per-member constants (dens_*_table below), in both families too: a context's are an ensemble's of one member (dp_host.h
+// writes them; the ensemble's step kernels and the output stage read them, a context's step kernels take theirs as arguments).
 struct DpMember {
   double omega, aw1, aw2;  // aw1 = density*accel/9, aw2 = density*accel/36 (kernels.cl:14-15), in double
   double density;
@@ -641,6 +643,25 @@ struct DpMember {
   };
 };
 static_assert(sizeof(DpMember) == 64, "a member's constants are one 64-B line");
+
+// Open boundaries: member m's inlet profile u_in[ny] and, behind it, its rho_out lie m * (ny + 1) doubles into a second table,
+// which starts where the table of DpMember ends: one allocation, and DensArgs is the struct of a library without it.
+__host__ __device__ inline const double *dens_open_table(const DpMember *members, int n) {
+  return reinterpret_cast<const double *>(members + n);
+}
+// Moving walls: member m's rho_wall is entry m of a third table, behind the open-boundary table
+__host__ __device__ inline const double *dens_wall_table(const DpMember *members, int n, int ny) {
+  return dens_open_table(members, n) + (size_t)n * (ny + 1);
+}
+// Subgrid viscosity: member m's DpLes (tau0, les_k, magic; dp_kernels.h) is entry m of a fourth table, behind the wall table
+__host__ __device__ inline const DpLes *dens_les_table(const DpMember *members, int n, int ny) {
+  return reinterpret_cast<const DpLes *>(dens_wall_table(members, n, ny) + n);
+}
+
+// Body force: member m's F_x, F_y are entry m of a fifth table, double[n][2], behind the subgrid table
+__host__ __device__ inline const double *dens_drive_table(const DpMember *members, int n, int ny) {
+  return reinterpret_cast<const double *>(dens_les_table(members, n, ny) + n);
+}
 
 // ---- the helper kernels: one set for both families --------------------------------------------------------------------
 // Each has a member axis (blockIdx.y; blockIdx.z in dp_reduce): member m's grid lies m * member_stride into cells, its mask

@@ -14,10 +14,8 @@
 // launch parities, so from the end of such a run until the next upload the array that holds a member's state is the
 // member's own (`par`).
 #include "../../include/lbm.h"
-#include "body_map.h"
 #include "dp_host.h"
 #include "dp_steady_kernels.h"
-#include "host_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -32,8 +30,6 @@ namespace {
 
 constexpr long kDensMaxCells = 300L * 1024;   // up to here lbm_dp itself takes the LDS-tile form (multistep_effective, lbm_dp.cpp)
 constexpr int kDensMaxMembers = 65535;        // member index = blockIdx.y (blockIdx.z in dp_reduce)
-constexpr size_t kDensRingBytes = 32u << 20;  // per-step segment sums of all members buffered between reductions
-constexpr int kDensRingMax = 256;
 constexpr long kDensSegsPerBlock = 4096;      // segments per block of the first reduction stage: lbm_dp.cpp's kDpSegsPerBlock
 
 // The instantiated form of d2q9_dp_ensemble<16, TY, TMAX, threads>: 16 x 16 at T <= 3 with 1024 threads, two workgroups per
@@ -63,27 +59,15 @@ struct lbm_dens {
   BodyMap body;                    // the host's copy of what the mask was made of (body_map.h)
   DpMember *members = nullptr;     // [n], then the open-boundary table double[n][ny + 1] (dens_open_table), then rho_wall[n]
                                    // (dens_wall_table), then DpLes[n] (dens_les_table), then the body forces double[n][2]
-                                   // (dens_drive_table)
+                                   // (dens_drive_table): dp_host.h allocates and writes them, the kernels read them
   double *seg = nullptr;           // [ring][n][ny][nseg]
   double *red = nullptr;           // [ring][n][red_blocks]: first reduction stage
   double *av_sum = nullptr;        // [n][max_iters]
   double *fin_partials = nullptr;  // [n][fin_blocks]
   double *force_rec = nullptr;     // option "force": [2][n][max_iters], F_x then F_y per member and step
   double *force_now = nullptr;     // [2][n]: lbm_dforce_ens's F_x, F_y (allocated by the first call)
-  bool force = false;              // option "force": the kernels' FORCE instances, three values per segment
-  bool trt = false;                // lbm_dtrt_ens_set: the kernels' TRT instances, for all members
-  std::vector<double> magic;       // [n]: every member's magic parameter, 0 while the ensemble is BGK
-  std::vector<double> omega_m;     // [n]: the host's copy of DpMember::omega_m (BGK: the member's omega)
-  bool open = false;               // lbm_dopen_ens_set: the kernels' OPEN instances for all members, no accelerate_flow
-  std::vector<double> open_host;   // [n][ny + 1]: per member u_in[ny], then rho_out (empty while off); on the device behind `members`
-  bool wall = false;               // lbm_dwall_ens_set: the kernels' WALL instances for all members
-  std::vector<double> wall_u;      // [2][n][ny][nx]: the host's copy of the wall velocities, u_x then u_y (empty while off)
-  std::vector<double> rho_wall;    // [n]: the members' wall densities (empty while off); on the device behind the open table
-  double *wall_dev = nullptr;      // [2][n][ny][nx] (allocated by the first lbm_dwall_ens_set that switches on)
-  bool les = false;                // lbm_dles_ens_set: the kernels' LES instances, for all members
-  std::vector<double> les_c;       // [n]: every member's Smagorinsky constant, 0 while the setting is off
-  bool drive = false;              // lbm_ddrive_ens_set: the kernels' DRIVE instances, for all members
-  std::vector<double> drive_f;     // [n][2]: every member's force density, 0 while the setting is off
+  FlowState flow;                  // "force", lbm_dtrt_ens_set, lbm_dopen_ens_set, lbm_dwall_ens_set, lbm_dles_ens_set,
+                                   // lbm_ddrive_ens_set: the members' settings (dp_host.h), all off by default
   ScalarState scalar;              // lbm_dscalar_ens_set: the members' scalars (dp_host.h), off by default
   BuoyState buoy;                  // lbm_dbuoy_ens_set: the scalars act back on the members' flows (dp_host.h), off by default
   int nseg = 1, red_blocks = 1, fin_blocks = 1;
@@ -114,54 +98,21 @@ void free_dens(lbm_dens *e) {
   if (e->fin_partials) (void)hipFree(e->fin_partials);
   if (e->force_rec) (void)hipFree(e->force_rec);
   if (e->force_now) (void)hipFree(e->force_now);
-  if (e->wall_dev) (void)hipFree(e->wall_dev);
   if (e->steady_words) (void)hipFree(e->steady_words);
   if (e->steady_inv) (void)hipFree(e->steady_inv);
   if (e->steady_count_host) (void)hipHostFree(e->steady_count_host);
   if (e->stage) (void)hipFree(e->stage);
+  if (e->flow.wall_dev) (void)hipFree(e->flow.wall_dev);
   scalar_free(e->scalar);
   buoy_free(e->buoy);
   queue_destroy(e->q);
   delete e;
 }
 
-// values per segment and step: |u|, and F_x, F_y with the option "force"
-int seg_values(const lbm_dens *e) { return e->force ? 3 : 1; }
-
-// The ring of per-step segment sums of all members and the first reduction stage's partials, (re)allocated for the values
-// a segment carries (alloc_ring of lbm_dp.cpp).  How many steps lie between two reductions decides no sum.
-int alloc_ring(lbm_dens *e) {
-  const size_t all_step = (size_t)e->n * e->ny * e->nseg * seg_values(e);
-  e->ring = ring_steps(all_step * sizeof(double), kDensTMax, kDensRingMax, kDensRingBytes);
-  if (e->seg) HIP_TRY(hipFree(e->seg));
-  e->seg = nullptr;
-  if (e->red) HIP_TRY(hipFree(e->red));
-  e->red = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->seg), (size_t)e->ring * all_step * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->red), (size_t)e->ring * e->n * e->red_blocks * sizeof(double)));
-  return LBM_OK;
-}
-
-// The table of per-member constants with these second relaxation rates, to the device
-int upload_members(lbm_dens *e, const std::vector<double> &omega_m) {
-  std::vector<DpMember> t(e->n);
-  for (int i = 0; i < e->n; i++) {
-    t[i] = member_constants<DpMember>(e->p[i]);
-    t[i].omega_m = omega_m[i];
-  }
-  HIP_TRY(hipMemcpy(e->members, t.data(), t.size() * sizeof(DpMember), hipMemcpyHostToDevice));
-  return LBM_OK;
-}
-
-// The table of per-member subgrid constants for these Smagorinsky constants and magic parameters, to the device: tau0 and
-// les_k by the header's host statements.  Written by lbm_dles_ens_set and again by lbm_dtrt_ens_set, so that the two may be
-// set in either order.
-int upload_les(lbm_dens *e, const std::vector<double> &c, const std::vector<double> &magic) {
-  std::vector<DpLes> t(e->n);
-  for (int i = 0; i < e->n; i++) t[i] = dp_les_constants(e->p[i].omega, c[i], magic[i]);
-  HIP_TRY(hipMemcpy(const_cast<DpLes *>(dens_les_table(e->members, e->n, e->ny)), t.data(), t.size() * sizeof(DpLes),
-                    hipMemcpyHostToDevice));
-  return LBM_OK;
+// the members' grids and their ring as the setters take them (dp_host.h)
+FlowGrid flow_grid(lbm_dens *e) {
+  return FlowGrid{e->n, e->p.data(), e->members, e->q, e->steps_done, e->seg, e->red, e->ring, (size_t)e->ny * e->nseg,
+                  e->red_blocks, kDensTMax};
 }
 
 int build_dens(lbm_dens *e, const int32_t *obstacles) {
@@ -178,12 +129,11 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
   e->red_blocks = (int)std::min(512L, div_up((long)per_step, kDensSegsPerBlock));
   e->fin_blocks = (int)std::max(1L, std::min(div_up((long)cells_per, kBlock), 2048L));
   const size_t all_step = (size_t)n * per_step;
-  e->ring = ring_steps(all_step * sizeof(double), kDensTMax, kDensRingMax, kDensRingBytes);
+  e->ring = ring_steps_of(n, per_step, 1, kDensTMax);
 
   // what the ensemble needs against what the device has free: refuse here rather than fail half-way through
   const size_t cells_bytes = ((size_t)n * e->member_stride + 32) * sizeof(double);
-  const size_t tables = (size_t)n * (sizeof(DpMember) + (size_t)(ny + 2) * sizeof(double) + sizeof(DpLes) + sizeof(DpDrive));
-  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + tables +
+  const size_t need = 2 * cells_bytes + (size_t)n * cells_per + 64 + flow_table_bytes(n, ny) +
                       (size_t)e->ring * all_step * sizeof(double) + (size_t)e->ring * n * e->red_blocks * sizeof(double) +
                       (size_t)n * e->max_iters * sizeof(double) + (size_t)n * e->fin_blocks * sizeof(double);
   size_t free_b = 0, total_b = 0;
@@ -198,20 +148,15 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
     HIP_TRY(hipMemset(e->cells[i], 0, cells_bytes));
   }
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->mask), (size_t)n * cells_per + 64));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->members), tables));
-  if (int rc = alloc_ring(e)) return rc;
+  // the members' tables, every option off: in double these are lbm_dp.cpp's own statements, a member's constants are a context's
+  if (int rc = flow_create(e->flow, &e->members, e->p.data(), n)) return rc;
+  if (int rc = alloc_ring(flow_grid(e), 1)) return rc;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->av_sum), (size_t)n * e->max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->fin_partials), (size_t)n * e->fin_blocks * sizeof(double)));
   // the members' byte masks from the caller's int32[n][ny][nx]
   if (int rc = upload_mask(e->mask, obstacles, (size_t)n * cells_per)) return rc;
   body_reset(e->body, obstacles, (size_t)n * cells_per);
-  // in double these are lbm_dp.cpp's own statements (run_dp_impl, lbm_dp_upload): a member's constants are a context's
-  e->magic.assign(n, 0.0);
-  e->les_c.assign(n, 0.0);
-  e->drive_f.assign(2 * (size_t)n, 0.0);
-  e->omega_m.resize(n);
-  for (int i = 0; i < n; i++) e->omega_m[i] = e->p[i].omega;
-  return upload_members(e, e->omega_m);
+  return LBM_OK;
 }
 
 // FORCE from the option "force", TRT from lbm_dtrt_ens_set, OPEN from lbm_dopen_ens_set, WALL from lbm_dwall_ens_set, LES from
@@ -220,12 +165,13 @@ int build_dens(lbm_dens *e, const int32_t *obstacles) {
 // leg of a steady run
 void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
   const dim3 grid(e->tiles, e->n), block(kDensThreads);
-  dp_with_flags(e->force, e->trt, e->open, e->wall, e->les, e->drive, [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
+  const FlowState &f = e->flow;
+  dp_with_flags(f.force, f.trt, f.open, f.wall, f.les, f.drive, [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
     constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value,
                    LES = decltype(les)::value, DRIVE = decltype(drive)::value;
     DensArgsOf<WALL> w{};
     static_cast<DensArgs &>(w) = a;
-    if constexpr (WALL) w.wall_u = e->wall_dev;
+    if constexpr (WALL) w.wall_u = e->flow.wall_dev;
     if (!active)
       hipLaunchKernelGGL((d2q9_dp_ensemble<kDensTX, kDensTY, kDensTMax, kDensThreads, FORCE, TRT, OPEN, WALL, LES, DRIVE>), grid, block, 0,
                          e->q.st, w);
@@ -235,50 +181,30 @@ void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
   });
 }
 
-// the members' grids as the scalar's helpers take them (dp_host.h), and where the scalar reads the members' body forces
+// the members' grids as the scalar's helpers take them (dp_host.h), and where the output stage and the scalar read the
+// members' body forces
 ScalarGrid scalar_grid(const lbm_dens *e) { return ScalarGrid{e->n, e->nx, e->ny, e->plane_stride, e->member_stride}; }
-const double *scalar_drive(const lbm_dens *e) { return e->drive ? dens_drive_table(e->members, e->n, e->ny) : nullptr; }
-
-// Buoyancy: the members' table as the settings stand now (dp_host.h: buoy_table), before a run and before the output stage.  The
-// flow constants are those the tables behind `members` hold, from the host's copies.
-int buoy_sync(lbm_dens *e) {
-  std::vector<DpBuoyMember> t(e->n, DpBuoyMember{});
-  const double *u_in = dens_open_table(e->members, e->n);
-  for (int i = 0; i < e->n; i++) {
-    const DpMember m = member_constants<DpMember>(e->p[i]);
-    t[i].buoy.f0_x = e->drive_f[2 * (size_t)i];
-    t[i].buoy.f0_y = e->drive_f[2 * (size_t)i + 1];
-    t[i].omega = e->p[i].omega;
-    t[i].omega_m = e->omega_m[i];
-    t[i].aw1 = m.aw1;
-    t[i].aw2 = m.aw2;
-    t[i].rho_out = e->open ? e->open_host[(size_t)i * (e->ny + 1) + e->ny] : 0.0;
-    t[i].rho_wall = e->wall ? e->rho_wall[i] : 0.0;
-    t[i].les = dp_les_constants(e->p[i].omega, e->les_c[i], e->magic[i]);
-    t[i].u_in = u_in + (size_t)i * (e->ny + 1);
-  }
-  return buoy_table(e->buoy, e->q.st, t);
-}
+const double *drive_dev(const lbm_dens *e) { return e->flow.drive ? dens_drive_table(e->members, e->n, e->ny) : nullptr; }
 
 // nsteps steps from step count `first` on, enqueued: the prologue, the launches, the reductions into the record.  Flips
 // e->cur per launch; the caller counts the steps.  active: as launch_dens.
 int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   const size_t per_step = (size_t)e->ny * e->nseg, all_step = (size_t)e->n * per_step;
-  const int nval = seg_values(e);
+  const int nval = seg_values(e->flow);
   const size_t slot = all_step * nval;   // one step in the ring: [nval][n][ny][nseg]
   // with a scalar on every launch advances one step: the scalar reads each step's velocities (never during a steady run, which
   // is refused while a scalar is on)
   const bool scalar = e->scalar.on;
   const ScalarGrid sgrid = scalar_grid(e);
   if (scalar)
-    if (int rc = scalar_begin_run(e->scalar, sgrid, scalar_drive(e), 2ull)) return rc;
+    if (int rc = scalar_begin_run(e->scalar, sgrid, drive_dev(e))) return rc;
   // with buoyancy on the flow step is d2q9_dp_buoyant, one step per launch (never during a steady run)
   const bool buoy = scalar && e->buoy.on;
   if (buoy)
-    if (int rc = buoy_sync(e)) return rc;
+    if (int rc = buoy_sync(e->buoy, e->flow, flow_grid(e))) return rc;
   // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
   // into the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
-  if (!e->open) {
+  if (!e->flow.open) {
     hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
                        e->member_stride, (const uint8_t *)e->mask, (const DpMember *)e->members, e->nx, e->ny, active);
     HIP_TRY(hipGetLastError());
@@ -309,7 +235,7 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
       if (int rc = flush()) return rc;
     // scalar step n before flow step n, on the state that flow step streams
     if (scalar)
-      if (int rc = scalar_step(e->scalar, sgrid, e->q.st, e->cells[e->cur], e->mask, e->open, buoy ? e->buoy.table : nullptr)) return rc;
+      if (int rc = scalar_step(e->scalar, sgrid, e->q.st, e->cells[e->cur], e->mask, e->flow.open, buoy ? e->buoy.table : nullptr)) return rc;
     if (buoy) {
       // flow step n reads the scalar array that scalar step n has just written
       DpBuoyArgs b{};
@@ -318,15 +244,15 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
       b.mask = e->mask;
       b.scalar = e->scalar.g[e->scalar.cur];
       b.members = e->buoy.table;
-      b.wall_u = e->wall_dev;
+      b.wall_u = e->flow.wall_dev;
       b.seg = e->seg + (size_t)e->ring_fill * slot;
       b.plane_stride = e->plane_stride;
       b.member_stride = e->member_stride;
       b.nx = e->nx;
       b.ny = e->ny;
       b.lanes_per_row = e->nseg * 8;
-      b.accel_row = (!e->open && i + adv < nsteps) ? e->ny - 2 : -1;
-      if (int rc = buoy_launch(e->q.st, e->force, e->trt, e->open, e->wall, e->les, b, e->n)) return rc;
+      b.accel_row = (!e->flow.open && i + adv < nsteps) ? e->ny - 2 : -1;
+      if (int rc = buoy_launch(e->q.st, e->flow.force, e->flow.trt, e->flow.open, e->flow.wall, e->flow.les, b, e->n)) return rc;
       e->cur ^= 1;
       e->ring_fill += adv;
       i += adv;
@@ -346,7 +272,7 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
     a.nseg = e->nseg;
     a.tiles_x = e->tiles_x;
     a.T = adv;
-    a.accel_next = (!e->open && i + adv < nsteps) ? 1 : 0;
+    a.accel_next = (!e->flow.open && i + adv < nsteps) ? 1 : 0;
     launch_dens(e, a, active);
     HIP_TRY(hipGetLastError());
     e->cur ^= 1;
@@ -460,11 +386,11 @@ int final_fields_dens(lbm_dens *e, double *const (&d)[4]) {
   // buoyancy: the half-force of the scalar state that is current, per cell (a scalar is never on while the ensemble is ragged)
   const bool buoy = e->scalar.on && e->buoy.on;
   if (buoy)
-    if (int rc = buoy_sync(e)) return rc;
+    if (int rc = buoy_sync(e->buoy, e->flow, flow_grid(e))) return rc;
   hipLaunchKernelGGL(dp_final_fields, dim3(e->fin_blocks, e->n), dim3(kBlock), 0, e->q.st,
                      (const double *)e->cells[e->ragged ? 0 : e->cur], (const double *)e->cells[1], member_parity(e), e->plane_stride,
                      e->member_stride, e->nx, (const uint8_t *)e->mask, (size_t)e->nx * e->ny, (const DpMember *)e->members,
-                     e->drive ? dens_drive_table(e->members, e->n, e->ny) : (const double *)nullptr,
+                     drive_dev(e),
                      buoy ? (const double *)e->scalar.g[e->scalar.cur] : (const double *)nullptr,
                      buoy ? (const DpBuoyMember *)e->buoy.table : (const DpBuoyMember *)nullptr, d[0], d[1], d[2], d[3], e->fin_partials);
   HIP_TRY(hipGetLastError());
@@ -649,25 +575,8 @@ int lbm_dforce_ens_set_option(lbm_dens *e, const char *key, long value) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (!key) return lbm_fail(LBM_ERR_ARG, "key is NULL");
   if (strcmp(key, "force")) return lbm_fail(LBM_ERR_ARG, "unknown option '%s' (a double-precision ensemble has \"force\")", key);
-  if (value != 0 && value != 1) return lbm_fail(LBM_ERR_ARG, "force must be 0 or 1 (got %ld)", value);
-  if (e->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "\"force\" is set before the first step (%d done): the record holds every step since "
-                    "lbm_dens_upload", e->steps_done);
-  if ((value != 0) == e->force) return LBM_OK;
-  if (int rc = queue_sync(e->q)) return rc;
-  const bool before = e->force;
-  e->force = value != 0;
-  int rc = alloc_ring(e);
-  if (rc == LBM_OK && e->force && !e->force_rec)
-    rc = hip_alloc(reinterpret_cast<void **>(&e->force_rec), 2 * (size_t)e->n * e->max_iters * sizeof(double));
-  if (rc != LBM_OK) {
-    // back to a ring that fits the option as it was
-    const std::string keep = lbm_last_error();
-    e->force = before;
-    if (alloc_ring(e) != LBM_OK) e->failed = true;
-    return fail_again(rc, keep);
-  }
-  return LBM_OK;
+  if (int rc = force_check(value)) return rc;
+  return force_set(e->flow, flow_grid(e), value, true, e->force_rec, e->failed);
 }
 
 int lbm_dforce_ens_get_option(const lbm_dens *e, const char *key, long *value) {
@@ -675,7 +584,7 @@ int lbm_dforce_ens_get_option(const lbm_dens *e, const char *key, long *value) {
   if (!key) return lbm_fail(LBM_ERR_ARG, "key is NULL");
   if (!value) return lbm_fail(LBM_ERR_ARG, "value is NULL");
   if (strcmp(key, "force")) return lbm_fail(LBM_ERR_ARG, "unknown option '%s' (a double-precision ensemble has \"force\")", key);
-  *value = e->force ? 1 : 0;
+  *value = e->flow.force ? 1 : 0;
   return LBM_OK;
 }
 
@@ -683,7 +592,7 @@ int lbm_dforce_ens_record(lbm_dens *e, double *fx_out, double *fy_out) {
   // argument errors before a device is touched
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (!fx_out && !fy_out) return lbm_fail(LBM_ERR_ARG, "fx_out and fy_out are both NULL");
-  if (!e->force)
+  if (!e->flow.force)
     return lbm_fail(LBM_ERR_STATE, "no force record: option \"force\" is off (lbm_dforce_ens_set_option before the first step)");
   if (int rc = queue_sync(e->q)) return rc;
   const int T = e->steps_done;
@@ -717,7 +626,7 @@ int lbm_dforce_ens(lbm_dens *e, double *fx, double *fy) {
   a.member_stride = e->member_stride;
   a.nx = e->nx;
   a.ny = e->ny;
-  a.no_accel = e->open ? 1 : 0;
+  a.no_accel = e->flow.open ? 1 : 0;
   if (int rc = force_state(e->q.st, a, e->nseg, e->n, e->seg, e->red, e->red_blocks, e->force_now)) return rc;
   std::vector<double> f(2 * n);
   HIP_TRY(hipMemcpyAsync(f.data(), e->force_now, f.size() * sizeof(double), hipMemcpyDeviceToHost, e->q.st));
@@ -731,11 +640,11 @@ int lbm_dforce_ens(lbm_dens *e, double *fx, double *fy) {
 
 int lbm_dbody_ens_set(lbm_dens *e, const int32_t *body) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  if (e->force && e->steps_done != 0)
+  if (e->flow.force && e->steps_done != 0)
     return lbm_fail(LBM_ERR_STATE, "with \"force\" on, a body map is set before the first step (%d done): one record holds one body",
                     e->steps_done);
   if (int rc = queue_sync(e->q)) return rc;
-  return body_apply(e->body, e->mask, body, e->n, e->ny, e->nx, true, e->open);
+  return body_apply(e->body, e->mask, body, e->n, e->ny, e->nx, true, e->flow.open);
 }
 
 int lbm_dbody_ens_get(lbm_dens *e, int32_t *body_out) {
@@ -751,7 +660,7 @@ int lbm_dbody_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol)
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
   if (e->scalar.on) return refuse_steady_scalar("lbm_dbody_steady_run");
-  if (!e->force)
+  if (!e->flow.force)
     return lbm_fail(LBM_ERR_STATE, "the drag criterion reads the force record: option \"force\" is off (lbm_dforce_ens_set_option "
                     "switches it on before the first step)");
   bool launched = false;
@@ -759,90 +668,31 @@ int lbm_dbody_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol)
   return latch_failure(rc, launched, e->q.st, &e->failed);
 }
 
+// The six setters: the NULL checks, the check of every member's values (dp_host.h), then the set.
 int lbm_dtrt_ens_set(lbm_dens *e, const double *magic) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  // every member is checked before anything changes, on the host or on the device
-  std::vector<double> omega_m(e->n);
-  for (int m = 0; m < e->n; m++) {
-    const double omega = e->p[m].omega;
-    omega_m[m] = omega;
-    if (!magic) continue;
-    if (!(magic[m] > 0.0) || !std::isfinite(magic[m]))
-      return lbm_fail(LBM_ERR_ARG, "member %d: magic must be finite and positive (got %g); an ensemble is all TRT or, with a NULL "
-                      "array, all BGK", m, magic[m]);
-    if (!(1.0 / omega - 0.5 > 0.0))
-      return lbm_fail(LBM_ERR_ARG, "member %d: the two-relaxation-time operator needs 1/omega - 1/2 > 0: omega is %g", m, omega);
-    omega_m[m] = dp_trt_omega_minus(omega, magic[m]);
-  }
-  if (e->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "the collision operator is set before the first step (%d done): one record holds one operator",
-                    e->steps_done);
-  if (int rc = queue_sync(e->q)) return rc;
-  if (int rc = upload_members(e, omega_m)) return rc;
-  e->trt = magic != nullptr;
-  if (magic) e->magic.assign(magic, magic + e->n);
-  else e->magic.assign(e->n, 0.0);
-  e->omega_m = omega_m;
-  // the subgrid table carries the magic parameter: the TRT + LES instances recompute the second rate per cell
-  if (e->les) return upload_les(e, e->les_c, e->magic);
-  return LBM_OK;
+  if (int rc = trt_check(e->p.data(), e->n, magic, true)) return rc;
+  return trt_set(e->flow, flow_grid(e), magic);
 }
 
 int lbm_dtrt_ens_get(const lbm_dens *e, double *magic_out, double *omega_minus_out) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (!magic_out && !omega_minus_out) return lbm_fail(LBM_ERR_ARG, "magic_out and omega_minus_out are both NULL");
-  if (magic_out) std::copy(e->magic.begin(), e->magic.end(), magic_out);
-  if (omega_minus_out) std::copy(e->omega_m.begin(), e->omega_m.end(), omega_minus_out);
+  trt_get(e->flow, magic_out, omega_minus_out);
   return LBM_OK;
 }
 
 int lbm_dopen_ens_set(lbm_dens *e, const double *u_in, const double *rho_out) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (u_in && !rho_out) return lbm_fail(LBM_ERR_ARG, "rho_out is NULL (u_in is not: every member needs its outlet density)");
-  // every member is checked before anything changes, on the host or on the device
-  const size_t ny = (size_t)e->ny;
-  std::vector<double> table;
-  if (u_in) {
-    table.resize((size_t)e->n * (ny + 1));
-    for (int m = 0; m < e->n; m++) {
-      if (!positive_finite(rho_out[m]))
-        return lbm_fail(LBM_ERR_ARG, "member %d: rho_out must be finite and positive (got %g)", m, rho_out[m]);
-      for (size_t y = 0; y < ny; y++) {
-        const double u = u_in[(size_t)m * ny + y];
-        if (!std::isfinite(u) || !(u < 1.0))
-          return lbm_fail(LBM_ERR_ARG, "member %d: u_in of row %d must be finite and below 1 (got %g)", m, (int)y, u);
-        table[(size_t)m * (ny + 1) + y] = u;
-      }
-      table[(size_t)m * (ny + 1) + ny] = rho_out[m];
-    }
-  }
-  if (e->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "open boundaries are set before the first step (%d done): one record holds one flow",
-                    e->steps_done);
-  if (!u_in && !e->open) return LBM_OK;
-  if (int rc = queue_sync(e->q)) return rc;
-  HIP_TRY(hipSetDevice(e->q.dev));
-  if (u_in)
-    HIP_TRY(hipMemcpy(const_cast<double *>(dens_open_table(e->members, e->n)), table.data(), table.size() * sizeof(double),
-                      hipMemcpyHostToDevice));
-  // the device mask under the column rule, or without it again
-  if (int rc = body_rewrite(e->body, e->mask, e->nx, u_in != nullptr)) return rc;
-  e->open = u_in != nullptr;
-  e->open_host.swap(table);
-  return LBM_OK;
+  if (int rc = open_check(e->p.data(), e->n, u_in, rho_out, true)) return rc;
+  return open_set(e->flow, flow_grid(e), e->body, e->mask, u_in, rho_out);
 }
 
 int lbm_dopen_ens_get(const lbm_dens *e, int *on_out, double *u_in_out, double *rho_out_out) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (!on_out && !u_in_out && !rho_out_out) return lbm_fail(LBM_ERR_ARG, "on_out, u_in_out and rho_out_out are all NULL");
-  if (on_out) *on_out = e->open ? 1 : 0;
-  if (!e->open) return LBM_OK;
-  const size_t ny = (size_t)e->ny;
-  for (int m = 0; m < e->n; m++) {
-    const double *row = e->open_host.data() + (size_t)m * (ny + 1);
-    if (u_in_out) std::copy(row, row + ny, u_in_out + (size_t)m * ny);
-    if (rho_out_out) rho_out_out[m] = row[ny];
-  }
+  open_get(e->flow, e->n, e->ny, on_out, u_in_out, rho_out_out);
   return LBM_OK;
 }
 
@@ -852,118 +702,41 @@ int lbm_dwall_ens_set(lbm_dens *e, const double *u_x, const double *u_y, const d
     return lbm_fail(LBM_ERR_ARG, "%s is NULL and %s is not: a wall velocity has two components (both NULL: off)", u_x ? "u_y" : "u_x",
                     u_x ? "u_x" : "u_y");
   if (u_x && !rho_wall) return lbm_fail(LBM_ERR_ARG, "rho_wall is NULL (u_x is not: every member needs its wall density)");
-  // every member is checked before anything changes, on the host or on the device
-  if (u_x) {
-    for (int m = 0; m < e->n; m++)
-      if (!positive_finite(rho_wall[m]))
-        return lbm_fail(LBM_ERR_ARG, "member %d: rho_wall must be finite and positive (got %g)", m, rho_wall[m]);
-    if (int rc = wall_check(e->body, u_x, u_y, e->n, e->ny, e->nx, true)) return rc;
-  }
-  if (e->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "wall velocities are set before the first step (%d done): one record holds one flow", e->steps_done);
-  if (!u_x) {
-    e->wall = false;
-    e->wall_u.clear();
-    e->rho_wall.clear();
-    return LBM_OK;
-  }
-  if (int rc = queue_sync(e->q)) return rc;
-  HIP_TRY(hipSetDevice(e->q.dev));
-  const size_t all = (size_t)e->n * e->nx * e->ny;
-  if (!e->wall_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->wall_dev), 2 * all * sizeof(double)));
-  std::vector<double> u(2 * all);
-  std::copy(u_x, u_x + all, u.begin());
-  std::copy(u_y, u_y + all, u.begin() + all);
-  HIP_TRY(hipMemcpy(e->wall_dev, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(const_cast<double *>(dens_wall_table(e->members, e->n, e->ny)), rho_wall, (size_t)e->n * sizeof(double),
-                    hipMemcpyHostToDevice));
-  e->wall = true;
-  e->wall_u.swap(u);
-  e->rho_wall.assign(rho_wall, rho_wall + e->n);
-  return LBM_OK;
+  if (int rc = wall_values_check(e->body, e->p.data(), e->n, u_x, u_y, rho_wall, true)) return rc;
+  return wall_set(e->flow, flow_grid(e), u_x, u_y, rho_wall);
 }
 
 int lbm_dwall_ens_get(const lbm_dens *e, int *on_out, double *u_x_out, double *u_y_out, double *rho_wall_out) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (!on_out && !u_x_out && !u_y_out && !rho_wall_out)
     return lbm_fail(LBM_ERR_ARG, "on_out, u_x_out, u_y_out and rho_wall_out are all NULL");
-  if (on_out) *on_out = e->wall ? 1 : 0;
-  if (!e->wall) return LBM_OK;
-  const size_t all = (size_t)e->n * e->nx * e->ny;
-  if (u_x_out) std::copy(e->wall_u.begin(), e->wall_u.begin() + all, u_x_out);
-  if (u_y_out) std::copy(e->wall_u.begin() + all, e->wall_u.end(), u_y_out);
-  if (rho_wall_out) std::copy(e->rho_wall.begin(), e->rho_wall.end(), rho_wall_out);
+  wall_get(e->flow, on_out, u_x_out, u_y_out, rho_wall_out);
   return LBM_OK;
 }
 
 int lbm_dles_ens_set(lbm_dens *e, const double *c) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  // every member is checked before anything changes, on the host or on the device
-  if (c)
-    for (int m = 0; m < e->n; m++)
-      if (!(c[m] > 0.0) || !std::isfinite(c[m]))
-        return lbm_fail(LBM_ERR_ARG, "member %d: the Smagorinsky constant c must be finite and positive (got %g); an ensemble has the "
-                        "subgrid viscosity on for all members or, with a NULL array, off", m, c[m]);
-  if (e->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "the subgrid viscosity is set before the first step (%d done): one record holds one operator",
-                    e->steps_done);
-  if (!c) {
-    e->les = false;
-    e->les_c.assign(e->n, 0.0);
-    return LBM_OK;
-  }
-  if (int rc = queue_sync(e->q)) return rc;
-  HIP_TRY(hipSetDevice(e->q.dev));
-  const std::vector<double> cs(c, c + e->n);
-  if (int rc = upload_les(e, cs, e->magic)) return rc;
-  e->les = true;
-  e->les_c = cs;
-  return LBM_OK;
+  if (int rc = les_check(e->n, c, true)) return rc;
+  return les_set(e->flow, flow_grid(e), c);
 }
 
 int lbm_dles_ens_get(const lbm_dens *e, double *c_out, double *les_k_out) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (!c_out && !les_k_out) return lbm_fail(LBM_ERR_ARG, "c_out and les_k_out are both NULL");
-  for (int m = 0; m < e->n; m++) {
-    if (c_out) c_out[m] = e->les_c[m];
-    if (les_k_out) les_k_out[m] = dp_les_constants(e->p[m].omega, e->les_c[m], 0.0).les_k;
-  }
+  les_get(e->flow, e->p.data(), e->n, c_out, les_k_out);
   return LBM_OK;
 }
 
 int lbm_ddrive_ens_set(lbm_dens *e, const double *f) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
-  // every member is checked before anything changes, on the host or on the device
-  if (f)
-    for (int m = 0; m < e->n; m++) {
-      const double f_x = f[2 * (size_t)m], f_y = f[2 * (size_t)m + 1];
-      if (!std::isfinite(f_x) || !std::isfinite(f_y))
-        return lbm_fail(LBM_ERR_ARG, "member %d: the body force must be finite (got f_x = %g, f_y = %g)", m, f_x, f_y);
-      if (!dp_drive_on(f_x, f_y))
-        return lbm_fail(LBM_ERR_ARG, "member %d: the body force is (0, 0); an ensemble has the body force on for all members or, "
-                        "with a NULL array, off", m);
-    }
-  if (e->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "the body force is set before the first step (%d done): one record holds one flow", e->steps_done);
-  if (!f) {
-    e->drive = false;
-    e->drive_f.assign(2 * (size_t)e->n, 0.0);
-    return LBM_OK;
-  }
-  if (int rc = queue_sync(e->q)) return rc;
-  HIP_TRY(hipSetDevice(e->q.dev));
-  HIP_TRY(hipMemcpy(const_cast<double *>(dens_drive_table(e->members, e->n, e->ny)), f, 2 * (size_t)e->n * sizeof(double),
-                    hipMemcpyHostToDevice));
-  e->drive = true;
-  e->drive_f.assign(f, f + 2 * (size_t)e->n);
-  return LBM_OK;
+  if (int rc = drive_check(e->n, f, true)) return rc;
+  return drive_set(e->flow, flow_grid(e), f);
 }
 
 int lbm_ddrive_ens_get(const lbm_dens *e, int *on_out, double *f_out) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (!on_out && !f_out) return lbm_fail(LBM_ERR_ARG, "on_out and f_out are both NULL");
-  if (on_out) *on_out = e->drive ? 1 : 0;
-  if (f_out) std::copy(e->drive_f.begin(), e->drive_f.end(), f_out);
+  drive_get(e->flow, on_out, f_out);
   return LBM_OK;
 }
 
@@ -977,14 +750,8 @@ int lbm_dscalar_ens_set(lbm_dens *e, const double *diffusivity, const double *c0
   if (diffusivity && e->ragged) return refuse_ragged(e);
   if (!diffusivity && e->buoy.on) return buoy_refuse_scalar_off();
   if (int rc = queue_sync(e->q)) return rc;
-  if (!diffusivity) {
-    // the arrays stay until the ensemble goes; the handle runs as one that never had a scalar
-    e->scalar.on = false;
-    e->scalar.diffusivity.clear();
-    e->scalar.omega_s.clear();
-    return LBM_OK;
-  }
-  return scalar_set(e->scalar, gr, e->q.st, diffusivity, c0, c_wall, c_in, scalar_drive(e), 2ull);
+  if (!diffusivity) return scalar_off(e->scalar);
+  return scalar_set(e->scalar, gr, e->q.st, diffusivity, c0, c_wall, c_in, drive_dev(e));
 }
 
 int lbm_dscalar_ens_get(const lbm_dens *e, int *on_out, double *diffusivity_out, double *omega_s_out) {

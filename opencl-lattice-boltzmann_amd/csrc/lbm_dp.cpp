@@ -7,10 +7,7 @@
 // of row ny-2, and the second reduction stage over the buffered steps.  The reference's counterpart is its one grid and
 // in-order queue (d2q9-bgk.c:221-239), in the precision of its fp64 ancestor.
 #include "../../include/lbm.h"
-#include "body_map.h"
 #include "dp_host.h"
-#include "dp_kernels.h"
-#include "host_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -34,8 +31,6 @@ namespace {
 
 constexpr int kDpTX = 16, kDpTY = LBM_DP_TY, kDpTMax = LBM_DP_TMAX;
 constexpr long kDpAutoMultiCells = 300L * 1024;  // the library's bound for "launch-bound" (multistep_effective, lbm_hip.cpp)
-constexpr size_t kDpRingBytes = 32u << 20;       // per-step segment sums buffered between reductions
-constexpr int kDpRingMax = 256;
 constexpr long kDpSegsPerBlock = 4096;           // segments per block of the first reduction stage
 
 }  // namespace
@@ -47,9 +42,10 @@ struct lbm_dp {
   double *cells[2] = {nullptr, nullptr};
   uint8_t *mask = nullptr;        // [ny][nx]: 0 fluid, 1 blocked and counted in the force, 2 blocked outside the body
   BodyMap body;                   // the host's copy of what the mask was made of (body_map.h)
-  DpMember *members = nullptr;    // [1]: this grid's constants as the helper kernels read them (dp_kernels.h); the step kernels
-                                  // take omega, omega_m, aw1, aw2 as arguments, and the table's omega, omega_m are not read;
-                                  // behind it double[2], the body force as dp_final_fields reads it (drive_dev)
+  DpMember *members = nullptr;    // [1]: this grid's constants as the helper kernels read them (dp_kernels.h), and behind it the
+                                  // option tables of an ensemble of one member (dens_*_table; dp_host.h writes them).  The step
+                                  // kernels take their constants as arguments, from flow's host copies; of the tables they read
+                                  // the inlet profile (dens_open_table), and dp_final_fields the body force (dens_drive_table)
   double *seg = nullptr;          // [ring][ny][nseg]
   double *red = nullptr;          // [ring][red_blocks]: first reduction stage
   double *av_sum = nullptr;       // [max_iters]
@@ -60,19 +56,8 @@ struct lbm_dp {
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
   int multistep = -1;             // option "multistep": -1 auto, 0 one step per launch, 1..8
-  bool force = false;             // option "force": the kernels' FORCE instances, three values per segment
-  double magic = 0.0;             // lbm_dtrt_set: 0 = BGK, > 0 = the TRT instances with this magic parameter
-  double omega_m = 0.0;           // the second relaxation rate of `magic` and p.omega (dp_trt_omega_minus); BGK: p.omega
-  bool open = false;              // lbm_dopen_set: the kernels' OPEN instances, no accelerate_flow
-  std::vector<double> u_in;       // [ny]: the host's copy of the inlet profile (empty while off)
-  double rho_out = 0.0;           // the outlet density
-  double *u_in_dev = nullptr;     // [ny] (allocated by the first lbm_dopen_set that switches on)
-  bool wall = false;              // lbm_dwall_set: the kernels' WALL instances
-  std::vector<double> wall_u;     // [2][ny][nx]: the host's copy of the wall velocities, u_x then u_y (empty while off)
-  double rho_wall = 0.0;          // the wall density
-  double *wall_dev = nullptr;     // [2][ny][nx] (allocated by the first lbm_dwall_set that switches on)
-  double les_c = 0.0;             // lbm_dles_set: 0 = off, > 0 = the LES instances with this Smagorinsky constant
-  double drive[2] = {0.0, 0.0};   // lbm_ddrive_set: (0, 0) = off, else the DRIVE instances with this force density
+  FlowState flow;                 // "force", lbm_dtrt_set, lbm_dopen_set, lbm_dwall_set, lbm_dles_set, lbm_ddrive_set: the settings
+                                  // of one member (dp_host.h), all off by default; a setter's 0 is that header's NULL array
   ScalarState scalar;             // lbm_dscalar_set: the scalar (dp_host.h), off by default
   BuoyState buoy;                 // lbm_dbuoy_set: the scalar acts back on the flow (dp_host.h), off by default
   int cur = 0, steps_done = 0;
@@ -99,29 +84,16 @@ void free_dp(lbm_dp *d) {
   if (d->fin_partials) (void)hipFree(d->fin_partials);
   if (d->force_rec) (void)hipFree(d->force_rec);
   if (d->force_now) (void)hipFree(d->force_now);
-  if (d->u_in_dev) (void)hipFree(d->u_in_dev);
-  if (d->wall_dev) (void)hipFree(d->wall_dev);
+  if (d->flow.wall_dev) (void)hipFree(d->flow.wall_dev);
   scalar_free(d->scalar);
   buoy_free(d->buoy);
   queue_destroy(d->q);
   delete d;
 }
 
-// values per segment and step: |u|, and F_x, F_y with the option "force"
-int seg_values(const lbm_dp *d) { return d->force ? 3 : 1; }
-
-// The ring of per-step segment sums and the first reduction stage's partials, (re)allocated for the values a segment
-// carries: the ring holds as many steps as fit kDpRingBytes.  How many steps lie between two reductions decides no sum.
-int alloc_ring(lbm_dp *d) {
-  const size_t per_step = (size_t)d->p.ny * d->nseg * seg_values(d);
-  d->ring = ring_steps(per_step * sizeof(double), kMultiMaxT, kDpRingMax, kDpRingBytes);
-  if (d->seg) HIP_TRY(hipFree(d->seg));
-  d->seg = nullptr;
-  if (d->red) HIP_TRY(hipFree(d->red));
-  d->red = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->seg), (size_t)d->ring * per_step * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->red), (size_t)d->ring * d->red_blocks * sizeof(double)));
-  return LBM_OK;
+// the grid and its ring as the setters take them (dp_host.h): a context is one member
+FlowGrid flow_grid(lbm_dp *d) {
+  return FlowGrid{1, &d->p, d->members, d->q, d->steps_done, d->seg, d->red, d->ring, (size_t)d->p.ny * d->nseg, d->red_blocks, kMultiMaxT};
 }
 
 int build_dp(lbm_dp *d, const int32_t *obstacles) {
@@ -135,13 +107,13 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
   d->tiles = d->tiles_x * (int)div_up(ny, kDpTY);
   const size_t per_step = (size_t)ny * d->nseg;
   d->red_blocks = (int)std::min(512L, div_up((long)per_step, kDpSegsPerBlock));
-  d->ring = ring_steps(per_step * sizeof(double), kMultiMaxT, kDpRingMax, kDpRingBytes);
+  d->ring = ring_steps_of(1, per_step, 1, kMultiMaxT);
   d->fin_blocks = (int)std::max(1L, std::min(div_up((long)cells, kBlock), 2048L));
   if ((long)d->lanes_per_row * ny > 0x7fffffffL)
     return lbm_fail(LBM_ERR_ARG, "a grid of %dx%d cells is beyond the 2^31 lanes of one launch", nx, ny);
 
   const size_t grid_bytes = (9 * d->plane_stride * ny + 32) * sizeof(double);
-  const size_t need = 2 * grid_bytes + cells + 64 + sizeof(DpMember) + sizeof(DpDrive) + (size_t)d->ring * per_step * sizeof(double) +
+  const size_t need = 2 * grid_bytes + cells + 64 + flow_table_bytes(1, ny) + (size_t)d->ring * per_step * sizeof(double) +
                       (size_t)d->ring * d->red_blocks * sizeof(double) + (size_t)d->p.max_iters * sizeof(double) +
                       (size_t)d->fin_blocks * sizeof(double);
   size_t free_b = 0, total_b = 0;
@@ -156,14 +128,11 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
     HIP_TRY(hipMemset(d->cells[i], 0, grid_bytes));
   }
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->mask), cells + 64));
-  if (int rc = alloc_ring(d)) return rc;
+  if (int rc = alloc_ring(flow_grid(d), 1)) return rc;
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->av_sum), (size_t)d->p.max_iters * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->fin_partials), (size_t)d->fin_blocks * sizeof(double)));
-  // a table of one member: aw1, aw2 are run_dp_impl's statements, and the rest state's w0..w2 come from here alone
-  const DpMember m = member_constants<DpMember>(d->p);
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->members), sizeof(DpMember) + sizeof(DpDrive)));
-  HIP_TRY(hipMemcpy(d->members, &m, sizeof(DpMember), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d->members + 1, 0, sizeof(DpDrive)));
+  // the tables of one member: aw1, aw2 are run_dp_impl's statements, and the rest state's w0..w2 come from here alone
+  if (int rc = flow_create(d->flow, &d->members, &d->p, 1)) return rc;
   body_reset(d->body, obstacles, cells);
   return upload_mask(d->mask, obstacles, cells);
 }
@@ -174,46 +143,29 @@ int build_dp(lbm_dp *d, const int32_t *obstacles) {
 // what a WALL instance takes beyond the arguments of the kernel without it
 DpWall wall_args(const lbm_dp *d) {
   const size_t n = (size_t)d->p.nx * d->p.ny;
-  return DpWall{d->wall_dev, d->wall_dev + n, d->rho_wall};
+  return DpWall{d->flow.wall_dev, d->flow.wall_dev + n, d->flow.rho_wall[0]};
 }
 
 // what an LES instance takes beyond them: the header's two host statements, and the magic parameter as set (either order)
-DpLes les_args(const lbm_dp *d) { return dp_les_constants(d->p.omega, d->les_c, d->magic); }
+DpLes les_args(const lbm_dp *d) { return les_constants(d->flow, &d->p, 0); }
 
-// whether the body force is on, and where dp_final_fields reads it (NULL while it is off)
-bool drive_on(const lbm_dp *d) { return dp_drive_on(d->drive[0], d->drive[1]); }
-const double *drive_dev(const lbm_dp *d) { return drive_on(d) ? reinterpret_cast<const double *>(d->members + 1) : nullptr; }
+// what a DRIVE instance takes beyond them, and where dp_final_fields and the scalar read the same pair (NULL while it is off)
+DpDrive drive_args(const lbm_dp *d) { return DpDrive{d->flow.drive_f[0], d->flow.drive_f[1]}; }
+const double *drive_dev(const lbm_dp *d) { return d->flow.drive ? dens_drive_table(d->members, 1, d->p.ny) : nullptr; }
 
 // the grid as the scalar's helpers take it (dp_host.h): a context is one member
 ScalarGrid scalar_grid(const lbm_dp *d) { return ScalarGrid{1, d->p.nx, d->p.ny, d->plane_stride, 0}; }
 
-// Buoyancy: the table of one member as the settings stand now (dp_host.h: buoy_table), before a run and before the output stage
-int buoy_sync(lbm_dp *d) {
-  std::vector<DpBuoyMember> t(1, DpBuoyMember{});
-  const DpMember m = member_constants<DpMember>(d->p);
-  t[0].buoy.f0_x = d->drive[0];
-  t[0].buoy.f0_y = d->drive[1];
-  t[0].omega = d->p.omega;
-  t[0].omega_m = d->omega_m;
-  t[0].aw1 = m.aw1;
-  t[0].aw2 = m.aw2;
-  t[0].rho_out = d->rho_out;
-  t[0].rho_wall = d->rho_wall;
-  t[0].les = les_args(d);
-  t[0].u_in = d->u_in_dev;
-  return buoy_table(d->buoy, d->q.st, t);
-}
-
 void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
-  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, drive_on(d),
-                [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
+  const FlowState &f = d->flow;
+  dp_with_flags(f.force, f.trt, f.open, f.wall, f.les, f.drive, [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
     constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value,
                    LES = decltype(les)::value, DRIVE = decltype(drive)::value;
     DpMultiArgsOf<WALL, LES, DRIVE> w{};
     static_cast<DpMultiArgs &>(w) = a;
     if constexpr (WALL) w.wall = wall_args(d);
     if constexpr (LES) w.les = les_args(d);
-    if constexpr (DRIVE) w.drive = DpDrive{d->drive[0], d->drive[1]};
+    if constexpr (DRIVE) w.drive = drive_args(d);
     hipLaunchKernelGGL((d2q9_dp_multi<kDpTX, kDpTY, kDpTMax, FORCE, TRT, OPEN, WALL, LES, DRIVE>), dim3(d->tiles), dim3(kMultiThreads), 0,
                        d->q.st, w);
   });
@@ -221,15 +173,15 @@ void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
 
 void launch_step(const lbm_dp *d, const DpStepArgs &a) {
   const dim3 grid((unsigned)div_up((long)d->lanes_per_row * d->p.ny, kBlock));
-  dp_with_flags(d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, drive_on(d),
-                [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
+  const FlowState &f = d->flow;
+  dp_with_flags(f.force, f.trt, f.open, f.wall, f.les, f.drive, [&](auto force, auto trt, auto open, auto wall, auto les, auto drive) {
     constexpr bool FORCE = decltype(force)::value, TRT = decltype(trt)::value, OPEN = decltype(open)::value, WALL = decltype(wall)::value,
                    LES = decltype(les)::value, DRIVE = decltype(drive)::value;
     DpStepArgsOf<WALL, LES, DRIVE> w{};
     static_cast<DpStepArgs &>(w) = a;
     if constexpr (WALL) w.wall = wall_args(d);
     if constexpr (LES) w.les = les_args(d);
-    if constexpr (DRIVE) w.drive = DpDrive{d->drive[0], d->drive[1]};
+    if constexpr (DRIVE) w.drive = drive_args(d);
     hipLaunchKernelGGL((d2q9_dp_step<FORCE, TRT, OPEN, WALL, LES, DRIVE>), grid, dim3(kBlock), 0, d->q.st, w);
   });
 }
@@ -244,23 +196,26 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   const int nx = d->p.nx, ny = d->p.ny;
   const double aw1 = d->p.density * d->p.accel / 9.0;   // kernels.cl:14-15
   const double aw2 = d->p.density * d->p.accel / 36.0;
+  // the member's settings as the step kernels take them: element 0 of the host copies, and the profile in the table of one
+  const double omega_m = d->flow.omega_m[0], rho_out = d->flow.open_host[ny];
+  const double *u_in = dens_open_table(d->members, 1);
   const size_t per_step = (size_t)ny * d->nseg;
-  const int nval = seg_values(d);
+  const int nval = seg_values(d->flow);
   const size_t slot = per_step * nval;   // one step in the ring: [nval][ny][nseg]
   const int T = multistep_effective(d);
   // with a scalar on every launch advances one step, in the kernel form "multistep" chooses: the scalar reads each step's velocities
   const bool scalar = d->scalar.on;
   const ScalarGrid sgrid = scalar_grid(d);
   if (scalar)
-    if (int rc = scalar_begin_run(d->scalar, sgrid, drive_dev(d), 0ull)) return rc;
+    if (int rc = scalar_begin_run(d->scalar, sgrid, drive_dev(d))) return rc;
   // with buoyancy on there is one kernel form, d2q9_dp_buoyant: "multistep" chooses nothing
   const bool buoy = scalar && d->buoy.on;
   if (buoy)
-    if (int rc = buoy_sync(d)) return rc;
+    if (int rc = buoy_sync(d->buoy, d->flow, flow_grid(d))) return rc;
   if (int rc = timed_begin(d->q, timed)) return rc;
   // prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53); later steps get theirs fused into
   // the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
-  if (!d->open) {
+  if (!d->flow.open) {
     hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(nx, 128), 1), dim3(128), 0, d->q.st, d->cells[d->cur], d->plane_stride, 0ull,
                        (const uint8_t *)d->mask, (const DpMember *)d->members, nx, ny, (const int *)nullptr);
     HIP_TRY(hipGetLastError());
@@ -290,8 +245,8 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       if (int rc = flush()) return rc;
     // scalar step n before flow step n, on the state that flow step streams
     if (scalar)
-      if (int rc = scalar_step(d->scalar, sgrid, d->q.st, d->cells[d->cur], d->mask, d->open, buoy ? d->buoy.table : nullptr)) return rc;
-    const bool accel_next = !d->open && i + adv < nsteps;
+      if (int rc = scalar_step(d->scalar, sgrid, d->q.st, d->cells[d->cur], d->mask, d->flow.open, buoy ? d->buoy.table : nullptr)) return rc;
+    const bool accel_next = !d->flow.open && i + adv < nsteps;
     double *seg = d->seg + (size_t)d->ring_fill * slot;
     if (buoy) {
       // flow step n reads the scalar array that scalar step n has just written
@@ -301,7 +256,7 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.mask = d->mask;
       a.scalar = d->scalar.g[d->scalar.cur];
       a.members = d->buoy.table;
-      a.wall_u = d->wall_dev;
+      a.wall_u = d->flow.wall_dev;
       a.seg = seg;
       a.plane_stride = d->plane_stride;
       a.member_stride = 0;
@@ -309,7 +264,7 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.ny = ny;
       a.lanes_per_row = d->lanes_per_row;
       a.accel_row = accel_next ? ny - 2 : -1;
-      if (int rc = buoy_launch(d->q.st, d->force, d->magic > 0.0, d->open, d->wall, d->les_c > 0.0, a, 1)) return rc;
+      if (int rc = buoy_launch(d->q.st, d->flow.force, d->flow.trt, d->flow.open, d->flow.wall, d->flow.les, a, 1)) return rc;
     } else if (T > 0) {
       DpMultiArgs a{};
       a.src = d->cells[d->cur];
@@ -327,9 +282,9 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.omega = d->p.omega;
       a.aw1 = aw1;
       a.aw2 = aw2;
-      a.omega_m = d->omega_m;
-      a.u_in = d->u_in_dev;
-      a.rho_out = d->rho_out;
+      a.omega_m = omega_m;
+      a.u_in = u_in;
+      a.rho_out = rho_out;
       launch_multi(d, a);
     } else {
       DpStepArgs a{};
@@ -345,9 +300,9 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
       a.omega = d->p.omega;
       a.aw1 = aw1;
       a.aw2 = aw2;
-      a.omega_m = d->omega_m;
-      a.u_in = d->u_in_dev;
-      a.rho_out = d->rho_out;
+      a.omega_m = omega_m;
+      a.u_in = u_in;
+      a.rho_out = rho_out;
       launch_step(d, a);
     }
     HIP_TRY(hipGetLastError());
@@ -372,7 +327,7 @@ int final_fields_dp(lbm_dp *d, double *const (&dst)[4]) {
   // buoyancy: the half-force of the scalar state that is current, per cell
   const bool buoy = d->scalar.on && d->buoy.on;
   if (buoy)
-    if (int rc = buoy_sync(d)) return rc;
+    if (int rc = buoy_sync(d->buoy, d->flow, flow_grid(d))) return rc;
   hipLaunchKernelGGL(dp_final_fields, dim3(d->fin_blocks, 1), dim3(kBlock), 0, d->q.st, (const double *)d->cells[d->cur],
                      (const double *)nullptr, (const int *)nullptr, d->plane_stride, 0ull, d->p.nx, (const uint8_t *)d->mask, n,
                      (const DpMember *)d->members, drive_dev(d), buoy ? (const double *)d->scalar.g[d->scalar.cur] : (const double *)nullptr,
@@ -404,7 +359,6 @@ int lbm_dp_create(lbm_dp **out, const lbm_dparams *p, const int32_t *obstacles) 
 
   lbm_dp *d = new lbm_dp();
   d->p = *p;
-  d->omega_m = p->omega;
   if (int rc = build_dp(d, obstacles)) {
     const std::string keep = lbm_last_error();
     free_dp(d);
@@ -446,7 +400,7 @@ int lbm_dp_upload_obstacles(lbm_dp *d, const int32_t *obstacles) {
   body_reset(d->body, obstacles, (size_t)d->p.nx * d->p.ny);
   // wall velocities stay as set: a kernel reads one only while its cell is blocked; so do the scalar's state and its c_wall
   // open boundaries stay on: the blocked cells of columns 0 and nx - 1 are outside every body
-  if (d->open) return body_rewrite(d->body, d->mask, d->p.nx, true);
+  if (d->flow.open) return body_rewrite(d->body, d->mask, d->p.nx, true);
   return LBM_OK;
 }
 
@@ -529,25 +483,8 @@ int lbm_dp_set_option(lbm_dp *d, const char *key, long value) {
     return LBM_OK;
   }
   if (!strcmp(key, "force")) {
-    if (value != 0 && value != 1) return lbm_fail(LBM_ERR_ARG, "force must be 0 or 1 (got %ld)", value);
-    if (d->steps_done != 0)
-      return lbm_fail(LBM_ERR_STATE, "\"force\" is set before the first step (%d done): the record holds every step since "
-                      "lbm_dp_upload", d->steps_done);
-    if ((value != 0) == d->force) return LBM_OK;
-    if (int rc = queue_sync(d->q)) return rc;
-    const bool before = d->force;
-    d->force = value != 0;
-    int rc = alloc_ring(d);
-    if (rc == LBM_OK && d->force && !d->force_rec)
-      rc = hip_alloc(reinterpret_cast<void **>(&d->force_rec), 2 * (size_t)d->p.max_iters * sizeof(double));
-    if (rc != LBM_OK) {
-      // back to a ring that fits the option as it was
-      const std::string keep = lbm_last_error();
-      d->force = before;
-      if (alloc_ring(d) != LBM_OK) d->failed = true;
-      return fail_again(rc, keep);
-    }
-    return LBM_OK;
+    if (int rc = force_check(value)) return rc;
+    return force_set(d->flow, flow_grid(d), value, false, d->force_rec, d->failed);
   }
   return lbm_fail(LBM_ERR_ARG, "unknown option '%s' (a double-precision context has \"multistep\" and \"force\")", key);
 }
@@ -559,7 +496,7 @@ int lbm_dp_get_option(const lbm_dp *d, const char *key, long *value) {
     return LBM_OK;
   }
   if (!strcmp(key, "force")) {
-    *value = d->force ? 1 : 0;
+    *value = d->flow.force ? 1 : 0;
     return LBM_OK;
   }
   return lbm_fail(LBM_ERR_ARG, "unknown option '%s' (a double-precision context has \"multistep\" and \"force\")", key);
@@ -569,7 +506,7 @@ int lbm_dforce_record(lbm_dp *d, double *fx_out, double *fy_out) {
   // argument errors before a device is touched
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
   if (!fx_out && !fy_out) return lbm_fail(LBM_ERR_ARG, "fx_out and fy_out are both NULL");
-  if (!d->force) return lbm_fail(LBM_ERR_STATE, "no force record: option \"force\" is off (lbm_dp_set_option before the first step)");
+  if (!d->flow.force) return lbm_fail(LBM_ERR_STATE, "no force record: option \"force\" is off (lbm_dp_set_option before the first step)");
   if (int rc = queue_sync(d->q)) return rc;
   double *outs[2] = {fx_out, fy_out};
   for (int c = 0; c < 2; c++)
@@ -591,7 +528,7 @@ int lbm_dforce(lbm_dp *d, double *fx, double *fy) {
   a.plane_stride = d->plane_stride;
   a.nx = d->p.nx;
   a.ny = d->p.ny;
-  a.no_accel = d->open ? 1 : 0;
+  a.no_accel = d->flow.open ? 1 : 0;
   if (int rc = force_state(d->q.st, a, d->nseg, 1, d->seg, d->red, d->red_blocks, d->force_now)) return rc;
   double f[2] = {0.0, 0.0};
   HIP_TRY(hipMemcpyAsync(f, d->force_now, sizeof(f), hipMemcpyDeviceToHost, d->q.st));
@@ -603,11 +540,11 @@ int lbm_dforce(lbm_dp *d, double *fx, double *fy) {
 
 int lbm_dbody_set(lbm_dp *d, const int32_t *body) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
-  if (d->force && d->steps_done != 0)
+  if (d->flow.force && d->steps_done != 0)
     return lbm_fail(LBM_ERR_STATE, "with \"force\" on, a body map is set before the first step (%d done): one record holds one body",
                     d->steps_done);
   if (int rc = queue_sync(d->q)) return rc;
-  return body_apply(d->body, d->mask, body, 1, d->p.ny, d->p.nx, false, d->open);
+  return body_apply(d->body, d->mask, body, 1, d->p.ny, d->p.nx, false, d->flow.open);
 }
 
 int lbm_dbody_get(lbm_dp *d, int32_t *body_out) {
@@ -618,151 +555,80 @@ int lbm_dbody_get(lbm_dp *d, int32_t *body_out) {
   return LBM_OK;
 }
 
+// The six setters: the context's value as dp_host.h takes it (an array of one member; the context's "0 = off" is its NULL), the
+// check of the values, which reads nothing of the context but p, then the set.
 int lbm_dtrt_set(lbm_dp *d, double magic) {
-  // argument errors before anything of the context is read
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
-  if (!(magic >= 0.0) || !std::isfinite(magic))
-    return lbm_fail(LBM_ERR_ARG, "magic must be 0 (BGK) or finite and positive (got %g)", magic);
-  if (magic > 0.0 && !(1.0 / d->p.omega - 0.5 > 0.0))
-    return lbm_fail(LBM_ERR_ARG, "the two-relaxation-time operator needs 1/omega - 1/2 > 0: omega is %g", d->p.omega);
-  if (d->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "the collision operator is set before the first step (%d done): one record holds one operator",
-                    d->steps_done);
-  d->magic = magic;
-  d->omega_m = magic > 0.0 ? dp_trt_omega_minus(d->p.omega, magic) : d->p.omega;
-  return LBM_OK;
+  const double *on = magic == 0.0 ? nullptr : &magic;
+  if (int rc = trt_check(&d->p, 1, on, false)) return rc;
+  return trt_set(d->flow, flow_grid(d), on);
 }
 
 int lbm_dtrt_get(const lbm_dp *d, double *magic_out, double *omega_minus_out) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
   if (!magic_out && !omega_minus_out) return lbm_fail(LBM_ERR_ARG, "magic_out and omega_minus_out are both NULL");
-  if (magic_out) *magic_out = d->magic;
-  if (omega_minus_out) *omega_minus_out = d->omega_m;
+  trt_get(d->flow, magic_out, omega_minus_out);
   return LBM_OK;
 }
 
 int lbm_dopen_set(lbm_dp *d, const double *u_in, double rho_out) {
-  // argument errors before anything of the context is read, or before a device is touched
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
-  if (u_in && !positive_finite(rho_out)) return lbm_fail(LBM_ERR_ARG, "rho_out must be finite and positive (got %g)", rho_out);
-  if (u_in)
-    for (int y = 0; y < d->p.ny; y++)
-      if (!std::isfinite(u_in[y]) || !(u_in[y] < 1.0))
-        return lbm_fail(LBM_ERR_ARG, "u_in of row %d must be finite and below 1 (got %g)", y, u_in[y]);
-  if (d->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "open boundaries are set before the first step (%d done): one record holds one flow",
-                    d->steps_done);
-  if (!u_in && !d->open) return LBM_OK;
-  if (int rc = queue_sync(d->q)) return rc;
-  HIP_TRY(hipSetDevice(d->q.dev));
-  if (u_in) {
-    if (!d->u_in_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->u_in_dev), (size_t)d->p.ny * sizeof(double)));
-    HIP_TRY(hipMemcpy(d->u_in_dev, u_in, (size_t)d->p.ny * sizeof(double), hipMemcpyHostToDevice));
-  }
-  // the device mask under the column rule, or without it again
-  if (int rc = body_rewrite(d->body, d->mask, d->p.nx, u_in != nullptr)) return rc;
-  d->open = u_in != nullptr;
-  if (u_in) d->u_in.assign(u_in, u_in + d->p.ny);
-  else d->u_in.clear();
-  d->rho_out = u_in ? rho_out : 0.0;
-  return LBM_OK;
+  if (int rc = open_check(&d->p, 1, u_in, &rho_out, false)) return rc;
+  return open_set(d->flow, flow_grid(d), d->body, d->mask, u_in, &rho_out);
 }
 
 int lbm_dopen_get(const lbm_dp *d, int *on_out, double *u_in_out, double *rho_out_out) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
   if (!on_out && !u_in_out && !rho_out_out) return lbm_fail(LBM_ERR_ARG, "on_out, u_in_out and rho_out_out are all NULL");
-  if (on_out) *on_out = d->open ? 1 : 0;
-  if (d->open && u_in_out) std::copy(d->u_in.begin(), d->u_in.end(), u_in_out);
-  if (d->open && rho_out_out) *rho_out_out = d->rho_out;
+  open_get(d->flow, 1, d->p.ny, on_out, u_in_out, rho_out_out);
   return LBM_OK;
 }
 
 int lbm_dwall_set(lbm_dp *d, const double *u_x, const double *u_y, double rho_wall) {
-  // argument errors before anything of the context is read, or before a device is touched
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
   if ((u_x == nullptr) != (u_y == nullptr))
     return lbm_fail(LBM_ERR_ARG, "%s is NULL and %s is not: a wall velocity has two components (both NULL: off)", u_x ? "u_y" : "u_x",
                     u_x ? "u_x" : "u_y");
-  if (u_x && !positive_finite(rho_wall)) return lbm_fail(LBM_ERR_ARG, "rho_wall must be finite and positive (got %g)", rho_wall);
-  if (u_x)
-    if (int rc = wall_check(d->body, u_x, u_y, 1, d->p.ny, d->p.nx, false)) return rc;
-  if (d->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "wall velocities are set before the first step (%d done): one record holds one flow", d->steps_done);
-  if (!u_x) {
-    d->wall = false;
-    d->wall_u.clear();
-    d->rho_wall = 0.0;
-    return LBM_OK;
-  }
-  if (int rc = queue_sync(d->q)) return rc;
-  HIP_TRY(hipSetDevice(d->q.dev));
-  const size_t n = (size_t)d->p.nx * d->p.ny;
-  if (!d->wall_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d->wall_dev), 2 * n * sizeof(double)));
-  std::vector<double> u(2 * n);
-  std::copy(u_x, u_x + n, u.begin());
-  std::copy(u_y, u_y + n, u.begin() + n);
-  HIP_TRY(hipMemcpy(d->wall_dev, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice));
-  d->wall = true;
-  d->wall_u.swap(u);
-  d->rho_wall = rho_wall;
-  return LBM_OK;
+  if (int rc = wall_values_check(d->body, &d->p, 1, u_x, u_y, &rho_wall, false)) return rc;
+  return wall_set(d->flow, flow_grid(d), u_x, u_y, &rho_wall);
 }
 
 int lbm_dwall_get(const lbm_dp *d, int *on_out, double *u_x_out, double *u_y_out, double *rho_wall_out) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
   if (!on_out && !u_x_out && !u_y_out && !rho_wall_out)
     return lbm_fail(LBM_ERR_ARG, "on_out, u_x_out, u_y_out and rho_wall_out are all NULL");
-  if (on_out) *on_out = d->wall ? 1 : 0;
-  if (!d->wall) return LBM_OK;
-  const size_t n = (size_t)d->p.nx * d->p.ny;
-  if (u_x_out) std::copy(d->wall_u.begin(), d->wall_u.begin() + n, u_x_out);
-  if (u_y_out) std::copy(d->wall_u.begin() + n, d->wall_u.end(), u_y_out);
-  if (rho_wall_out) *rho_wall_out = d->rho_wall;
+  wall_get(d->flow, on_out, u_x_out, u_y_out, rho_wall_out);
   return LBM_OK;
 }
 
 int lbm_dles_set(lbm_dp *d, double c) {
-  // argument errors before anything of the context is read
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
-  if (!(c >= 0.0) || !std::isfinite(c))
-    return lbm_fail(LBM_ERR_ARG, "the Smagorinsky constant c must be 0 (off) or finite and positive (got %g)", c);
-  if (d->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "the subgrid viscosity is set before the first step (%d done): one record holds one operator",
-                    d->steps_done);
-  d->les_c = c;
-  return LBM_OK;
+  const double *on = c == 0.0 ? nullptr : &c;
+  if (int rc = les_check(1, on, false)) return rc;
+  return les_set(d->flow, flow_grid(d), on);
 }
 
 int lbm_dles_get(const lbm_dp *d, double *c_out, double *les_k_out) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
   if (!c_out && !les_k_out) return lbm_fail(LBM_ERR_ARG, "c_out and les_k_out are both NULL");
-  if (c_out) *c_out = d->les_c;
-  if (les_k_out) *les_k_out = les_args(d).les_k;
+  les_get(d->flow, &d->p, 1, c_out, les_k_out);
   return LBM_OK;
 }
 
 int lbm_ddrive_set(lbm_dp *d, double f_x, double f_y) {
-  // argument errors before anything of the context is read
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
-  if (!std::isfinite(f_x) || !std::isfinite(f_y))
-    return lbm_fail(LBM_ERR_ARG, "the body force must be finite (got f_x = %g, f_y = %g)", f_x, f_y);
-  if (d->steps_done != 0)
-    return lbm_fail(LBM_ERR_STATE, "the body force is set before the first step (%d done): one record holds one flow", d->steps_done);
-  if (int rc = queue_sync(d->q)) return rc;
-  HIP_TRY(hipSetDevice(d->q.dev));
-  // the copy the output stage reads; the step kernels take the two components as arguments
   const double f[2] = {f_x, f_y};
-  HIP_TRY(hipMemcpy(d->members + 1, f, sizeof(f), hipMemcpyHostToDevice));
-  d->drive[0] = f_x;
-  d->drive[1] = f_y;
-  return LBM_OK;
+  if (int rc = drive_check(1, f, false)) return rc;
+  return drive_set(d->flow, flow_grid(d), dp_drive_on(f_x, f_y) ? f : nullptr);
 }
 
 int lbm_ddrive_get(const lbm_dp *d, double *f_x_out, double *f_y_out) {
   if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
   if (!f_x_out && !f_y_out) return lbm_fail(LBM_ERR_ARG, "f_x_out and f_y_out are both NULL");
-  if (f_x_out) *f_x_out = d->drive[0];
-  if (f_y_out) *f_y_out = d->drive[1];
+  double f[2];
+  drive_get(d->flow, nullptr, f);
+  if (f_x_out) *f_x_out = f[0];
+  if (f_y_out) *f_y_out = f[1];
   return LBM_OK;
 }
 
@@ -777,14 +643,8 @@ int lbm_dscalar_set(lbm_dp *d, double diffusivity, const double *c0, const doubl
     if (int rc = scalar_check(gr, false, &diffusivity, c0, c_wall, c_in)) return rc;
   if (diffusivity == 0.0 && d->buoy.on) return buoy_refuse_scalar_off();
   if (int rc = queue_sync(d->q)) return rc;
-  if (diffusivity == 0.0) {
-    // the arrays stay until the context goes; the handle runs as one that never had a scalar
-    d->scalar.on = false;
-    d->scalar.diffusivity.clear();
-    d->scalar.omega_s.clear();
-    return LBM_OK;
-  }
-  return scalar_set(d->scalar, gr, d->q.st, &diffusivity, c0, c_wall, c_in, drive_dev(d), 0ull);
+  if (diffusivity == 0.0) return scalar_off(d->scalar);
+  return scalar_set(d->scalar, gr, d->q.st, &diffusivity, c0, c_wall, c_in, drive_dev(d));
 }
 
 int lbm_dscalar_get(const lbm_dp *d, int *on_out, double *diffusivity_out, double *omega_s_out) {

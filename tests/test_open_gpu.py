@@ -377,6 +377,29 @@ def test_off_and_set_then_unset_leave_the_periodic_bits(lbm, multistep):
     assert all(np.array_equal(a, b) for a, b in zip(*snaps))
 
 
+def test_a_second_setting_after_off_replaces_the_first(lbm):
+    """Set, unset, set again with another profile and outlet density, then one step against the restatement on the second
+    setting: the device copy of the profile is rewritten in place and nothing of the first setting stays.  17x16: nx odd, one
+    whole tile and a ragged one; the form with one step a launch and the LDS-tile form."""
+    nx, ny = 17, 16
+    p, ob, body, cells0, u_in = open_case(lbm, nx, ny, 2)
+    other, rho = profile(nx, ny, seed=1, scale=0.5), 0.0985
+    want, _ = _open_ref.step(cells0, ob, p.omega, None, other, rho)
+    first, _ = _open_ref.step(cells0, ob, p.omega, None, u_in, RHO_OUT)
+    assert not np.array_equal(want, first)
+    for multistep in (0, 8):
+        with lbm.LBMDouble(p, ob) as sim:
+            sim.set_option("multistep", multistep)
+            sim.set_open(u_in, RHO_OUT)
+            sim.set_open(None)
+            sim.set_open(other, rho)
+            got = sim.open()
+            assert np.array_equal(got[0], other) and got[1] == rho
+            sim.upload(cells0)
+            sim.run(1)
+            assert np.array_equal(sim.download(av_vels=False)[0], want), multistep
+
+
 def test_errors_and_what_keeps_the_setting(lbm):
     lib = lbm.load_library()
     p, ob, body, cells0, u_in = open_case(lbm, 33, 19, 8)
