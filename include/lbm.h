@@ -1250,6 +1250,79 @@ int lbm_dbuoy_ens_set(lbm_dens *e, const double *b /*[n][3] or NULL*/);
  * and b_out), or a NULL ensemble: LBM_ERR_ARG. */
 int lbm_dbuoy_ens_get(const lbm_dens *e, int *on_out, double *b_out /*[n][3]*/);
 
+/*
+ * ---- Scalar record: what the scalar holds and carries per step, and steady runs that stop each member on it -----------------------
+ *
+ * "Scalar transport" and "Buoyancy" both say that steady runs stay refused while a scalar is on ("a member that stops would need a
+ * gated scalar kernel, which is out of scope").  For lbm_dsteady_run and lbm_dbody_steady_run that stands, with the same code and
+ * message: their criteria judge the flow alone, and a passive scalar is still moving long after its flow has settled.  This section
+ * lifts the remark for a criterion of the scalar's own.  The flow has av_vels and the force record per step; with the record on,
+ * the scalar has three sums per step, and lbm_drecord_steady_run stops every member of an ensemble where one of them has settled.
+ * Off by default.  The reference has no counterpart.
+ *
+ * Definition.  Per step t and per member, three sums over the FLUID cells, taken inside scalar step t from values that step holds
+ * anyway.  With h[0..4] the cell's five gathered values behind the wall, inlet and outlet statements of "Scalar transport", and
+ * (u_x, u_y) the velocity that step advects with (the output stage's; with buoyancy less half of the cell's own force):
+ *     c = (((h[0] + h[1]) + h[2]) + h[3]) + h[4];     content: the sum of c
+ *     q_x = c * u_x;                                  flux_x:  the sum of q_x
+ *     q_y = c * u_y;                                  flux_y:  the sum of q_y
+ * c is the collision's own sum and the products are those under its a_x and a_y.  A blocked cell adds +0.0.  All in double,
+ * contraction off, one IEEE operation per written operator.
+ *
+ * Order of summation, fixed as for av_vels: the two cells of a lane (a + b, or a + 0.0 where the lane has no second cell; an idle
+ * lane of the row's last segment holds 0.0); the eight lanes of a 16-cell row segment in the tree of xor 1, 2, 4; then the
+ * segments of the step, [ny][nseg] per member, through the reduction that av_vels takes (in one stage, or in two where a step has
+ * many segments), from a ring of the scalar's own.  A member of an ensemble equals a context, and a run in pieces one run, bit for
+ * bit.  flux_x / N_fluid * H / (D dC) is the convective part of the volume-averaged Nusselt number of a side-heated cavity, flux_y
+ * the same for a layer heated from below.
+ *
+ * Nothing else moves.  With the record on the scalar step is dp_scalar_step_rec, the same lane body: cells, scalar populations,
+ * av_vels, the force record and the four fields are the same bits with the record on as with it off.
+ *
+ * When it is accepted.  Only with a scalar on (otherwise LBM_ERR_ARG) and only while steps_done is 0, the rule of lbm_dbuoy_set:
+ * LBM_ERR_STATE after a step, until the next upload of the flow.  Switching the scalar off while the record is on is
+ * LBM_ERR_STATE.  lbm_dscalar_set with new fields and lbm_dscalar_upload between runs leave the recorded entries as they are; the
+ * uploads of the flow keep the setting and start the record anew.
+ *
+ * Steady runs.  lbm_drecord_steady_run is lbm_dsteady_run in everything but the criterion: the legs, check points, polling, limits
+ * and the words of lbm_dsteady_steps are those of "Steady runs of a double-precision ensemble".  A(s) is entry s - 1 of the chosen
+ * value's record of the member as lbm_drecord_ens returns it, nothing multiplied into it; a member stops at a check point s
+ * where fabs(A(s) - A(s - window)) <= rel_tol * fabs(A(s)), difference and bound as separate statements.  A leg launches, per step
+ * and under the members' words: the scalar step dp_scalar_step_rec, and the flow step d2q9_dp_ensemble_gated at depth 1 or, with
+ * buoyancy, d2q9_dp_buoyant_gated.  A member stopped at count c holds the bits of an lbm_dens_run(e, c) in one piece, cells, scalar
+ * and every record.  Afterwards a ragged ensemble is read member by member from the array that holds each (lbm_dscalar_ens_field,
+ * lbm_dscalar_ens_download, the fields with buoyancy); lbm_dscalar_ens_set and lbm_dscalar_ens_upload are refused with
+ * LBM_ERR_STATE until lbm_dens_upload, which keeps every member's scalar state, unchanged.
+ *
+ * Names: lbm_drecord_*, on both double-precision handles, beside lbm_dscalar_* (the ten entry points of "Scalar transport").  Out
+ * of scope: fp32 contexts and fp32 ensembles, which get nothing; a criterion on more than one value; wall fluxes (the conductive
+ * part of a Nusselt number is a difference of the reported field).
+ */
+
+/* Switch the record of a double-precision context on (1) or off (0, the default).  LBM_ERR_ARG: a NULL context, a value other than
+ * 0 and 1, the scalar is off.  LBM_ERR_STATE: steps done.  Synchronises. */
+int lbm_drecord_set(lbm_dp *d, int on);
+
+/* on_out: 1 while the record is on, else 0.  A NULL argument: LBM_ERR_ARG. */
+int lbm_drecord_get(const lbm_dp *d, int *on_out);
+
+/* The three records, lbm_dp_steps_done(d) entries each.  Any output may be NULL; all three NULL, or a NULL context: LBM_ERR_ARG,
+ * before a device is touched.  LBM_ERR_STATE: the record is off.  Synchronises. */
+int lbm_drecord(lbm_dp *d, double *content_out /*[steps_done]*/, double *flux_x_out /*[steps_done]*/,
+                       double *flux_y_out /*[steps_done]*/);
+
+/* The same for a double-precision ensemble, all members on or off together: double[n][steps_done] per value; a member that
+ * lbm_drecord_steady_run stopped earlier holds +0.0 from its own count on (lbm_dforce_ens_record's rule). */
+int lbm_drecord_ens_set(lbm_dens *e, int on);
+int lbm_drecord_ens_get(const lbm_dens *e, int *on_out);
+int lbm_drecord_ens(lbm_dens *e, double *content_out /*[n][steps_done]*/, double *flux_x_out /*[n][steps_done]*/,
+                           double *flux_y_out /*[n][steps_done]*/);
+
+/* Advance every member until ITS OWN record of the scalar has settled, at most max_steps steps (beside lbm_dsteady_run, whose
+ * refusals it shares).  which: 0 content, 1 flux_x, 2 flux_y.  LBM_ERR_ARG, before a device is touched: a NULL ensemble, max_steps
+ * < 0, window < 1, rel_tol negative or not finite, which outside 0 .. 2, the record is off.  Synchronises. */
+int lbm_drecord_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol, int which);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
     "lbm_dscalar_set", "lbm_dscalar_get", "lbm_dscalar_field", "lbm_dscalar_download", "lbm_dscalar_upload",
     "lbm_dscalar_ens_set", "lbm_dscalar_ens_get", "lbm_dscalar_ens_field", "lbm_dscalar_ens_download", "lbm_dscalar_ens_upload",
     "lbm_dbuoy_set", "lbm_dbuoy_get", "lbm_dbuoy_ens_set", "lbm_dbuoy_ens_get",
+    "lbm_drecord_set", "lbm_drecord_get", "lbm_drecord",
+    "lbm_drecord_ens_set", "lbm_drecord_ens_get", "lbm_drecord_ens", "lbm_drecord_steady_run",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -203,6 +205,13 @@ def load_library():
     L.lbm_dbuoy_get.argtypes = [vp, ctypes.POINTER(ci), vp, ctypes.POINTER(ctypes.c_double)]
     L.lbm_dbuoy_ens_set.argtypes = [vp, vp]
     L.lbm_dbuoy_ens_get.argtypes = [vp, ctypes.POINTER(ci), vp]
+    L.lbm_drecord_set.argtypes = [vp, ci]
+    L.lbm_drecord_get.argtypes = [vp, ctypes.POINTER(ci)]
+    L.lbm_drecord.argtypes = [vp, vp, vp, vp]
+    L.lbm_drecord_ens_set.argtypes = [vp, ci]
+    L.lbm_drecord_ens_get.argtypes = [vp, ctypes.POINTER(ci)]
+    L.lbm_drecord_ens.argtypes = [vp, vp, vp, vp]
+    L.lbm_drecord_steady_run.argtypes = [vp, ci, ci, ctypes.c_double, ci]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -743,6 +752,25 @@ class LBMDouble(_Handle):
         _check(self.lib.lbm_dbuoy_get(self.ctx, ctypes.byref(on), b.ctypes.data, ctypes.byref(c_ref)), "lbm_dbuoy_get")
         return ((float(b[0]), float(b[1])), c_ref.value) if on.value else None
 
+    def set_scalar_record(self, on):
+        """The scalar's record (lbm_drecord_set): per step the sums of c, c u_x and c u_y over the fluid cells.  Off by
+        default.  Needs a scalar on; only before the first step."""
+        _check(self.lib.lbm_drecord_set(self.ctx, 1 if on else 0), "lbm_drecord_set")
+
+    def scalar_record_on(self):
+        """True while the scalar's record is on (lbm_drecord_get)"""
+        on = ctypes.c_int()
+        _check(self.lib.lbm_drecord_get(self.ctx, ctypes.byref(on)), "lbm_drecord_get")
+        return bool(on.value)
+
+    def scalar_record(self):
+        """(content, flux_x, flux_y), float64[steps_done] each: the scalar's record of every step since the upload
+        (lbm_drecord); needs set_scalar_record(True) before the first step."""
+        steps = self.steps_done
+        c, fx, fy = (np.zeros(max(steps, 1), dtype=np.float64) for _ in range(3))
+        _check(self.lib.lbm_drecord(self.ctx, c.ctypes.data, fx.ctypes.data, fy.ctypes.data), "lbm_drecord")
+        return c[:steps], fx[:steps], fy[:steps]
+
     def force_record(self):
         """(F_x float64[steps_done], F_y float64[steps_done]): the force of every step since the upload; needs
         set_option("force", 1) before the first step."""
@@ -1093,14 +1121,43 @@ class EnsembleDouble(_EnsembleOf):
         _check(self.lib.lbm_dbuoy_ens_get(self.ens, ctypes.byref(on), b.ctypes.data), "lbm_dbuoy_ens_get")
         return b if on.value else None
 
+    def set_scalar_record(self, on):
+        """The scalars' record of all members (lbm_drecord_ens_set): per step and member the sums of c, c u_x and c u_y
+        over the fluid cells.  Off by default.  Needs the scalars on; only before the first step."""
+        _check(self.lib.lbm_drecord_ens_set(self.ens, 1 if on else 0), "lbm_drecord_ens_set")
+
+    def scalar_record_on(self):
+        """True while the scalars' record is on (lbm_drecord_ens_get)"""
+        on = ctypes.c_int()
+        _check(self.lib.lbm_drecord_ens_get(self.ens, ctypes.byref(on)), "lbm_drecord_ens_get")
+        return bool(on.value)
+
+    def scalar_record(self):
+        """(content, flux_x, flux_y), float64[n, steps_done] each: every member's record of every step since the upload, +0.0 at
+        and beyond the count of a member that run_until() stopped earlier (lbm_drecord_ens); needs
+        set_scalar_record(True) before the first step."""
+        steps = self.steps_done
+        c, fx, fy = (np.zeros((self.n, max(steps, 1)), dtype=np.float64) for _ in range(3))
+        _check(self.lib.lbm_drecord_ens(self.ens, c.ctypes.data, fx.ctypes.data, fy.ctypes.data), "lbm_drecord_ens")
+        return c[:, :steps].copy(), fx[:, :steps].copy(), fy[:, :steps].copy()
+
+    SCALAR_CRITERIA = {"scalar": 0, "scalar_flux_x": 1, "scalar_flux_y": 2}
+
     def run_until(self, max_steps, window=64, rel_tol=1e-4, on="av_vels"):
         """_EnsembleOf.run_until with a choice of criterion: on="av_vels" (lbm_dsteady_run), or on="drag"
         (lbm_dbody_steady_run): |F(s) - F(s - window)| <= rel_tol |F(s)| on the member's own F_x record, the force on its body
-        (set_body); needs set_option("force", 1) before the first step."""
+        (set_body); needs set_option("force", 1) before the first step.  on="scalar", "scalar_flux_x" or "scalar_flux_y"
+        (lbm_drecord_steady_run): the same rule on the member's own content, flux_x or flux_y record of its scalar; needs
+        set_scalar_record(True) before the first step."""
         if on == "av_vels":
             return super().run_until(max_steps, window=window, rel_tol=rel_tol)
+        if on in self.SCALAR_CRITERIA:
+            _check(self.lib.lbm_drecord_steady_run(self.ens, max_steps, window, rel_tol, self.SCALAR_CRITERIA[on]),
+                   "lbm_drecord_steady_run")
+            return self.member_steps()
         if on != "drag":
-            raise ValueError("run_until(on=%r): the criteria are \"av_vels\" and \"drag\"" % (on,))
+            raise ValueError("run_until(on=%r): the criteria are \"av_vels\", \"drag\", \"scalar\", \"scalar_flux_x\" and "
+                             "\"scalar_flux_y\"" % (on,))
         _check(self.lib.lbm_dbody_steady_run(self.ens, max_steps, window, rel_tol), "lbm_dbody_steady_run")
         return self.member_steps()
 

@@ -415,14 +415,22 @@ struct ScalarState {
   double *c_in = nullptr;                     // [members][ny]
   lbm::DpScalarMember *table = nullptr;       // [members]
   const double *table_drive = nullptr;        // the body-force table the device table was written for
+  // the record (include/lbm.h, "Scalar record"; lbm_drecord_*), off by default; allocated by the first call that switches on
+  bool record = false;
+  double *rec = nullptr;                      // [3][members][max_iters]: content, flux_x, flux_y per member and step
+  double *rec_seg = nullptr;                  // [rec_ring][3][members][ny][nseg]: the scalar's own ring of segment sums
+  double *rec_red = nullptr;                  // [rec_ring][members][red_blocks]: first reduction stage
+  int rec_ring = 0;                           // steps the ring holds
 };
 
 struct ScalarGrid {
   int members, nx, ny;
   size_t plane_stride, flow_member_stride;   // doubles
+  int red_blocks = 1, max_iters = 0;         // the record: the flow's blocks of the first reduction stage, and its record's length
   size_t cells() const { return (size_t)nx * ny; }
   size_t member_stride() const { return 5 * plane_stride * (size_t)ny; }
   int lanes_per_row() const { return (int)(div_up(div_up(nx, 2), 8) * 8); }
+  size_t per_step() const { return (size_t)ny * (lanes_per_row() / 8); }   // one member's segments of one step
   dim3 helper_grid() const { return dim3((unsigned)std::min(div_up((long)cells(), 256), 1024L), members); }
 };
 
@@ -432,6 +440,9 @@ static inline void scalar_free(ScalarState &s) {
   if (s.c_wall) (void)hipFree(s.c_wall);
   if (s.c_in) (void)hipFree(s.c_in);
   if (s.table) (void)hipFree(s.table);
+  if (s.rec) (void)hipFree(s.rec);
+  if (s.rec_seg) (void)hipFree(s.rec_seg);
+  if (s.rec_red) (void)hipFree(s.rec_red);
 }
 
 // What lbm_dscalar_set / lbm_dscalar_ens_set refuse: everything is checked before anything changes.  ens: the message names the
@@ -531,9 +542,11 @@ static inline int scalar_off(ScalarState &s) {
 }
 
 // One scalar step of all members on the flow state `flow` (the array the flow's next launch streams), enqueued; flips s.cur.
-// buoy: NULL (the passive scalar), or the members' buoyant constants (dp_scalar_step<true>)
+// buoy: NULL (the passive scalar), or the members' buoyant constants (dp_scalar_step<true>).  With the record on the kernel is
+// dp_scalar_step_rec, which writes the step's segment sums into slot `slot` of the scalar's ring; active: NULL, or the members'
+// words during a leg of a steady run (which the callers refuse without the record).
 static inline int scalar_step(ScalarState &s, const ScalarGrid &gr, hipStream_t st, const double *flow, const uint8_t *mask, bool open,
-                              const lbm::DpBuoyMember *buoy = nullptr) {
+                              const lbm::DpBuoyMember *buoy, int slot, const int *active) {
   lbm::DpScalarBuoyArgs a{};
   a.flow = flow;
   a.src = s.g[s.cur];
@@ -549,8 +562,16 @@ static inline int scalar_step(ScalarState &s, const ScalarGrid &gr, hipStream_t 
   a.open = open ? 1 : 0;
   a.buoy = buoy;
   const dim3 grid((unsigned)div_up((long)a.lanes_per_row * gr.ny, lbm::kBlock), gr.members);
-  if (buoy) hipLaunchKernelGGL(lbm::dp_scalar_step<true>, grid, dim3(lbm::kBlock), 0, st, a);
-  else hipLaunchKernelGGL(lbm::dp_scalar_step<false>, grid, dim3(lbm::kBlock), 0, st, static_cast<const lbm::DpScalarArgs &>(a));
+  if (s.record) {
+    double *seg = s.rec_seg + (size_t)slot * 3 * gr.members * gr.per_step();
+    if (buoy) hipLaunchKernelGGL(lbm::dp_scalar_step_rec<true>, grid, dim3(lbm::kBlock), 0, st, a, seg, active);
+    else hipLaunchKernelGGL(lbm::dp_scalar_step_rec<false>, grid, dim3(lbm::kBlock), 0, st, static_cast<const lbm::DpScalarArgs &>(a), seg,
+                            active);
+  } else if (buoy) {
+    hipLaunchKernelGGL(lbm::dp_scalar_step<true>, grid, dim3(lbm::kBlock), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(lbm::dp_scalar_step<false>, grid, dim3(lbm::kBlock), 0, st, static_cast<const lbm::DpScalarArgs &>(a));
+  }
   HIP_TRY(hipGetLastError());
   s.cur ^= 1;
   return LBM_OK;
@@ -562,26 +583,113 @@ static inline int scalar_begin_run(ScalarState &s, const ScalarGrid &gr, const d
   return scalar_table(s, gr, s.omega_s, drive);
 }
 
+// ---- the scalar's record (include/lbm.h, "Scalar record") ----
+// How many steps a run may buffer between two flushes: the flow's ring, and with the record on the scalar's as well
+static inline int scalar_ring_limit(const ScalarState &s, int flow_ring) { return s.on && s.record ? std::min(flow_ring, s.rec_ring) : flow_ring; }
+
+// Beside the flow's flush, for both hosts: the `fill` buffered steps of the scalar's ring through reduce_steps into entries
+// `first` on of the three records, each value's segments by the launches that serve av_vels.  active: as reduce_steps.
+static inline int scalar_flush(const ScalarState &s, const ScalarGrid &gr, hipStream_t st, int fill, int first, const int *active) {
+  if (!s.on || !s.record || fill == 0) return LBM_OK;
+  const size_t per_step = gr.per_step(), all_step = (size_t)gr.members * per_step;
+  for (int v = 0; v < 3; v++)
+    if (int rc = reduce_steps(st, s.rec_seg + (size_t)v * all_step, 3 * all_step, per_step, fill, gr.members, s.rec_red, gr.red_blocks,
+                              s.rec + ((size_t)v * gr.members) * gr.max_iters + first, (unsigned long long)gr.max_iters, active))
+      return rc;
+  return LBM_OK;
+}
+
+// lbm_drecord_set / lbm_drecord_ens_set behind their NULL checks: the buoyancy rule.  The caller synchronises
+// between the check and the set.
+static inline int scalar_record_check(const ScalarState &s, int on, int steps_done, bool ens) {
+  if (on != 0 && on != 1) return lbm_fail(LBM_ERR_ARG, "on must be 0 or 1 (got %d)", on);
+  if (!s.on)
+    return lbm_fail(LBM_ERR_ARG, "the scalar's record needs a scalar: the scalar is off (%s switches it on first)",
+                    ens ? "lbm_dscalar_ens_set" : "lbm_dscalar_set");
+  if (steps_done != 0)
+    return lbm_fail(LBM_ERR_STATE, "the scalar's record is set before the first step (%d done): it holds every step since %s", steps_done,
+                    ens ? "lbm_dens_upload" : "lbm_dp_upload");
+  return LBM_OK;
+}
+
+static inline int scalar_record_set(ScalarState &s, const ScalarGrid &gr, int on) {
+  if (on && !s.rec_seg) {
+    const size_t all_step = (size_t)gr.members * gr.per_step();
+    const int ring = ring_steps_of(gr.members, gr.per_step(), 3, 1);
+    double *rec = nullptr, *seg = nullptr, *red = nullptr;
+    int rc = hip_alloc(reinterpret_cast<void **>(&rec), 3 * (size_t)gr.members * gr.max_iters * sizeof(double));
+    if (rc == LBM_OK) rc = hip_alloc(reinterpret_cast<void **>(&seg), (size_t)ring * 3 * all_step * sizeof(double));
+    if (rc == LBM_OK) rc = hip_alloc(reinterpret_cast<void **>(&red), (size_t)ring * gr.members * gr.red_blocks * sizeof(double));
+    if (rc != LBM_OK) {
+      const std::string keep = lbm_last_error();
+      if (rec) (void)hipFree(rec);
+      if (seg) (void)hipFree(seg);
+      if (red) (void)hipFree(red);
+      return fail_again(rc, keep);
+    }
+    s.rec = rec;
+    s.rec_seg = seg;
+    s.rec_red = red;
+    s.rec_ring = ring;
+  }
+  s.record = on != 0;
+  return LBM_OK;
+}
+
+static inline int scalar_record_refuse_scalar_off() {
+  return lbm_fail(LBM_ERR_STATE, "the scalar cannot be switched off while its record is on (lbm_drecord_set / "
+                  "lbm_drecord_ens_set switches the record off first)");
+}
+
+// lbm_drecord / lbm_drecord_ens behind their NULL checks and the caller's synchronisation: T = steps_done entries a
+// member and value; m_steps: NULL, or the members' own counts of a ragged ensemble, beyond which a member holds +0.0
+static inline int scalar_record_read(const ScalarState &s, const ScalarGrid &gr, int T, const int *m_steps, double *const (&outs)[3]) {
+  for (int v = 0; v < 3; v++) {
+    if (!outs[v] || T == 0) continue;
+    HIP_TRY(hipMemcpy2D(outs[v], (size_t)T * sizeof(double), s.rec + (size_t)v * gr.members * gr.max_iters,
+                        (size_t)gr.max_iters * sizeof(double), (size_t)T * sizeof(double), gr.members, hipMemcpyDeviceToHost));
+    if (m_steps)
+      for (int m = 0; m < gr.members; m++)
+        for (int t = m_steps[m]; t < T; t++) outs[v][(size_t)m * T + t] = 0.0;
+  }
+  return LBM_OK;
+}
+
+static inline int scalar_record_refuse_off(const char *what, bool ens) {
+  return lbm_fail(LBM_ERR_STATE, "%s: no scalar record: it is off (%s before the first step)", what,
+                  ens ? "lbm_drecord_ens_set" : "lbm_drecord_set");
+}
+
 static inline int scalar_refuse_off(const char *what) {
   return lbm_fail(LBM_ERR_ARG, "%s: the scalar is off (lbm_dscalar_set / lbm_dscalar_ens_set with a positive diffusivity switches it on)", what);
 }
 
 // The output stage and the two transfers, behind the caller's checks and synchronisation.  The array that is not current is
-// scratch between runs (5 members nx ny doubles at most).
-static inline int scalar_field(ScalarState &s, const ScalarGrid &gr, hipStream_t st, const uint8_t *mask, double *c_out) {
-  double *stage = s.g[s.cur ^ 1];
-  hipLaunchKernelGGL(lbm::dp_scalar_field, gr.helper_grid(), dim3(256), 0, st, (const double *)s.g[s.cur], (unsigned long long)gr.plane_stride,
-                     (unsigned long long)gr.member_stride(), gr.nx, mask, gr.cells(), stage);
+// scratch between runs (5 members nx ny doubles at most).  ScalarPlace: where a ragged ensemble's members lie and where its
+// output is staged instead (both arrays hold states then); a default one is a handle that is not ragged.
+struct ScalarPlace {
+  const int *par = nullptr;   // the members' flow parities (steady_words.h)
+  int off = 0;                // member m's scalar is in g[par[m] ^ off]
+  double *stage = nullptr;    // 5 members nx ny doubles
+};
+
+static inline int scalar_field(ScalarState &s, const ScalarGrid &gr, hipStream_t st, const uint8_t *mask, double *c_out,
+                               const ScalarPlace &at = ScalarPlace{}) {
+  double *stage = at.par ? at.stage : s.g[s.cur ^ 1];
+  const int cur = at.par ? at.off : s.cur;
+  hipLaunchKernelGGL(lbm::dp_scalar_field, gr.helper_grid(), dim3(256), 0, st, (const double *)s.g[cur], (const double *)s.g[cur ^ 1], at.par,
+                     (unsigned long long)gr.plane_stride, (unsigned long long)gr.member_stride(), gr.nx, mask, gr.cells(), stage);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(c_out, stage, (size_t)gr.members * gr.cells() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return LBM_OK;
 }
 
-static inline int scalar_download(ScalarState &s, const ScalarGrid &gr, hipStream_t st, double *g_out) {
-  double *stage = s.g[s.cur ^ 1];
-  hipLaunchKernelGGL(lbm::dp_scalar_pack<false>, gr.helper_grid(), dim3(256), 0, st, s.g[s.cur], (unsigned long long)gr.plane_stride,
-                     (unsigned long long)gr.member_stride(), gr.nx, gr.cells(), stage);
+static inline int scalar_download(ScalarState &s, const ScalarGrid &gr, hipStream_t st, double *g_out, const ScalarPlace &at = ScalarPlace{}) {
+  double *stage = at.par ? at.stage : s.g[s.cur ^ 1];
+  const int cur = at.par ? at.off : s.cur;
+  hipLaunchKernelGGL(lbm::dp_scalar_pack<false>, gr.helper_grid(), dim3(256), 0, st, s.g[cur], s.g[cur ^ 1], at.par,
+                     (unsigned long long)gr.plane_stride, (unsigned long long)gr.member_stride(), gr.nx, gr.cells(), stage);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(g_out, stage, 5 * (size_t)gr.members * gr.cells() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -591,10 +699,21 @@ static inline int scalar_download(ScalarState &s, const ScalarGrid &gr, hipStrea
 static inline int scalar_upload(ScalarState &s, const ScalarGrid &gr, hipStream_t st, const double *g) {
   double *stage = s.g[s.cur ^ 1];
   HIP_TRY(hipMemcpyAsync(stage, g, 5 * (size_t)gr.members * gr.cells() * sizeof(double), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(lbm::dp_scalar_pack<true>, gr.helper_grid(), dim3(256), 0, st, s.g[s.cur], (unsigned long long)gr.plane_stride,
-                     (unsigned long long)gr.member_stride(), gr.nx, gr.cells(), stage);
+  hipLaunchKernelGGL(lbm::dp_scalar_pack<true>, gr.helper_grid(), dim3(256), 0, st, s.g[s.cur], (double *)nullptr, (const int *)nullptr,
+                     (unsigned long long)gr.plane_stride, (unsigned long long)gr.member_stride(), gr.nx, gr.cells(), stage);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
+  return LBM_OK;
+}
+
+// The end of raggedness for the scalar (lbm_dens_upload): every member's state, unchanged, onto g[off], which becomes current; one
+// copy launch over the members whose flow parity is 1
+static inline int scalar_gather(ScalarState &s, const ScalarGrid &gr, hipStream_t st, const int *par, int off) {
+  hipLaunchKernelGGL(lbm::dp_scalar_gather, dim3(64, gr.members), dim3(256), 0, st, s.g[off], (const double *)s.g[off ^ 1], par,
+                     (unsigned long long)gr.member_stride());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  s.cur = off;
   return LBM_OK;
 }
 
@@ -693,11 +812,15 @@ static inline int buoy_sync(BuoyState &b, const FlowState &s, const FlowGrid &g)
 }
 
 // One buoyant flow step of all members, enqueued: the instance the five options choose
-static inline int buoy_launch(hipStream_t st, bool force, bool trt, bool open, bool wall, bool les, const lbm::DpBuoyArgs &a, int members) {
+// active: NULL, or the members' words during a leg of a steady run (d2q9_dp_buoyant_gated)
+static inline int buoy_launch(hipStream_t st, bool force, bool trt, bool open, bool wall, bool les, const lbm::DpBuoyArgs &a, int members,
+                              const int *active = nullptr) {
   const dim3 grid((unsigned)div_up((long)a.lanes_per_row * a.ny, lbm::kBlock), members);
   lbm::dp_with_flags(force, trt, open, wall, les, false, [&](auto fo, auto tr, auto op, auto wa, auto le, auto) {
-    hipLaunchKernelGGL((lbm::d2q9_dp_buoyant<decltype(fo)::value, decltype(tr)::value, decltype(op)::value, decltype(wa)::value,
-                                            decltype(le)::value>), grid, dim3(lbm::kBlock), 0, st, a);
+    constexpr bool FORCE = decltype(fo)::value, TRT = decltype(tr)::value, OPEN = decltype(op)::value, WALL = decltype(wa)::value,
+                   LES = decltype(le)::value;
+    if (!active) hipLaunchKernelGGL((lbm::d2q9_dp_buoyant<FORCE, TRT, OPEN, WALL, LES>), grid, dim3(lbm::kBlock), 0, st, a);
+    else hipLaunchKernelGGL((lbm::d2q9_dp_buoyant_gated<FORCE, TRT, OPEN, WALL, LES>), grid, dim3(lbm::kBlock), 0, st, a, active);
   });
   HIP_TRY(hipGetLastError());
   return LBM_OK;

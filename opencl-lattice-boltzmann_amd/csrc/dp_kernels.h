@@ -747,12 +747,14 @@ static __global__ void dp_pack_planes(double *cells, double *cells_alt, const in
 // double[members][gridDim.x]: the per-block sums of u.  cells_alt, par: as dp_pack_planes.  drive: NULL, or the members' body
 // forces, double[members][2] (include/lbm.h, "Body force": the reported velocity is corrected by half of it).  buoy: NULL, or the
 // members' buoyant constants, and scalar the current scalar array, member m 5 * plane_stride * ny doubles in (include/lbm.h,
-// "Buoyancy": the half-force of each cell is that of its own five stored scalar values; drive is not read)
+// "Buoyancy": the half-force of each cell is that of its own five stored scalar values; drive is not read); scalar_alt: the
+// scalar array of a member whose word par[m] is set (the scalar's two arrays in the order of the flow's)
 static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *cells, const double *cells_alt, const int *par,
                                                                  unsigned long long plane_stride,
                                                                  unsigned long long member_stride, int nx, const uint8_t *mask,
                                                                  size_t n, const DpMember *members, const double *drive,
-                                                                 const double *scalar, const DpBuoyMember *buoy,
+                                                                 const double *scalar, const double *scalar_alt,
+                                                                 const DpBuoyMember *buoy,
                                                                  double *u_x, double *u_y, double *u, double *pressure,
                                                                  double *partials) {
 #pragma clang fp contract(off)
@@ -766,6 +768,7 @@ static __global__ __launch_bounds__(kBlock) void dp_final_fields(const double *c
   DpBuoy bu{};
   if (buoy) {
     bu = buoy[blockIdx.y].buoy;
+    if (par && par[blockIdx.y]) scalar = scalar_alt;
     scalar += (size_t)blockIdx.y * (5 * plane_stride * (n / nx));
   }
   double tot_u = 0.0;

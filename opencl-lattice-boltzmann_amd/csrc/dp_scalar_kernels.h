@@ -12,6 +12,9 @@
 //                     No LDS, no atomics.  <false>: the passive scalar.  <true>: a scalar that acts back (include/lbm.h,
 //                     "Buoyancy"): the velocity it advects with is less half of each cell's own force; two more 16-B loads per lane
 //                     (the cell's own g_2, g_4), about 173 B per update.
+//   dp_scalar_step_rec  the same lane body with the scalar's record (include/lbm.h, "Scalar record"): three segment sums a step,
+//                     and the members' `active` words of a steady run
+//   dp_scalar_gather  after a steady run that left the members on different arrays: every member onto one
 //   dp_scalar_init    g_k = w_k c0 on every cell
 //   dp_scalar_field   output stage: the sum of a fluid cell's five stored values, 0.0 on a blocked cell
 //   dp_scalar_pack    device layout <-> double[members][5][ny][nx] (dp_pack_planes with five planes)
@@ -104,87 +107,37 @@ static __global__ __launch_bounds__(kBlock) void dp_scalar_step(const DpScalarAr
   const int y = (int)(t / lpr);
   const int x0 = 2 * (int)(t - (unsigned)y * lpr);
   if (y >= a.ny || x0 >= a.nx) return;
-  const DpScalarMember mc = a.members[blockIdx.y];
-  const bool has_b = x0 + 1 < a.nx;
-  const size_t ps = a.plane_stride, frs = 9 * ps, grs = 5 * ps;
-  const int ys = (y == 0) ? a.ny - 1 : y - 1, yn = (y + 1 == a.ny) ? 0 : y + 1;
-  const int xw = (x0 == 0) ? a.nx - 1 : x0 - 1;
-  const int xe = (x0 + 2 < a.nx) ? x0 + 2 : 0;  // east of cell x0+1, or of x0 when x0 is the row's last cell
-  const double *fc = a.flow + mc.flow_off + (size_t)y * frs + x0;
-  const double *gc = a.src + mc.state_off + (size_t)y * grs;
-  const double *gs = a.src + mc.state_off + (size_t)ys * grs, *gn = a.src + mc.state_off + (size_t)yn * grs;
-  v2d f[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) f[k] = *reinterpret_cast<const v2d *>(fc + k * ps);
-  const v2d c0 = *reinterpret_cast<const v2d *>(gc + x0);
-  const v2d c1 = *reinterpret_cast<const v2d *>(gc + ps + x0);
-  const v2d c3 = *reinterpret_cast<const v2d *>(gc + 3 * ps + x0);
-  const v2d c2 = *reinterpret_cast<const v2d *>(gs + 2 * ps + x0);
-  const v2d c4 = *reinterpret_cast<const v2d *>(gn + 4 * ps + x0);
-  const double w1 = gc[ps + xw], e3 = gc[3 * ps + xe];
-  const uint8_t *mask = a.mask + mc.cell_off;
-  const uint8_t *mrow = mask + (size_t)y * a.nx, *msth = mask + (size_t)ys * a.nx, *mnth = mask + (size_t)yn * a.nx;
-  const double *cw = a.c_wall + mc.cell_off;
-  const bool ob_a = mrow[x0] != 0, ob_b = has_b && mrow[x0 + 1] != 0;
-  const bool blk_w = mrow[xw] != 0, blk_e = mrow[xe] != 0;
+  constexpr bool RECORD = false;
+  [[maybe_unused]] double rec[3];
+#include "dp_scalar_lane.inl"
+}
 
-  // cell x of this row: own = its stored g_0, g_1, g_3; east / west: the streamed values and whether their cells are blocked
-  auto cell = [&](int x, bool blocked, double own0, double own1, double own3, double from_w, bool w_blocked, int x_w, double from_e,
-                  bool e_blocked, int x_e, double from_s, double from_n, const double (&fl)[9], const double *drv, double (&out)[5]) {
-    if (blocked) {
-      out[0] = own0; out[1] = own1; out[2] = gc[2 * ps + x]; out[3] = own3; out[4] = gc[4 * ps + x];
-      return;
-    }
-    double h[5];
-    h[0] = own0;
-    h[1] = w_blocked ? dp_scalar_wall(own3, cw[(size_t)y * a.nx + x_w]) : from_w;
-    h[3] = e_blocked ? dp_scalar_wall(own1, cw[(size_t)y * a.nx + x_e]) : from_e;
-    h[2] = from_s;
-    if (msth[x] != 0) h[2] = dp_scalar_wall(gc[4 * ps + x], cw[(size_t)ys * a.nx + x]);
-    h[4] = from_n;
-    if (mnth[x] != 0) h[4] = dp_scalar_wall(gc[2 * ps + x], cw[(size_t)yn * a.nx + x]);
-    if (a.open) {
-      if (x == 0) h[1] = a.c_in[mc.in_off + y] - (((h[0] + h[2]) + h[3]) + h[4]);
-      if (x == a.nx - 1) h[3] = own3;
-    }
-    double u_x, u_y, uu, pr;
-    dp_output_cell(fl, drv, u_x, u_y, uu, pr);
-    dp_scalar_collide(h, u_x, u_y, mc.omega_s, out);
-  };
-
-  double fa[9], fb[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    fa[k] = f[k].x;
-    fb[k] = f[k].y;
+// dp_scalar_step with the scalar's record: seg = [3][members][ny][nseg], the segment sums of c, c u_x and c u_y of this step, each
+// the lane's pair sum through dp_segment_tree8 as d2q9_dp_buoyant forms the flow's (the lane body under the lane test, the trees
+// and the stores of lane 0 of each segment outside it: every lane of a wave takes part in the shuffles).  active: NULL for an
+// ordinary run, or the members' words during a leg of a steady run (dp_steady_kernels.h): the workgroups of a stopped member
+// return before any load, uniformly.  No LDS, no atomics.
+template <bool BUOY>
+static __global__ __launch_bounds__(kBlock) void dp_scalar_step_rec(const DpScalarArgsOf<BUOY> a, double *seg, const int *active) {
+#pragma clang fp contract(off)
+  if (active && active[blockIdx.y] == 0) return;
+  const unsigned t = blockIdx.x * kBlock + threadIdx.x;
+  const unsigned lpr = (unsigned)a.lanes_per_row;
+  const int y = (int)(t / lpr);
+  const unsigned lane = t - (unsigned)y * lpr;
+  const int x0 = 2 * (int)lane;
+  constexpr bool RECORD = true;
+  double rec[3] = {0.0, 0.0, 0.0};
+  if (y < a.ny && x0 < a.nx) {
+#include "dp_scalar_lane.inl"
   }
-  double oa[5], ob[5];
-  // the force of each cell's own five stored values; without BUOY the member's body force, or NULL
-  [[maybe_unused]] double pa[2], pb[2];
-  const double *drv_a = mc.drive, *drv_b = mc.drive;
-  if constexpr (BUOY) {
-    const DpBuoy bu = a.buoy[blockIdx.y].buoy;
-    const v2d o2 = *reinterpret_cast<const v2d *>(gc + 2 * ps + x0);
-    const v2d o4 = *reinterpret_cast<const v2d *>(gc + 4 * ps + x0);
-    const double sa[5] = {c0.x, c1.x, o2.x, c3.x, o4.x}, sb[5] = {c0.y, c1.y, o2.y, c3.y, o4.y};
-    const DpDrive fa_ = dp_buoy_force(sa, bu), fb_ = dp_buoy_force(sb, bu);
-    pa[0] = fa_.f_x, pa[1] = fa_.f_y;
-    pb[0] = fb_.f_x, pb[1] = fb_.f_y;
-    drv_a = pa, drv_b = pb;
-  }
-  // cell a: its west neighbour is column xw, its east neighbour cell b or, where the lane has none, column xe
-  cell(x0, ob_a, c0.x, c1.x, c3.x, w1, blk_w, xw, has_b ? c3.y : e3, has_b ? ob_b : blk_e, has_b ? x0 + 1 : xe, c2.x, c4.x, fa, drv_a, oa);
-  double *d = a.dst + mc.state_off + (size_t)y * grs + x0;
-  if (has_b) {
-    cell(x0 + 1, ob_b, c0.y, c1.y, c3.y, c1.x, ob_a, x0, e3, blk_e, xe, c2.y, c4.y, fb, drv_b, ob);
+  const unsigned nseg = lpr >> 3;
+  const size_t per = (size_t)a.ny * nseg, comp = (size_t)gridDim.y * per;
+  const size_t at = (size_t)blockIdx.y * per + (size_t)y * nseg + (lane >> 3);
 #pragma unroll
-    for (int k = 0; k < 5; k++) {
-      v2d v = {oa[k], ob[k]};
-      *reinterpret_cast<v2d *>(d + k * ps) = v;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 5; k++) d[k * ps] = oa[k];
+  for (int v = 0; v < 3; v++) {
+    const double s = dp_segment_tree8(rec[v]);
+    if (y < a.ny && (lane & 7u) == 0) seg[(size_t)v * comp + at] = s;
   }
 }
 
@@ -204,10 +157,13 @@ static __global__ void dp_scalar_init(double *g, unsigned long long plane_stride
   }
 }
 
-// output stage per member: out = double[members][ny][nx]
-static __global__ void dp_scalar_field(const double *g, unsigned long long plane_stride, unsigned long long member_stride, int nx,
-                                       const uint8_t *mask, size_t n, double *out) {
+// output stage per member: out = double[members][ny][nx].  g_alt, par: NULL, or the other scalar array and one word per member
+// that says which of the two holds that member's state (0: g, 1: g_alt) once members have stopped on different launch parities
+// (dp_pack_planes)
+static __global__ void dp_scalar_field(const double *g, const double *g_alt, const int *par, unsigned long long plane_stride,
+                                       unsigned long long member_stride, int nx, const uint8_t *mask, size_t n, double *out) {
 #pragma clang fp contract(off)
+  if (par && par[blockIdx.y]) g = g_alt;
   g += (size_t)blockIdx.y * member_stride;
   mask += (size_t)blockIdx.y * n;
   out += (size_t)blockIdx.y * n;
@@ -222,10 +178,11 @@ static __global__ void dp_scalar_field(const double *g, unsigned long long plane
   }
 }
 
-// device layout <-> the caller's double[members][5][ny][nx].  TO_DEVICE: flat -> g, else g -> flat.
+// device layout <-> the caller's double[members][5][ny][nx].  TO_DEVICE: flat -> g, else g -> flat.  g_alt, par: as dp_scalar_field.
 template <bool TO_DEVICE>
-static __global__ void dp_scalar_pack(double *g, unsigned long long plane_stride, unsigned long long member_stride, int nx, size_t n,
-                                      double *flat) {
+static __global__ void dp_scalar_pack(double *g, double *g_alt, const int *par, unsigned long long plane_stride,
+                                      unsigned long long member_stride, int nx, size_t n, double *flat) {
+  if (par && par[blockIdx.y]) g = g_alt;
   g += (size_t)blockIdx.y * member_stride;
   flat += (size_t)blockIdx.y * 5 * n;
   for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
@@ -237,6 +194,15 @@ static __global__ void dp_scalar_pack(double *g, unsigned long long plane_stride
       else flat[k * n + c] = g[k * plane_stride + i];
     }
   }
+}
+
+// Every member whose word par[m] is set: its state from g_alt onto g (member_stride doubles, the padding between rows with it).
+// The others' workgroups return at once.
+static __global__ void dp_scalar_gather(double *g, const double *g_alt, const int *par, unsigned long long member_stride) {
+  if (par[blockIdx.y] == 0) return;
+  g += (size_t)blockIdx.y * member_stride;
+  g_alt += (size_t)blockIdx.y * member_stride;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < member_stride; i += (size_t)gridDim.x * blockDim.x) g[i] = g_alt[i];
 }
 
 }  // namespace lbm

@@ -82,6 +82,9 @@ struct lbm_dens {
   double *stage = nullptr;           // device, double[n][9][ny][nx]: staging of downloads while the ensemble is ragged
   std::vector<int> m_steps, m_conv;  // host copies of the words after the last steady run (empty: none since the upload)
   bool ragged = false;               // members stopped at different step counts: download and output only, until an upload
+  int scalar_off = 0;                // while ragged with a scalar on: member m's scalar lies in scalar.g[par[m] ^ scalar_off] (cur and
+                                     // scalar.cur both flip once per step: their difference is constant over a run)
+  double *scalar_stage = nullptr;    // device, double[n][5][ny][nx]: staging of the scalar's output while the ensemble is ragged
 };
 
 namespace {
@@ -102,6 +105,7 @@ void free_dens(lbm_dens *e) {
   if (e->steady_inv) (void)hipFree(e->steady_inv);
   if (e->steady_count_host) (void)hipHostFree(e->steady_count_host);
   if (e->stage) (void)hipFree(e->stage);
+  if (e->scalar_stage) (void)hipFree(e->scalar_stage);
   if (e->flow.wall_dev) (void)hipFree(e->flow.wall_dev);
   scalar_free(e->scalar);
   buoy_free(e->buoy);
@@ -183,7 +187,9 @@ void launch_dens(const lbm_dens *e, const DensArgs &a, const int *active) {
 
 // the members' grids as the scalar's helpers take them (dp_host.h), and where the output stage and the scalar read the
 // members' body forces
-ScalarGrid scalar_grid(const lbm_dens *e) { return ScalarGrid{e->n, e->nx, e->ny, e->plane_stride, e->member_stride}; }
+ScalarGrid scalar_grid(const lbm_dens *e) {
+  return ScalarGrid{e->n, e->nx, e->ny, e->plane_stride, e->member_stride, e->red_blocks, e->max_iters};
+}
 const double *drive_dev(const lbm_dens *e) { return e->flow.drive ? dens_drive_table(e->members, e->n, e->ny) : nullptr; }
 
 // nsteps steps from step count `first` on, enqueued: the prologue, the launches, the reductions into the record.  Flips
@@ -192,13 +198,13 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   const size_t per_step = (size_t)e->ny * e->nseg, all_step = (size_t)e->n * per_step;
   const int nval = seg_values(e->flow);
   const size_t slot = all_step * nval;   // one step in the ring: [nval][n][ny][nseg]
-  // with a scalar on every launch advances one step: the scalar reads each step's velocities (never during a steady run, which
-  // is refused while a scalar is on)
+  // with a scalar on every launch advances one step: the scalar reads each step's velocities (during a steady run, which needs
+  // the scalar's record, through dp_scalar_step_rec under `active`)
   const bool scalar = e->scalar.on;
   const ScalarGrid sgrid = scalar_grid(e);
   if (scalar)
     if (int rc = scalar_begin_run(e->scalar, sgrid, drive_dev(e))) return rc;
-  // with buoyancy on the flow step is d2q9_dp_buoyant, one step per launch (never during a steady run)
+  // with buoyancy on the flow step is d2q9_dp_buoyant, one step per launch (d2q9_dp_buoyant_gated during a steady run)
   const bool buoy = scalar && e->buoy.on;
   if (buoy)
     if (int rc = buoy_sync(e->buoy, e->flow, flow_grid(e))) return rc;
@@ -222,6 +228,8 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
                                 record, active))
         return rc;
     }
+    // the scalar's record: the same steps of its own ring
+    if (int rc = scalar_flush(e->scalar, sgrid, e->q.st, e->ring_fill, batch_first, active)) return rc;
     batch_first += e->ring_fill;
     e->ring_fill = 0;
     return LBM_OK;
@@ -231,11 +239,13 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
     // the remaining steps in as few launches as possible, of equal depth (8 steps at 3 a launch: 3 + 3 + 2)
     const int rem = nsteps - i;
     const int adv = scalar ? 1 : equal_depth(rem, kDensTMax);
-    if (e->ring_fill + adv > e->ring)
+    if (e->ring_fill + adv > scalar_ring_limit(e->scalar, e->ring))
       if (int rc = flush()) return rc;
     // scalar step n before flow step n, on the state that flow step streams
     if (scalar)
-      if (int rc = scalar_step(e->scalar, sgrid, e->q.st, e->cells[e->cur], e->mask, e->flow.open, buoy ? e->buoy.table : nullptr)) return rc;
+      if (int rc = scalar_step(e->scalar, sgrid, e->q.st, e->cells[e->cur], e->mask, e->flow.open, buoy ? e->buoy.table : nullptr,
+                               e->ring_fill, active))
+        return rc;
     if (buoy) {
       // flow step n reads the scalar array that scalar step n has just written
       DpBuoyArgs b{};
@@ -252,7 +262,7 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
       b.ny = e->ny;
       b.lanes_per_row = e->nseg * 8;
       b.accel_row = (!e->flow.open && i + adv < nsteps) ? e->ny - 2 : -1;
-      if (int rc = buoy_launch(e->q.st, e->flow.force, e->flow.trt, e->flow.open, e->flow.wall, e->flow.les, b, e->n)) return rc;
+      if (int rc = buoy_launch(e->q.st, e->flow.force, e->flow.trt, e->flow.open, e->flow.wall, e->flow.les, b, e->n, active)) return rc;
       e->cur ^= 1;
       e->ring_fill += adv;
       i += adv;
@@ -331,8 +341,8 @@ int steady_alloc(lbm_dens *e) {
   return LBM_OK;
 }
 
-// drag_rec: NULL for the av_vels criterion, the members' F_x records for the drag criterion (dens_steady_check without a
-// factor); everything else is one loop
+// drag_rec: NULL for the av_vels criterion; the members' F_x records for the drag criterion, or one value of the scalar's record
+// for lbm_drecord_steady_run (dens_steady_check without a factor); everything else is one loop
 int steady_impl(lbm_dens *e, int max_steps, int window, double rel_tol, const double *drag_rec, bool *launched) {
   if (int rc = check_runnable(max_steps, e->failed, "ensemble")) return rc;  // max_steps >= 0 here (lbm_dsteady_run)
   if (e->ragged) return refuse_ragged(e);
@@ -341,6 +351,7 @@ int steady_impl(lbm_dens *e, int max_steps, int window, double rel_tol, const do
   HIP_TRY(hipSetDevice(e->q.dev));
   if (int rc = steady_alloc(e)) return rc;
   const int n = e->n, s0 = e->steps_done;
+  const int scalar_off = e->cur ^ e->scalar.cur;
   const SteadyWords w = steady_words(e);
   const dim3 mgrid((unsigned)div_up(n, 256)), mblock(256);
   *launched = true;
@@ -367,7 +378,23 @@ int steady_impl(lbm_dens *e, int max_steps, int window, double rel_tol, const do
       if (*e->steady_count_host == 0) break;
     }
   }
-  return steady_read_back(e->q, w.par, n, e->m_steps, e->m_conv, &e->steps_done, &e->ragged, &e->cur);
+  if (int rc = steady_read_back(e->q, w.par, n, e->m_steps, e->m_conv, &e->steps_done, &e->ragged, &e->cur)) return rc;
+  // the scalar's arrays in the order of the flow's: a member's scalar lies where its flow parity and the run's offset say
+  e->scalar_off = scalar_off;
+  if (e->scalar.on && !e->ragged) e->scalar.cur = e->cur ^ scalar_off;
+  return LBM_OK;
+}
+
+// where a ragged ensemble's scalars lie and where their output is staged (dp_host.h); a default place while it is not ragged
+int scalar_place(lbm_dens *e, ScalarPlace *at) {
+  *at = ScalarPlace{};
+  if (!e->ragged) return LBM_OK;
+  if (!e->scalar_stage)
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->scalar_stage), (size_t)e->n * 5 * e->nx * e->ny * sizeof(double)));
+  at->par = steady_words(e).par;
+  at->off = e->scalar_off;
+  at->stage = e->scalar_stage;
+  return LBM_OK;
 }
 
 // Where downloads and the output stage put their results on the device: the grid array that is not current is scratch
@@ -383,7 +410,8 @@ int stage_of(lbm_dens *e, double **stage) {
 // the output stage of all members, each from the array that holds it, into `d[0..3]` (any may be NULL) and the per-block
 // sums of u
 int final_fields_dens(lbm_dens *e, double *const (&d)[4]) {
-  // buoyancy: the half-force of the scalar state that is current, per cell (a scalar is never on while the ensemble is ragged)
+  // buoyancy: the half-force of the scalar state that is current, per cell; while the ensemble is ragged each member's scalar
+  // from the array that holds it, the scalar's two arrays in the order of the flow's
   const bool buoy = e->scalar.on && e->buoy.on;
   if (buoy)
     if (int rc = buoy_sync(e->buoy, e->flow, flow_grid(e))) return rc;
@@ -391,7 +419,8 @@ int final_fields_dens(lbm_dens *e, double *const (&d)[4]) {
                      (const double *)e->cells[e->ragged ? 0 : e->cur], (const double *)e->cells[1], member_parity(e), e->plane_stride,
                      e->member_stride, e->nx, (const uint8_t *)e->mask, (size_t)e->nx * e->ny, (const DpMember *)e->members,
                      drive_dev(e),
-                     buoy ? (const double *)e->scalar.g[e->scalar.cur] : (const double *)nullptr,
+                     buoy ? (const double *)e->scalar.g[e->ragged ? e->scalar_off : e->scalar.cur] : (const double *)nullptr,
+                     buoy ? (const double *)e->scalar.g[e->ragged ? e->scalar_off ^ 1 : e->scalar.cur ^ 1] : (const double *)nullptr,
                      buoy ? (const DpBuoyMember *)e->buoy.table : (const DpBuoyMember *)nullptr, d[0], d[1], d[2], d[3], e->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
@@ -459,6 +488,9 @@ int lbm_dens_upload(lbm_dens *e, const double *cells) {
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->q.st));
+  // the scalar survives an upload of the flow: after a ragged run every member's state comes onto one array, unchanged
+  if (e->ragged && e->scalar.on)
+    if (int rc = scalar_gather(e->scalar, scalar_grid(e), e->q.st, steady_words(e).par, e->scalar_off)) return rc;
   e->cur = 0;
   e->steps_done = 0;
   e->ring_fill = 0;
@@ -749,6 +781,7 @@ int lbm_dscalar_ens_set(lbm_dens *e, const double *diffusivity, const double *c0
     if (int rc = scalar_check(gr, true, diffusivity, c0, c_wall, c_in)) return rc;
   if (diffusivity && e->ragged) return refuse_ragged(e);
   if (!diffusivity && e->buoy.on) return buoy_refuse_scalar_off();
+  if (!diffusivity && e->scalar.on && e->scalar.record) return scalar_record_refuse_scalar_off();
   if (int rc = queue_sync(e->q)) return rc;
   if (!diffusivity) return scalar_off(e->scalar);
   return scalar_set(e->scalar, gr, e->q.st, diffusivity, c0, c_wall, c_in, drive_dev(e));
@@ -771,7 +804,9 @@ int lbm_dscalar_ens_field(lbm_dens *e, double *c_out) {
   if (!c_out) return lbm_fail(LBM_ERR_ARG, "c_out is NULL");
   if (!e->scalar.on) return scalar_refuse_off("lbm_dscalar_ens_field");
   if (int rc = queue_sync(e->q)) return rc;
-  return scalar_field(e->scalar, scalar_grid(e), e->q.st, e->mask, c_out);
+  ScalarPlace at;
+  if (int rc = scalar_place(e, &at)) return rc;
+  return scalar_field(e->scalar, scalar_grid(e), e->q.st, e->mask, c_out, at);
 }
 
 int lbm_dscalar_ens_download(lbm_dens *e, double *g_out) {
@@ -779,15 +814,56 @@ int lbm_dscalar_ens_download(lbm_dens *e, double *g_out) {
   if (!g_out) return lbm_fail(LBM_ERR_ARG, "g_out is NULL");
   if (!e->scalar.on) return scalar_refuse_off("lbm_dscalar_ens_download");
   if (int rc = queue_sync(e->q)) return rc;
-  return scalar_download(e->scalar, scalar_grid(e), e->q.st, g_out);
+  ScalarPlace at;
+  if (int rc = scalar_place(e, &at)) return rc;
+  return scalar_download(e->scalar, scalar_grid(e), e->q.st, g_out, at);
 }
 
 int lbm_dscalar_ens_upload(lbm_dens *e, const double *g) {
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (!g) return lbm_fail(LBM_ERR_ARG, "g is NULL");
   if (!e->scalar.on) return scalar_refuse_off("lbm_dscalar_ens_upload");
+  if (e->ragged) return refuse_ragged(e);
   if (int rc = queue_sync(e->q)) return rc;
   return scalar_upload(e->scalar, scalar_grid(e), e->q.st, g);
+}
+
+int lbm_drecord_ens_set(lbm_dens *e, int on) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (int rc = scalar_record_check(e->scalar, on, e->steps_done, true)) return rc;
+  if (int rc = queue_sync(e->q)) return rc;
+  HIP_TRY(hipSetDevice(e->q.dev));
+  return scalar_record_set(e->scalar, scalar_grid(e), on);
+}
+
+int lbm_drecord_ens_get(const lbm_dens *e, int *on_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!on_out) return lbm_fail(LBM_ERR_ARG, "on_out is NULL");
+  *on_out = e->scalar.on && e->scalar.record ? 1 : 0;
+  return LBM_OK;
+}
+
+int lbm_drecord_ens(lbm_dens *e, double *content_out, double *flux_x_out, double *flux_y_out) {
+  // argument errors before a device is touched
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!content_out && !flux_x_out && !flux_y_out) return lbm_fail(LBM_ERR_ARG, "content_out, flux_x_out and flux_y_out are all NULL");
+  if (!e->scalar.on || !e->scalar.record) return scalar_record_refuse_off("lbm_drecord_ens", true);
+  if (int rc = queue_sync(e->q)) return rc;
+  double *const outs[3] = {content_out, flux_x_out, flux_y_out};
+  return scalar_record_read(e->scalar, scalar_grid(e), e->steps_done, e->ragged ? e->m_steps.data() : nullptr, outs);
+}
+
+int lbm_drecord_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol, int which) {
+  // every argument error is reported before the ensemble or a device is touched
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
+  if (which < 0 || which > 2) return lbm_fail(LBM_ERR_ARG, "which must be 0 (content), 1 (flux_x) or 2 (flux_y) (got %d)", which);
+  if (!e->scalar.on || !e->scalar.record)
+    return lbm_fail(LBM_ERR_ARG, "the scalar criterion reads the scalar's record: it is off (lbm_dscalar_ens_set, then "
+                    "lbm_drecord_ens_set before the first step)");
+  bool launched = false;
+  const int rc = steady_impl(e, max_steps, window, rel_tol, e->scalar.rec + (size_t)which * e->n * e->max_iters, &launched);
+  return latch_failure(rc, launched, e->q.st, &e->failed);
 }
 
 int lbm_dbuoy_ens_set(lbm_dens *e, const double *b) {

@@ -154,7 +154,7 @@ DpDrive drive_args(const lbm_dp *d) { return DpDrive{d->flow.drive_f[0], d->flow
 const double *drive_dev(const lbm_dp *d) { return d->flow.drive ? dens_drive_table(d->members, 1, d->p.ny) : nullptr; }
 
 // the grid as the scalar's helpers take it (dp_host.h): a context is one member
-ScalarGrid scalar_grid(const lbm_dp *d) { return ScalarGrid{1, d->p.nx, d->p.ny, d->plane_stride, 0}; }
+ScalarGrid scalar_grid(const lbm_dp *d) { return ScalarGrid{1, d->p.nx, d->p.ny, d->plane_stride, 0, d->red_blocks, d->p.max_iters}; }
 
 void launch_multi(const lbm_dp *d, const DpMultiArgs &a) {
   const FlowState &f = d->flow;
@@ -232,6 +232,8 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
                                 0ull, nullptr))
         return rc;
     }
+    // the scalar's record: the same steps of its own ring
+    if (int rc = scalar_flush(d->scalar, sgrid, d->q.st, d->ring_fill, batch_first, nullptr)) return rc;
     batch_first += d->ring_fill;
     d->ring_fill = 0;
     return LBM_OK;
@@ -241,11 +243,13 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
     // the LDS-tile form: the remaining steps in as few launches as possible, of equal depth (20 steps at T = 8: 7 + 7 + 6)
     const int rem = nsteps - i;
     const int adv = (T > 0 && !scalar) ? equal_depth(rem, T) : 1;
-    if (d->ring_fill + adv > d->ring)
+    if (d->ring_fill + adv > scalar_ring_limit(d->scalar, d->ring))
       if (int rc = flush()) return rc;
     // scalar step n before flow step n, on the state that flow step streams
     if (scalar)
-      if (int rc = scalar_step(d->scalar, sgrid, d->q.st, d->cells[d->cur], d->mask, d->flow.open, buoy ? d->buoy.table : nullptr)) return rc;
+      if (int rc = scalar_step(d->scalar, sgrid, d->q.st, d->cells[d->cur], d->mask, d->flow.open, buoy ? d->buoy.table : nullptr,
+                               d->ring_fill, nullptr))
+        return rc;
     const bool accel_next = !d->flow.open && i + adv < nsteps;
     double *seg = d->seg + (size_t)d->ring_fill * slot;
     if (buoy) {
@@ -331,7 +335,7 @@ int final_fields_dp(lbm_dp *d, double *const (&dst)[4]) {
   hipLaunchKernelGGL(dp_final_fields, dim3(d->fin_blocks, 1), dim3(kBlock), 0, d->q.st, (const double *)d->cells[d->cur],
                      (const double *)nullptr, (const int *)nullptr, d->plane_stride, 0ull, d->p.nx, (const uint8_t *)d->mask, n,
                      (const DpMember *)d->members, drive_dev(d), buoy ? (const double *)d->scalar.g[d->scalar.cur] : (const double *)nullptr,
-                     buoy ? (const DpBuoyMember *)d->buoy.table : (const DpBuoyMember *)nullptr, dst[0], dst[1], dst[2], dst[3],
+                     (const double *)nullptr, buoy ? (const DpBuoyMember *)d->buoy.table : (const DpBuoyMember *)nullptr, dst[0], dst[1], dst[2], dst[3],
                      d->fin_partials);
   HIP_TRY(hipGetLastError());
   return LBM_OK;
@@ -642,6 +646,7 @@ int lbm_dscalar_set(lbm_dp *d, double diffusivity, const double *c0, const doubl
   if (diffusivity > 0.0)
     if (int rc = scalar_check(gr, false, &diffusivity, c0, c_wall, c_in)) return rc;
   if (diffusivity == 0.0 && d->buoy.on) return buoy_refuse_scalar_off();
+  if (diffusivity == 0.0 && d->scalar.on && d->scalar.record) return scalar_record_refuse_scalar_off();
   if (int rc = queue_sync(d->q)) return rc;
   if (diffusivity == 0.0) return scalar_off(d->scalar);
   return scalar_set(d->scalar, gr, d->q.st, &diffusivity, c0, c_wall, c_in, drive_dev(d));
@@ -679,6 +684,31 @@ int lbm_dscalar_upload(lbm_dp *d, const double *g) {
   if (!d->scalar.on) return scalar_refuse_off("lbm_dscalar_upload");
   if (int rc = queue_sync(d->q)) return rc;
   return scalar_upload(d->scalar, scalar_grid(d), d->q.st, g);
+}
+
+int lbm_drecord_set(lbm_dp *d, int on) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (int rc = scalar_record_check(d->scalar, on, d->steps_done, false)) return rc;
+  if (int rc = queue_sync(d->q)) return rc;
+  HIP_TRY(hipSetDevice(d->q.dev));
+  return scalar_record_set(d->scalar, scalar_grid(d), on);
+}
+
+int lbm_drecord_get(const lbm_dp *d, int *on_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!on_out) return lbm_fail(LBM_ERR_ARG, "on_out is NULL");
+  *on_out = d->scalar.on && d->scalar.record ? 1 : 0;
+  return LBM_OK;
+}
+
+int lbm_drecord(lbm_dp *d, double *content_out, double *flux_x_out, double *flux_y_out) {
+  // argument errors before a device is touched
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!content_out && !flux_x_out && !flux_y_out) return lbm_fail(LBM_ERR_ARG, "content_out, flux_x_out and flux_y_out are all NULL");
+  if (!d->scalar.on || !d->scalar.record) return scalar_record_refuse_off("lbm_drecord", false);
+  if (int rc = queue_sync(d->q)) return rc;
+  double *const outs[3] = {content_out, flux_x_out, flux_y_out};
+  return scalar_record_read(d->scalar, scalar_grid(d), d->steps_done, nullptr, outs);
 }
 
 int lbm_dbuoy_set(lbm_dp *d, double b_x, double b_y, double c_ref) {
