@@ -39,15 +39,15 @@ $(PKG)/csrc/lbm_ensemble.o: $(PKG)/csrc/lbm_ensemble.cpp $(PKG)/csrc/ensemble_ke
 # measurement build of another tile shape (csrc/lbm_dp.cpp, LBM_DP_TY / LBM_DP_TMAX).
 # csrc/dp_scalar_kernels.h and csrc/dp_buoyant_kernels.h with their lane bodies csrc/dp_scalar_lane.inl and csrc/dp_buoyant_lanes.inl
 # (the scalar's kernels and the buoyant flow step, included through
-# dp_host.h) stay out of CSRC with them.
-$(PKG)/csrc/lbm_dp.o: $(PKG)/csrc/lbm_dp.cpp $(PKG)/csrc/body_map.h $(PKG)/csrc/dp_host.h $(PKG)/csrc/dp_scalar_kernels.h $(PKG)/csrc/dp_scalar_lane.inl $(PKG)/csrc/dp_buoyant_kernels.h $(PKG)/csrc/dp_buoyant_lanes.inl $(PKG)/csrc/dp_kernels.h $(PKG)/csrc/dp_tile.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h include/lbm.h
+# dp_host.h) stay out of CSRC with them, and so do csrc/dp_stats_kernels.h and csrc/stats_plan.h (the running statistics).
+$(PKG)/csrc/lbm_dp.o: $(PKG)/csrc/lbm_dp.cpp $(PKG)/csrc/body_map.h $(PKG)/csrc/dp_host.h $(PKG)/csrc/dp_stats_kernels.h $(PKG)/csrc/stats_plan.h $(PKG)/csrc/dp_scalar_kernels.h $(PKG)/csrc/dp_scalar_lane.inl $(PKG)/csrc/dp_buoyant_kernels.h $(PKG)/csrc/dp_buoyant_lanes.inl $(PKG)/csrc/dp_kernels.h $(PKG)/csrc/dp_tile.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h include/lbm.h
 	$(HIPCC) $(HIPFLAGS) $(LBM_DP_FLAGS) -c $(PKG)/csrc/lbm_dp.cpp -o $@
 
 # The double-precision ensembles (lbm_dens_*) are a fifth unit: the member axis of ensemble_kernels.h over the arithmetic of
 # dp_kernels.h, which it includes, and their steady runs (lbm_dsteady_*: dp_steady_kernels.h over the words of steady_words.h,
 # which is in CSRC because the third unit includes it).  Out of CSRC for the same reason.  LBM_DENS_FLAGS: a measurement build that forces one
 # tile shape (csrc/lbm_dens.cpp, LBM_DENS_TY / LBM_DENS_TMAX / LBM_DENS_THREADS; tools/dp_ensemble_ab.py).
-$(PKG)/csrc/lbm_dens.o: $(PKG)/csrc/lbm_dens.cpp $(PKG)/csrc/body_map.h $(PKG)/csrc/dp_host.h $(PKG)/csrc/dp_scalar_kernels.h $(PKG)/csrc/dp_scalar_lane.inl $(PKG)/csrc/dp_buoyant_kernels.h $(PKG)/csrc/dp_buoyant_lanes.inl $(PKG)/csrc/dp_ensemble_kernels.h $(PKG)/csrc/dp_steady_kernels.h $(PKG)/csrc/steady_words.h $(PKG)/csrc/dp_kernels.h $(PKG)/csrc/dp_tile.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h include/lbm.h
+$(PKG)/csrc/lbm_dens.o: $(PKG)/csrc/lbm_dens.cpp $(PKG)/csrc/body_map.h $(PKG)/csrc/dp_host.h $(PKG)/csrc/dp_stats_kernels.h $(PKG)/csrc/stats_plan.h $(PKG)/csrc/dp_scalar_kernels.h $(PKG)/csrc/dp_scalar_lane.inl $(PKG)/csrc/dp_buoyant_kernels.h $(PKG)/csrc/dp_buoyant_lanes.inl $(PKG)/csrc/dp_ensemble_kernels.h $(PKG)/csrc/dp_steady_kernels.h $(PKG)/csrc/steady_words.h $(PKG)/csrc/dp_kernels.h $(PKG)/csrc/dp_tile.h $(PKG)/csrc/d2q9_kernels.h $(PKG)/csrc/lbm_error.h $(PKG)/csrc/host_common.h include/lbm.h
 	$(HIPCC) $(HIPFLAGS) $(LBM_DENS_FLAGS) -c $(PKG)/csrc/lbm_dens.cpp -o $@
 
 $(LIB): $(PKG)/csrc/lbm_hip.o $(PKG)/csrc/lbm_deep.o $(PKG)/csrc/lbm_ensemble.o $(PKG)/csrc/lbm_dp.o $(PKG)/csrc/lbm_dens.o

@@ -1323,6 +1323,77 @@ int lbm_drecord_ens(lbm_dens *e, double *content_out /*[n][steps_done]*/, double
  * < 0, window < 1, rel_tol negative or not finite, which outside 0 .. 2, the record is off.  Synchronises. */
 int lbm_drecord_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol, int which);
 
+/*
+ * ---- Running statistics: time means and Reynolds stresses, sums over time per cell ------------------------------------------------
+ *
+ * The records above (av_vels, the force, the scalar) are sums over space per step.  This section adds the other half, sums over
+ * time per cell: with statistics on, a context holds six sums per cell, double[6][ny][nx], and a sample count; each member of an
+ * ensemble holds its own.  Off by default.  The reference has no counterpart.
+ *
+ * Definition.  A sample at step count s reads the four fields exactly as lbm_dp_final_state (lbm_dens_final_state) would return
+ * them after s steps: the half-force corrections of "Body force" and "Buoyancy" included, and a blocked cell giving 0, 0, 0,
+ * density / 3.  Per cell, all in double, contraction off, one IEEE operation per written operator:
+ *     S[0] = S[0] + u_x;
+ *     S[1] = S[1] + u_y;
+ *     S[2] = S[2] + pressure;
+ *     S[3] = S[3] + u_x * u_x;
+ *     S[4] = S[4] + u_y * u_y;
+ *     S[5] = S[5] + u_x * u_y;
+ * Samples are taken in order of s, so every S[v] is a left-to-right sum; there is no cross-lane or cross-cell arithmetic, so no
+ * order of summation needs fixing.  The means are S[0..2] / samples, the Reynolds stresses S[3] / samples - mean(u_x)^2 and so on,
+ * formed by the caller.  Raw sums have a caveat: a covariance loses as many digits as the variance is small against the squared
+ * mean (fluctuations of 1e-3 on a mean of 0.1 keep about 10 digits in double).
+ *
+ * When a sample is taken.  lbm_dstats_set(d, every) with every >= 1 switches the statistics on: it allocates the six planes (48 B
+ * per cell beside the 144 B of the two grids), sets them to +0.0, sets the sample count to 0 and the origin s0 to the step count
+ * as it stands.  It is accepted between runs at ANY step count: statistics usually start behind a transient.  Samples are taken at
+ * every step count s = s0 + j * every, j >= 1, that a run reaches: a run of nsteps from step count `first` takes the sample points
+ * in (first, first + nsteps].  A run in pieces takes the samples of one run and leaves the same bits.  Setting again while on
+ * starts anew, with zeros and a new origin; every may change.  every == 0 switches the statistics off and frees the planes.
+ * lbm_dp_upload, lbm_dens_upload and lbm_dp_upload_obstacles keep the setting and start the statistics anew, the origin at the
+ * step count behind the upload.
+ *
+ * How a run takes them.  The run is cut at its sample points.  Every piece is enqueued the way a run of its length is: the
+ * prologue accelerate_flow (none with open boundaries), launches of equal depth within the piece (one step each with a scalar
+ * on), the next step's acceleration fused only inside the piece.  Behind a piece that ends on a sample point one kernel,
+ * dp_stats_sample, reads the current arrays - the state the output stage would read - and adds to the planes.  The ring of
+ * per-step segment sums and its flushes carry across the cuts: a cut costs one sample launch and one accelerate launch, no
+ * synchronisation and no reduction launch.
+ *
+ * Nothing else moves.  lbm_dp_run(a) then lbm_dp_run(b) equals lbm_dp_run(a + b) bit for bit, in both families and with every
+ * option; a run with statistics on is such a run in pieces with a kernel between them that writes the planes alone.  So cells,
+ * av_vels, the force record, the fields, the Reynolds number, the scalar and its record are the same bits with statistics on as
+ * with them off.
+ *
+ * When it is refused.  Everything is checked before anything changes.  LBM_ERR_ARG: a NULL handle, every < 0, all-NULL outputs of
+ * a getter.  LBM_ERR_ARG, as long as statistics are on, from lbm_dsteady_run, lbm_dbody_steady_run and lbm_drecord_steady_run,
+ * with a message that names lbm_dstats_ens_set: a member that stops would need a gated sample kernel, which is out of scope.
+ * LBM_ERR_STATE: lbm_dstats_ens_set with every >= 1 on a ragged ensemble; lbm_dstats / lbm_dstats_ens while the statistics are
+ * off.  LBM_ERR_HIP: the planes do not fit the device's memory; statistics are then off and nothing else has changed.
+ *
+ * Names: lbm_dstats_*, on both double-precision handles.  Out of scope: fp32 contexts and fp32 ensembles, which get nothing;
+ * moments of the scalar (the mean of C, turbulent heat fluxes); steady runs with statistics on; a per-member every; statistics
+ * fused into a flow kernel; shifted or Welford accumulation.
+ */
+
+/* Switch the statistics of a double-precision context on (every >= 1: a sample every so many steps from now) or off (0, the
+ * default).  LBM_ERR_ARG, before the context is read: a NULL context, every < 0.  LBM_ERR_HIP: no memory for the planes.
+ * Synchronises. */
+int lbm_dstats_set(lbm_dp *d, int every);
+
+/* every_out: the setting, 0 while off; origin_out: the step count the sample points are counted from; samples_out: the samples
+ * taken since.  Zeros while off.  Any output may be NULL; all three NULL, or a NULL context: LBM_ERR_ARG. */
+int lbm_dstats_get(const lbm_dp *d, int *every_out, int *origin_out, int *samples_out);
+
+/* The six planes of sums.  LBM_ERR_ARG: a NULL argument.  LBM_ERR_STATE: the statistics are off.  Synchronises. */
+int lbm_dstats(lbm_dp *d, double *sums_out /*[6][ny][nx]*/);
+
+/* The same for a double-precision ensemble: one every for all members, each member its own planes, all with one origin and one
+ * count.  LBM_ERR_STATE: every >= 1 on a ragged ensemble. */
+int lbm_dstats_ens_set(lbm_dens *e, int every);
+int lbm_dstats_ens_get(const lbm_dens *e, int *every_out, int *origin_out, int *samples_out);
+int lbm_dstats_ens(lbm_dens *e, double *sums_out /*[n][6][ny][nx]*/);
+
 const char *lbm_last_error(void);
 const char *lbm_version(void);
 

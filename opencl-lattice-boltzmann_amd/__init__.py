@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "lbm_dbuoy_set", "lbm_dbuoy_get", "lbm_dbuoy_ens_set", "lbm_dbuoy_ens_get",
     "lbm_drecord_set", "lbm_drecord_get", "lbm_drecord",
     "lbm_drecord_ens_set", "lbm_drecord_ens_get", "lbm_drecord_ens", "lbm_drecord_steady_run",
+    "lbm_dstats_set", "lbm_dstats_get", "lbm_dstats", "lbm_dstats_ens_set", "lbm_dstats_ens_get", "lbm_dstats_ens",
 ]
 
 TRANSPORTS = {"auto": 0, "rccl": 1, "copy": 2, "peer": 3}
@@ -212,6 +213,12 @@ def load_library():
     L.lbm_drecord_ens_get.argtypes = [vp, ctypes.POINTER(ci)]
     L.lbm_drecord_ens.argtypes = [vp, vp, vp, vp]
     L.lbm_drecord_steady_run.argtypes = [vp, ci, ci, ctypes.c_double, ci]
+    L.lbm_dstats_set.argtypes = [vp, ci]
+    L.lbm_dstats_get.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.lbm_dstats.argtypes = [vp, vp]
+    L.lbm_dstats_ens_set.argtypes = [vp, ci]
+    L.lbm_dstats_ens_get.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.lbm_dstats_ens.argtypes = [vp, vp]
     L.lbm_last_error.restype = cp
     L.lbm_version.restype = cp
     _lib = L
@@ -540,11 +547,60 @@ class LBM(_Handle):
                 f.write("%d:\t%.12E\n" % (i, v))
 
 
-class LBMDouble(_Handle):
+class _Stats:
+    """The running statistics of the double-precision families (include/lbm.h, "Running statistics"): the four methods LBMDouble
+    and EnsembleDouble share.  A class names its entry points' prefix in `_stats` and the leading axes of its arrays in
+    `_stats_lead()`."""
+
+    def set_stats(self, every):
+        """Statistics on (lbm_dstats_set / lbm_dstats_ens_set): a sample of u_x, u_y, pressure and their three products per cell
+        every `every` steps, counted from the step count as it stands; 0 = off.  Accepted between runs at any step count; setting
+        again starts anew.  The uploads keep the setting and start anew; steady runs are refused while it is on."""
+        _check(getattr(self.lib, self._stats + "_set")(getattr(self, self._handle), int(every)), self._stats + "_set")
+
+    def stats_state(self):
+        """(every, origin, samples), or None while the statistics are off"""
+        every, origin, samples = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _check(getattr(self.lib, self._stats + "_get")(getattr(self, self._handle), ctypes.byref(every), ctypes.byref(origin),
+                                                       ctypes.byref(samples)), self._stats + "_get")
+        return (every.value, origin.value, samples.value) if every.value else None
+
+    def stats_sums(self):
+        """The raw sums, float64[6, ny, nx] (an ensemble: [n, 6, ny, nx]): S[0..5] of u_x, u_y, pressure, u_x u_x, u_y u_y, u_x u_y"""
+        sums = np.zeros(self._stats_lead() + (6, self.ny, self.nx), dtype=np.float64)
+        _check(getattr(self.lib, self._stats)(getattr(self, self._handle), sums.ctypes.data), self._stats)
+        return sums
+
+    def stats(self):
+        """{"samples", "u_x", "u_y", "pressure", "uxux", "uyuy", "uxuy"}: the count, the time means S[v] / samples and the
+        covariances (Reynolds stresses) S[3] / samples - u_x * u_x and so on, float64[ny, nx] each (an ensemble: [n, ny, nx]),
+        formed here in numpy from stats_sums().  Zero samples: LBMError.
+
+        The caveat of raw sums: a covariance loses as many digits as the variance is small against the squared mean.  In fp64 this
+        leaves about 10 digits for fluctuations of 1e-3 on a mean of 0.1; a variance may round below zero, by rounding alone."""
+        state = self.stats_state()
+        if state is None or state[2] == 0:
+            raise LBMError("stats(): no samples yet (set_stats(every), then run past a sample point)")
+        samples = state[2]
+        S = np.moveaxis(self.stats_sums(), -3, 0)
+        u_x = S[0] / samples
+        u_y = S[1] / samples
+        pressure = S[2] / samples
+        uxux = S[3] / samples - u_x * u_x
+        uyuy = S[4] / samples - u_y * u_y
+        uxuy = S[5] / samples - u_x * u_y
+        return {"samples": samples, "u_x": u_x, "u_y": u_y, "pressure": pressure, "uxux": uxux, "uyuy": uyuy, "uxuy": uxuy}
+
+
+class LBMDouble(_Handle, _Stats):
     """A double-precision context (lbm_dp): one grid on the current device in fp64, the precision of the reference's golden
     files.  Mirrors LBM with double in place of float: create -> upload -> run -> sync -> download -> destroy.  `params`:
     DParams (make_dparams, read_inputs_double); `obstacles`: int32[ny, nx]."""
     _prefix, _handle = "lbm_dp", "ctx"
+    _stats = "lbm_dstats"
+
+    def _stats_lead(self):
+        return ()
 
     def __init__(self, params, obstacles):
         self.lib = load_library()
@@ -896,13 +952,17 @@ class Ensemble(_EnsembleOf):
     _prefix, _dtype, _ptype, _steady = "lbm_ens", np.float32, Params, "lbm_steady"
 
 
-class EnsembleDouble(_EnsembleOf):
+class EnsembleDouble(_EnsembleOf, _Stats):
     """N independent double-precision simulations of one grid size, advanced together (lbm_dens): one launch per several
     timesteps for all members, every member bit-identical to an LBMDouble on the same inputs.  Mirrors Ensemble with double
     in place of float.  `params`: a list of DParams that share nx, ny and max_iters (sweep_dparams); `obstacles`:
     int32[n, ny, nx], or one [ny, nx] map for all members.  run_until() stops a member where an LBMDouble run to the same
     count would be, bit for bit, av_vels included."""
     _prefix, _dtype, _ptype, _steady = "lbm_dens", np.float64, DParams, "lbm_dsteady"
+    _stats = "lbm_dstats_ens"
+
+    def _stats_lead(self):
+        return (self.n,)
 
     def __init__(self, params, obstacles):
         params = list(params)

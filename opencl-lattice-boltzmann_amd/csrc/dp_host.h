@@ -1,13 +1,16 @@
 // Where lbm_dp.cpp and lbm_dens.cpp drive the helper kernels of dp_kernels.h with the same statements: the second reduction
 // stage, the force of the current state, the settings of the six flow options with their device tables, the scalar
-// (dp_scalar_kernels.h) and buoyancy (dp_buoyant_kernels.h), for `members` grids (a context: 1).  Plain functions over the fields
+// (dp_scalar_kernels.h), buoyancy (dp_buoyant_kernels.h) and the running statistics (dp_stats_kernels.h, stats_plan.h), for `members`
+// grids (a context: 1).  Plain functions over the fields
 // they need, as host_common.h's; static, because the kernels they launch are each unit's own copies.
 #pragma once
 #include "body_map.h"
 #include "dp_buoyant_kernels.h"
 #include "dp_kernels.h"
 #include "dp_scalar_kernels.h"
+#include "dp_stats_kernels.h"
 #include "host_common.h"
+#include "stats_plan.h"
 
 #include <cstdio>
 #include <cstring>
@@ -824,6 +827,124 @@ static inline int buoy_launch(hipStream_t st, bool force, bool trt, bool open, b
   });
   HIP_TRY(hipGetLastError());
   return LBM_OK;
+}
+
+// ---- running statistics (include/lbm.h, "Running statistics"; lbm_dstats_*) --------------------------------------------------
+// What a handle holds of them beside its ScalarState, and what the two hosts say alike: the set, the restart behind an upload, the
+// sample launch behind a piece of a run (stats_plan.h cuts the run) and the read-back.  The grid is described as for the scalar
+// (ScalarGrid: members, nx, ny, plane_stride, the flow's member stride).  The count of samples is the host's: a sample is taken
+// where it is enqueued.
+struct StatsState {
+  int every = 0;            // 0: off
+  int origin = 0;           // the step count the sample points are counted from
+  int samples = 0;
+  double *sums = nullptr;   // [members][6][ny][plane_stride], allocated while on
+};
+
+static inline void stats_free(StatsState &s) {
+  if (s.sums) (void)hipFree(s.sums);
+  s = StatsState{};
+}
+
+static inline size_t stats_bytes(const ScalarGrid &gr) { return (size_t)gr.members * 6 * gr.ny * gr.plane_stride * sizeof(double); }
+
+// what lbm_dstats_set / lbm_dstats_ens_set refuse of their value, before the handle is read
+static inline int stats_check(int every) {
+  if (every < 0) return lbm_fail(LBM_ERR_ARG, "every must be >= 1, or 0 (off) (got %d)", every);
+  return LBM_OK;
+}
+
+// Zeros, no samples, and the origin at this step count: behind a set and behind the uploads, which keep the setting
+static inline int stats_restart(StatsState &s, const ScalarGrid &gr, hipStream_t st, int steps_done) {
+  if (!s.sums) return LBM_OK;
+  HIP_TRY(hipMemsetAsync(s.sums, 0, stats_bytes(gr), st));
+  HIP_TRY(hipStreamSynchronize(st));
+  s.samples = 0;
+  s.origin = steps_done;
+  return LBM_OK;
+}
+
+// Behind stats_check and the caller's synchronisation.  every == 0: off, the planes go.  Setting again while on starts anew.
+// Where the planes do not fit the device the statistics are off as before and nothing else has changed.
+static inline int stats_set(StatsState &s, const ScalarGrid &gr, hipStream_t st, int every, int steps_done) {
+  if (every == 0) {
+    stats_free(s);
+    return LBM_OK;
+  }
+  const bool fresh = !s.sums;
+  if (fresh) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (stats_bytes(gr) > free_b)
+      return lbm_fail(LBM_ERR_HIP, "the statistics of %d grid%s of %dx%d need %.1f MiB of device memory (48 B per cell), %.1f MiB are free",
+                      gr.members, gr.members == 1 ? "" : "s", gr.nx, gr.ny, (double)stats_bytes(gr) / 1048576.0, (double)free_b / 1048576.0);
+    if (int rc = hip_alloc(reinterpret_cast<void **>(&s.sums), stats_bytes(gr))) {
+      s.sums = nullptr;
+      return rc;
+    }
+  }
+  if (int rc = stats_restart(s, gr, st, steps_done)) {
+    const std::string keep = lbm_last_error();
+    if (fresh) stats_free(s);
+    return fail_again(rc, keep);
+  }
+  s.every = every;
+  return LBM_OK;
+}
+
+static inline void stats_get(const StatsState &s, int *every_out, int *origin_out, int *samples_out) {
+  if (every_out) *every_out = s.every;
+  if (origin_out) *origin_out = s.origin;
+  if (samples_out) *samples_out = s.samples;
+}
+
+// One sample of all members, enqueued behind a piece of a run that ends on a sample point: the state dp_final_fields would read.
+// cells, mask, members, drive: dp_final_fields' arguments of the handle as it stands; scalar and buoy: NULL, or the current scalar
+// array and the members' buoyant constants (buoy_sync has written them before the run).
+static inline int stats_sample(StatsState &s, const ScalarGrid &gr, hipStream_t st, const double *cells, const uint8_t *mask,
+                               const lbm::DpMember *members, const double *drive, const double *scalar, const lbm::DpBuoyMember *buoy) {
+  lbm::DpStatsArgs a{};
+  a.cells = cells;
+  a.mask = mask;
+  a.members = members;
+  a.drive = drive;
+  a.scalar = scalar;
+  a.buoy = buoy;
+  a.sums = s.sums;
+  a.plane_stride = gr.plane_stride;
+  a.member_stride = gr.flow_member_stride;
+  a.nx = gr.nx;
+  a.ny = gr.ny;
+  a.xblocks = (int)div_up(div_up(gr.nx, 2), lbm::kStatsLanes);
+  // about 2048 blocks at most, eight a CU; a block strides over the rows beyond
+  a.rowgroups = (int)std::min(div_up(gr.ny, lbm::kStatsRows), std::max(1L, 2048L / ((long)a.xblocks * gr.members)));
+  const dim3 grid((unsigned)(a.xblocks * a.rowgroups), gr.members);
+  if (buoy) hipLaunchKernelGGL(lbm::dp_stats_sample<true>, grid, dim3(lbm::kBlock), 0, st, a);
+  else hipLaunchKernelGGL(lbm::dp_stats_sample<false>, grid, dim3(lbm::kBlock), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  s.samples++;
+  return LBM_OK;
+}
+
+// lbm_dstats / lbm_dstats_ens behind their checks and the caller's synchronisation: one pitched copy into double[members][6][ny][nx]
+static inline int stats_read(const StatsState &s, const ScalarGrid &gr, double *sums_out) {
+  HIP_TRY(hipMemcpy2D(sums_out, (size_t)gr.nx * sizeof(double), s.sums, gr.plane_stride * sizeof(double), (size_t)gr.nx * sizeof(double),
+                      (size_t)gr.members * 6 * gr.ny, hipMemcpyDeviceToHost));
+  return LBM_OK;
+}
+
+static inline int stats_refuse_off(const char *what, bool ens) {
+  return lbm_fail(LBM_ERR_STATE, "%s: no sums: the statistics are off (%s with every >= 1 switches them on)", what,
+                  ens ? "lbm_dstats_ens_set" : "lbm_dstats_set");
+}
+
+static inline int stats_refuse_steady(const char *what) {
+  return lbm_fail(LBM_ERR_ARG, "%s: the running statistics are on (lbm_dstats_ens_set): a member that stops would need a gated sample "
+                  "kernel, which is out of scope; lbm_dstats_ens_set(e, 0) switches them off for a steady run", what);
+}
+
+static inline int stats_refuse_plan(int first, int origin) {
+  return lbm_fail(LBM_ERR_STATE, "the statistics' origin %d lies beyond the step count %d of this run", origin, first);
 }
 
 }  // namespace lbm_host

@@ -70,6 +70,7 @@ struct lbm_dens {
                                    // lbm_ddrive_ens_set: the members' settings (dp_host.h), all off by default
   ScalarState scalar;              // lbm_dscalar_ens_set: the members' scalars (dp_host.h), off by default
   BuoyState buoy;                  // lbm_dbuoy_ens_set: the scalars act back on the members' flows (dp_host.h), off by default
+  StatsState stats;                // lbm_dstats_ens_set: the members' running statistics (dp_host.h), off by default
   int nseg = 1, red_blocks = 1, fin_blocks = 1;
   int tiles_x = 1, tiles = 1;
   int ring = 8, ring_fill = 0;
@@ -109,6 +110,7 @@ void free_dens(lbm_dens *e) {
   if (e->flow.wall_dev) (void)hipFree(e->flow.wall_dev);
   scalar_free(e->scalar);
   buoy_free(e->buoy);
+  stats_free(e->stats);
   queue_destroy(e->q);
   delete e;
 }
@@ -193,7 +195,8 @@ ScalarGrid scalar_grid(const lbm_dens *e) {
 const double *drive_dev(const lbm_dens *e) { return e->flow.drive ? dens_drive_table(e->members, e->n, e->ny) : nullptr; }
 
 // nsteps steps from step count `first` on, enqueued: the prologue, the launches, the reductions into the record.  Flips
-// e->cur per launch; the caller counts the steps.  active: as launch_dens.
+// e->cur per launch; the caller counts the steps.  active: as launch_dens.  With the running statistics on the run is cut at its
+// sample points (stats_plan.h): every piece is enqueued as a run of its length, with a sample behind it where it ends on one.
 int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   const size_t per_step = (size_t)e->ny * e->nseg, all_step = (size_t)e->n * per_step;
   const int nval = seg_values(e->flow);
@@ -208,13 +211,8 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
   const bool buoy = scalar && e->buoy.on;
   if (buoy)
     if (int rc = buoy_sync(e->buoy, e->flow, flow_grid(e))) return rc;
-  // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
-  // into the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
-  if (!e->flow.open) {
-    hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
-                       e->member_stride, (const uint8_t *)e->mask, (const DpMember *)e->members, e->nx, e->ny, active);
-    HIP_TRY(hipGetLastError());
-  }
+  std::vector<StatsPiece> pieces;
+  if (!stats_plan(first, nsteps, e->stats.origin, e->stats.every, pieces)) return stats_refuse_plan(first, e->stats.origin);
 
   int batch_first = first;
   // second reduction stage over the buffered steps: |u| into av_sum and, with "force", F_x and F_y into their records,
@@ -234,60 +232,79 @@ int enqueue_steps(lbm_dens *e, int nsteps, int first, const int *active) {
     e->ring_fill = 0;
     return LBM_OK;
   };
-  int i = 0;
-  while (i < nsteps) {
-    // the remaining steps in as few launches as possible, of equal depth (8 steps at 3 a launch: 3 + 3 + 2)
-    const int rem = nsteps - i;
-    const int adv = scalar ? 1 : equal_depth(rem, kDensTMax);
-    if (e->ring_fill + adv > scalar_ring_limit(e->scalar, e->ring))
-      if (int rc = flush()) return rc;
-    // scalar step n before flow step n, on the state that flow step streams
-    if (scalar)
-      if (int rc = scalar_step(e->scalar, sgrid, e->q.st, e->cells[e->cur], e->mask, e->flow.open, buoy ? e->buoy.table : nullptr,
-                               e->ring_fill, active))
-        return rc;
-    if (buoy) {
-      // flow step n reads the scalar array that scalar step n has just written
-      DpBuoyArgs b{};
-      b.src = e->cells[e->cur];
-      b.dst = e->cells[e->cur ^ 1];
-      b.mask = e->mask;
-      b.scalar = e->scalar.g[e->scalar.cur];
-      b.members = e->buoy.table;
-      b.wall_u = e->flow.wall_dev;
-      b.seg = e->seg + (size_t)e->ring_fill * slot;
-      b.plane_stride = e->plane_stride;
-      b.member_stride = e->member_stride;
-      b.nx = e->nx;
-      b.ny = e->ny;
-      b.lanes_per_row = e->nseg * 8;
-      b.accel_row = (!e->flow.open && i + adv < nsteps) ? e->ny - 2 : -1;
-      if (int rc = buoy_launch(e->q.st, e->flow.force, e->flow.trt, e->flow.open, e->flow.wall, e->flow.les, b, e->n, active)) return rc;
+  // the ring of segment sums and its flushes carry across the cuts
+  auto enqueue_piece = [&](int len) -> int {
+    // prologue: accelerate_flow of the first step on the current grids (kernels.cl:9-53); later steps get theirs fused
+    // into the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
+    if (!e->flow.open) {
+      hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(e->nx, 128), e->n), dim3(128), 0, e->q.st, e->cells[e->cur], e->plane_stride,
+                         e->member_stride, (const uint8_t *)e->mask, (const DpMember *)e->members, e->nx, e->ny, active);
+      HIP_TRY(hipGetLastError());
+    }
+    int i = 0;
+    while (i < len) {
+      // the remaining steps in as few launches as possible, of equal depth (8 steps at 3 a launch: 3 + 3 + 2)
+      const int rem = len - i;
+      const int adv = scalar ? 1 : equal_depth(rem, kDensTMax);
+      if (e->ring_fill + adv > scalar_ring_limit(e->scalar, e->ring))
+        if (int rc = flush()) return rc;
+      // scalar step n before flow step n, on the state that flow step streams
+      if (scalar)
+        if (int rc = scalar_step(e->scalar, sgrid, e->q.st, e->cells[e->cur], e->mask, e->flow.open, buoy ? e->buoy.table : nullptr,
+                                 e->ring_fill, active))
+          return rc;
+      if (buoy) {
+        // flow step n reads the scalar array that scalar step n has just written
+        DpBuoyArgs b{};
+        b.src = e->cells[e->cur];
+        b.dst = e->cells[e->cur ^ 1];
+        b.mask = e->mask;
+        b.scalar = e->scalar.g[e->scalar.cur];
+        b.members = e->buoy.table;
+        b.wall_u = e->flow.wall_dev;
+        b.seg = e->seg + (size_t)e->ring_fill * slot;
+        b.plane_stride = e->plane_stride;
+        b.member_stride = e->member_stride;
+        b.nx = e->nx;
+        b.ny = e->ny;
+        b.lanes_per_row = e->nseg * 8;
+        b.accel_row = (!e->flow.open && i + adv < len) ? e->ny - 2 : -1;
+        if (int rc = buoy_launch(e->q.st, e->flow.force, e->flow.trt, e->flow.open, e->flow.wall, e->flow.les, b, e->n, active)) return rc;
+        e->cur ^= 1;
+        e->ring_fill += adv;
+        i += adv;
+        continue;
+      }
+      DensArgs a{};
+      a.src = e->cells[e->cur];
+      a.dst = e->cells[e->cur ^ 1];
+      a.mask = e->mask;
+      a.members = e->members;
+      a.seg = e->seg + (size_t)e->ring_fill * slot;
+      a.plane_stride = e->plane_stride;
+      a.member_stride = e->member_stride;
+      a.seg_step = slot;
+      a.nx = e->nx;
+      a.ny = e->ny;
+      a.nseg = e->nseg;
+      a.tiles_x = e->tiles_x;
+      a.T = adv;
+      a.accel_next = (!e->flow.open && i + adv < len) ? 1 : 0;
+      launch_dens(e, a, active);
+      HIP_TRY(hipGetLastError());
       e->cur ^= 1;
       e->ring_fill += adv;
       i += adv;
-      continue;
     }
-    DensArgs a{};
-    a.src = e->cells[e->cur];
-    a.dst = e->cells[e->cur ^ 1];
-    a.mask = e->mask;
-    a.members = e->members;
-    a.seg = e->seg + (size_t)e->ring_fill * slot;
-    a.plane_stride = e->plane_stride;
-    a.member_stride = e->member_stride;
-    a.seg_step = slot;
-    a.nx = e->nx;
-    a.ny = e->ny;
-    a.nseg = e->nseg;
-    a.tiles_x = e->tiles_x;
-    a.T = adv;
-    a.accel_next = (!e->flow.open && i + adv < nsteps) ? 1 : 0;
-    launch_dens(e, a, active);
-    HIP_TRY(hipGetLastError());
-    e->cur ^= 1;
-    e->ring_fill += adv;
-    i += adv;
+    return LBM_OK;
+  };
+  for (const StatsPiece &piece : pieces) {
+    if (int rc = enqueue_piece(piece.len)) return rc;
+    // the sample behind a piece that ends on a sample point: the state lbm_dens_final_state would read here
+    if (piece.sample)
+      if (int rc = stats_sample(e->stats, sgrid, e->q.st, e->cells[e->cur], e->mask, e->members, drive_dev(e),
+                                buoy ? e->scalar.g[e->scalar.cur] : nullptr, buoy ? e->buoy.table : nullptr))
+        return rc;
   }
   return flush();
 }
@@ -497,7 +514,8 @@ int lbm_dens_upload(lbm_dens *e, const double *cells) {
   e->ragged = false;
   e->m_steps.clear();
   e->m_conv.clear();
-  return LBM_OK;
+  // the statistics keep their setting and start anew
+  return stats_restart(e->stats, scalar_grid(e), e->q.st, e->steps_done);
 }
 
 int lbm_dens_run(lbm_dens *e, int nsteps) {
@@ -591,6 +609,7 @@ int lbm_dsteady_run(lbm_dens *e, int max_steps, int window, double rel_tol) {
   // every argument error is reported before the ensemble or a device is touched
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
+  if (e->stats.every) return stats_refuse_steady("lbm_dsteady_run");
   if (e->scalar.on) return refuse_steady_scalar("lbm_dsteady_run");
   bool launched = false;
   const int rc = steady_impl(e, max_steps, window, rel_tol, nullptr, &launched);
@@ -691,6 +710,7 @@ int lbm_dbody_steady_run(lbm_dens *e, int max_steps, int window, double rel_tol)
   // every argument error is reported before the ensemble or a device is touched
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
+  if (e->stats.every) return stats_refuse_steady("lbm_dbody_steady_run");
   if (e->scalar.on) return refuse_steady_scalar("lbm_dbody_steady_run");
   if (!e->flow.force)
     return lbm_fail(LBM_ERR_STATE, "the drag criterion reads the force record: option \"force\" is off (lbm_dforce_ens_set_option "
@@ -858,6 +878,7 @@ int lbm_drecord_steady_run(lbm_dens *e, int max_steps, int window, double rel_to
   if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
   if (int rc = check_steady_args(max_steps, window, rel_tol)) return rc;
   if (which < 0 || which > 2) return lbm_fail(LBM_ERR_ARG, "which must be 0 (content), 1 (flux_x) or 2 (flux_y) (got %d)", which);
+  if (e->stats.every) return stats_refuse_steady("lbm_drecord_steady_run");
   if (!e->scalar.on || !e->scalar.record)
     return lbm_fail(LBM_ERR_ARG, "the scalar criterion reads the scalar's record: it is off (lbm_dscalar_ens_set, then "
                     "lbm_drecord_ens_set before the first step)");
@@ -886,6 +907,30 @@ int lbm_dbuoy_ens_get(const lbm_dens *e, int *on_out, double *b_out) {
     else std::fill(b_out, b_out + 3 * (size_t)e->n, 0.0);
   }
   return LBM_OK;
+}
+
+int lbm_dstats_ens_set(lbm_dens *e, int every) {
+  // argument errors before anything of the ensemble is read
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (int rc = stats_check(every)) return rc;
+  if (every && e->ragged) return refuse_ragged(e);
+  if (int rc = queue_sync(e->q)) return rc;
+  return stats_set(e->stats, scalar_grid(e), e->q.st, every, e->steps_done);
+}
+
+int lbm_dstats_ens_get(const lbm_dens *e, int *every_out, int *origin_out, int *samples_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!every_out && !origin_out && !samples_out) return lbm_fail(LBM_ERR_ARG, "every_out, origin_out and samples_out are all NULL");
+  stats_get(e->stats, every_out, origin_out, samples_out);
+  return LBM_OK;
+}
+
+int lbm_dstats_ens(lbm_dens *e, double *sums_out) {
+  if (!e) return lbm_fail(LBM_ERR_ARG, "ensemble is NULL");
+  if (!sums_out) return lbm_fail(LBM_ERR_ARG, "sums_out is NULL");
+  if (!e->stats.every) return stats_refuse_off("lbm_dstats_ens", true);
+  if (int rc = queue_sync(e->q)) return rc;
+  return stats_read(e->stats, scalar_grid(e), sums_out);
 }
 
 void lbm_dens_destroy(lbm_dens *e) {

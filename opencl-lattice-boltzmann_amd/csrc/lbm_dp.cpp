@@ -60,6 +60,7 @@ struct lbm_dp {
                                   // of one member (dp_host.h), all off by default; a setter's 0 is that header's NULL array
   ScalarState scalar;             // lbm_dscalar_set: the scalar (dp_host.h), off by default
   BuoyState buoy;                 // lbm_dbuoy_set: the scalar acts back on the flow (dp_host.h), off by default
+  StatsState stats;               // lbm_dstats_set: the running statistics (dp_host.h), off by default
   int cur = 0, steps_done = 0;
   bool failed = false;
 };
@@ -87,6 +88,7 @@ void free_dp(lbm_dp *d) {
   if (d->flow.wall_dev) (void)hipFree(d->flow.wall_dev);
   scalar_free(d->scalar);
   buoy_free(d->buoy);
+  stats_free(d->stats);
   queue_destroy(d->q);
   delete d;
 }
@@ -212,14 +214,10 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
   const bool buoy = scalar && d->buoy.on;
   if (buoy)
     if (int rc = buoy_sync(d->buoy, d->flow, flow_grid(d))) return rc;
+  // running statistics: the run is cut at its sample points (stats_plan.h); off, it is one piece
+  std::vector<StatsPiece> pieces;
+  if (!stats_plan(d->steps_done, nsteps, d->stats.origin, d->stats.every, pieces)) return stats_refuse_plan(d->steps_done, d->stats.origin);
   if (int rc = timed_begin(d->q, timed)) return rc;
-  // prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53); later steps get theirs fused into
-  // the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
-  if (!d->flow.open) {
-    hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(nx, 128), 1), dim3(128), 0, d->q.st, d->cells[d->cur], d->plane_stride, 0ull,
-                       (const uint8_t *)d->mask, (const DpMember *)d->members, nx, ny, (const int *)nullptr);
-    HIP_TRY(hipGetLastError());
-  }
 
   int batch_first = d->steps_done;
   // second reduction stage over the buffered steps
@@ -238,81 +236,100 @@ int run_dp_impl(lbm_dp *d, int nsteps, bool timed, double *ms, bool *launched) {
     d->ring_fill = 0;
     return LBM_OK;
   };
-  int i = 0;
-  while (i < nsteps) {
-    // the LDS-tile form: the remaining steps in as few launches as possible, of equal depth (20 steps at T = 8: 7 + 7 + 6)
-    const int rem = nsteps - i;
-    const int adv = (T > 0 && !scalar) ? equal_depth(rem, T) : 1;
-    if (d->ring_fill + adv > scalar_ring_limit(d->scalar, d->ring))
-      if (int rc = flush()) return rc;
-    // scalar step n before flow step n, on the state that flow step streams
-    if (scalar)
-      if (int rc = scalar_step(d->scalar, sgrid, d->q.st, d->cells[d->cur], d->mask, d->flow.open, buoy ? d->buoy.table : nullptr,
-                               d->ring_fill, nullptr))
-        return rc;
-    const bool accel_next = !d->flow.open && i + adv < nsteps;
-    double *seg = d->seg + (size_t)d->ring_fill * slot;
-    if (buoy) {
-      // flow step n reads the scalar array that scalar step n has just written
-      DpBuoyArgs a{};
-      a.src = d->cells[d->cur];
-      a.dst = d->cells[d->cur ^ 1];
-      a.mask = d->mask;
-      a.scalar = d->scalar.g[d->scalar.cur];
-      a.members = d->buoy.table;
-      a.wall_u = d->flow.wall_dev;
-      a.seg = seg;
-      a.plane_stride = d->plane_stride;
-      a.member_stride = 0;
-      a.nx = nx;
-      a.ny = ny;
-      a.lanes_per_row = d->lanes_per_row;
-      a.accel_row = accel_next ? ny - 2 : -1;
-      if (int rc = buoy_launch(d->q.st, d->flow.force, d->flow.trt, d->flow.open, d->flow.wall, d->flow.les, a, 1)) return rc;
-    } else if (T > 0) {
-      DpMultiArgs a{};
-      a.src = d->cells[d->cur];
-      a.dst = d->cells[d->cur ^ 1];
-      a.mask = d->mask;
-      a.seg = seg;
-      a.plane_stride = d->plane_stride;
-      a.seg_step = slot;
-      a.nx = nx;
-      a.ny = ny;
-      a.nseg = d->nseg;
-      a.tiles_x = d->tiles_x;
-      a.T = adv;
-      a.accel_next = accel_next ? 1 : 0;
-      a.omega = d->p.omega;
-      a.aw1 = aw1;
-      a.aw2 = aw2;
-      a.omega_m = omega_m;
-      a.u_in = u_in;
-      a.rho_out = rho_out;
-      launch_multi(d, a);
-    } else {
-      DpStepArgs a{};
-      a.src = d->cells[d->cur];
-      a.dst = d->cells[d->cur ^ 1];
-      a.mask = d->mask;
-      a.seg = seg;
-      a.plane_stride = d->plane_stride;
-      a.nx = nx;
-      a.ny = ny;
-      a.lanes_per_row = d->lanes_per_row;
-      a.accel_row = accel_next ? ny - 2 : -1;
-      a.omega = d->p.omega;
-      a.aw1 = aw1;
-      a.aw2 = aw2;
-      a.omega_m = omega_m;
-      a.u_in = u_in;
-      a.rho_out = rho_out;
-      launch_step(d, a);
+  // every piece as a run of its length is enqueued; the ring of segment sums and its flushes carry across the cuts
+  auto enqueue_piece = [&](int len) -> int {
+    // prologue: accelerate_flow of the first step on the current grid (kernels.cl:9-53); later steps get theirs fused into
+    // the previous launch's write of row ny-2.  Open boundaries: no accelerate_flow anywhere.
+    if (!d->flow.open) {
+      hipLaunchKernelGGL(dp_accelerate_row, dim3(div_up(nx, 128), 1), dim3(128), 0, d->q.st, d->cells[d->cur], d->plane_stride, 0ull,
+                         (const uint8_t *)d->mask, (const DpMember *)d->members, nx, ny, (const int *)nullptr);
+      HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipGetLastError());
-    d->cur ^= 1;
-    d->ring_fill += adv;
-    i += adv;
+    int i = 0;
+    while (i < len) {
+      // the LDS-tile form: the remaining steps in as few launches as possible, of equal depth (20 steps at T = 8: 7 + 7 + 6)
+      const int rem = len - i;
+      const int adv = (T > 0 && !scalar) ? equal_depth(rem, T) : 1;
+      if (d->ring_fill + adv > scalar_ring_limit(d->scalar, d->ring))
+        if (int rc = flush()) return rc;
+      // scalar step n before flow step n, on the state that flow step streams
+      if (scalar)
+        if (int rc = scalar_step(d->scalar, sgrid, d->q.st, d->cells[d->cur], d->mask, d->flow.open, buoy ? d->buoy.table : nullptr,
+                                 d->ring_fill, nullptr))
+          return rc;
+      const bool accel_next = !d->flow.open && i + adv < len;
+      double *seg = d->seg + (size_t)d->ring_fill * slot;
+      if (buoy) {
+        // flow step n reads the scalar array that scalar step n has just written
+        DpBuoyArgs a{};
+        a.src = d->cells[d->cur];
+        a.dst = d->cells[d->cur ^ 1];
+        a.mask = d->mask;
+        a.scalar = d->scalar.g[d->scalar.cur];
+        a.members = d->buoy.table;
+        a.wall_u = d->flow.wall_dev;
+        a.seg = seg;
+        a.plane_stride = d->plane_stride;
+        a.member_stride = 0;
+        a.nx = nx;
+        a.ny = ny;
+        a.lanes_per_row = d->lanes_per_row;
+        a.accel_row = accel_next ? ny - 2 : -1;
+        if (int rc = buoy_launch(d->q.st, d->flow.force, d->flow.trt, d->flow.open, d->flow.wall, d->flow.les, a, 1)) return rc;
+      } else if (T > 0) {
+        DpMultiArgs a{};
+        a.src = d->cells[d->cur];
+        a.dst = d->cells[d->cur ^ 1];
+        a.mask = d->mask;
+        a.seg = seg;
+        a.plane_stride = d->plane_stride;
+        a.seg_step = slot;
+        a.nx = nx;
+        a.ny = ny;
+        a.nseg = d->nseg;
+        a.tiles_x = d->tiles_x;
+        a.T = adv;
+        a.accel_next = accel_next ? 1 : 0;
+        a.omega = d->p.omega;
+        a.aw1 = aw1;
+        a.aw2 = aw2;
+        a.omega_m = omega_m;
+        a.u_in = u_in;
+        a.rho_out = rho_out;
+        launch_multi(d, a);
+      } else {
+        DpStepArgs a{};
+        a.src = d->cells[d->cur];
+        a.dst = d->cells[d->cur ^ 1];
+        a.mask = d->mask;
+        a.seg = seg;
+        a.plane_stride = d->plane_stride;
+        a.nx = nx;
+        a.ny = ny;
+        a.lanes_per_row = d->lanes_per_row;
+        a.accel_row = accel_next ? ny - 2 : -1;
+        a.omega = d->p.omega;
+        a.aw1 = aw1;
+        a.aw2 = aw2;
+        a.omega_m = omega_m;
+        a.u_in = u_in;
+        a.rho_out = rho_out;
+        launch_step(d, a);
+      }
+      HIP_TRY(hipGetLastError());
+      d->cur ^= 1;
+      d->ring_fill += adv;
+      i += adv;
+    }
+    return LBM_OK;
+  };
+  for (const StatsPiece &piece : pieces) {
+    if (int rc = enqueue_piece(piece.len)) return rc;
+    // the sample behind a piece that ends on a sample point: the state lbm_dp_final_state would read here
+    if (piece.sample)
+      if (int rc = stats_sample(d->stats, sgrid, d->q.st, d->cells[d->cur], d->mask, d->members, drive_dev(d),
+                                buoy ? d->scalar.g[d->scalar.cur] : nullptr, buoy ? d->buoy.table : nullptr))
+        return rc;
   }
   if (int rc = flush()) return rc;
   d->steps_done += nsteps;
@@ -393,7 +410,8 @@ int lbm_dp_upload(lbm_dp *d, const double *cells) {
   d->cur = 0;
   d->steps_done = 0;
   d->ring_fill = 0;
-  return LBM_OK;
+  // the statistics keep their setting and start anew
+  return stats_restart(d->stats, scalar_grid(d), d->q.st, d->steps_done);
 }
 
 int lbm_dp_upload_obstacles(lbm_dp *d, const int32_t *obstacles) {
@@ -404,8 +422,10 @@ int lbm_dp_upload_obstacles(lbm_dp *d, const int32_t *obstacles) {
   body_reset(d->body, obstacles, (size_t)d->p.nx * d->p.ny);
   // wall velocities stay as set: a kernel reads one only while its cell is blocked; so do the scalar's state and its c_wall
   // open boundaries stay on: the blocked cells of columns 0 and nx - 1 are outside every body
-  if (d->flow.open) return body_rewrite(d->body, d->mask, d->p.nx, true);
-  return LBM_OK;
+  if (d->flow.open)
+    if (int rc = body_rewrite(d->body, d->mask, d->p.nx, true)) return rc;
+  // the statistics keep their setting and start anew: the sums before and behind it would be those of two geometries
+  return stats_restart(d->stats, scalar_grid(d), d->q.st, d->steps_done);
 }
 
 int lbm_dp_run(lbm_dp *d, int nsteps) {
@@ -733,6 +753,29 @@ int lbm_dbuoy_get(const lbm_dp *d, int *on_out, double *b_out, double *c_ref_out
   }
   if (c_ref_out) *c_ref_out = d->buoy.on ? d->buoy.b[2] : 0.0;
   return LBM_OK;
+}
+
+int lbm_dstats_set(lbm_dp *d, int every) {
+  // argument errors before anything of the context is read
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (int rc = stats_check(every)) return rc;
+  if (int rc = queue_sync(d->q)) return rc;
+  return stats_set(d->stats, scalar_grid(d), d->q.st, every, d->steps_done);
+}
+
+int lbm_dstats_get(const lbm_dp *d, int *every_out, int *origin_out, int *samples_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!every_out && !origin_out && !samples_out) return lbm_fail(LBM_ERR_ARG, "every_out, origin_out and samples_out are all NULL");
+  stats_get(d->stats, every_out, origin_out, samples_out);
+  return LBM_OK;
+}
+
+int lbm_dstats(lbm_dp *d, double *sums_out) {
+  if (!d) return lbm_fail(LBM_ERR_ARG, "context is NULL");
+  if (!sums_out) return lbm_fail(LBM_ERR_ARG, "sums_out is NULL");
+  if (!d->stats.every) return stats_refuse_off("lbm_dstats", false);
+  if (int rc = queue_sync(d->q)) return rc;
+  return stats_read(d->stats, scalar_grid(d), sums_out);
 }
 
 void lbm_dp_destroy(lbm_dp *d) {
